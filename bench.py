@@ -28,9 +28,15 @@ After the idle seconds of plan building the GPU needs ~25 ms of continuous work 
 (measured: 0.618 -> 0.565 -> 0.550 ms per step over the first three 20-step windows after idle); the driver's
 `--warmup 5 --steps 20` would otherwise time the ramp.
 
-Rank 0 prints ONE JSON line; extra keys: `roofline` (tile kernel, HIP events on the launch stream, algorithmic
-bytes 68 m + 24 n per evaluation) and, at N = 1, `cpu_baseline` (the reference formulation in plain PyTorch on
-the host cores, on a bounded sample).
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, the launch-mode probe of
+`--launch auto`, pre-heat, the W warm-up steps and the K timed steps.  `--full` adds the measurements that take runs of
+their own: the other launch modes (`*_ms_per_step`), `roofline` (tile kernel, HIP events on the launch stream,
+algorithmic bytes 68 m + 24 n per evaluation), `raw_c_abi_tets_per_s`, per-rank kernel times and, at N = 1,
+`cpu_baseline` (the reference formulation in plain PyTorch on the host cores, on a bounded sample).
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step: `energy.npy` (float32 scalar, the
+job-wide energy) and `grad.npy` (float32, n x 3, the gradient w.r.t. the vertex positions; `grad_rank<r>.npy` per rank
+when N > 1).  Scenes and deformations are seeded, so the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -94,7 +100,17 @@ def parse(argv=None):
     p.add_argument("--dry-run", action="store_true",
                    help="no GPU work: exercise rank launch, process group, energy all-reduce check and the JSON line "
                         "(CPU test of the N > 1 plumbing, gloo)")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the other launch modes, the roofline leg (tile kernel "
+                        "events), the raw C-ABI loop and, at N = 1, the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's outputs (energy, gradient) as DIR/<name>.npy")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
 
 
 def _cpu_model() -> str:
@@ -323,7 +339,7 @@ def _run_rank(args, stdout_fd: int) -> None:
     x = torch.nn.Parameter(torch.from_numpy(x_host).to(dev))
     m_local, n_local = sc.n_tets, sc.n_vertices
     cpu_sample = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         # the CPU baseline runs on the same inputs: the first K spheres of this very scene, with these positions
         tets_per_sphere = max(m_local // max(my_spheres, 1), 1)
         k = args.cpu_sample_spheres if args.cpu_sample_spheres > 0 else max(1, min(my_spheres, 2_700_000 // tets_per_sphere))
@@ -503,8 +519,19 @@ def _run_rank(args, stdout_fd: int) -> None:
         e_sum = sum(float(p) for p in parts)
         assert abs(e_global - e_sum) <= 1e-5 * abs(e_sum) + 1e-30, f"all-reduced energy {e_global} != sum of rank energies {e_sum}"
 
+    if args.dump_outputs:
+        # what a caller of the timed path received in its last timed step, before any later leg overwrites the buffers: the
+        # replay's static gradient buffer, or x.grad for the paths that go through backward()
+        import numpy as np
+        grad = graphed.grad if launch_mode == "graph" else x.grad
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "grad.npy" if world == 1 else f"grad_rank{rank}.npy"),
+                grad.detach().to(torch.float32).cpu().numpy())
+        if rank == 0:
+            np.save(os.path.join(args.dump_outputs, "energy.npy"), np.asarray(e_global, dtype=np.float32))
+
     others = {}
-    if world == 1:                                     # the other launch modes, for the record
+    if args.full and world == 1:                       # the other launch modes, for the record
         for name, fn in (("eager_autograd", step_eager), ("graph_replay", step_graph), ("graph_autograd", step_graph_autograd)):
             if fn is main_fn or (graphed is None and fn is not step_eager) or sharded is not None:
                 continue
@@ -513,43 +540,45 @@ def _run_rank(args, stdout_fd: int) -> None:
             if reducer is not None:
                 reducer.results()
 
-    # ---- roofline leg: the tile kernel alone, HIP events on the launch stream (raw C-ABI evaluations) ----
-    preheat()
-    torch.cuda.synchronize(dev)
-    energy.tet_sp.set_timing(True)
-    for _ in range(max(args.steps, 50)):               # (at least 50 launches: a 20-launch average moves by 3 % between runs)
-        raw()
-    torch.cuda.synchronize(dev)
-    tile_ms, finish_ms, n_eval = energy.tet_sp.get_timing()
-    energy.tet_sp.set_timing(False)
-    tile_ms /= max(n_eval, 1)
-    finish_ms /= max(n_eval, 1)
-    b_alg = 68.0 * m_local + 24.0 * n_local           # bytes per fused fwd+bwd evaluation
-    achieved = b_alg / (tile_ms * 1e-3) / 1e9 if tile_ms > 0 else 0.0
-    # HBM bytes per launch from the PMC counters cannot be collected inside this process (rocprofv3 wraps the command: separate
-    # --pmc passes, tools/profile_round.sh); the figure of the last profiled run is reported only while the kernel and the plan
-    # layout it was measured on are the ones running now (fingerprint of kernels.hip + plan.cpp + plan.h), otherwise null
-    traffic, traffic_note = None, "no PMC pass on record for this workload (tools/profile_round.sh)"
-    prof = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(prof):
-        try:
-            from tssplat_amd import _build
-            rec = json.load(open(prof)).get(f"{args.scene}x{my_spheres}")
-            if rec is not None:
-                if rec.get("sources") == _build.traffic_digest():
-                    traffic, traffic_note = rec["hbm_bytes_per_launch"], f"rocprofv3 PMC passes of {rec['round']}, same kernel and plan sources"
-                else:
-                    traffic_note = (f"dropped: profiles/traffic.json ({rec.get('round')}) was measured on other kernel / plan sources "
-                                    f"({rec.get('sources', 'unstamped')} != {_build.traffic_digest()}); re-run tools/profile_round.sh")
-                    print("bench.py: " + traffic_note, file=sys.stderr)
-        except Exception as exc:                       # noqa: BLE001
-            traffic, traffic_note = None, f"profiles/traffic.json unreadable: {exc}"
-    torch.cuda.synchronize(dev)
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        raw()
-    torch.cuda.synchronize(dev)
-    raw_elapsed = time.perf_counter() - t1
+    tile_ms = finish_ms = 0.0
+    if args.full:
+        # ---- roofline leg: the tile kernel alone, HIP events on the launch stream (raw C-ABI evaluations) ----
+        preheat()
+        torch.cuda.synchronize(dev)
+        energy.tet_sp.set_timing(True)
+        for _ in range(max(args.steps, 50)):               # (at least 50 launches: a 20-launch average moves by 3 % between runs)
+            raw()
+        torch.cuda.synchronize(dev)
+        tile_ms, finish_ms, n_eval = energy.tet_sp.get_timing()
+        energy.tet_sp.set_timing(False)
+        tile_ms /= max(n_eval, 1)
+        finish_ms /= max(n_eval, 1)
+        b_alg = 68.0 * m_local + 24.0 * n_local           # bytes per fused fwd+bwd evaluation
+        achieved = b_alg / (tile_ms * 1e-3) / 1e9 if tile_ms > 0 else 0.0
+        # HBM bytes per launch from the PMC counters cannot be collected inside this process (rocprofv3 wraps the command: separate
+        # --pmc passes, tools/profile_round.sh); the figure of the last profiled run is reported only while the kernel and the plan
+        # layout it was measured on are the ones running now (fingerprint of kernels.hip + plan.cpp + plan.h), otherwise null
+        traffic, traffic_note = None, "no PMC pass on record for this workload (tools/profile_round.sh)"
+        prof = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(prof):
+            try:
+                from tssplat_amd import _build
+                rec = json.load(open(prof)).get(f"{args.scene}x{my_spheres}")
+                if rec is not None:
+                    if rec.get("sources") == _build.traffic_digest():
+                        traffic, traffic_note = rec["hbm_bytes_per_launch"], f"rocprofv3 PMC passes of {rec['round']}, same kernel and plan sources"
+                    else:
+                        traffic_note = (f"dropped: profiles/traffic.json ({rec.get('round')}) was measured on other kernel / plan sources "
+                                        f"({rec.get('sources', 'unstamped')} != {_build.traffic_digest()}); re-run tools/profile_round.sh")
+                        print("bench.py: " + traffic_note, file=sys.stderr)
+            except Exception as exc:                       # noqa: BLE001
+                traffic, traffic_note = None, f"profiles/traffic.json unreadable: {exc}"
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            raw()
+        torch.cuda.synchronize(dev)
+        raw_elapsed = time.perf_counter() - t1
 
     mt = torch.tensor([m_local], device=dev, dtype=torch.float64)
     if world > 1:
@@ -611,31 +640,34 @@ def _run_rank(args, stdout_fd: int) -> None:
                           "and the penalty are pinned to reference code; tools/pin_L_with_pypgo.py settles it where libpgo exists",
             },
             "per_rank": {"ms_per_step": [r[0] for r in per_rank], "tets": [int(r[1]) for r in per_rank],
-                         "tile_kernel_ms": [r[2] for r in per_rank], "finish_kernel_ms": [r[3] for r in per_rank],
                          "ms_per_step_min": min(r[0] for r in per_rank), "ms_per_step_max": max(r[0] for r in per_rank)},
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "tile_energy_kernel<WITH_GRAD=true>",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_note": traffic_note,
-                "algorithmic_bytes_per_launch": b_alg,
-                "kernel_ms": tile_ms,
-                "finish_kernel_ms": finish_ms,
-                "launches": int(n_eval),               # evaluations behind kernel_ms (at least 50, whatever --steps says)
-                # SURVEY 8(d) defines the roofline on t(fwd+bwd), i.e. on the whole step -- tile kernel + finish kernel +
-                # whatever the launch path adds -- not on the dominant kernel alone: this rank's bytes / the timed step
-                "achieved_step": b_alg / (elapsed / args.steps) / 1e9,
-                "frac_step": b_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
-                "frac_kernels": b_alg / ((tile_ms + finish_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS if tile_ms > 0 else 0.0,
-            },
-            "raw_c_abi_tets_per_s": m_local * args.steps / raw_elapsed,
             "energy": e_global,
             "plan_build_s": t_plan,
         }
+        if args.full:
+            out["per_rank"].update({"tile_kernel_ms": [r[2] for r in per_rank], "finish_kernel_ms": [r[3] for r in per_rank]})
+            out.update({
+                "roofline": {
+                    "bound": "hbm",
+                    "kernel": "tile_energy_kernel<WITH_GRAD=true>",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic,
+                    "traffic_note": traffic_note,
+                    "algorithmic_bytes_per_launch": b_alg,
+                    "kernel_ms": tile_ms,
+                    "finish_kernel_ms": finish_ms,
+                    "launches": int(n_eval),               # evaluations behind kernel_ms (at least 50, whatever --steps says)
+                    # SURVEY 8(d) defines the roofline on t(fwd+bwd), i.e. on the whole step -- tile kernel + finish kernel +
+                    # whatever the launch path adds -- not on the dominant kernel alone: this rank's bytes / the timed step
+                    "achieved_step": b_alg / (elapsed / args.steps) / 1e9,
+                    "frac_step": b_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
+                    "frac_kernels": b_alg / ((tile_ms + finish_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS if tile_ms > 0 else 0.0,
+                },
+                "raw_c_abi_tets_per_s": m_local * args.steps / raw_elapsed,
+            })
         out.update(others)
         if cpu_sample is not None:
             out["cpu_baseline"] = cpu_baseline(args, torch, scenes, cpu_sample[0], cpu_sample[1], c1, c2, total_spheres)

@@ -31,6 +31,7 @@ import pytest
 import torch
 
 REF = "/root/reference"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))     # this checkout, wherever it lies
 pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "renderers", "mesh_rasterizer.py")),
                                 reason="the reference checkout only exists in the authoring container")
 
@@ -153,7 +154,7 @@ def _veg(tmp_path):
 
 def test_reference_geometry_runs_unmodified_on_the_shims(reference_modules, tmp_path):
     geo, _, _ = reference_modules
-    assert geo.__file__.startswith(REF) and sys.modules["pypgo"].__file__.startswith("/root/repo")
+    assert geo.__file__.startswith(REF) and sys.modules["pypgo"].__file__.startswith(ROOT + os.sep)
     path, v, t = _veg(tmp_path)
     g = geo.TetMeshGeometry(_Cfg(use_smooth_barrier=False, initial_mesh_path=path, smooth_barrier_param=None, optimize_geo=True))
     assert np.array_equal(g.tetmesh.elem, t) and np.allclose(g.tetmesh.vtx_init, v)

@@ -25,14 +25,14 @@ done
 cd $R
 rm -f $OUT/parity.txt
 TSSPLAT_AMD_PARITY_REPORT=$OUT/parity.txt python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; tail -2 $OUT/pytest_gpu.log
-python bench.py > $OUT/bench_kuhn19x512.json 2> $OUT/bench_kuhn19x512.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_kuhn19x512_driver.json 2>> $OUT/bench_kuhn19x512.log
-python bench.py --scene aveg --spheres 952 --no-cpu-baseline > $OUT/bench_avegx952.json 2> $OUT/bench_avegx952.log
-python bench.py --scene delaunay6000 --spheres 540 --no-cpu-baseline > $OUT/bench_delaunay6000x540.json 2> $OUT/bench_delaunay6000x540.log
+python bench.py --full > $OUT/bench_kuhn19x512.json 2> $OUT/bench_kuhn19x512.log
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_kuhn19x512_driver.json 2>> $OUT/bench_kuhn19x512.log
+python bench.py --full --scene aveg --spheres 952 --no-cpu-baseline > $OUT/bench_avegx952.json 2> $OUT/bench_avegx952.log
+python bench.py --full --scene delaunay6000 --spheres 540 --no-cpu-baseline > $OUT/bench_delaunay6000x540.json 2> $OUT/bench_delaunay6000x540.log
 for cfg in "kuhn19 256" "kuhn8 256" "kuhn8 64"; do set -- $cfg
-  python bench.py --scene $1 --spheres $2 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_$1x$2.json 2> $OUT/bench_$1x$2.log
+  python bench.py --full --scene $1 --spheres $2 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_$1x$2.json 2> $OUT/bench_$1x$2.log
 done
-python bench.py --gpus 2 --dist-backend gloo --all-ranks-on-device0 --steps 20 --warmup 5 > $OUT/bench_2rank_dev0.json 2> $OUT/bench_2rank_dev0.log
+python bench.py --full --gpus 2 --dist-backend gloo --all-ranks-on-device0 --steps 20 --warmup 5 > $OUT/bench_2rank_dev0.json 2> $OUT/bench_2rank_dev0.log
 python tools/scaling_model.py $ROUND --out $OUT/scaling_model.json > $OUT/scaling_model.log 2>&1
 python tools/host_overhead.py > $OUT/host_overhead.txt 2>&1
 python tools/bench_operator.py > $OUT/bench_operator.txt 2>&1

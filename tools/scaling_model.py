@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(spheres, steps, window, extra=()):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--spheres", str(spheres), "--steps", str(steps), "--warmup", "20",
-           "--no-cpu-baseline", "--force-collective", "--energy-window", str(window), *extra]
+           "--full", "--no-cpu-baseline", "--force-collective", "--energy-window", str(window), *extra]
     p = subprocess.run(cmd, capture_output=True, text=True)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if not lines:
