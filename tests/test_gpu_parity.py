@@ -250,7 +250,7 @@ def test_forward_only_equals_fused_and_is_deterministic(ext):
     assert abs(e_fwd[0] - e_fused[0]) <= 1e-6 * abs(e_fused[0])
 
 
-def test_autograd_surface_and_cache(ext):
+def test_function_surface_and_cache(ext):
     """SmoothnessBarrierFunc contract (energies/smooth_barrier.py:9-31) and the fused-pass cache."""
     from tssplat_amd import scenes
     from tssplat_amd.energies import SmoothnessBarrierEnergy, SmoothnessBarrierFunc
@@ -262,12 +262,12 @@ def test_autograd_surface_and_cache(ext):
 
     sc = scenes.make_scene("kuhn8", 3)
     mod = SmoothnessBarrierEnergy(sc.rest, sc.tets, Flags)
-    mod._ext = None        # the Python Function and the operator functions' fused cache (the C++ node keeps its gradient in its
-                           # own context: test_cpp_autograd_nodes_equal_python_nodes)
+    # SmoothnessBarrierFunc called directly: the Python Function and the operator functions' fused cache (the module's C++ node
+    # keeps its gradient in its own context: test_cpp_autograd_nodes_equal_python_nodes)
     x = torch.nn.Parameter(torch.from_numpy(scenes.deform(sc, 0.3)).cuda())
     c1, c2 = mod.coeff_scheduler(1200)
     assert abs(c1 / Flags.smooth_eng_coeff - 16.0) < 1e-9
-    e = mod(x, 1200, c1, c2)                                   # it > 1000 -> order 4
+    e = SmoothnessBarrierFunc.apply(x, mod.tet_sp, c1, c2, 4)  # it = 1200 > 1000 -> order 4 (the module's choice: e_ng below)
     assert e.dim() == 0 and e.dtype == torch.float32 and e.is_cuda
     assert mod.tet_sp._cache is not None                       # fused pass ran
     loss = 2.5 * e + 1.0
@@ -296,7 +296,7 @@ def test_autograd_surface_and_cache(ext):
     assert mod.tet_sp._cache is None and abs(float(e_ng) - E) <= 1e-5 * abs(E)
     # ... and such a call between `loss = energy(x)` and `loss.backward()` leaves the kept gradient in place
     x.grad = None
-    e = mod(x, 1200, c1, c2)
+    e = SmoothnessBarrierFunc.apply(x, mod.tet_sp, c1, c2, 4)
     kept = mod.tet_sp._cache
     with torch.no_grad():
         mod(x, 1200, c1, c2)
@@ -895,11 +895,34 @@ def test_fused_train_loop_equals_eager(ext):
 
 
 def test_cpp_autograd_nodes_equal_python_nodes(ext):
-    """``SmoothnessBarrierEnergy`` runs its autograd node in C++ (csrc/torch_autograd.cpp) when the in-tree
-    extension is there.  Same library calls as the Python Functions, so: bitwise-equal energies and gradients, eager and
-    replayed, with a second loss term, a CPU grad_output, the order switch and the stale-backward check."""
+    """``SmoothnessBarrierEnergy`` runs its autograd node in C++ (csrc/torch_autograd.cpp).  Same library calls
+    as the same nodes spelled as Python Functions, so: bitwise-equal energies and gradients, eager and replayed, with a second loss
+    term, a CPU grad_output, the order switch and the stale-backward check."""
     from tssplat_amd import _capi, scenes
-    from tssplat_amd.energies import SmoothnessBarrierEnergy
+    from tssplat_amd.energies import GraphedSmoothnessBarrier, SmoothnessBarrierEnergy, SmoothnessBarrierFunc
+
+    class GraphReplayRef(torch.autograd.Function):
+        """The replayed node in Python: forward = one replay (energy and gradient into the static buffers) and the ticket bump,
+        backward = ``grad_output x`` the static gradient, a fresh tensor."""
+
+        @staticmethod
+        def forward(ctx, x_cur, graphed, c1, c2, order):
+            energy, grad = graphed.evaluate(c1, c2, order)
+            ctx.graphed = graphed
+            ctx.ticket = graphed.ticket = graphed.ticket + 1
+            return energy.detach()
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            if grad_output is None:
+                return None, None, None, None, None
+            graphed = ctx.graphed
+            if ctx.ticket != graphed.ticket:
+                raise RuntimeError("backward() of a graph-replayed energy after a newer evaluation overwrote its static gradient buffer")
+            go = grad_output
+            if go.device != graphed.grad.device or go.dtype != torch.float32:
+                go = go.detach().to(device=graphed.grad.device, dtype=torch.float32, non_blocking=True)
+            return graphed.grad * go, None, None, None, None
 
     class Flags:
         smooth_eng_coeff = 2e-4 / 6
@@ -912,18 +935,25 @@ def test_cpp_autograd_nodes_equal_python_nodes(ext):
     w = torch.randn_like(x0)
     for graph in (False, True):
         cpp = SmoothnessBarrierEnergy(sc.rest, sc.tets, Flags, graph=graph)
-        py = SmoothnessBarrierEnergy(sc.rest, sc.tets, Flags, graph=graph)
-        py._ext = None                                              # force the Python Functions
+        py = SmoothnessBarrierEnergy(sc.rest, sc.tets, Flags)      # (its TetSpheres object and schedule: the Python side's)
         xc, xp = torch.nn.Parameter(x0.clone()), torch.nn.Parameter(x0.clone())
+        gr = GraphedSmoothnessBarrier(py, xp.detach()) if graph else None
+
+        def py_energy(x, it, c1, c2):
+            order = 4 if it > Flags.increase_order_iter else 2
+            if gr is not None:
+                return GraphReplayRef.apply(x, gr, c1, c2, order)
+            return SmoothnessBarrierFunc.apply(x, py.tet_sp, c1, c2, order)
+
         for it in (0, 7, 600, 1001, 1500):
-            for mod, x in ((cpp, xc), (py, xp)):
+            for mod, energy, x in ((cpp, cpp, xc), (py, py_energy, xp)):
                 x.grad = None
                 c1, c2 = mod.coeff_scheduler(it)
-                loss = (w * x).sum() * 1e-3 + 0.5 * mod(x, it, c1, c2)
+                loss = (w * x).sum() * 1e-3 + 0.5 * energy(x, it, c1, c2)
                 loss.backward()
                 with torch.no_grad():
                     x.add_(-1e-3 * x.grad.clamp(-0.05, 0.05))       # in place: the replay keeps its storage
-            e_c, e_p = float(cpp(xc, it, *cpp.coeff_scheduler(it)).detach()), float(py(xp, it, *py.coeff_scheduler(it)).detach())
+            e_c, e_p = float(cpp(xc, it, *cpp.coeff_scheduler(it)).detach()), float(py_energy(xp, it, *py.coeff_scheduler(it)).detach())
             assert np.isfinite(e_c) and e_c == e_p, (graph, it, e_c, e_p)
             assert torch.equal(xc.grad, xp.grad), (graph, it)
             assert torch.equal(xc, xp)

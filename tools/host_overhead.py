@@ -74,11 +74,15 @@ def trainer_step(mod):
     return f
 for graph in (False, True):
     m_cpp = SmoothnessBarrierEnergy(sc.rest, sc.tets, F, graph=graph)
-    m_py = SmoothnessBarrierEnergy(sc.rest, sc.tets, F, graph=graph)
-    m_py._ext = None
     tag = "graph=True " if graph else "eager      "
     run(f"trainer-shaped step, {tag} C++ autograd node", trainer_step(m_cpp), N=4000)
-    run(f"trainer-shaped step, {tag} Python autograd Function", trainer_step(m_py), N=4000)
+def trainer_step_func(i):                # the same step through the Python Function (order 2: it < increase_order_iter)
+    x.grad = None
+    it = i % 900
+    c1, c2 = en.coeff_scheduler(it)
+    loss = (w * x).sum() + SmoothnessBarrierFunc.apply(x, ts, c1, c2, 2)
+    loss.backward()
+run("trainer-shaped step, eager       Python autograd Function", trainer_step_func, N=4000)
 def only_energy(mod):
     def f(i):
         x.grad = None

@@ -2,10 +2,10 @@
 //
 // What they stand for: SmoothnessBarrierFunc of /root/reference/energies/smooth_barrier.py:9-31 -- forward = the energy,
 // backward = grad_output x dE/dx -- for code shaped like /root/reference/trainer.py:94-130
-// (loss = image_loss + energy(x, it, c1, c2); loss.backward()).  The Python twins (energies/smooth_barrier.py:
-// SmoothnessBarrierFunc, energies/graphed.py: GraphReplayFunc) cost 70-110 us of host time per step on the MI355X box
-// for 17 us of kernels on a 64-sphere batch (profiles/r03_host_overhead.txt): a Python autograd.Function round trip,
-// ctypes marshalling of ten arguments, two Python frames per pass.  Here the node is created and run by the C++ autograd
+// (loss = image_loss + energy(x, it, c1, c2); loss.backward()).  The same nodes as Python autograd.Functions (the eager one
+// stays as the reference-spelled surface, energies/smooth_barrier.py: SmoothnessBarrierFunc) cost 70-110 us of host time per
+// step on the MI355X box for 17 us of kernels on a 64-sphere batch (profiles/r03_host_overhead.txt): a Python
+// autograd.Function round trip, ctypes marshalling of ten arguments, two Python frames per pass.  Here the node is created and run by the C++ autograd
 // engine and the evaluation is ONE call into the C ABI (include/tssplat_amd.h):
 //     energy_replay -> tsamd_graph_launch   (the library-owned HIP graph; static energy / gradient buffers)
 //     energy_eval   -> tsamd_forward_backward (eager; fresh tensors)

@@ -4,9 +4,9 @@
 // Independent tet-spheres shard over the GPUs of a node by whole spheres (the reference concatenates them with a running vertex
 // offset, /root/reference/geometry/tetmesh_geometry.py:310-331); the only cross-rank step of an evaluation is the sum of the
 // scalar energies.  tssplat_amd/sharding.py: OverlappedEnergyAllReduce issues that all-reduce once per evaluation from a helper
-// thread, so that the training thread never pays for a collective call.  A Python helper thread still competes for the
-// interpreter lock: measured on the MI355X box (tools/host_overhead.py, 64 x kuhn8) reserve + commit cost the training thread 45 us
-// per step, of a 64 us step -- the hand-offs of the lock around every call of the helper.  This class is the same protocol with a
+// thread, so that the training thread never pays for a collective call.  A Python helper thread would compete for the
+// interpreter lock: measured on the MI355X box (tools/host_overhead.py, 64 x kuhn8) reserve + commit of one cost the training thread
+// 45 us per step, of a 64 us step -- the hand-offs of the lock around every call of the helper.  This class runs the protocol on a
 // std::thread: reserve() / commit() are a few hundred nanoseconds of bookkeeping plus one event record, the collective is issued
 // through c10d::ProcessGroup::allreduce without the interpreter, value() releases the lock while it waits.
 //

@@ -14,8 +14,8 @@ The result is the same energy and the same gradient as ``SmoothnessBarrierEnergy
 every ``step``).  ``step`` itself does not go through autograd: add ``self.grad`` to the parameter's ``.grad`` (or
 hand it to ``AdamUniform``) yourself.  For code shaped like the reference trainer (``loss = ... + energy(x, it, c1, c2)``,
 ``loss.backward()``, /root/reference/trainer.py:94-130) ``SmoothnessBarrierEnergy(..., graph=True)`` wraps the same
-replay in an autograd node (``GraphReplayFunc``): the trainer keeps its shape and gets the replayed kernels -- though
-on this path the ~70 us that ``torch.autograd`` itself spends on a custom Function round trip dominate the step.
+replay in an autograd node (the C++ node ``energy_replay`` of csrc/torch_autograd.cpp: forward = one replay, backward =
+``grad_output x`` the replay's gradient): the trainer keeps its shape and gets the replayed kernels.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 from .. import _capi, tet_spheres_ext
 from .smooth_barrier import SmoothnessBarrierEnergy
 
-__all__ = ["GraphedSmoothnessBarrier", "GraphReplayFunc"]
+__all__ = ["GraphedSmoothnessBarrier"]
 
 _lib = _capi.load()
 
@@ -58,7 +58,7 @@ class GraphedSmoothnessBarrier:
         self._scale = torch.full((1,), float(grad_scale), dtype=torch.float32, device=dev)
         self._graphs: dict[int, C.c_void_p] = {}
         # evaluations so far (a backward must belong to the latest one): a one-element CPU tensor so that the C++ autograd node
-        # (csrc/torch_autograd.cpp) and GraphReplayFunc count on the same cell
+        # (csrc/torch_autograd.cpp) and SmoothnessBarrierEnergy.evaluate_direct count on the same cell
         self.ticket_tensor = torch.zeros(1, dtype=torch.int64)
         self._ticket_cell = self.ticket_tensor.numpy()      # (the same memory: a numpy scalar access costs 0.1 us, a tensor index 3 us)
 
@@ -119,33 +119,3 @@ class GraphedSmoothnessBarrier:
             c1, c2 = self.module.coeff_scheduler(it)
         order = 4 if it > self.module.FLAGS.increase_order_iter else 2
         return self.evaluate(c1, c2, order, energy_copy)
-
-
-class GraphReplayFunc(torch.autograd.Function):
-    """The autograd node of ``SmoothnessBarrierEnergy(..., graph=True)``: same ``apply(x, ., c1, c2, order)`` shape as
-    ``SmoothnessBarrierFunc`` (reference energies/smooth_barrier.py:9-31), with the evaluation replayed from a HIP graph.
-
-    forward: one replay (tile + finish kernels: energy AND the unscaled gradient, into static buffers), returns the
-    energy buffer (a fresh tensor object on the same storage -- valid until the next evaluation, like every output of a
-    graphed callable).  backward: ``grad_output * gradient`` -- one small elementwise kernel, no second evaluation, and a
-    fresh tensor, so ``x.grad`` never aliases the static buffer."""
-
-    @staticmethod
-    def forward(ctx, x_cur, graphed, c1, c2, order):
-        energy, grad = graphed.evaluate(c1, c2, order)
-        ctx.graphed = graphed
-        ctx.ticket = graphed.ticket = graphed.ticket + 1
-        return energy.detach()
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        if grad_output is None:
-            return None, None, None, None, None
-        graphed = ctx.graphed
-        if ctx.ticket != graphed.ticket:
-            raise RuntimeError("backward() of a graph-replayed energy after a newer evaluation overwrote its static gradient "
-                               "buffer: call backward() before the next forward, or use graph=False")
-        go = grad_output
-        if go.device != graphed.grad.device or go.dtype != torch.float32:
-            go = go.detach().to(device=graphed.grad.device, dtype=torch.float32, non_blocking=True)
-        return graphed.grad * go, None, None, None, None

@@ -11,14 +11,12 @@ The reference itself has no distributed code; this is new host l
 by world_size-2 and -8 gloo tests on CPU (tests/test_sharding_gloo.py).
 
 Three forms of that exchange: ``WindowedEnergyAllReduce`` (one collective per window of steps, issued by the caller: bench.py's loop),
-``OverlappedEnergyAllReduce`` (issued by a helper thread -- csrc/torch_exchange.cpp when the in-tree extension is there --, per step or
-per window, values readable by ticket) and the plain per-call all-reduce; ``ShardedSmoothnessBarrierEnergy`` is the module a trainer
+``OverlappedEnergyAllReduce`` (issued by the helper thread of csrc/torch_exchange.cpp, per step or per window, values
+readable by ticket) and the plain per-call all-reduce; ``ShardedSmoothnessBarrierEnergy`` is the module a trainer
 holds, ``JobWideEnergy`` the tensor its ``forward`` returns.
 """
 from __future__ import annotations
 
-import queue
-import threading
 from typing import Callable, Sequence
 
 import numpy as np
@@ -205,7 +203,7 @@ class OverlappedEnergyAllReduce:
 
     ``submit(local_energy)`` (the training thread) copies the scalar into a ring slot on the current stream, records an event
     and hands (slot, event) to the helper thread -- a few microseconds, no collective call.  The helper makes a side stream
-    wait for the event and enqueues ``dist.all_reduce(slot, async_op=True)`` there (RCCL on a GPU node: the collective's own
+    wait for the event and enqueues the slot's all-reduce there (RCCL on a GPU node: the collective's own
     stream then waits for the side stream, never for the compute stream, and the compute stream never waits for it); the
     20-40 us a collective call costs the host (profiles/r05_scaling_model.json: 63.5 -> 89.7 us per step at 64 spheres per
     rank) are spent next to the training thread, not in it.  ``value(ticket)`` waits -- host-side until the helper has
@@ -218,136 +216,42 @@ class OverlappedEnergyAllReduce:
     it).  A slot is re-used after ``depth`` tickets: older values have expired.
 
     With one rank or no initialised process group the collective is the identity; everything else runs unchanged.
+
+    The protocol and its helper thread are ``EnergyExchange`` of the in-tree C++ extension (csrc/torch_exchange.cpp: a std::thread,
+    c10d called without the interpreter; a Python helper thread would compete with the training thread for the interpreter lock);
+    this class is its Python surface.
     """
 
-    def __init__(self, device, group=None, depth: int = 256, use_extension: bool = True, every: int = 1):
+    def __init__(self, device, group=None, depth: int = 256, every: int = 1):
         if depth < 2:
             raise ValueError("depth must be >= 2")
         if every < 1 or depth % every or depth < 2 * every:
             raise ValueError("`every` must divide the ring depth at least twice")
         self.device, self.group, self.depth, self.every = torch.device(device), group, int(depth), int(every)
-        self._committed = self._issued_upto = 0
         self.ring = torch.zeros(self.depth, dtype=torch.float32, device=self.device)
-        self._slots = [self.ring[s:s + 1] for s in range(self.depth)]
-        self._cuda = self.device.type == "cuda"
-        self._side = torch.cuda.Stream(self.device) if self._cuda else None
-        self._events = [torch.cuda.Event() for _ in range(self.depth)] if self._cuda else None
-        self._works: list = [None] * self.depth
-        self._issued = [threading.Event() for _ in range(self.depth)]
-        for ev in self._issued:
-            ev.set()
-        self._ticket_of_slot = [-1] * self.depth
-        self._next = 0
-        self._q: queue.SimpleQueue = queue.SimpleQueue()
-        self._thread: threading.Thread | None = None
-        self._error: BaseException | None = None
-        self._active = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) >= 1
-        self._collectives = 0
-        # The helper thread lives in the in-tree C++ extension when that is there (csrc/torch_exchange.cpp: same protocol, a
-        # std::thread, c10d called without the interpreter); the Python thread below is the fallback.  A Python helper competes
-        # with the training thread for the interpreter lock: 45 us of a 64 us step on the MI355X box (tools/host_overhead.py).
-        self._cxx = None
-        if use_extension:
-            from . import _capi
-            ext = _capi.autograd_ext()
-            if ext is not None and hasattr(ext, "EnergyExchange"):
-                pg = None
-                if self._active:
-                    pg = group if group is not None else dist.distributed_c10d._get_default_group()
-                self._cxx = ext.EnergyExchange(self.ring, pg, self.every)
+        pg = None                                             # (no process group: the exchange is the identity)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) >= 1:
+            pg = group if group is not None else dist.distributed_c10d._get_default_group()
+        from . import _capi
+        self._cxx = _capi.autograd_ext().EnergyExchange(self.ring, pg, self.every)
 
     @property
     def collectives(self) -> int:
-        return int(self._cxx.collectives) if self._cxx is not None else self._collectives
+        return int(self._cxx.collectives)
 
-    # ---- helper thread (fallback) ----
-    def _worker(self) -> None:
-        # What this thread does per collective while it holds the interpreter lock is what the training thread loses: the
-        # process group's own allreduce (one pybind call that releases the lock) instead of dist.all_reduce (argument checks,
-        # two logging decorators), the side stream made current ONCE for the thread, the slot views cut beforehand.
-        pg = self.group if self.group is not None else dist.distributed_c10d._get_default_group()
-        if self._cuda:
-            torch.cuda.set_device(self.device)
-            torch.cuda.set_stream(self._side)
-        opts = dist.AllreduceOptions()
-        opts.reduceOp = dist.ReduceOp.SUM
-        while True:
-            item = self._q.get()
-            if item is None:
-                return
-            s, count = item
-            try:
-                if self._cuda:
-                    self._side.wait_event(self._events[s])
-                w = pg.allreduce([self.ring[s:s + count]], opts)
-                for k in range(count):
-                    self._works[s + k] = w                    # (every slot of the window waits on the same handle)
-                self._collectives += 1
-            except BaseException as exc:                      # noqa: BLE001  (handed to the reader)
-                self._error = exc
-            finally:
-                for k in range(count):
-                    self._issued[s + k].set()
-
-    def _settle(self, s: int) -> None:
-        """The collective that last used slot ``s`` has been issued and the CURRENT stream is ordered behind its completion."""
-        self._issued[s].wait()
-        if self._error is not None:
-            raise RuntimeError("the energy all-reduce failed in the helper thread") from self._error
-        w = self._works[s]
-        if w is not None:
-            if not w.is_completed():                          # (a finished collective needs no wait on the calling stream)
-                w.wait()                                      # (RCCL: stream-side; gloo: the host waits)
-            w0 = s - s % self.every                           # (every slot of a window shares the handle: one wait serves them all)
-            for k in range(w0, w0 + self.every):
-                if self._works[k] is w:
-                    self._works[k] = None
-
-    # ---- training thread ----
     def reserve(self) -> tuple[int, torch.Tensor]:
         """A ticket and its ring slot (a one-element view): the caller has the local energy written there ON THE CURRENT STREAM --
         a replay does it itself, ``tsamd_graph_launch_to`` -- and then calls :meth:`commit`."""
-        if self._cxx is not None:
-            return self._cxx.reserve()
-        t = self._next
-        self._next += 1
-        s = t % self.depth
-        if self._ticket_of_slot[s] >= 0:
-            self._settle(s)                                   # (depth tickets old: long done; orders the overwrite behind it)
-        self._ticket_of_slot[s] = t
-        return t, self._slots[s]
+        return self._cxx.reserve()
 
     def commit(self, ticket: int) -> None:
         """Tickets are committed in the order they were reserved.  With ``every`` > 1 the collective covers the slots of a window
         and goes out with the window's last ticket."""
-        if self._cxx is not None:
-            return self._cxx.commit(ticket)
-        if ticket != self._committed:
-            raise RuntimeError("tickets are committed in the order they were reserved")
-        self._committed += 1
-        if self._committed % self.every == 0:
-            self._issue(self._issued_upto, self._committed - self._issued_upto)
+        self._cxx.commit(ticket)
 
     def flush(self) -> None:
         """The all-reduce of the committed part of the current window now (a collective: every rank, at the same ticket)."""
-        if self._cxx is not None:
-            return self._cxx.flush()
-        if self._committed > self._issued_upto:
-            self._issue(self._issued_upto, self._committed - self._issued_upto)
-
-    def _issue(self, first: int, count: int) -> None:
-        self._issued_upto = first + count
-        if not self._active:
-            return
-        s0 = first % self.depth
-        for k in range(count):
-            self._issued[s0 + k].clear()
-        if self._cuda:
-            self._events[s0].record(torch.cuda.current_stream(self.device))
-        if self._thread is None:
-            self._thread = threading.Thread(target=self._worker, name="tssplat_amd-energy-allreduce", daemon=True)
-            self._thread.start()
-        self._q.put((s0, count))
+        self._cxx.flush()
 
     def submit(self, local_energy: torch.Tensor) -> int:
         t, slot = self.reserve()
@@ -357,36 +261,14 @@ class OverlappedEnergyAllReduce:
 
     def value(self, ticket: int) -> torch.Tensor:
         """Job-wide energy of ``ticket`` (0-dim, a fresh tensor)."""
-        if self._cxx is not None:
-            return self._cxx.value(ticket)
-        if not 0 <= ticket < self._next:
-            raise ValueError(f"unknown ticket {ticket}")
-        s = ticket % self.depth
-        if self._ticket_of_slot[s] != ticket:
-            raise RuntimeError(f"the job-wide energy of evaluation {ticket} has expired: {self._next - ticket} evaluations ago, the ring keeps "
-                               f"{self.depth} (read it sooner, or build the module with a larger `depth`)")
-        if ticket >= self._issued_upto:
-            raise RuntimeError(f"the job-wide energy of evaluation {ticket} is not on its way yet: with every = {self.every} the all-reduce of a "
-                               f"window is issued with its last evaluation ({self._issued_upto} evaluations are covered so far).  Read it later, "
-                               "call flush() on EVERY rank, or build the module with every = 1")
-        self._settle(s)
-        return self.ring[s].clone()
+        return self._cxx.value(ticket)
 
     def drain(self) -> None:
         """Every collective submitted so far has been issued and the current stream is ordered behind all of them."""
-        if self._cxx is not None:
-            return self._cxx.drain()
-        for s in range(self.depth):
-            if 0 <= self._ticket_of_slot[s] < self._issued_upto:
-                self._settle(s)
+        self._cxx.drain()
 
     def close(self) -> None:
-        if self._cxx is not None:
-            self._cxx.close()
-        if self._thread is not None:
-            self._q.put(None)
-            self._thread.join(timeout=10)
-            self._thread = None
+        self._cxx.close()
 
     def __del__(self):
         try:
