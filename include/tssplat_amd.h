@@ -378,6 +378,34 @@ int tsamd_antialias_backward(const float *color_dev, const float *rast_dev, cons
                              int32_t n_channels, const float *grad_out_dev, float pos_gradient_boost, float *grad_color_dev, float *grad_pos_dev,
                              void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Hash-grid encoding (the texture stage's colour field): tiny-cuda-nn's `Grid` encoding, 3-D input, trilinear,
+ *   tsamd_grid_encode          <- tcnn.Encoding(3, {"otype": "HashGrid" | "DenseGrid" | "Grid", ...})(x)   models/networks.py:97-106
+ *   tsamd_grid_encode_backward <- its backward w.r.t. the parameters and (optionally) x
+ * Semantics (Instant-NGP, Mueller et al. 2022, as tiny-cuda-nn's published grid.h states them) are fixed by
+ * tests/hashgrid_oracle.py; PARITY UNPINNED against the library itself.  Config: n_levels 1 .. 32, n_features_per_level in
+ * {1, 2, 4, 8}, log2_hashmap_size 1 .. 30, base_resolution >= 1, per_level_scale >= 1, dense 0 (Hash: levels above
+ * 2^log2_hashmap_size entries are hashed) or 1 (Dense: no cap).  x_dev: [n_points, 3] f32 (not clamped); params_dev:
+ * [n_params] f32, level-major, n_features_per_level contiguous values per entry; out_dev / grad_out_dev: [n_points,
+ * n_levels * n_features_per_level] f32, level-major columns.  params_dev, out_dev, grad_out_dev and grad_params_dev must be
+ * aligned to one entry's vector (4, 8 or 16 bytes).  Stateless; the current HIP device is used.
+ *
+ * tsamd_grid_layout (host only): per-level first entry (offsets_out, n_levels + 1 values, the last = total entries),
+ * resolution, hashed flag (1 = prime hash, 0 = dense index) and float32 scale, and the parameter count.  Each output may be NULL.
+ * tsamd_grid_encode_backward ADDS dL/dparams into grad_params_dev (zero it first; NULL: not computed; a float-atomic sum,
+ * not bitwise repeatable) and WRITES dL/dx into grad_x_dev ([n_points, 3], NULL: not computed).  The forward and dL/dx are
+ * bitwise repeatable. */
+int tsamd_grid_layout(int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size, int32_t base_resolution,
+                      float per_level_scale, int32_t dense, int64_t *offsets_out, int32_t *resolution_out, int32_t *hashed_out,
+                      float *scale_out, int64_t *n_params_out);
+int tsamd_grid_encode(const float *x_dev, int64_t n_points, const float *params_dev, int32_t n_levels, int32_t n_features_per_level,
+                      int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, int32_t dense, float *out_dev,
+                      void *stream);
+int tsamd_grid_encode_backward(const float *x_dev, int64_t n_points, const float *params_dev, int32_t n_levels,
+                               int32_t n_features_per_level, int32_t log2_hashmap_size, int32_t base_resolution,
+                               float per_level_scale, int32_t dense, const float *grad_out_dev, float *grad_params_dev,
+                               float *grad_x_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

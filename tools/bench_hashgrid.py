@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""The texture stage's hash-grid encoding on one GPU: the HIP kernels (tssplat_amd.encoding) against a plain-torch restatement of
+the same semantics (gathers + index_add_, kept here and not in the product), forward and forward + backward (dL/dparams).
+
+Workloads, both with the default ExplicitMaterial config (16 levels, F = 2, T = 2^19, base 16):
+  texture  the foreground pixels, in pixel order, of tests/golden/mario_mesh.npz under scenes.dataset_mvps(views) at res^2,
+           mapped into [0, 1]^3 as contract_to_unisphere does;
+  random   as many uniform random points in [0, 1]^3 (the worst case: no two neighbouring lanes share a cell).
+
+    python tools/bench_hashgrid.py [--views 120 --res 512 --reps 10]
+
+One JSON line per workload: Mpoints/s, ms, the gather and atomic-add bytes per second, the speed-up, the torch path's per-level
+split and the largest difference between the two paths.  Byte counts are nominal (8 corners x F x 4 B per point and level)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DEFAULT = {"otype": "HashGrid", "n_levels": 16, "n_features_per_level": 2, "log2_hashmap_size": 19, "base_resolution": 16,
+           "per_level_scale": 1.447269237440378}
+PRIMES = (1, 2654435761, 805459861)
+
+
+def texture_points(views: int, res: int) -> torch.Tensor:
+    from tssplat_amd import dr, scenes
+    m = np.load(os.path.join(ROOT, "tests", "golden", "mario_mesh.npz"))
+    v = torch.from_numpy(m["vertices"].astype(np.float32)).cuda()
+    tri = torch.from_numpy(m["faces"].astype(np.int32)).cuda()
+    mvp = torch.from_numpy(scenes.dataset_mvps(views).astype(np.float32)).cuda()
+    pos = torch.matmul(torch.cat([v, torch.ones_like(v[:, :1])], 1), mvp.transpose(1, 2)).contiguous()
+    rast, _ = dr.rasterize(dr.RasterizeCudaContext(), pos, tri, resolution=[res, res], grad_db=False)
+    p, _ = dr.interpolate(v[None], rast, tri)
+    return ((p[rast[..., 3] > 0] + 1) * 0.5).contiguous()
+
+
+class TorchGrid:
+    """The encoding restated with torch ops: per level, 8 corner indices (int64 arithmetic masked to uint32), gathers, weights;
+    backward = index_add_ of weight x dL/dy into the table."""
+
+    def __init__(self, layout, F):
+        self.lay, self.F = layout, F
+
+    def corners(self, x, l):
+        M = 0xFFFFFFFF
+        scale = float(self.lay["scale"][l])
+        pos = torch.addcmul(torch.full_like(x, 0.5), x, torch.full_like(x, scale))
+        fl = torch.floor(pos)
+        cell = fl.to(torch.int64) & M
+        frac = pos - fl
+        res, entries, hashed = int(self.lay["res"][l]), int(self.lay["offset"][l + 1] - self.lay["offset"][l]), bool(self.lay["is_hash"][l])
+        out = []
+        for c in range(8):
+            b = [(c >> d) & 1 for d in range(3)]
+            cx, cy, cz = [(cell[:, d] + b[d]) & M for d in range(3)]
+            if hashed:
+                i = (cx * PRIMES[0] & M) ^ (cy * PRIMES[1] & M) ^ (cz * PRIMES[2] & M)
+            else:
+                i = (cx + cy * res + (cz * ((res * res) & M) & M)) & M
+            w = torch.ones_like(frac[:, 0])
+            for d in range(3):
+                w = w * (frac[:, d] if b[d] else 1.0 - frac[:, d])
+            out.append((i % entries + int(self.lay["offset"][l]), w))
+        return out
+
+    def forward(self, x, P, levels=None):
+        Pv = P.view(-1, self.F)
+        cols, saved = [], []
+        for l in (range(len(self.lay["res"])) if levels is None else levels):
+            acc = torch.zeros(x.shape[0], self.F, device=x.device)
+            cs = self.corners(x, l)
+            for i, w in cs:
+                acc += w[:, None] * Pv.index_select(0, i)
+            cols.append(acc)
+            saved.append((l, cs))
+        return torch.cat(cols, 1), saved
+
+    def backward(self, saved, g, n_params):
+        gP = torch.zeros(n_params // self.F, self.F, device=g.device)
+        for k, (l, cs) in enumerate(saved):
+            gl = g[:, k * self.F:(k + 1) * self.F]
+            for i, w in cs:
+                gP.index_add_(0, i, w[:, None] * gl)
+        return gP.view(-1)
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def bench(name, x, reps):
+    from tssplat_amd import encoding
+    enc = encoding.GridEncoding(3, DEFAULT).cuda()
+    with torch.no_grad():
+        enc.params.uniform_(-1, 1)
+    lay = enc.layout
+    F, L = 2, 16
+    N = int(x.shape[0])
+    g = torch.randn(N, L * F, device="cuda")
+    tg = TorchGrid(lay, F)
+
+    def hip_fwd():
+        with torch.no_grad():
+            return enc(x)
+
+    def hip_fb():
+        enc.params.grad = None
+        enc(x).backward(g)
+
+    def torch_fwd():
+        with torch.no_grad():
+            return tg.forward(x, enc.params)[0]
+
+    def torch_fb():
+        with torch.no_grad():
+            y, saved = tg.forward(x, enc.params)
+            return tg.backward(saved, g, lay["n_params"])
+
+    t_hf, t_hfb = timed(hip_fwd, reps), timed(hip_fb, reps)
+    t_tf, t_tfb = timed(torch_fwd, max(1, reps // 5)), timed(torch_fb, max(1, reps // 5))
+    levels = {}
+    for l in range(L):
+        levels[l] = round(timed(lambda: tg.forward(x, enc.params, levels=[l]), 1), 3)
+    y_h, y_t = hip_fwd(), torch_fwd()
+    hip_fb()
+    gp_t = torch_fb()
+    gather = N * L * 8 * F * 4
+    rec = {
+        "workload": name, "points": N, "reps": reps,
+        "hip_fwd_ms": round(t_hf, 3), "hip_fwd_bwd_ms": round(t_hfb, 3), "hip_bwd_ms": round(t_hfb - t_hf, 3),
+        "torch_fwd_ms": round(t_tf, 3), "torch_fwd_bwd_ms": round(t_tfb, 3),
+        "speedup_fwd": round(t_tf / t_hf, 2), "speedup_fwd_bwd": round(t_tfb / t_hfb, 2),
+        "hip_fwd_mpoints_per_s": round(N / t_hf / 1e3, 1), "hip_fwd_bwd_mpoints_per_s": round(N / t_hfb / 1e3, 1),
+        "hip_fwd_gather_tb_per_s": round(gather / t_hf / 1e9, 3),
+        "hip_bwd_nominal_atomic_tb_per_s": round(gather / max(t_hfb - t_hf, 1e-6) / 1e9, 3),
+        "guide_ceilings_tb_per_s": {"atomic_add_f32_256B_rows": 1.3, "atomic_add_f32_64_rows_per_wave": 0.08, "random_row_gather_mall": 8.6},
+        "torch_fwd_ms_per_level": levels,
+        "max_abs_diff_fwd": float((y_h - y_t).abs().max()),
+        "max_abs_diff_dparams": float((enc.params.grad - gp_t).abs().max()),
+        "max_abs_dparams": float(gp_t.abs().max()),
+    }
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--views", type=int, default=120)
+    ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    pts = texture_points(a.views, a.res)
+    recs = [bench(f"texture_{a.views}x{a.res}", pts, a.reps)]
+    g = torch.Generator(device="cuda").manual_seed(0)
+    recs.append(bench("random_unit_cube", torch.rand(pts.shape[0], 3, device="cuda", generator=g), a.reps))
+    for r in recs:
+        print(json.dumps(r))
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(recs, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()

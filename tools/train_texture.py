@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""The reference's texture stage (trainer.py:44-49,56,102-104) on this package: geometry frozen, ExplicitMaterial (hash grid +
+VanillaMLP) as the renderer's materials, `L1Loss` on RGB x 20, AdamUniform over renderer.parameters().  The targets are rendered
+here from a known colour field on tests/golden/mario_mesh.npz under scenes.dataset_mvps(views) (the reference's img_data/ is
+empty).
+
+    python tools/train_texture.py [--views 16 --res 256 --iters 300 --lr 0.01]
+
+One JSON line: the loss at the first and last iteration, ms per iteration, and the split of one iteration's forward + backward
+into encode (hash grid), MLP and the rest (rasterise, interpolate, antialias, loss), timed stage by stage on the same points."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+class Field(torch.nn.Module):
+    """The known colour field the targets are rendered from."""
+
+    def forward(self, positions):
+        return {"color": 0.5 + 0.5 * torch.sin(torch.stack([3.0 * positions[..., 0] + 1.0, 4.0 * positions[..., 1],
+                                                             5.0 * positions[..., 2] - 0.5], -1))}
+
+
+def timed(fn, reps=5):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def run(views=16, res=256, iters=300, lr=0.01):
+    from tssplat_amd import geometry, materials, renderers, scenes
+    from tssplat_amd.utils.optimizer import AdamUniform
+    torch.cuda.set_device(0)
+    m = np.load(os.path.join(ROOT, "tests", "golden", "mario_mesh.npz"))
+    v, f = m["vertices"].astype(np.float32), m["faces"].astype(np.int32)
+    geo = geometry.TetMeshGeometry(v, np.zeros((0, 4), np.int32), use_smooth_barrier=False, optimize_geo=False,
+                                   surface_vid=np.arange(v.shape[0], dtype=np.int32), surface_fid=f)
+    mvp = torch.from_numpy(scenes.dataset_mvps(views).astype(np.float32)).cuda()
+    bg = torch.ones(views, res, res, 3, device="cuda")
+    with torch.no_grad():
+        target = renderers.MeshRasterizer(geo, Field())(mvp, only_alpha=False, iter_num=0, resolution=res, background=bg)["shaded"].clone()
+    torch.manual_seed(0)
+    mat = materials.ExplicitMaterial({"n_output_dims": 3, "material_activation": "sigmoid"})
+    ren = renderers.MeshRasterizer(geo, mat)
+    opt = AdamUniform(ren.parameters(), lr=lr)
+    loss_fn = torch.nn.L1Loss()
+
+    def step(it):
+        out = ren(mvp, only_alpha=False, iter_num=it, resolution=res, background=bg)
+        loss = loss_fn(out["shaded"][..., :3], target[..., :3]) * 20           # trainer.py:102-104
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        return loss
+
+    losses = []
+    step(0)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for it in range(iters):
+        losses.append(step(it).detach())
+    b.record()
+    torch.cuda.synchronize()
+    ms_iter = a.elapsed_time(b) / iters
+    losses = [float(l) for l in losses]
+
+    # stage split on the same foreground points
+    with torch.no_grad():
+        from tssplat_amd import dr
+        pos_clip = ren.transform_pos(mvp, geo.tet_v).contiguous()
+        rast, _ = dr.rasterize(ren.glctx, pos_clip, geo.surface_fid, resolution=[res, res], grad_db=False)
+        p, _ = dr.interpolate(geo.tet_v[None], rast, geo.surface_fid)
+        pts = materials.contract_to_unisphere(p[rast[..., 3] > 0], mat.bbox).contiguous()
+    enc, mlp = mat.encoding, mat.feature_network
+    e = enc(pts).detach()
+    ge = torch.randn_like(e)
+    gm = torch.randn(pts.shape[0], 3, device="cuda")
+
+    def enc_fb():
+        enc(pts).backward(ge)
+
+    def mlp_fb():
+        mlp(e.requires_grad_(True)).backward(gm)
+    ms_enc, ms_mlp = timed(enc_fb), timed(mlp_fb)
+    return {"views": views, "res": res, "iters": iters, "lr": lr, "foreground_points": int(pts.shape[0]),
+            "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)], "loss_ratio": round(losses[-1] / losses[0], 4),
+            "ms_per_iter": round(ms_iter, 3),
+            "split_ms": {"encode_fwd_bwd": round(ms_enc, 3), "mlp_fwd_bwd": round(ms_mlp, 3),
+                         "render_loss_optimizer_rest": round(ms_iter - ms_enc - ms_mlp, 3)}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--views", type=int, default=16)
+    ap.add_argument("--res", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--lr", type=float, default=0.01)
+    a = ap.parse_args()
+    print(json.dumps(run(a.views, a.res, a.iters, a.lr)))
+
+
+if __name__ == "__main__":
+    main()

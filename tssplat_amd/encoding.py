@@ -1,0 +1,137 @@
+"""Multiresolution hash-grid encoding on the gfx950 kernels (csrc/grid_kernels.hip): the colour field's input encoding of the
+texture stage (/root/reference/materials/explicit_material.py, models/networks.py:97-106, ``tcnn.Encoding``).
+
+Semantics: tiny-cuda-nn's ``Grid`` encoding (Instant-NGP, Mueller et al. 2022) as tests/hashgrid_oracle.py restates it --
+PARITY UNPINNED against the library itself (CUDA only, not available here).  ``params`` holds the table in tiny-cuda-nn's
+layout (level-major, ``n_features_per_level`` contiguous fp32 values per entry); the per-level layout comes from the library's
+own host function (``tsamd_grid_layout``), so the Python and C layouts cannot drift apart.
+
+What it does not do, loudly: ``Tiled`` grids, ``Nearest`` / ``Smoothstep`` interpolation, inputs other than 3-D,
+``n_features_per_level`` outside {1, 2, 4, 8}, more than 32 levels, half precision, CPU tensors.  The initial parameters are
+uniform in [-1e-4, 1e-4] from a torch generator seeded with ``seed`` (tiny-cuda-nn's range; its PRNG stream is not reproduced).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _capi
+from .tet_spheres_ext import _device_ctx, _stream_ptr
+
+__all__ = ["GridEncoding", "parse_grid_config", "grid_layout"]
+
+_lib = _capi.load()
+
+_OTYPES = {"hashgrid": "Hash", "densegrid": "Dense", "grid": None}
+
+
+def parse_grid_config(n_input_dims: int, config: dict) -> dict:
+    """The accepted ``tcnn.Encoding`` grid configs, normalised; ValueError on anything else."""
+    cfg = dict(config)
+    otype = str(cfg.get("otype", "")).lower()
+    if otype not in _OTYPES:
+        raise ValueError(f"tssplat_amd encoding: otype {cfg.get('otype')!r} is not offered (HashGrid, DenseGrid, Grid only)")
+    gtype = _OTYPES[otype] or str(cfg.get("type", "Hash"))
+    if gtype not in ("Hash", "Dense"):
+        raise ValueError(f"tssplat_amd encoding: grid type {gtype!r} is not offered (Hash or Dense; Tiled is not)")
+    if n_input_dims != 3:
+        raise ValueError(f"tssplat_amd encoding: n_input_dims = {n_input_dims}: only 3-D inputs are offered")
+    interp = cfg.get("interpolation", "Linear")
+    if interp != "Linear":
+        raise ValueError(f"tssplat_amd encoding: interpolation {interp!r} is not offered (Linear only)")
+    out = {
+        "n_levels": int(cfg.get("n_levels", 16)),
+        "n_features_per_level": int(cfg.get("n_features_per_level", 2)),
+        "log2_hashmap_size": int(cfg.get("log2_hashmap_size", 19)),
+        "base_resolution": int(cfg.get("base_resolution", 16)),
+        "per_level_scale": float(cfg.get("per_level_scale", 2.0)),
+        "dense": gtype == "Dense",
+    }
+    if out["n_features_per_level"] not in (1, 2, 4, 8):
+        raise ValueError(f"tssplat_amd encoding: n_features_per_level = {out['n_features_per_level']} (1, 2, 4 or 8 only)")
+    return out
+
+
+def _args(cfg: dict) -> tuple:
+    return (cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"], cfg["base_resolution"],
+            C.c_float(cfg["per_level_scale"]), int(cfg["dense"]))
+
+
+def grid_layout(cfg: dict) -> dict:
+    """Per-level first entry (``offset``, L + 1 values), ``res``, ``is_hash``, float32 ``scale`` and ``n_params`` (tsamd_grid_layout)."""
+    L = cfg["n_levels"]
+    off = np.zeros(L + 1, np.int64)
+    res = np.zeros(L, np.int32)
+    hashed = np.zeros(L, np.int32)
+    scale = np.zeros(L, np.float32)
+    n = C.c_int64(0)
+    _capi.check(_lib.tsamd_grid_layout(*_args(cfg), off.ctypes.data, res.ctypes.data, hashed.ctypes.data, scale.ctypes.data, C.byref(n)))
+    return {"offset": off, "res": res, "is_hash": hashed.astype(bool), "scale": scale, "n_params": int(n.value)}
+
+
+def _check_input(x: torch.Tensor, n_input_dims: int) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("tssplat_amd encoding: x must be a GPU tensor (there is no CPU fallback)")
+    if x.dtype != torch.float32:
+        raise RuntimeError("tssplat_amd encoding: x must be float32")
+    if x.dim() != 2 or x.shape[1] != n_input_dims:
+        raise RuntimeError(f"tssplat_amd encoding: x must be [N, {n_input_dims}], got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+class _GridEncodeFunc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, params, cfg, n_output_dims):
+        N = int(x.shape[0])
+        out = torch.empty((N, n_output_dims), dtype=torch.float32, device=x.device)
+        with _device_ctx(x.device):
+            _capi.check(_lib.tsamd_grid_encode(x.data_ptr(), N, params.data_ptr(), *_args(cfg), out.data_ptr(), _stream_ptr(x.device)))
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, params)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, params = ctx.saved_tensors
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_p):
+            return None, None, None, None
+        g = grad_out.contiguous()
+        N = int(x.shape[0])
+        grad_p = torch.zeros_like(params) if need_p else None
+        grad_x = torch.empty_like(x) if need_x else None
+        with _device_ctx(x.device):
+            _capi.check(_lib.tsamd_grid_encode_backward(x.data_ptr(), N, params.data_ptr(), *_args(ctx.cfg), g.data_ptr(),
+                                                        None if grad_p is None else grad_p.data_ptr(),
+                                                        None if grad_x is None else grad_x.data_ptr(), _stream_ptr(x.device)))
+        return grad_x, grad_p, None, None
+
+
+class GridEncoding(torch.nn.Module):
+    """``tcnn.Encoding(3, grid_config)``: ``forward(x [N, 3] fp32 on the GPU) -> [N, n_levels * n_features_per_level]``."""
+
+    def __init__(self, n_input_dims: int, config: dict, seed: int = 1337):
+        super().__init__()
+        self.cfg = parse_grid_config(n_input_dims, config)
+        self.layout = grid_layout(self.cfg)
+        self.n_input_dims = n_input_dims
+        self.n_output_dims = self.cfg["n_levels"] * self.cfg["n_features_per_level"]
+        gen = torch.Generator().manual_seed(int(seed))
+        init = torch.rand(self.layout["n_params"], generator=gen, dtype=torch.float32) * 2e-4 - 1e-4
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.params = torch.nn.Parameter(init.to(dev))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = _check_input(x, self.n_input_dims)
+        if not self.params.is_cuda or self.params.device != x.device:
+            raise RuntimeError("tssplat_amd encoding: params and x must live on the same GPU")
+        return _GridEncodeFunc.apply(x, self.params, self.cfg, self.n_output_dims)
+
+    def extra_repr(self) -> str:
+        c = self.cfg
+        return (f"{'Dense' if c['dense'] else 'Hash'}, n_levels={c['n_levels']}, F={c['n_features_per_level']}, "
+                f"log2_T={c['log2_hashmap_size']}, base={c['base_resolution']}, per_level_scale={c['per_level_scale']:.6g}, "
+                f"n_params={self.layout['n_params']}")
+
