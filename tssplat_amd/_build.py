@@ -20,9 +20,9 @@ LIB = os.path.join(_HERE, "libtssplat_amd.so")
 _OBJ = os.path.join(_HERE, "_obj")
 ARCH = "gfx950"
 
-SOURCES = ["plan.cpp", "conflict_opt.cpp", "capi.cpp", "kernels.hip", "surface.cpp", "surface_capi.cpp", "surface_kernels.hip",
+SOURCES = ["plan.cpp", "partition.cpp", "conflict_opt.cpp", "capi.cpp", "kernels.hip", "surface.cpp", "surface_capi.cpp", "surface_kernels.hip",
            "raster_capi.cpp", "raster_kernels.hip", "aa_kernels.hip", "grid_capi.cpp", "grid_kernels.hip"]
-HEADERS = ["plan.h", "conflict_opt.h", "kernels.h", "surface.h", "raster.h", "grid.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
+HEADERS = ["plan.h", "partition.h", "conflict_opt.h", "kernels.h", "surface.h", "raster.h", "grid.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
 
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-pthread"]
 # -fno-slp-vectorize: SLP packs the 3x3 algebra into v_pk_*_f32, which runs at the scalar-fp32 rate on
@@ -58,7 +58,7 @@ def traffic_digest() -> str:
     tools/summarize_prof.py stamps profiles/traffic.json with it when it condenses the rocprofv3 PMC passes; bench.py reports
     ``roofline.traffic`` only while the stamp matches the sources it runs."""
     h = hashlib.sha256()
-    for name in ("kernels.hip", "plan.cpp", "plan.h"):
+    for name in ("kernels.hip", "plan.cpp", "plan.h", "partition.cpp"):
         with open(os.path.join(CSRC, name), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

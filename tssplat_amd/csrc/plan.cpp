@@ -1,6 +1,6 @@
 // Host-side construction of the tiling plan: face adjacency, connected
 // components (= tet-spheres), recursive coordinate bisection into LDS-sized
-// tiles with a one-ring face halo, per-tile local indexing, and the staging /
+// tiles with a one-ring face halo (re-cut into compact cells by partition.cpp), per-tile local indexing, and the staging /
 // finish lists for vertices that more than one tile touches.
 //
 // Replaces the role of libpgo in the reference's constructor
@@ -11,6 +11,7 @@
 #include "plan.h"
 
 #include "conflict_opt.h"
+#include "partition.h"
 
 #include <algorithm>
 #include <atomic>
@@ -147,58 +148,10 @@ int build_adjacency(const int32_t *tets, int64_t n, int64_t m, std::vector<int32
     return OK;
 }
 
-namespace {
-
-// per-worker scratch with O(1) reset through stamps
-struct Scratch {
-    std::vector<int32_t> tet_stamp, tet_slot, vert_stamp, vert_local;
-    int32_t stamp = 0;
-    void init(int64_t m, int64_t n)
-    {
-        if (int64_t(tet_stamp.size()) != m) {
-            tet_stamp.assign(size_t(m), 0);
-            tet_slot.assign(size_t(m), 0);
-        }
-        if (int64_t(vert_stamp.size()) != n) {
-            vert_stamp.assign(size_t(n), 0);
-            vert_local.assign(size_t(n), 0);
-        }
-    }
-    int32_t next()
-    {
-        if (stamp > std::numeric_limits<int32_t>::max() - 8) {
-            std::fill(tet_stamp.begin(), tet_stamp.end(), 0);
-            std::fill(vert_stamp.begin(), vert_stamp.end(), 0);
-            stamp = 0;
-        }
-        stamp += 2;
-        return stamp;  // `stamp` marks owned, `stamp+1` marks halo
-    }
-};
-
-struct Limits {
-    int64_t budget;
-    int64_t max_spad;
-    int64_t pad_unit = 4;
-    bool rebuild = false;
-    bool fits(int64_t n_slots, int64_t n_verts) const
-    {
-        const int64_t sp = (n_slots + pad_unit - 1) / pad_unit * pad_unit;
-        return sp <= max_spad && n_verts <= kMaxTileVerts && tile_lds_bytes(sp, n_verts, rebuild) <= budget;
-    }
-};
-
-struct Mesh {
-    const float *rest;
-    const int32_t *tets;
-    const int32_t *nbr;
-    int64_t n, m;
-};
-
 // owned + one-ring halo size and the number of tile vertices they touch (a vertex met by more than kMaxRank slots of
 // the tile is split into several tile vertices of at most kMaxRank slots each, see build_plan)
 void measure(const Mesh &M, const int32_t *owned, int64_t cnt, Scratch &S, int64_t &n_slots, int64_t &n_verts,
-             std::vector<int32_t> *halo_out = nullptr)
+             std::vector<int32_t> *halo_out)
 {
     const int32_t so = S.next(), sh = so + 1;
     for (int64_t i = 0; i < cnt; ++i) S.tet_stamp[owned[i]] = so;
@@ -233,6 +186,8 @@ void measure(const Mesh &M, const int32_t *owned, int64_t cnt, Scratch &S, int64
     n_slots = cnt + halo;
     n_verts = verts;
 }
+
+namespace {
 
 inline uint32_t spread10(uint32_t v)
 {
@@ -586,6 +541,7 @@ int build_plan(const float *rest, int64_t n, const int32_t *tets, int64_t m, con
     target = std::max<int64_t>(1, target);
 
     std::vector<std::vector<std::vector<int32_t>>> group_tiles(groups.size());
+    std::vector<uint8_t> group_fitted(groups.size(), 0);   // the bisection found the fewest parts that fit (strict)
     std::atomic<int> first_rc{0};
     std::string split_err;
     std::atomic<bool> err_set{false};
@@ -615,6 +571,7 @@ int build_plan(const float *rest, int64_t n, const int32_t *tets, int64_t m, con
                     k = std::max<int64_t>(k + 1, (k * 103 + 99) / 100);
                 }
                 if (!done) group_tiles[size_t(g)].clear();
+                group_fitted[size_t(g)] = done ? 1 : 0;
             }
             sp.strict = false;
             sp.failed = false;
@@ -632,6 +589,54 @@ int build_plan(const float *rest, int64_t n, const int32_t *tets, int64_t m, con
     }
 
     timer.lap("bisection");
+    // ---- partition: compact cells with fewer halo slots (partition.cpp) where the bisection found a strict fit ----
+    // k runs upward from the bisection's slots over the slot capacity, at most four values and never past the bisection's own
+    // count; the cells replace the bisection's leaves when there are fewer of them, or as many at a lower cost
+    // (kPartSlotWeight * slots + tile vertices).  Otherwise the bisection stands: the plan is never worse than it.  No cell may
+    // need more LDS than the largest tile of the bisection, so the launch (dynamic LDS, workgroups per CU) stays as it was.
+    std::vector<int64_t> rcb_slots(groups.size(), 0), rcb_cost(groups.size(), 0), rcb_lds(groups.size(), 0);
+    parallel_chunks(int64_t(groups.size()), 16, nthreads, [&](int64_t b, int64_t e, int w) {
+        Scratch &S = get_scratch(w);
+        for (int64_t g = b; g < e; ++g)
+            for (const auto &l : group_tiles[size_t(g)]) {
+                int64_t ns, nv;
+                measure(M, l.data(), int64_t(l.size()), S, ns, nv);
+                rcb_slots[size_t(g)] += ns;
+                rcb_cost[size_t(g)] += kPartSlotWeight * ns + nv;
+                const int64_t sp = (ns + lim.pad_unit - 1) / lim.pad_unit * lim.pad_unit;
+                rcb_lds[size_t(g)] = std::max(rcb_lds[size_t(g)], tile_lds_bytes(sp, nv, rebuild));
+            }
+    });
+    Limits cell_lim = lim;
+    cell_lim.budget = 0;
+    for (int64_t l : rcb_lds) cell_lim.budget = std::max(cell_lim.budget, std::min(lim.budget, l));
+    std::atomic<int64_t> n_cut{0}, n_refined{0};
+    parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int w) {
+        Scratch &S = get_scratch(w);
+        std::vector<std::vector<int32_t>> parts;
+        for (int64_t g = b; g < e; ++g) {
+            if (!group_fitted[size_t(g)]) continue;
+            const Group &G = groups[size_t(g)];
+            const int32_t *ids = comp_tets.data() + comp_start[G.cb];
+            const int64_t cnt = comp_start[G.ce] - comp_start[G.cb];
+            auto &leaves = group_tiles[size_t(g)];
+            const int64_t k_rcb = int64_t(leaves.size());
+            n_cut.fetch_add(1, std::memory_order_relaxed);
+            const int64_t k_lo = (rcb_slots[size_t(g)] + s_cap - 1) / s_cap;
+            int64_t cost;
+            if (!partition_component(M, cell_lim, cen.data(), ids, cnt, k_lo, std::min(k_rcb, k_lo + 3), S, parts, cost)) continue;
+            if (int64_t(parts.size()) > k_rcb || (int64_t(parts.size()) == k_rcb && cost >= rcb_cost[size_t(g)])) continue;
+            n_refined.fetch_add(1, std::memory_order_relaxed);
+            leaves.clear();
+            std::string unused_err;
+            Splitter sp{M, lim, cen, S, leaves, unused_err};
+            for (auto &part : parts) sp.emit(part.data(), int64_t(part.size()));
+        }
+    });
+    if (timer.on)
+        std::fprintf(stderr, "[plan] partition: %lld cut components, %lld refined, %lld keep the bisection\n", (long long)n_cut.load(),
+                     (long long)n_refined.load(), (long long)(n_cut.load() - n_refined.load()));
+    timer.lap("partition (cells + refinement)");
     std::vector<std::vector<int32_t>> tiles_owned;
     for (auto &gt : group_tiles)
         for (auto &t : gt) tiles_owned.push_back(std::move(t));
