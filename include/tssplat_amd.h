@@ -406,6 +406,42 @@ int tsamd_grid_encode_backward(const float *x_dev, int64_t n_points, const float
                                float per_level_scale, int32_t dense, const float *grad_out_dev, float *grad_params_dev,
                                float *grad_x_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Fully fused MLP (the texture stage's colour MLP when its config names a tcnn network): tiny-cuda-nn's FullyFusedMLP,
+ *   tsamd_mlp_forward  <- tcnn.Network(n_in, n_out, {"otype": "FullyFusedMLP" | "CutlassMLP" | "MLP", ...})(x)   models/networks.py:314-321
+ *   tsamd_mlp_backward <- its backward w.r.t. the parameters and (optionally) x
+ * Semantics are fixed by tests/mlp_oracle.py; PARITY UNPINNED against the library itself.  Config: n_neurons W in {16, 32,
+ * 64, 128}, n_hidden_layers L 1 .. 8, n_input_dims 1 .. 256, n_output_dims 1 .. 64, activation NONE or RELU, output_activation
+ * NONE or SIGMOID.  Bias-free; in_w = next_multiple(n_input_dims, 16), out_w = next_multiple(n_output_dims, 16).  params_dev:
+ * [n_params] f32 = L + 1 row-major [out, in] matrices one after another: [W, in_w], (L - 1) x [W, W], [out_w, W].  Padded input
+ * columns read 1.0 (the first matrix's padded columns act as a bias); padded output rows are computed and discarded.
+ * Forward per row: a0 = fp16(x); a_l = fp16(act(sum_k fp16(W_l[j,k]) a_{l-1}[k])) with fp32 sums; y = out_act(sum_k
+ * fp16(W_out[j,k]) a_L[k]) in fp32, returned as f32 (tiny-cuda-nn returns half).  Backward with the loss scale S = 128 of
+ * tiny-cuda-nn's torch binding: delta_out = fp16(S dy out_act'(z)) (S dy above 65504 is not guarded), delta_l =
+ * fp16((sum_j fp16(W_{l+1}[j,k]) delta_{l+1}[j]) act'(a_l)) with ReLU' = (a_l > 0) on the stored fp16 a_l,
+ * dW_l = (sum over rows of delta_l (x) a_{l-1}) / S in fp32, dx = (sum_j fp16(W_1[j,k]) delta_1[j]) / S.  x_dev: [n_rows,
+ * n_input_dims] f32; y_dev / grad_y_dev: [n_rows, n_output_dims] f32.  Stateless and stream-ordered; the current HIP device is
+ * used; nothing is allocated and the host is never synchronised.  n_rows = 0 is a no-op that needs no device.
+ *
+ * tsamd_mlp_layout (host only): n_params, in_w and out_w (each output may be NULL).
+ * tsamd_mlp_workspace_bytes (host only): the workspace tsamd_mlp_backward needs for n_rows rows when it computes grad_params
+ * (one partial per workgroup, summed in a fixed order); -1 on an invalid config.
+ * tsamd_mlp_backward WRITES dL/dparams into grad_params_dev ([n_params], NULL: not computed) and dL/dx into grad_x_dev
+ * ([n_rows, n_input_dims], NULL: not computed).  No float atomics: y, dx and dW are bitwise repeatable for a given n_rows. */
+#define TSAMD_MLP_ACT_NONE 0
+#define TSAMD_MLP_ACT_RELU 1
+#define TSAMD_MLP_ACT_SIGMOID 2
+int tsamd_mlp_layout(int32_t n_input_dims, int32_t n_output_dims, int32_t n_neurons, int32_t n_hidden_layers, int32_t activation,
+                     int32_t output_activation, int64_t *n_params_out, int32_t *in_width_out, int32_t *out_width_out);
+int64_t tsamd_mlp_workspace_bytes(int64_t n_rows, int32_t n_input_dims, int32_t n_output_dims, int32_t n_neurons,
+                                  int32_t n_hidden_layers, int32_t activation, int32_t output_activation);
+int tsamd_mlp_forward(const float *x_dev, int64_t n_rows, const float *params_dev, int32_t n_input_dims, int32_t n_output_dims,
+                      int32_t n_neurons, int32_t n_hidden_layers, int32_t activation, int32_t output_activation, float *y_dev,
+                      void *stream);
+int tsamd_mlp_backward(const float *x_dev, int64_t n_rows, const float *params_dev, int32_t n_input_dims, int32_t n_output_dims,
+                       int32_t n_neurons, int32_t n_hidden_layers, int32_t activation, int32_t output_activation,
+                       const float *grad_y_dev, float *grad_params_dev, float *grad_x_dev, void *workspace_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,8 +3,9 @@
 
 Same names, same constructor arguments and the same forward arithmetic as the reference; configs are plain dicts (or any
 object with ``.get`` / attribute access, such as an OmegaConf node) instead of the reference's OmegaConf plumbing
-(``config_to_primitive``, networks.py:52-53).  ``tcnn.Encoding`` is the HIP grid encoding; the tcnn-only network routes
-(``TCNNNetwork``, ``TCNNNetworkWithInputEncoding``) raise, as :mod:`tssplat_amd.tcnn` does.
+(``config_to_primitive``, networks.py:52-53).  ``tcnn.Encoding`` is the HIP grid encoding; the tcnn network routes
+(``TCNNNetwork``, ``TCNNNetworkWithInputEncoding``) run the HIP fused MLP for otypes FullyFusedMLP / CutlassMLP / MLP and raise
+for other otypes, as :mod:`tssplat_amd.tcnn` does.
 """
 from __future__ import annotations
 
@@ -18,7 +19,8 @@ import torch.nn.functional as F
 from . import tcnn
 
 __all__ = ["get_activation", "get_encoding", "get_mlp", "scale_tensor", "TCNNEncoding", "ProgressiveBandHashGrid",
-           "ProgressiveBandFrequency", "CompositeEncoding", "VanillaMLP", "SphereInitVanillaMLP"]
+           "ProgressiveBandFrequency", "CompositeEncoding", "VanillaMLP", "SphereInitVanillaMLP", "TCNNNetwork",
+           "NetworkWithInputEncoding", "TCNNNetworkWithInputEncoding", "create_network_with_input_encoding", "ToDTypeWrapper"]
 
 
 def _get(config, key, default=None):
@@ -235,15 +237,76 @@ class SphereInitVanillaMLP(nn.Module):
         return nn.Softplus(beta=100)
 
 
+class TCNNNetwork(nn.Module):
+    """networks.py:314-321: ``tcnn.Network`` (the HIP fused MLP), output cast to float32."""
+
+    def __init__(self, dim_in: int, dim_out: int, config: dict) -> None:
+        super().__init__()
+        with torch.cuda.device(_rank()):
+            self.network = tcnn.Network(dim_in, dim_out, config)
+
+    def forward(self, x):
+        return self.network(x).float()
+
+
 def get_mlp(n_input_dims, n_output_dims, config) -> nn.Module:
-    """networks.py:324-339; the tcnn route (``TCNNNetwork``) raises through tssplat_amd.tcnn.Network."""
+    """networks.py:324-339; the tcnn route is ``TCNNNetwork`` (the HIP fused MLP; otypes other than FullyFusedMLP /
+    CutlassMLP / MLP raise through tssplat_amd.tcnn.Network)."""
     otype = _get(config, "otype")
     if otype == "VanillaMLP":
         return VanillaMLP(n_input_dims, n_output_dims, _primitive(config))
     if otype == "SphereInitVanillaMLP":
         return SphereInitVanillaMLP(n_input_dims, n_output_dims, _primitive(config))
     assert _get(config, "sphere_init", False) is False, "sphere_init=True only supported by VanillaMLP"
-    return tcnn.Network(n_input_dims, n_output_dims, _primitive(config))
+    return TCNNNetwork(n_input_dims, n_output_dims, _primitive(config))
+
+
+class NetworkWithInputEncoding(nn.Module):
+    """networks.py:342-348."""
+
+    def __init__(self, encoding, network):
+        super().__init__()
+        self.encoding, self.network = encoding, network
+
+    def forward(self, x):
+        return self.network(self.encoding(x))
+
+
+class TCNNNetworkWithInputEncoding(nn.Module):
+    """networks.py:351-371: ``tcnn.NetworkWithInputEncoding`` (grid encoding + HIP fused MLP), output cast to float32."""
+
+    def __init__(self, n_input_dims: int, n_output_dims: int, encoding_config: dict, network_config: dict) -> None:
+        super().__init__()
+        with torch.cuda.device(_rank()):
+            self.network_with_input_encoding = tcnn.NetworkWithInputEncoding(
+                n_input_dims=n_input_dims, n_output_dims=n_output_dims, encoding_config=encoding_config,
+                network_config=network_config)
+
+    def forward(self, x):
+        return self.network_with_input_encoding(x).float()
+
+
+def create_network_with_input_encoding(n_input_dims: int, n_output_dims: int, encoding_config, network_config) -> nn.Module:
+    """networks.py:374-394 (input in [0, 1])."""
+    if _get(encoding_config, "otype") in ["VanillaFrequency", "ProgressiveBandHashGrid"] or \
+            _get(network_config, "otype") in ["VanillaMLP", "SphereInitVanillaMLP"]:
+        encoding = get_encoding(n_input_dims, encoding_config)
+        network = get_mlp(encoding.n_output_dims, n_output_dims, network_config)
+        return NetworkWithInputEncoding(encoding, network)
+    return TCNNNetworkWithInputEncoding(n_input_dims=n_input_dims, n_output_dims=n_output_dims,
+                                        encoding_config=_primitive(encoding_config), network_config=_primitive(network_config))
+
+
+class ToDTypeWrapper(nn.Module):
+    """networks.py:397-404."""
+
+    def __init__(self, module: nn.Module, dtype: torch.dtype):
+        super().__init__()
+        self.module = module
+        self.dtype = dtype
+
+    def forward(self, x):
+        return self.module(x).to(self.dtype)
 
 
 def scale_tensor(dat, inp_scale, tgt_scale):

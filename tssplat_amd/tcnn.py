@@ -1,14 +1,17 @@
 """A ``tinycudann``-named stand-in: ``import tssplat_amd.tcnn as tcnn`` where the reference does ``import tinycudann as tcnn``
 (models/networks.py:2).  tiny-cuda-nn is a CUDA-only library; what the reference's texture stage takes from it is the grid
 encoding (``tcnn.Encoding``, models/networks.py:97-106 and :113-116), served here by the HIP kernels of
-:mod:`tssplat_amd.encoding`.  The fused MLPs (``tcnn.Network``, ``tcnn.NetworkWithInputEncoding``) are not offered: the
-reference's default MLP is ``VanillaMLP`` (plain ``nn.Linear``, models/networks.py:195-235), which needs nothing from here.
+:mod:`tssplat_amd.encoding`, and the fully fused MLP (``tcnn.Network``, ``tcnn.NetworkWithInputEncoding``,
+models/networks.py:314-404) for network otypes ``FullyFusedMLP`` / ``CutlassMLP`` / ``MLP``, served by the HIP kernels of
+:mod:`tssplat_amd.network`.  Other network otypes raise ``NotImplementedError``: the reference's default MLP is
+``VanillaMLP`` (plain ``nn.Linear``, models/networks.py:195-235), which needs nothing from here.
 """
 from __future__ import annotations
 
 import torch
 
-from .encoding import GridEncoding
+from .encoding import GridEncoding, _GridEncodeFunc, _check_input
+from .network import FusedMLP, fused_mlp, is_network_otype
 
 __all__ = ["Encoding", "Network", "NetworkWithInputEncoding"]
 
@@ -23,13 +26,48 @@ class Encoding(GridEncoding):
         super().__init__(n_input_dims, encoding_config, seed=seed)
 
 
-class Network(torch.nn.Module):
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("tssplat_amd.tcnn.Network: tiny-cuda-nn's fused MLPs are not offered; use the "
-                                  "VanillaMLP route (mlp_network_config otype 'VanillaMLP', plain nn.Linear)")
+def _check_network_otype(cls: str, network_config) -> None:
+    otype = network_config.get("otype") if network_config is not None else None
+    if not is_network_otype(otype):
+        raise NotImplementedError(f"tssplat_amd.tcnn.{cls}: network otype {otype!r} is not offered (FullyFusedMLP, CutlassMLP or "
+                                  "MLP); use the VanillaMLP route (mlp_network_config otype 'VanillaMLP', plain nn.Linear)")
+
+
+class Network(FusedMLP):
+    """``tcnn.Network(n_input_dims, n_output_dims, network_config, seed=1337)``: the fused MLP of :mod:`tssplat_amd.network`;
+    float32 output."""
+
+    def __init__(self, n_input_dims: int, n_output_dims: int, network_config: dict, seed: int = 1337):
+        _check_network_otype("Network", network_config)
+        super().__init__(n_input_dims, n_output_dims, network_config, seed=seed)
 
 
 class NetworkWithInputEncoding(torch.nn.Module):
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("tssplat_amd.tcnn.NetworkWithInputEncoding: tiny-cuda-nn's fused MLPs are not offered; use "
-                                  "tcnn.Encoding followed by the VanillaMLP route (plain nn.Linear)")
+    """``tcnn.NetworkWithInputEncoding(n_input_dims, n_output_dims, encoding_config, network_config, seed=1337)``: the grid
+    encoding followed by the fused MLP.  ``params`` is one Parameter, ``[network params | encoding params]`` (tiny-cuda-nn's
+    order, unpinned), split in two by views."""
+
+    def __init__(self, n_input_dims: int, n_output_dims: int, encoding_config: dict, network_config: dict = None, seed: int = 1337):
+        super().__init__()
+        _check_network_otype("NetworkWithInputEncoding", network_config)     # before the encoding config is parsed
+        enc = GridEncoding(n_input_dims, encoding_config, seed=seed)
+        net = FusedMLP(enc.n_output_dims, n_output_dims, network_config, seed=seed)
+        self.encoding_cfg, self.network_cfg = enc.cfg, net.cfg
+        self.n_input_dims, self.n_output_dims = int(n_input_dims), int(n_output_dims)
+        self.n_network_params = net.layout["n_params"]
+        self.params = torch.nn.Parameter(torch.cat([net.params.detach(), enc.params.detach()]))
+
+    @property
+    def network_params(self) -> torch.Tensor:
+        return self.params[: self.n_network_params]
+
+    @property
+    def encoding_params(self) -> torch.Tensor:
+        return self.params[self.n_network_params:]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = _check_input(x, self.n_input_dims)
+        if not self.params.is_cuda or self.params.device != x.device:
+            raise RuntimeError("tssplat_amd network: params and x must live on the same GPU")
+        features = _GridEncodeFunc.apply(x, self.encoding_params, self.encoding_cfg, self.network_cfg["n_input_dims"])
+        return fused_mlp(features, self.network_params, self.network_cfg)
