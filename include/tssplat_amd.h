@@ -104,6 +104,23 @@ typedef struct tsamd_plan_info {
     int32_t n_planes;            /* dword planes per tile slot: 13; 22 with an explicit element operator (18 when it is symmetric); 4 with rebuild_dminv */
 } tsamd_plan_info;
 
+/* How the plan was cut, next to what a halo-free plan would carry (host side; valid for host_only handles too).  Every
+ * owned tet is a slot that has to be there; the halo slots and the staged rows exist only because tet-spheres are cut into
+ * several tiles, so owned_tets is the lower bound of the slots and 0 that of the rows, and min_tiles = the fewest tiles
+ * that could hold total_slots at all. */
+typedef struct tsamd_partition_info {
+    int64_t owned_tets;          /* = n_tets                                                         */
+    int64_t halo_slots;          /* total_slots - owned_tets                                         */
+    int64_t staged_rows;         /* = shared_vertex_copies                                           */
+    int64_t n_tiles;
+    int64_t tile_capacity;       /* slots one tile can hold: lanes x slots per lane of the plan's launch shape          */
+    int64_t min_tiles;           /* ceil(total_slots / tile_capacity)                                */
+    int64_t cut_components;      /* tet-spheres too large for one tile                               */
+    int64_t bisection_components;/* ... of which kept the coordinate bisection's tiles (the compact cells did not beat them) */
+    int64_t cut_templates;       /* ... of which were cut themselves: the others are copies of one of them and took its cut over */
+    double mean_fill, max_fill;  /* slots of a tile over tile_capacity                               */
+} tsamd_partition_info;
+
 /* One tile of the plan, as host pointers into the handle (valid until tsamd_destroy).
  * Exists so tests can replay the exact data the kernels consume. */
 typedef struct tsamd_tile_view {
@@ -160,6 +177,7 @@ void tsamd_destroy(tsamd_handle *h);
 int64_t tsamd_num_vertices(const tsamd_handle *h);
 int64_t tsamd_num_tets(const tsamd_handle *h);
 int tsamd_get_plan_info(const tsamd_handle *h, tsamd_plan_info *out);
+int tsamd_get_partition_info(const tsamd_handle *h, tsamd_partition_info *out);
 int tsamd_get_tile(const tsamd_handle *h, int64_t tile, tsamd_tile_view *out);
 /* finish lists: vertex k (global id vid[k]) = sum of staging rows [off[k], off[k+1]);
  * idx[tile.stage_off + j] = the staging row the tile's j-th shared tile vertex (in tile vertex order) writes -- the same

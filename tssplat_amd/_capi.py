@@ -53,6 +53,14 @@ class PlanInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class PartitionInfo(C.Structure):
+    _fields_ = [
+        ("owned_tets", C.c_int64), ("halo_slots", C.c_int64), ("staged_rows", C.c_int64), ("n_tiles", C.c_int64),
+        ("tile_capacity", C.c_int64), ("min_tiles", C.c_int64), ("cut_components", C.c_int64),
+        ("bisection_components", C.c_int64), ("cut_templates", C.c_int64), ("mean_fill", C.c_double), ("max_fill", C.c_double),
+    ]
+
+
 class TileView(C.Structure):
     _fields_ = [
         ("n_slots", C.c_int32), ("n_owned", C.c_int32), ("s_pad", C.c_int32), ("n_verts", C.c_int32),
@@ -77,6 +85,7 @@ SIGNATURES = {
     "tsamd_num_vertices": (C.c_int64, [C.c_void_p]),
     "tsamd_num_tets": (C.c_int64, [C.c_void_p]),
     "tsamd_get_plan_info": (C.c_int, [C.c_void_p, C.POINTER(PlanInfo)]),
+    "tsamd_get_partition_info": (C.c_int, [C.c_void_p, C.POINTER(PartitionInfo)]),
     "tsamd_get_tile": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(TileView)]),
     "tsamd_get_finish_lists": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int32)),
                                          C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]),

@@ -389,6 +389,27 @@ int tsamd_get_plan_info(const tsamd_handle *h, tsamd_plan_info *out)
     return TSAMD_OK;
 }
 
+int tsamd_get_partition_info(const tsamd_handle *h, tsamd_partition_info *out)
+{
+    if (!h || !out) return fail(TSAMD_ERR_INVALID_ARGUMENT, "null argument");
+    const tsamd::Plan &P = h->plan;
+    std::memset(out, 0, sizeof(*out));
+    out->owned_tets = P.m;
+    out->halo_slots = P.total_slots - P.m;
+    out->staged_rows = P.n_stage;
+    out->n_tiles = int64_t(P.tiles.size());
+    out->tile_capacity = int64_t(P.block_threads) * P.spt;
+    out->min_tiles = out->tile_capacity > 0 ? (P.total_slots + out->tile_capacity - 1) / out->tile_capacity : 0;
+    out->cut_components = P.n_cut_components;
+    out->bisection_components = P.n_bisection_components;
+    out->cut_templates = P.n_cut_templates;
+    if (out->n_tiles > 0 && out->tile_capacity > 0) {
+        out->mean_fill = double(P.total_slots) / (double(out->n_tiles) * double(out->tile_capacity));
+        out->max_fill = double(P.max_slots) / double(out->tile_capacity);
+    }
+    return TSAMD_OK;
+}
+
 int tsamd_get_tile(const tsamd_handle *h, int64_t tile, tsamd_tile_view *out)
 {
     if (!h || !out) return fail(TSAMD_ERR_INVALID_ARGUMENT, "null argument");

@@ -3,20 +3,27 @@
 // What a tile costs the energy kernels is its SLOTS -- the owned tets plus the one-ring face halo, each streamed (52 B) and run
 // through pass 1, pass 3 and the scatter -- and its tile vertices, whose partial sums go through the staging rows when another
 // tile meets the vertex too (plan.h).  Both grow with the surface between tiles, and the recursive coordinate bisection of
-// build_plan cuts slabs with a lot of surface.  Here the sphere is cut into compact cells instead:
-//   1. seed k cells with the bisection of the rest centroids by tet count;
+// build_plan cuts slabs with a lot of surface.  Here the sphere is cut into compact cells instead, for every k the caller allows:
+//   1. seed k cells with the bisection of the rest centroids by tet count -- or, when step 4 cannot make those fit, with k
+//      centroids spread by farthest-point sampling;
 //   2. slot-balanced Lloyd iterations: every tet joins the cell of least |x - c|^2 - w among the centres nearest its own cell's,
 //      and the weight w of a cell falls when it holds more slots than the mean (a power diagram);
 //   3. every cell keeps its largest face-connected piece, the other pieces join the neighbouring cells;
-//   4. boundary moves between face-adjacent cells (Fiduccia-Mattheyses style, greedy): first out of every cell that does not fit
-//      until it fits, then any move that lowers kPartSlotWeight * slots + tile vertices and keeps both cells fitting and face-connected.
-// Everything runs in one thread per sphere over local indices in a fixed order, so the result does not depend on the number of
-// host threads.  A cell's slot count and tile vertices (kMaxRank slots per tile vertex, as measure() counts them) are kept
-// exact under every move through per-(cell, vertex) slot counts.
+//   4. boundary moves between face-adjacent cells: first out of every cell that does not fit until it fits, then
+//      Fiduccia-Mattheyses passes over kPartSlotWeight * slots + kPartRowWeight * staged rows.  A pass takes the best move of any
+//      unlocked tet from a queue ordered by (gain, tet id) -- also when that gain is zero or negative, which is what carries a cut
+//      across the plateaus of a lattice --, locks the tet, and in the end rolls back to the cheapest prefix of its moves.  Every
+//      move keeps both cells fitting and face-connected, so every prefix is a valid cut.
+// Everything runs in one thread per sphere over local indices in a fixed order with ties broken by tet id, so the result does
+// not depend on the number of host threads.  A cell's slot count and tile vertices (kMaxRank slots per tile vertex, as
+// measure() counts them) and the staged rows of the whole cut are kept exact under every move through per-(cell, vertex) slot
+// counts and per-vertex copy counts.
 #include "partition.h"
 
 #include <algorithm>
 #include <cmath>
+#include <set>
+#include <utility>
 
 namespace tsamd {
 namespace {
@@ -24,7 +31,9 @@ namespace {
 constexpr int kLloydIters = 12;
 constexpr int kLloydFull = 4;                // of which assign every tet (the others: tets on a cell boundary)
 constexpr int kCandidates = 8;               // centres a tet looks at: the nearest ones to its own cell's centre
-constexpr int kImproveSweeps = 6;
+constexpr int kGrowRounds = 6;               // rounds of the balanced growth over the face adjacency
+constexpr int kFmPasses = 8;                 // at most; the passes end with the first one that finds nothing
+constexpr int kFmStall = 3000;               // moves a pass may go on past its cheapest prefix
 constexpr int kConnectProbe = 512;           // tets a connectivity probe may visit before it refuses the move
 constexpr int64_t kMaxIncidence = int64_t(1) << 23;   // (cells x vertices) counts one sphere may allocate
 
@@ -39,12 +48,20 @@ struct Part {
     std::vector<int32_t> part;    // cell of every tet
     std::vector<int64_t> owned, slots, verts;
     std::vector<int32_t> inc;     // k x nv: slots of the cell that meet the vertex
+    std::vector<int32_t> tot;     // nv: tile-vertex copies of the vertex over all cells
+    int64_t rows = 0;             // staged rows of the cut: the copies of every vertex that has more than one
     std::vector<int32_t> mark, queue;
     int32_t stamp = 0;
 
     explicit Part(const Limits &l) : lim(l) {}
 
-    int64_t cost(int64_t p) const { return kPartSlotWeight * slots[size_t(p)] + verts[size_t(p)]; }
+    static int64_t staged(int64_t c) { return c > 1 ? c : 0; }
+    int64_t total_slots() const
+    {
+        int64_t s = 0;
+        for (int64_t p = 0; p < k; ++p) s += slots[size_t(p)];
+        return s;
+    }
     bool fits(int64_t p) const { return lim.fits(slots[size_t(p)], verts[size_t(p)]); }
 
     // ---- 1. bisection seed ----
@@ -229,13 +246,86 @@ struct Part {
         }
     }
 
+    // ---- 3b. balanced growth over the face adjacency ----
+    // Every cell starts again from the tet nearest its centroid and claims tets breadth-first across faces, the cell that
+    // holds the fewest tets always moving next.  The cells that come out are balls of the mesh's own face-adjacency metric, not
+    // of the rest coordinates: where the mesh is a lattice their walls follow its planes, which is where a wall cuts the fewest
+    // faces.  Cells are face-connected by construction.
+    void grow(int rounds)
+    {
+        const size_t K = size_t(k);
+        std::vector<double> c(3 * K);
+        std::vector<int64_t> n_in(K);
+        std::vector<int32_t> centre(K), claimed(static_cast<size_t>(cnt));
+        std::vector<std::vector<int32_t>> fifo(K);
+        std::vector<size_t> head(K);
+        for (int it = 0; it < rounds; ++it) {
+            std::fill(c.begin(), c.end(), 0.0);
+            std::fill(n_in.begin(), n_in.end(), 0);
+            for (int64_t e = 0; e < cnt; ++e) {
+                const int32_t p = part[size_t(e)];
+                ++n_in[size_t(p)];
+                for (int d = 0; d < 3; ++d) c[3 * size_t(p) + d] += x[3 * size_t(e) + d];
+            }
+            std::vector<double> best(K, std::numeric_limits<double>::max());
+            std::fill(centre.begin(), centre.end(), -1);
+            for (int64_t e = 0; e < cnt; ++e) {
+                const int32_t p = part[size_t(e)];
+                double d2 = 0.0;
+                for (int d = 0; d < 3; ++d) {
+                    const double t = x[3 * size_t(e) + d] - c[3 * size_t(p) + d] / double(n_in[size_t(p)]);
+                    d2 += t * t;
+                }
+                if (d2 < best[size_t(p)]) {
+                    best[size_t(p)] = d2;
+                    centre[size_t(p)] = int32_t(e);
+                }
+            }
+            std::fill(claimed.begin(), claimed.end(), -1);
+            std::fill(n_in.begin(), n_in.end(), 0);
+            for (size_t p = 0; p < K; ++p) {
+                fifo[p].clear();
+                head[p] = 0;
+                if (centre[p] >= 0) fifo[p].push_back(centre[p]);
+            }
+            for (int64_t left = cnt; left > 0;) {
+                // the cell with the fewest tets that still has somewhere to go (ties: the lowest)
+                int64_t p = -1;
+                for (size_t q = 0; q < K; ++q) {
+                    while (head[q] < fifo[q].size() && claimed[size_t(fifo[q][head[q]])] >= 0) ++head[q];
+                    if (head[q] < fifo[q].size() && (p < 0 || n_in[q] < n_in[size_t(p)])) p = int64_t(q);
+                }
+                if (p < 0) break;   // (cannot happen on a face-connected component)
+                const int32_t e = fifo[size_t(p)][head[size_t(p)]++];
+                claimed[size_t(e)] = int32_t(p);
+                ++n_in[size_t(p)];
+                --left;
+                for (int f = 0; f < 4; ++f) {
+                    const int32_t r = nb[4 * size_t(e) + f];
+                    if (r >= 0 && claimed[size_t(r)] < 0) fifo[size_t(p)].push_back(r);
+                }
+            }
+            for (int64_t e = 0; e < cnt; ++e)
+                if (claimed[size_t(e)] >= 0) part[size_t(e)] = claimed[size_t(e)];
+        }
+    }
+
     // ---- exact slot / tile-vertex bookkeeping ----
+    void copy_changed(int32_t v, int d)
+    {
+        rows -= staged(tot[size_t(v)]);
+        tot[size_t(v)] += d;
+        rows += staged(tot[size_t(v)]);
+    }
     void add_slot(int32_t p, int32_t e)
     {
         ++slots[size_t(p)];
         for (int a = 0; a < 4; ++a) {
             int32_t &c = inc[size_t(p) * size_t(nv) + size_t(lv[4 * size_t(e) + a])];
-            if (c % kMaxRank == 0) ++verts[size_t(p)];
+            if (c % kMaxRank == 0) {
+                ++verts[size_t(p)];
+                copy_changed(lv[4 * size_t(e) + a], +1);
+            }
             ++c;
         }
     }
@@ -245,7 +335,10 @@ struct Part {
         for (int a = 0; a < 4; ++a) {
             int32_t &c = inc[size_t(p) * size_t(nv) + size_t(lv[4 * size_t(e) + a])];
             --c;
-            if (c % kMaxRank == 0) --verts[size_t(p)];
+            if (c % kMaxRank == 0) {
+                --verts[size_t(p)];
+                copy_changed(lv[4 * size_t(e) + a], -1);
+            }
         }
     }
     void build_state()
@@ -254,6 +347,8 @@ struct Part {
         slots.assign(size_t(k), 0);
         verts.assign(size_t(k), 0);
         inc.assign(size_t(k) * size_t(nv), 0);
+        tot.assign(size_t(nv), 0);
+        rows = 0;
         for (int64_t q = 0; q < cnt; ++q) {
             const int32_t pq = part[size_t(q)];
             ++owned[size_t(pq)];
@@ -314,28 +409,6 @@ struct Part {
         }
         return n;
     }
-    // change of cell p's tile vertices when the n tets t[] join (sign +1) or leave (-1) its slots
-    int64_t vert_delta(int32_t p, const int32_t *t, int n, int sign) const
-    {
-        int32_t vs[20], ds[20];
-        int m = 0;
-        for (int i = 0; i < n; ++i)
-            for (int a = 0; a < 4; ++a) {
-                const int32_t v = lv[4 * size_t(t[i]) + a];
-                int j = int(std::find(vs, vs + m, v) - vs);
-                if (j == m) {
-                    vs[m] = v;
-                    ds[m++] = 0;
-                }
-                ds[j] += sign;
-            }
-        int64_t d = 0;
-        for (int j = 0; j < m; ++j) {
-            const int32_t c = inc[size_t(p) * size_t(nv) + size_t(vs[j])];
-            d += copies(c + ds[j]) - copies(c);
-        }
-        return d;
-    }
     struct Move {
         int32_t e = -1, B = -1;
         int64_t dcost = 0, key = 0;
@@ -343,8 +416,9 @@ struct Part {
         int32_t gone[5], en[4];
         int64_t dsA = 0, dvA = 0, dsB = 0, dvB = 0;
     };
-    // evaluates moving e to B; false if B would not fit
-    bool evaluate(int32_t e, int32_t B, Move &mv) const
+    // evaluates moving e to B: the change of both cells' slots and tile vertices and of the cut's cost; false if B would not
+    // fit (`check` off: a move that only takes a recorded one back)
+    bool evaluate(int32_t e, int32_t B, Move &mv, bool check = true) const
     {
         const int32_t A = part[size_t(e)];
         mv.e = e;
@@ -353,10 +427,35 @@ struct Part {
         mv.ne = entering(e, B, mv.en);
         mv.dsA = -mv.nl;
         mv.dsB = mv.ne;
-        mv.dvB = vert_delta(B, mv.en, mv.ne, +1);
-        if (!lim.fits(slots[size_t(B)] + mv.dsB, verts[size_t(B)] + mv.dvB)) return false;
-        mv.dvA = vert_delta(A, mv.gone, mv.nl, -1);
-        mv.dcost = kPartSlotWeight * (mv.dsA + mv.dsB) + mv.dvA + mv.dvB;
+        // per vertex: slots that leave A and slots that join B
+        int32_t vs[36], dA[36], dB[36];
+        int m = 0;
+        auto note = [&](int32_t t, int32_t *d, int sign) {
+            for (int a = 0; a < 4; ++a) {
+                const int32_t v = lv[4 * size_t(t) + a];
+                int j = int(std::find(vs, vs + m, v) - vs);
+                if (j == m) {
+                    vs[m] = v;
+                    dA[m] = dB[m] = 0;
+                    ++m;
+                }
+                d[j] += sign;
+            }
+        };
+        for (int i = 0; i < mv.nl; ++i) note(mv.gone[i], dA, -1);
+        for (int i = 0; i < mv.ne; ++i) note(mv.en[i], dB, +1);
+        mv.dvA = mv.dvB = 0;
+        int64_t drows = 0;
+        for (int j = 0; j < m; ++j) {
+            const int32_t cA = inc[size_t(A) * size_t(nv) + size_t(vs[j])], cB = inc[size_t(B) * size_t(nv) + size_t(vs[j])];
+            const int64_t a = copies(cA + dA[j]) - copies(cA), b = copies(cB + dB[j]) - copies(cB);
+            mv.dvA += a;
+            mv.dvB += b;
+            const int64_t t = tot[size_t(vs[j])];
+            drows += staged(t + a + b) - staged(t);
+        }
+        if (check && !lim.fits(slots[size_t(B)] + mv.dsB, verts[size_t(B)] + mv.dvB)) return false;
+        mv.dcost = kPartSlotWeight * (mv.dsA + mv.dsB) + kPartRowWeight * drows;
         return true;
     }
     void apply(const Move &mv)
@@ -431,7 +530,7 @@ struct Part {
                     const int no = other_cells(e, oc);
                     for (int j = 0; j < no; ++j) {
                         if (!evaluate(e, oc[j], mv)) continue;
-                        mv.key = mv.dcost + kPartSlotWeight * mv.dsA + mv.dvA;
+                        mv.key = mv.dcost + kPartSlotWeight * mv.dsA + kPartRowWeight * mv.dvA;
                         if (have && mv.key >= best.key) continue;
                         if (!stays_connected(e)) break;
                         best = mv;
@@ -445,30 +544,144 @@ struct Part {
         return true;
     }
 
-    // ---- 4b. greedy sweeps of the moves that lower the cost ----
-    void improve()
+    // ---- 4b. Fiduccia-Mattheyses passes ----
+    // the cheapest move of e to a cell across one of its faces (ties: the lower cell); false if there is none that fits
+    bool best_move(int32_t e, Move &best) const
     {
-        for (int sweep = 0; sweep < kImproveSweeps; ++sweep) {
-            int64_t moved = 0;
-            for (int64_t e = 0; e < cnt; ++e) {
-                const int32_t A = part[size_t(e)];
-                if (owned[size_t(A)] <= 1) continue;
-                int32_t oc[4];
-                const int no = other_cells(int32_t(e), oc);
-                Move best, mv;
-                bool have = false;
-                for (int j = 0; j < no; ++j) {
-                    if (!evaluate(int32_t(e), oc[j], mv) || mv.dcost >= 0) continue;
-                    if (have && mv.dcost >= best.dcost) continue;
-                    best = mv;
-                    have = true;
-                }
-                if (have && stays_connected(int32_t(e))) {
-                    apply(best);
-                    ++moved;
+        if (owned[size_t(part[size_t(e)])] <= 1) return false;
+        int32_t oc[4];
+        const int no = other_cells(e, oc);
+        Move mv;
+        bool have = false;
+        for (int j = 0; j < no; ++j) {
+            if (!evaluate(e, oc[j], mv)) continue;
+            if (have && (mv.dcost > best.dcost || (mv.dcost == best.dcost && mv.B > best.B))) continue;
+            best = mv;
+            have = true;
+        }
+        return have;
+    }
+    std::set<std::pair<int64_t, int32_t>> fm_queue;   // (cost change, tet): the best gain first, ties by tet id
+    std::vector<int64_t> fm_key;                      // per tet: its cost change in the queue
+    std::vector<uint8_t> fm_queued, fm_locked;
+    void fm_drop(int32_t e)
+    {
+        if (!fm_queued[size_t(e)]) return;
+        fm_queue.erase({fm_key[size_t(e)], e});
+        fm_queued[size_t(e)] = 0;
+    }
+    void fm_refresh(int32_t e)
+    {
+        fm_drop(e);
+        Move mv;
+        if (fm_locked[size_t(e)] || !best_move(e, mv)) return;
+        fm_key[size_t(e)] = mv.dcost;
+        fm_queued[size_t(e)] = 1;
+        fm_queue.insert({mv.dcost, e});
+    }
+    // One pass; true if it lowered the cost.  The queue holds every unlocked tet's best move as it was last evaluated; a move is
+    // evaluated again when it comes up and goes back into the queue if its gain is no longer what the queue said (the slot
+    // counts of a vertex change under moves several tets away), so every move that is made is made at its exact gain.
+    bool fm_pass()
+    {
+        fm_queue.clear();
+        fm_key.assign(size_t(cnt), 0);
+        fm_queued.assign(size_t(cnt), 0);
+        fm_locked.assign(size_t(cnt), 0);
+        for (int64_t e = 0; e < cnt; ++e) fm_refresh(int32_t(e));
+        std::vector<std::pair<int32_t, int32_t>> done;   // (tet, the cell it came from)
+        int64_t cum = 0, best = 0;
+        size_t best_len = 0;
+        while (!fm_queue.empty() && done.size() - best_len < size_t(kFmStall)) {
+            const int32_t e = fm_queue.begin()->second;
+            Move mv;
+            if (!best_move(e, mv)) {
+                fm_drop(e);
+                continue;
+            }
+            if (mv.dcost != fm_key[size_t(e)]) {
+                fm_queue.erase(fm_queue.begin());
+                fm_key[size_t(e)] = mv.dcost;
+                fm_queue.insert({mv.dcost, e});
+                continue;
+            }
+            fm_drop(e);
+            if (!stays_connected(e)) continue;   // (it comes back when a move next to it changes its cell)
+            const int32_t A = part[size_t(e)];
+            apply(mv);
+            fm_locked[size_t(e)] = 1;
+            done.push_back({e, A});
+            cum += mv.dcost;
+            if (cum < best) {
+                best = cum;
+                best_len = done.size();
+            }
+            // the moves within two faces of e have changed
+            for (int f = 0; f < 4; ++f) {
+                const int32_t q = nb[4 * size_t(e) + f];
+                if (q < 0) continue;
+                fm_refresh(q);
+                for (int g = 0; g < 4; ++g) {
+                    const int32_t r = nb[4 * size_t(q) + g];
+                    if (r >= 0 && r != e) fm_refresh(r);
                 }
             }
-            if (moved == 0) break;
+        }
+        while (done.size() > best_len) {   // roll back to the cheapest prefix
+            Move mv;
+            evaluate(done.back().first, done.back().second, mv, false);
+            apply(mv);
+            done.pop_back();
+        }
+        return best < 0;
+    }
+    void improve()
+    {
+        for (int pass = 0; pass < kFmPasses; ++pass)
+            if (!fm_pass()) break;
+    }
+
+    // ---- 1b. seeds spread by farthest-point sampling over the rest centroids; every tet joins the nearest one ----
+    void seed_spread()
+    {
+        double mean[3] = {0.0, 0.0, 0.0};
+        for (int64_t e = 0; e < cnt; ++e)
+            for (int d = 0; d < 3; ++d) mean[d] += x[3 * size_t(e) + d];
+        for (int d = 0; d < 3; ++d) mean[d] /= double(cnt);
+        std::vector<double> d2(size_t(cnt), std::numeric_limits<double>::max());
+        auto dist2 = [&](int64_t e, const double *c) {
+            double s = 0.0;
+            for (int d = 0; d < 3; ++d) {
+                const double t = x[3 * size_t(e) + d] - c[d];
+                s += t * t;
+            }
+            return s;
+        };
+        int64_t far = 0;   // the first seed: the tet farthest from the mean (ties: the lowest id)
+        double far_d = -1.0;
+        for (int64_t e = 0; e < cnt; ++e) {
+            const double d = dist2(e, mean);
+            if (d > far_d) {
+                far_d = d;
+                far = e;
+            }
+        }
+        for (int64_t p = 0; p < k; ++p) {
+            const double *c = &x[3 * size_t(far)];
+            int64_t next_far = 0;
+            double next_d = -1.0;
+            for (int64_t e = 0; e < cnt; ++e) {
+                const double d = dist2(e, c);
+                if (d < d2[size_t(e)]) {
+                    d2[size_t(e)] = d;
+                    part[size_t(e)] = int32_t(p);
+                }
+                if (d2[size_t(e)] > next_d) {
+                    next_d = d2[size_t(e)];
+                    next_far = e;
+                }
+            }
+            far = next_far;
         }
     }
 };
@@ -476,11 +689,11 @@ struct Part {
 }  // namespace
 
 bool partition_component(const Mesh &M, const Limits &lim, const float *cen, const int32_t *ids, int64_t cnt,
-                         int64_t k_first, int64_t k_last, Scratch &S, std::vector<std::vector<int32_t>> &parts,
-                         int64_t &cost)
+                         const std::vector<std::vector<int32_t>> &incumbent, int64_t k_first, int64_t k_last, int64_t slot_cap,
+                         Scratch &S, std::vector<std::vector<int32_t>> &parts, CutStats &before, CutStats &after)
 {
     parts.clear();
-    cost = 0;
+    before = after = CutStats();
     k_first = std::max<int64_t>(2, k_first);
     k_last = std::min(k_last, cnt);
     if (k_first > k_last) return false;
@@ -508,32 +721,74 @@ bool partition_component(const Mesh &M, const Limits &lim, const float *cen, con
         }
         for (int d = 0; d < 3; ++d) P.x[3 * size_t(i) + d] = cen[3 * size_t(g) + d];
     }
-    if (k_last * P.nv > kMaxIncidence) return false;   // (the caller keeps the bisection)
+    if (std::max<int64_t>(k_last, int64_t(incumbent.size())) * P.nv > kMaxIncidence) return false;   // (the caller keeps its cut)
     P.mark.assign(size_t(cnt), 0);
-    std::vector<int32_t> idx(static_cast<size_t>(cnt));
-    for (int64_t k = k_first; k <= k_last; ++k) {
+    // the incumbent's figures, counted the same way
+    P.k = int64_t(incumbent.size());
+    P.part.assign(size_t(cnt), 0);
+    for (size_t p = 0; p < incumbent.size(); ++p)
+        for (int32_t g : incumbent[p]) P.part[size_t(S.tet_slot[size_t(g)])] = int32_t(p);
+    P.build_state();
+    before.parts = P.k;
+    before.slots = P.total_slots();
+    before.rows = P.rows;
+    std::vector<int32_t> idx(static_cast<size_t>(cnt)), best_part;
+    int64_t best_k = 0;
+    after = before;
+    // one k: cells of the rest coordinates and cells grown over the face adjacency, each refined; true if either fitted
+    auto try_k = [&](int64_t k) {
         P.k = k;
-        P.part.assign(size_t(cnt), 0);
-        for (int64_t i = 0; i < cnt; ++i) idx[size_t(i)] = int32_t(i);
-        int32_t next = 0;
-        P.seed(idx.data(), cnt, k, next);
-        P.lloyd();
-        P.connect();
-        P.build_state();
-        if (!P.repair()) continue;
-        P.improve();
-        std::vector<int64_t> at(size_t(k), -1);
-        for (int64_t p = 0; p < k; ++p)
-            if (P.owned[size_t(p)] > 0) {
-                at[size_t(p)] = int64_t(parts.size());
-                parts.emplace_back();
-                parts.back().reserve(size_t(P.owned[size_t(p)]));
-                cost += P.cost(p);
+        bool any = false;
+        for (int grown = 0; grown < 2; ++grown) {
+            bool fitted = false;
+            for (int spread = 0; spread < 2 && !fitted; ++spread) {
+                P.part.assign(size_t(cnt), 0);
+                if (spread) {
+                    P.seed_spread();
+                } else {
+                    for (int64_t i = 0; i < cnt; ++i) idx[size_t(i)] = int32_t(i);
+                    int32_t next = 0;
+                    P.seed(idx.data(), cnt, k, next);
+                }
+                P.lloyd();
+                P.connect();
+                if (grown) P.grow(kGrowRounds);
+                P.build_state();
+                fitted = P.repair();
             }
-        for (int64_t i = 0; i < cnt; ++i) parts[size_t(at[size_t(P.part[size_t(i)])])].push_back(ids[i]);
-        return true;
+            if (!fitted) continue;
+            any = true;
+            P.improve();
+            CutStats now;
+            for (int64_t p = 0; p < k; ++p) now.parts += P.owned[size_t(p)] > 0;
+            now.slots = P.total_slots();
+            now.rows = P.rows;
+            if (now.cost() >= after.cost()) continue;
+            after = now;
+            best_part = P.part;
+            best_k = k;
+        }
+        return any;
+    };
+    // upward from the caller's bound until two values of k have fitted (the cost rises with k from there on) ...
+    int fitted_ks = 0;
+    for (int64_t k = k_first; k <= k_last && fitted_ks < 2; ++k) fitted_ks += try_k(k) ? 1 : 0;
+    // ... and downward while the best cut's own slots would go into fewer tiles than the caller's bound assumed
+    for (int64_t k = k_first - 1; k >= 2 && best_k == k + 1 && (after.slots + slot_cap - 1) / slot_cap <= k; --k) try_k(k);
+    if (best_k == 0 || after.cost() * kPartMinSavingDen > before.cost() * (kPartMinSavingDen - 1)) {
+        after = before;
+        return false;
     }
-    return false;
+    std::vector<int64_t> at(size_t(best_k), -1);
+    for (int64_t i = 0; i < cnt; ++i) {
+        int64_t &a = at[size_t(best_part[size_t(i)])];
+        if (a < 0) {
+            a = int64_t(parts.size());
+            parts.emplace_back();
+        }
+        parts[size_t(a)].push_back(ids[i]);
+    }
+    return true;
 }
 
 }  // namespace tsamd

@@ -61,16 +61,33 @@ struct Mesh {
 void measure(const Mesh &M, const int32_t *owned, int64_t cnt, Scratch &S, int64_t &n_slots, int64_t &n_verts,
              std::vector<int32_t> *halo_out = nullptr);
 
-// what the partitioner minimises: kPartSlotWeight * slots + tile vertices (a slot streams 52 B and runs three passes; a tile
-// vertex shared with another tile costs a 12-byte staging row written and read back)
-constexpr int64_t kPartSlotWeight = 3;
+// What the partitioner minimises: kPartSlotWeight * slots + kPartRowWeight * staged rows, in the ratio of what the two were
+// measured to cost on MI355X (profiles/r07_partition_ab.json):
+//   a slot (owned or halo: 52 B streamed, pass 1, pass 3, the scatter)   ~ 13.7 ps  = 0.360 ms tile kernel / 26.24 M slots (512 x kuhn19)
+//   a staged row (12 B stored by the tile kernel, read by the finish kernel)  ~ 3.9 ps  = 22.8 us finish kernel / 5.86 M rows
+// i.e. 3.5 : 1.  A staged row is a tile-vertex copy of a vertex that has more than one copy in the whole plan; a vertex with a
+// single copy is written straight to the gradient and costs nothing here.
+constexpr int64_t kPartSlotWeight = 7;
+constexpr int64_t kPartRowWeight = 2;
 
-// Cuts the face-connected tets ids[0, cnt) (centroids cen, 3 per global tet) into k face-connected parts that all fit `lim`,
-// for the first k in [k_first, k_last] where that succeeds: slot-balanced k-means cells, then boundary moves between
-// face-adjacent parts that lower the cost (partition.cpp).  On success `parts` holds the k parts (global
-// tet ids, unordered), `cost` their summed cost, and the function returns true; false leaves `parts` empty.
+// The incumbent cut stands unless the new one saves at least 1 / kPartMinSavingDen = 2.5 % of its cost: alternated builds of one
+// plan spread by about 0.7 % in step time (profiles/r07_partition_ab.json), a saving below three times that cannot be told
+// from it, and a plan that does not change for nothing keeps its recorded traffic and timings valid.
+constexpr int64_t kPartMinSavingDen = 40;
+
+struct CutStats {
+    int64_t parts = 0, slots = 0, rows = 0;
+    int64_t cost() const { return kPartSlotWeight * slots + kPartRowWeight * rows; }
+};
+
+// Cuts the face-connected tets ids[0, cnt) (centroids cen, 3 per global tet) into face-connected parts that all fit `lim`:
+// slot-balanced k-means cells, then Fiduccia-Mattheyses passes of boundary moves between face-adjacent parts
+// (partition.cpp), for every k in [k_first, k_last]; the cheapest cut wins.  `incumbent` is the cut the caller already has (the
+// bisection's leaves); its figures come back in `before`.  Returns true, with the parts (global tet ids, unordered) in `parts`
+// and their figures in `after`, when a cut was found that saves at least 1 / kPartMinSavingDen of the incumbent's cost; false leaves `parts` empty
+// and `after` = `before`.
 bool partition_component(const Mesh &M, const Limits &lim, const float *cen, const int32_t *ids, int64_t cnt,
-                         int64_t k_first, int64_t k_last, Scratch &S, std::vector<std::vector<int32_t>> &parts,
-                         int64_t &cost);
+                         const std::vector<std::vector<int32_t>> &incumbent, int64_t k_first, int64_t k_last, int64_t slot_cap,
+                         Scratch &S, std::vector<std::vector<int32_t>> &parts, CutStats &before, CutStats &after);
 
 }  // namespace tsamd

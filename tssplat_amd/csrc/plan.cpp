@@ -591,18 +591,21 @@ int build_plan(const float *rest, int64_t n, const int32_t *tets, int64_t m, con
     timer.lap("bisection");
     // ---- partition: compact cells with fewer halo slots (partition.cpp) where the bisection found a strict fit ----
     // k runs upward from the bisection's slots over the slot capacity, at most four values and never past the bisection's own
-    // count; the cells replace the bisection's leaves when there are fewer of them, or as many at a lower cost
-    // (kPartSlotWeight * slots + tile vertices).  Otherwise the bisection stands: the plan is never worse than it.  No cell may
-    // need more LDS than the largest tile of the bisection, so the launch (dynamic LDS, workgroups per CU) stays as it was.
-    std::vector<int64_t> rcb_slots(groups.size(), 0), rcb_cost(groups.size(), 0), rcb_lds(groups.size(), 0);
+    // count; the cheapest cut of those replaces the bisection's leaves when it costs less than they do (kPartSlotWeight * slots +
+    // kPartRowWeight * staged rows).  Otherwise the bisection stands: the plan is never worse than it.  No cell may need more LDS
+    // than the largest tile of the bisection, so the launch (dynamic LDS, workgroups per CU) stays as it was.
+    //
+    // Batches repeat one template (the reference places copies of one tet-sphere too), and a cut only depends on the
+    // connectivity and, through the seeds, on the shape of the rest centroids.  So components are sorted into classes -- the same
+    // tets over the same vertices up to an offset of the ids, rest positions equal up to a translation and a uniform scale,
+    // both compared in full, not assumed --, the first component of a class is cut, and the others take its cut over.
+    std::vector<int64_t> rcb_lds(groups.size(), 0);
     parallel_chunks(int64_t(groups.size()), 16, nthreads, [&](int64_t b, int64_t e, int w) {
         Scratch &S = get_scratch(w);
         for (int64_t g = b; g < e; ++g)
             for (const auto &l : group_tiles[size_t(g)]) {
                 int64_t ns, nv;
                 measure(M, l.data(), int64_t(l.size()), S, ns, nv);
-                rcb_slots[size_t(g)] += ns;
-                rcb_cost[size_t(g)] += kPartSlotWeight * ns + nv;
                 const int64_t sp = (ns + lim.pad_unit - 1) / lim.pad_unit * lim.pad_unit;
                 rcb_lds[size_t(g)] = std::max(rcb_lds[size_t(g)], tile_lds_bytes(sp, nv, rebuild));
             }
@@ -610,32 +613,137 @@ int build_plan(const float *rest, int64_t n, const int32_t *tets, int64_t m, con
     Limits cell_lim = lim;
     cell_lim.budget = 0;
     for (int64_t l : rcb_lds) cell_lim.budget = std::max(cell_lim.budget, std::min(lim.budget, l));
-    std::atomic<int64_t> n_cut{0}, n_refined{0};
-    parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int w) {
-        Scratch &S = get_scratch(w);
-        std::vector<std::vector<int32_t>> parts;
+    // classes: a hash of the connectivity relative to the component's first tet and lowest vertex names a candidate, the
+    // candidate is the first component with that hash, and the comparison in full decides
+    struct Shape {
+        int32_t vbase = 0;
+        uint64_t hash = 0;
+        double lo[3], hi[3];
+    };
+    std::vector<Shape> shape(groups.size());
+    std::vector<int64_t> model(groups.size(), -1);   // the component whose cut this one takes over (itself: it is cut)
+    auto comp_ids = [&](int64_t g, int64_t &cnt) -> int32_t * {
+        cnt = comp_start[groups[size_t(g)].ce] - comp_start[groups[size_t(g)].cb];
+        return comp_tets.data() + comp_start[groups[size_t(g)].cb];
+    };
+    parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int) {
         for (int64_t g = b; g < e; ++g) {
             if (!group_fitted[size_t(g)]) continue;
-            const Group &G = groups[size_t(g)];
-            const int32_t *ids = comp_tets.data() + comp_start[G.cb];
-            const int64_t cnt = comp_start[G.ce] - comp_start[G.cb];
-            auto &leaves = group_tiles[size_t(g)];
+            int64_t cnt;
+            int32_t *ids = comp_ids(g, cnt);
+            std::sort(ids, ids + cnt);   // (the bisection has shuffled them: back to increasing order, the same in every copy)
+            Shape &sh = shape[size_t(g)];
+            sh.vbase = std::numeric_limits<int32_t>::max();
+            for (int d = 0; d < 3; ++d) {
+                sh.lo[d] = std::numeric_limits<double>::max();
+                sh.hi[d] = -std::numeric_limits<double>::max();
+            }
+            for (int64_t i = 0; i < cnt; ++i)
+                for (int a = 0; a < 4; ++a) {
+                    const int32_t v = tets[4 * int64_t(ids[i]) + a];
+                    sh.vbase = std::min(sh.vbase, v);
+                    for (int d = 0; d < 3; ++d) {
+                        sh.lo[d] = std::min(sh.lo[d], double(rest[3 * size_t(v) + d]));
+                        sh.hi[d] = std::max(sh.hi[d], double(rest[3 * size_t(v) + d]));
+                    }
+                }
+            uint64_t h = 1469598103934665603ull ^ uint64_t(cnt);
+            for (int64_t i = 0; i < cnt; ++i) {
+                h = (h ^ uint64_t(ids[i] - ids[0])) * 1099511628211ull;
+                for (int a = 0; a < 4; ++a) h = (h ^ uint64_t(tets[4 * int64_t(ids[i]) + a] - sh.vbase)) * 1099511628211ull;
+            }
+            sh.hash = h;
+        }
+    });
+    {
+        std::vector<std::pair<uint64_t, int64_t>> by_hash;
+        for (size_t g = 0; g < groups.size(); ++g)
+            if (group_fitted[g]) by_hash.push_back({shape[g].hash, int64_t(g)});
+        std::sort(by_hash.begin(), by_hash.end());
+        for (size_t i = 0; i < by_hash.size(); ++i)
+            model[size_t(by_hash[i].second)] = i > 0 && by_hash[i - 1].first == by_hash[i].first ? model[size_t(by_hash[i - 1].second)] : by_hash[i].second;
+    }
+    constexpr double kSimilarTol = 1e-4;   // of the component's extent; fp32 rounding of a placed copy is some 1e-6 of it
+    parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int) {
+        for (int64_t g = b; g < e; ++g) {
+            const int64_t r = model[size_t(g)];
+            if (r < 0 || r == g) continue;
+            int64_t cnt, cnt_r;
+            const int32_t *ids = comp_ids(g, cnt), *ids_r = comp_ids(r, cnt_r);
+            const Shape &sg = shape[size_t(g)], &sr = shape[size_t(r)];
+            bool same = cnt == cnt_r;
+            double ext_g = 0.0, ext_r = 0.0;
+            for (int d = 0; d < 3; ++d) {
+                ext_g = std::max(ext_g, sg.hi[d] - sg.lo[d]);
+                ext_r = std::max(ext_r, sr.hi[d] - sr.lo[d]);
+            }
+            same = same && ext_g > 0.0 && ext_r > 0.0;
+            const double scale = same ? ext_g / ext_r : 1.0;
+            for (int64_t i = 0; i < cnt && same; ++i) {
+                same = ids[i] - ids[0] == ids_r[i] - ids_r[0];
+                for (int a = 0; a < 4 && same; ++a) {
+                    const int32_t v = tets[4 * int64_t(ids[i]) + a], vr = tets[4 * int64_t(ids_r[i]) + a];
+                    same = v - sg.vbase == vr - sr.vbase;
+                    for (int d = 0; d < 3 && same; ++d)
+                        same = std::fabs((double(rest[3 * size_t(v) + d]) - sg.lo[d]) - scale * (double(rest[3 * size_t(vr) + d]) - sr.lo[d])) <= kSimilarTol * ext_g;
+                }
+            }
+            if (!same) model[size_t(g)] = g;   // (cut on its own)
+        }
+    });
+    std::vector<std::vector<std::vector<int32_t>>> cut(groups.size());   // of the components that are cut themselves
+    std::vector<uint8_t> refined(groups.size(), 0);
+    parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int w) {
+        Scratch &S = get_scratch(w);
+        for (int64_t g = b; g < e; ++g) {
+            if (model[size_t(g)] != g) continue;
+            int64_t cnt;
+            const int32_t *ids = comp_ids(g, cnt);
+            const auto &leaves = group_tiles[size_t(g)];
             const int64_t k_rcb = int64_t(leaves.size());
-            n_cut.fetch_add(1, std::memory_order_relaxed);
-            const int64_t k_lo = (rcb_slots[size_t(g)] + s_cap - 1) / s_cap;
-            int64_t cost;
-            if (!partition_component(M, cell_lim, cen.data(), ids, cnt, k_lo, std::min(k_rcb, k_lo + 3), S, parts, cost)) continue;
-            if (int64_t(parts.size()) > k_rcb || (int64_t(parts.size()) == k_rcb && cost >= rcb_cost[size_t(g)])) continue;
-            n_refined.fetch_add(1, std::memory_order_relaxed);
+            int64_t rcb_slots = 0;
+            for (const auto &l : leaves) {
+                int64_t ns, nv;
+                measure(M, l.data(), int64_t(l.size()), S, ns, nv);
+                rcb_slots += ns;
+            }
+            const int64_t k_lo = (rcb_slots + s_cap - 1) / s_cap;
+            CutStats before, after;
+            refined[size_t(g)] = partition_component(M, cell_lim, cen.data(), ids, cnt, leaves, k_lo, std::min(k_rcb, k_lo + 3), s_cap, S, cut[size_t(g)], before, after) ? 1 : 0;
+        }
+    });
+    int64_t n_cut = 0, n_refined = 0, n_models = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        if (model[g] < 0) continue;
+        ++n_cut;
+        n_models += model[g] == int64_t(g);
+        n_refined += refined[size_t(model[g])];
+    }
+    parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int w) {
+        Scratch &S = get_scratch(w);
+        std::vector<int32_t> part;
+        for (int64_t g = b; g < e; ++g) {
+            const int64_t r = model[size_t(g)];
+            if (r < 0 || !refined[size_t(r)]) continue;
+            int64_t cnt, cnt_r;
+            const int32_t *ids = comp_ids(g, cnt), *ids_r = comp_ids(r, cnt_r);
+            auto &leaves = group_tiles[size_t(g)];
             leaves.clear();
             std::string unused_err;
             Splitter sp{M, lim, cen, S, leaves, unused_err};
-            for (auto &part : parts) sp.emit(part.data(), int64_t(part.size()));
+            for (const auto &c : cut[size_t(r)]) {
+                part.resize(c.size());
+                for (size_t i = 0; i < c.size(); ++i) part[i] = c[i] - ids_r[0] + ids[0];
+                sp.emit(part.data(), int64_t(part.size()));
+            }
         }
     });
+    P.n_cut_components = n_cut;
+    P.n_bisection_components = n_cut - n_refined;
+    P.n_cut_templates = n_models;
     if (timer.on)
-        std::fprintf(stderr, "[plan] partition: %lld cut components, %lld refined, %lld keep the bisection\n", (long long)n_cut.load(),
-                     (long long)n_refined.load(), (long long)(n_cut.load() - n_refined.load()));
+        std::fprintf(stderr, "[plan] partition: %lld cut components, %lld refined, %lld keep the bisection (%lld cut themselves)\n", (long long)n_cut,
+                     (long long)n_refined, (long long)(n_cut - n_refined), (long long)n_models);
     timer.lap("partition (cells + refinement)");
     std::vector<std::vector<int32_t>> tiles_owned;
     for (auto &gt : group_tiles)

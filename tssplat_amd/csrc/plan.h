@@ -203,6 +203,9 @@ struct Plan {
     std::vector<int32_t> fin_vid, fin_off, fin_idx;
     int64_t n_stage = 0;             // rows in the staging buffer
     int64_t total_slots = 0, total_tile_verts = 0;
+    // the partition stage (statistics): tet-spheres cut into several tiles, those of them that kept the bisection's leaves, and
+    // the distinct templates among them (the components that were cut themselves; their copies took the cut over)
+    int64_t n_cut_components = 0, n_bisection_components = 0, n_cut_templates = 0;
     int32_t max_slots = 0, max_verts = 0, block_threads = 64, lds_bytes = 0, spt = kSlotsPerLane;
     int32_t n_planes = kPlanes;      // kPlanes, or kPlanesWeighted when an explicit operator was given
     int32_t vert_stride = 64;        // gvid entries per tile (tile t's ids start at t * vert_stride = its TileDesc::vert_off)

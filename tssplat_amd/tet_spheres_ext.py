@@ -180,7 +180,14 @@ class TetSpheres:
     def plan_info(self) -> dict:
         info = _capi.PlanInfo()
         _capi.check(_lib.tsamd_get_plan_info(self._handle(), C.byref(info)))
-        return info.as_dict()
+        out = info.as_dict()
+        # how the plan was cut (tsamd_partition_info): halo slots, staged rows, fill, spheres that kept the bisection
+        cut = _capi.PartitionInfo()
+        _capi.check(_lib.tsamd_get_partition_info(self._handle(), C.byref(cut)))
+        for k, _ in cut._fields_:
+            if k != "n_tiles":
+                out[k] = getattr(cut, k)
+        return out
 
     def set_timing(self, enable: bool) -> None:
         """Record HIP events around the kernels of every evaluation (bench.py roofline leg)."""
