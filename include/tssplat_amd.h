@@ -424,6 +424,29 @@ int tsamd_grid_encode_backward(const float *x_dev, int64_t n_points, const float
                                float per_level_scale, int32_t dense, const float *grad_out_dev, float *grad_params_dev,
                                float *grad_x_dev, void *stream);
 
+/* The sorted backward: the same gradients as tsamd_grid_encode_backward with dL/dparams summed without float atomics (per
+ * level: one (entry, source) record per point and corner, a stable radix sort by entry, a segmented sum in a fixed order).
+ *   Repeatability: for given x, grad_out, config and initial contents of grad_params_dev, the resulting grad_params_dev is one
+ *     bit pattern: the same across repeated calls, on any stream, whatever else the device is running, whatever the workspace
+ *     held on entry and wherever the workspace lies.  It is NOT promised to be invariant under a permutation of the points.
+ *   Accuracy: |g - ref| <= 2e-5 * sum|adds| + 1e-6 per value against the float64 oracle (tests/hashgrid_oracle.py), the atomic
+ *     route's bound.
+ *   Like tsamd_grid_encode_backward it ADDS into grad_params_dev (zero it first) and WRITES grad_x_dev (the same kernel: the
+ *     same bits).  grad_params_dev == NULL: dL/dx only, no workspace needed.
+ * The points go through in chunks of tsamd_grid_sorted_chunk_points() (a power of two), in order, on `stream`; the call makes no
+ * allocation and no host synchronisation.  workspace_dev: 256-byte aligned, at least
+ * tsamd_grid_backward_sorted_workspace_bytes(n_points, config) bytes (a function of n_points and the config only,
+ * non-decreasing in n_points and constant from one chunk on); its contents on entry do not matter.  A null, misaligned or
+ * too-small workspace is TSAMD_ERR_INVALID_ARGUMENT before anything is launched. */
+int64_t tsamd_grid_sorted_chunk_points(void);
+int tsamd_grid_backward_sorted_workspace_bytes(int64_t n_points, int32_t n_levels, int32_t n_features_per_level,
+                                               int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                                               int32_t dense, int64_t *bytes_out);
+int tsamd_grid_encode_backward_sorted(const float *x_dev, int64_t n_points, const float *params_dev, int32_t n_levels,
+                                      int32_t n_features_per_level, int32_t log2_hashmap_size, int32_t base_resolution,
+                                      float per_level_scale, int32_t dense, const float *grad_out_dev, float *grad_params_dev,
+                                      float *grad_x_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Fully fused MLP (the texture stage's colour MLP when its config names a tcnn network): tiny-cuda-nn's FullyFusedMLP,
  *   tsamd_mlp_forward  <- tcnn.Network(n_in, n_out, {"otype": "FullyFusedMLP" | "CutlassMLP" | "MLP", ...})(x)   models/networks.py:314-321

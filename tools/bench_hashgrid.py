@@ -7,7 +7,11 @@ Workloads, both with the default ExplicitMaterial config (16 levels, F = 2, T = 
            mapped into [0, 1]^3 as contract_to_unisphere does;
   random   as many uniform random points in [0, 1]^3 (the worst case: no two neighbouring lanes share a cell).
 
-    python tools/bench_hashgrid.py [--views 120 --res 512 --reps 10]
+    python tools/bench_hashgrid.py [--views 120 --res 512 --reps 10] [--param-grad atomic|sorted|both]
+
+--param-grad picks the route to dL/dparams that the HIP numbers are taken with (default: atomic).  ``both`` times the two
+routes on the same inputs in one run (HIP-event medians over --reps), reports sorted / atomic, the sorted route's workspace and
+its per-kernel split (key pass, each radix pass = histogram + scan + scatter, segmented sum + fold; torch.profiler kernel times).
 
 One JSON line per workload: Mpoints/s, ms, the gather and atomic-add bytes per second, the speed-up, the torch path's per-level
 split and the largest difference between the two paths.  Byte counts are nominal (8 corners x F x 4 B per point and level)."""
@@ -101,9 +105,47 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
-def bench(name, x, reps):
+def timed_median(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms))
+
+
+def sorted_kernel_split(fn):
+    """Device time of one call of ``fn`` per stage of the sorted route, from torch.profiler's kernel records in launch order:
+    a key kernel opens a level, every scatter closes a radix pass."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    evs = sorted((e for e in prof.events() if "grid_sorted_" in e.name), key=lambda e: e.time_range.start)
+    split, p = {}, 0
+    for e in evs:
+        us = e.device_time if hasattr(e, "device_time") else e.cuda_time
+        if "key_kernel" in e.name:
+            stage, p = "key_pass", 0
+        elif "sum_kernel" in e.name or "fold_kernel" in e.name:
+            stage = "segmented_sum"
+        else:
+            stage = f"radix_pass_{p}"
+            p += "scatter_kernel" in e.name
+        split[stage] = split.get(stage, 0.0) + us / 1e3
+    return {k: round(v, 3) for k, v in sorted(split.items())}, len(evs)
+
+
+def bench(name, x, reps, param_grad="atomic"):
     from tssplat_amd import encoding
-    enc = encoding.GridEncoding(3, DEFAULT).cuda()
+    enc = encoding.GridEncoding(3, DEFAULT, param_grad="sorted" if param_grad == "sorted" else "atomic").cuda()
     with torch.no_grad():
         enc.params.uniform_(-1, 1)
     lay = enc.layout
@@ -139,7 +181,7 @@ def bench(name, x, reps):
     gp_t = torch_fb()
     gather = N * L * 8 * F * 4
     rec = {
-        "workload": name, "points": N, "reps": reps,
+        "workload": name, "points": N, "reps": reps, "param_grad": enc.cfg["param_grad"],
         "hip_fwd_ms": round(t_hf, 3), "hip_fwd_bwd_ms": round(t_hfb, 3), "hip_bwd_ms": round(t_hfb - t_hf, 3),
         "torch_fwd_ms": round(t_tf, 3), "torch_fwd_bwd_ms": round(t_tfb, 3),
         "speedup_fwd": round(t_tf / t_hf, 2), "speedup_fwd_bwd": round(t_tfb / t_hfb, 2),
@@ -152,6 +194,36 @@ def bench(name, x, reps):
         "max_abs_diff_dparams": float((enc.params.grad - gp_t).abs().max()),
         "max_abs_dparams": float(gp_t.abs().max()),
     }
+    if param_grad == "both":
+        other = encoding.GridEncoding(3, DEFAULT, param_grad="sorted").cuda()
+        with torch.no_grad():
+            other.params.copy_(enc.params)
+
+        def sorted_fb():
+            other.params.grad = None
+            other(x).backward(g)
+
+        t_fwd = timed_median(hip_fwd, reps)
+        t_atomic, t_sorted = timed_median(hip_fb, reps), timed_median(sorted_fb, reps)
+        sorted_fb()
+        first = other.params.grad.clone()
+        sorted_fb()
+        try:
+            split, n_kernels = sorted_kernel_split(sorted_fb)
+        except Exception as e:                                        # (a profiler that is not there is said, not hidden)
+            split, n_kernels = f"torch.profiler failed: {e!r}", 0
+        records = N * L * 8
+        rec["param_grad_compare"] = {
+            "fwd_ms_median": round(t_fwd, 3),
+            "atomic_fwd_bwd_ms_median": round(t_atomic, 3), "sorted_fwd_bwd_ms_median": round(t_sorted, 3),
+            "atomic_bwd_ms": round(t_atomic - t_fwd, 3), "sorted_bwd_ms": round(t_sorted - t_fwd, 3),
+            "sorted_over_atomic_fwd_bwd": round(t_sorted / t_atomic, 3),
+            "sorted_over_atomic_bwd": round((t_sorted - t_fwd) / max(t_atomic - t_fwd, 1e-6), 3),
+            "sorted_workspace_bytes": encoding.sorted_workspace_bytes(other.cfg, N),
+            "sorted_records": records, "sorted_kernel_ms": split, "sorted_kernel_launches": n_kernels,
+            "sorted_repeats_bitwise": bool(torch.equal(first, other.params.grad)),
+            "sorted_max_abs_diff_dparams": float((other.params.grad - gp_t).abs().max()),
+        }
     return rec
 
 
@@ -160,13 +232,14 @@ def main():
     ap.add_argument("--views", type=int, default=120)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--param-grad", choices=("atomic", "sorted", "both"), default="atomic")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.cuda.set_device(0)
     pts = texture_points(a.views, a.res)
-    recs = [bench(f"texture_{a.views}x{a.res}", pts, a.reps)]
+    recs = [bench(f"texture_{a.views}x{a.res}", pts, a.reps, a.param_grad)]
     g = torch.Generator(device="cuda").manual_seed(0)
-    recs.append(bench("random_unit_cube", torch.rand(pts.shape[0], 3, device="cuda", generator=g), a.reps))
+    recs.append(bench("random_unit_cube", torch.rand(pts.shape[0], 3, device="cuda", generator=g), a.reps, a.param_grad))
     for r in recs:
         print(json.dumps(r))
     if a.out:

@@ -4,7 +4,8 @@ VanillaMLP) as the renderer's materials, `L1Loss` on RGB x 20, AdamUniform over 
 here from a known colour field on tests/golden/mario_mesh.npz under scenes.dataset_mvps(views) (the reference's img_data/ is
 empty).
 
-    python tools/train_texture.py [--views 16 --res 256 --iters 300 --lr 0.01 --mlp VanillaMLP|FullyFusedMLP]
+    python tools/train_texture.py [--views 16 --res 256 --iters 300 --lr 0.01 --mlp VanillaMLP|FullyFusedMLP
+                                    --param-grad atomic|sorted]
 
 One JSON line: the loss at the first and last iteration, ms per iteration, and the split of one iteration's forward + backward
 into encode (hash grid), MLP and the rest (rasterise, interpolate, antialias, loss), timed stage by stage on the same points."""
@@ -40,7 +41,7 @@ def timed(fn, reps=5):
     return a.elapsed_time(b) / reps
 
 
-def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP"):
+def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_grad="atomic"):
     from tssplat_amd import geometry, materials, renderers, scenes
     from tssplat_amd.utils.optimizer import AdamUniform
     torch.cuda.set_device(0)
@@ -57,6 +58,8 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP"):
     if mlp_otype != "VanillaMLP":                      # the default config's 32 -> 64 -> 3 network, served by tcnn.Network
         cfg["mlp_network_config"] = {"otype": mlp_otype, "activation": "ReLU", "output_activation": "none", "n_neurons": 64,
                                      "n_hidden_layers": 1}
+    if param_grad != "atomic":                         # the encoding's route to dL/dparams, as a key of its config
+        cfg["pos_encoding_config"] = dict(materials.ExplicitMaterial.Config(**cfg).pos_encoding_config, param_grad=param_grad)
     mat = materials.ExplicitMaterial(cfg)
     ren = renderers.MeshRasterizer(geo, mat)
     opt = AdamUniform(ren.parameters(), lr=lr)
@@ -100,7 +103,7 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP"):
     def mlp_fb():
         mlp(e.requires_grad_(True)).backward(gm)
     ms_enc, ms_mlp = timed(enc_fb), timed(mlp_fb)
-    return {"views": views, "res": res, "iters": iters, "lr": lr, "mlp": mlp_otype, "foreground_points": int(pts.shape[0]),
+    return {"views": views, "res": res, "iters": iters, "lr": lr, "mlp": mlp_otype, "param_grad": param_grad, "foreground_points": int(pts.shape[0]),
             "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)], "loss_ratio": round(losses[-1] / losses[0], 4),
             "ms_per_iter": round(ms_iter, 3),
             "split_ms": {"encode_fwd_bwd": round(ms_enc, 3), "mlp_fwd_bwd": round(ms_mlp, 3),
@@ -114,8 +117,10 @@ def main():
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--mlp", default="VanillaMLP", help="mlp_network_config otype (VanillaMLP or FullyFusedMLP)")
+    ap.add_argument("--param-grad", choices=("atomic", "sorted"), default="atomic",
+                    help="the hash grid's route to dL/dparams (sorted: bitwise repeatable)")
     a = ap.parse_args()
-    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp)))
+    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp, a.param_grad)))
 
 
 if __name__ == "__main__":

@@ -33,4 +33,53 @@ hipError_t launch_grid_encode(const float *x, int64_t n, const float *params, co
 hipError_t launch_grid_encode_backward(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features,
                                        const float *grad_out, float *grad_params, float *grad_x, hipStream_t stream);
 
+// The sorted route to dL/dparams: no float atomics.  Contract:
+//  * Repeatability: for given x, grad_out, config and initial contents of grad_params the resulting grad_params is ONE bit
+//    pattern -- across repeated calls, on any stream, whatever else the device runs, whatever the workspace held on entry and
+//    wherever it lies.  Every entry's adds are summed in an order fixed by (n, config) and the points' order; the result is not
+//    promised to be invariant under a permutation of the points.
+//  * Accuracy: |g - ref| <= 2e-5 * sum|adds| + 1e-6 against the float64 oracle (tests/hashgrid_oracle.py::encode_backward), the
+//    bound of the atomic route; fp32 sums of 512-record chunks added in chunk order stay orders of magnitude inside it.
+//  * Like the atomic route it ADDS into grad_params (zero it first).  dL/dx is the atomic route's kernel, bit for bit.
+//  * Points go through in chunks of kGridSortedChunk, in order, on the caller's stream; the workspace is bounded by one chunk.
+//    No allocation, no host synchronisation; all launch geometry is a function of (n, config).
+constexpr int64_t kGridSortedChunk = int64_t(1) << 20;     // points per chunk (8 records each)
+constexpr int kGridSortTile = 4096;                        // records per workgroup of a radix pass
+constexpr int kGridSumRun = 512;                           // records per wave of the segmented sum
+constexpr int64_t kGridWorkspaceAlign = 256;
+
+// Byte offsets of the workspace's parts (each kGridWorkspaceAlign-aligned) and its size: a function of min(n, chunk) and F.
+struct GridSortedWorkspace {
+    int64_t rec_a, rec_b;      // 8-byte records (entry << 32 | 8 * point + corner), ping and pong
+    int64_t gl;                // the level's grad_out slice, [points, F] f32
+    int64_t hist, tot;         // [256][tiles] digit counts of a radix pass, and the 256 digit totals
+    int64_t pkey, psum;        // boundary partials of the segmented sum: [2 * waves] keys, [2 * waves, F] sums
+    int64_t bytes;
+};
+
+inline GridSortedWorkspace grid_sorted_workspace(int64_t n, int32_t n_features)
+{
+    const int64_t nc = n < 0 ? 0 : (n < kGridSortedChunk ? n : kGridSortedChunk), n_rec = nc * 8;
+    const int64_t tiles = (n_rec + kGridSortTile - 1) / kGridSortTile, waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
+    GridSortedWorkspace ws{};
+    int64_t at = 0;
+    const auto take = [&at](int64_t bytes) {
+        const int64_t here = at;
+        at += (bytes + kGridWorkspaceAlign - 1) / kGridWorkspaceAlign * kGridWorkspaceAlign;
+        return here;
+    };
+    ws.rec_a = take(n_rec * 8);
+    ws.rec_b = take(n_rec * 8);
+    ws.gl = take(nc * n_features * 4);
+    ws.hist = take(256 * tiles * 4);
+    ws.tot = take(256 * 4);
+    ws.pkey = take(2 * waves * 4);
+    ws.psum = take(2 * waves * n_features * 4);
+    ws.bytes = nc > 0 ? at : 0;
+    return ws;
+}
+
+hipError_t launch_grid_encode_backward_sorted(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features,
+                                              const float *grad_out, float *grad_params, float *grad_x, void *workspace, hipStream_t stream);
+
 }  // namespace tsamd

@@ -158,4 +158,49 @@ int tsamd_grid_encode_backward(const float *x_dev, int64_t n_points, const float
     return TSAMD_OK;
 }
 
+int64_t tsamd_grid_sorted_chunk_points(void) { return tsamd::kGridSortedChunk; }
+
+int tsamd_grid_backward_sorted_workspace_bytes(int64_t n_points, int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size,
+                                               int32_t base_resolution, float per_level_scale, int32_t dense, int64_t *bytes_out)
+{
+    tsamd::GridLevels lv;
+    int64_t n_params = 0;
+    const int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
+    if (rc) return rc;
+    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
+    if (!bytes_out) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: bytes_out is null");
+    *bytes_out = tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes;
+    return TSAMD_OK;
+}
+
+int tsamd_grid_encode_backward_sorted(const float *x_dev, int64_t n_points, const float *params_dev, int32_t n_levels,
+                                      int32_t n_features_per_level, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                                      int32_t dense, const float *grad_out_dev, float *grad_params_dev, float *grad_x_dev, void *workspace_dev,
+                                      int64_t workspace_bytes, void *stream)
+{
+    tsamd::GridLevels lv;
+    int64_t n_params = 0;
+    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
+    if (rc) return rc;
+    rc = check_pointers(n_points, x_dev, params_dev, n_features_per_level);
+    if (rc) return rc;
+    if (n_points > 0 && !grad_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev is null");
+    const uintptr_t align = n_features_per_level == 1 ? 4 : (n_features_per_level == 2 ? 8 : 16);
+    if (reinterpret_cast<uintptr_t>(grad_out_dev) % align || reinterpret_cast<uintptr_t>(grad_params_dev) % align)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev / grad_params_dev not aligned to n_features_per_level floats (max 16 B)");
+    if (reinterpret_cast<uintptr_t>(grad_x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_x_dev is not float-aligned");
+    if (grad_params_dev) {                            // (dL/dx only needs no workspace)
+        const int64_t need = tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes;
+        if (need > 0 && !workspace_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is null");
+        if (reinterpret_cast<uintptr_t>(workspace_dev) % tsamd::kGridWorkspaceAlign)
+            return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is not aligned to 256 bytes");
+        if (workspace_bytes < need)
+            return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_bytes = " + std::to_string(workspace_bytes) + ", the sorted backward needs " +
+                                                             std::to_string(need) + " (tsamd_grid_backward_sorted_workspace_bytes)");
+    }
+    TSAMD_HIP(tsamd::launch_grid_encode_backward_sorted(x_dev, n_points, params_dev, lv, n_features_per_level, grad_out_dev, grad_params_dev,
+                                                        grad_x_dev, workspace_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
 }  // extern "C"

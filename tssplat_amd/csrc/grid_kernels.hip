@@ -9,9 +9,12 @@
 //                                    a wave that hit the same entry with the same corner (neighbouring pixels in one cell)
 //                                    summed their adds on chip
 //   grid_backward_x_kernel           dL/dx, one lane per point looping over the levels: plain stores, bitwise repeatable
+//   grid_sorted_*_kernel             the second route to dL/dparams (launch_grid_encode_backward_sorted), every level alike:
+//                                    (entry, source) records, a stable radix sort by entry, a segmented sum; no float atomics
 //
-// The forward and dL/dx are bitwise deterministic (fixed summation order); dL/dparams is a float-atomic sum and may differ in
-// the last bits from run to run (tiny-cuda-nn's is too).
+// The forward and dL/dx are bitwise deterministic (fixed summation order).  dL/dparams has two routes: the default one is a
+// float-atomic sum and may differ in the last bits from run to run (tiny-cuda-nn's does too); the sorted one adds every entry's
+// contributions in a fixed order and is bitwise repeatable (contract: grid.h).
 #include <hip/hip_runtime.h>
 
 #include "grid.h"
@@ -312,7 +315,403 @@ hipError_t backward_f(const float *x, int64_t n, const float *params, const Grid
     return hipSuccess;
 }
 
+// ------------------------------------------------------------------------------------------------ the sorted dL/dparams route
+// Per chunk of at most kGridSortedChunk points and per level: a key pass writes one record (entry << 32 | 8 * point + corner)
+// per (point, corner) and the level's slice of grad_out as a compact array; a stable LSD radix sort (8-bit digits, only the
+// bits the level's entry count needs) orders the records by entry; a segmented sum rebuilds w * g per record from the compact
+// arrays and adds every entry's run in a fixed order.  No float atomics; the only atomics count digits in LDS.
+using Rec = unsigned long long;
+
+constexpr int kSortBlock = 256;
+constexpr int kSortWaves = kSortBlock / 64;
+constexpr int kSortItems = kGridSortTile / kSortBlock;                 // records per lane of a sort tile
+constexpr int kSumSteps = kGridSumRun / 64;
+static_assert(kGridSortTile % (8 * kSortBlock) == 0 && kGridSumRun % 64 == 0, "tile / run sizes");
+
+// Exclusive prefix of v over the workgroup's kSortBlock threads in thread order (integer: exact), and the total.
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *wave_sums, uint32_t &total)
+{
+    const int lane = __lane_id(), wave = threadIdx.x / 64;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wave_sums[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kSortWaves; ++w) {
+        const uint32_t s = wave_sums[w];
+        if (w < wave) before += s;
+        total += s;
+    }
+    __syncthreads();
+    return before + inc - v;
+}
+
+// One workgroup per sort tile (kGridSortTile records = kGridSortTile / 8 points): records in (point, corner) order, the level's
+// grad_out slice compacted into gl, and the tile's histogram of the first digit.  hist is [digit][tile].
+template <int F>
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_key_kernel(const float *__restrict__ x, uint32_t n, GridLevels lv, int l,
+                                                                     const float *__restrict__ grad_out, Rec *__restrict__ rec,
+                                                                     float *__restrict__ gl, uint32_t *__restrict__ hist, uint32_t n_tiles)
+{
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const float scale = lv.scale[l];
+    const uint32_t res = lv.res[l], entries = lv.entries[l];
+    const bool hashed = lv.hashed[l] != 0;
+    const int64_t row = int64_t(lv.n_levels) * F;
+#pragma unroll
+    for (int r = 0; r < kGridSortTile / (8 * kSortBlock); ++r) {
+        const uint32_t i = blockIdx.x * (kGridSortTile / 8) + r * kSortBlock + threadIdx.x;
+        if (i >= n) continue;
+        float p[3], g[F];
+        load_point(x, i, p);
+        load_feat<F>(grad_out + i * row + int64_t(l) * F, g);
+        store_feat<F>(gl + int64_t(i) * F, g);
+        const Cell cl = cell_of(p, scale);
+        ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(rec + int64_t(i) * 8);
+#pragma unroll
+        for (int c = 0; c < 8; c += 2) {
+            const uint32_t k0 = corner_index(cl, c, res, entries, hashed), k1 = corner_index(cl, c + 1, res, entries, hashed);
+            dst[c / 2] = make_ulonglong2((Rec(k0) << 32) | (i * 8 + c), (Rec(k1) << 32) | (i * 8 + c + 1));
+            atomicAdd(&h[k0 & 0xff], 1u);
+            atomicAdd(&h[k1 & 0xff], 1u);
+        }
+    }
+    __syncthreads();
+    hist[threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// The per-tile digit histogram of a later radix pass.
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_hist_kernel(const Rec *__restrict__ rec, uint32_t n_rec, int shift,
+                                                                      uint32_t *__restrict__ hist, uint32_t n_tiles)
+{
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kSortItems; ++k) {
+        const uint32_t pos = blockIdx.x * kGridSortTile + k * kSortBlock + threadIdx.x;
+        if (pos < n_rec) atomicAdd(&h[uint32_t(rec[pos] >> (32 + shift)) & 0xff], 1u);
+    }
+    __syncthreads();
+    hist[threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// One workgroup per digit: its row of tile counts becomes the exclusive prefix inside the digit, tot[digit] the digit's count.
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_scan_kernel(uint32_t *__restrict__ hist, uint32_t n_tiles, uint32_t *__restrict__ tot)
+{
+    __shared__ uint32_t wave_sums[kSortWaves];
+    uint32_t *row = hist + blockIdx.x * n_tiles;
+    const uint32_t per = (n_tiles + kSortBlock - 1) / kSortBlock;
+    const uint32_t b = threadIdx.x * per, e = b + per < n_tiles ? b + per : n_tiles;
+    uint32_t s = 0;
+    for (uint32_t j = b; j < e; ++j) s += row[j];
+    uint32_t total;
+    uint32_t run = block_exclusive_scan(s, wave_sums, total);
+    for (uint32_t j = b; j < e; ++j) {
+        const uint32_t t = row[j];
+        row[j] = run;
+        run += t;
+    }
+    if (threadIdx.x == 0) tot[blockIdx.x] = total;
+}
+
+// Stable scatter of one radix pass.  Wave w of a tile owns the tile's w-th quarter and walks it 64 records at a time, so
+// (tile, wave, step, lane) is the input order.  A record's rank among the records of its digit: the digit's global base (scan
+// of tot), the tile's prefix inside the digit (hist), the earlier waves' counts (cnt after phase 2), the wave's earlier steps
+// (cnt, advanced by the first lane of each match group) and the lower lanes of its match mask.  Nothing takes an order from
+// the return value of an atomic.
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_scatter_kernel(const Rec *__restrict__ in, uint32_t n_rec, int shift,
+                                                                         const uint32_t *__restrict__ hist, const uint32_t *__restrict__ tot,
+                                                                         uint32_t n_tiles, Rec *__restrict__ out)
+{
+    __shared__ uint32_t cnt[kSortWaves][256];
+    __shared__ uint32_t wave_sums[kSortWaves];
+    const int lane = __lane_id(), wave = threadIdx.x / 64;
+#pragma unroll
+    for (int w = 0; w < kSortWaves; ++w) cnt[w][threadIdx.x] = 0;
+    uint32_t total;
+    const uint32_t digit_base = block_exclusive_scan(tot[threadIdx.x], wave_sums, total);     // (its barriers cover the zeroing)
+    const uint32_t wbase = blockIdx.x * kGridSortTile + wave * (kGridSortTile / kSortWaves);
+    Rec r[kSortItems];
+#pragma unroll
+    for (int k = 0; k < kSortItems; ++k) {
+        const uint32_t pos = wbase + k * 64 + lane;
+        r[k] = pos < n_rec ? in[pos] : ~Rec(0);
+        if (pos < n_rec) atomicAdd(&cnt[wave][uint32_t(r[k] >> (32 + shift)) & 0xff], 1u);
+    }
+    __syncthreads();
+    {
+        uint32_t run = digit_base + hist[threadIdx.x * n_tiles + blockIdx.x];
+#pragma unroll
+        for (int w = 0; w < kSortWaves; ++w) {
+            const uint32_t t = cnt[w][threadIdx.x];
+            cnt[w][threadIdx.x] = run;
+            run += t;
+        }
+    }
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1;
+#pragma unroll
+    for (int k = 0; k < kSortItems; ++k) {
+        const bool valid = wbase + k * 64 + lane < n_rec;
+        const uint32_t digit = uint32_t(r[k] >> (32 + shift)) & 0xff;
+        unsigned long long mask = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (digit >> b) & 1;
+            const unsigned long long m = __ballot(valid && bit);
+            mask &= bit ? m : ~m;
+        }
+        if (valid) {
+            const uint32_t base = cnt[wave][digit];
+            const uint32_t rank = __popcll(mask & below);
+            if (base + rank < n_rec) out[base + rank] = r[k];       // (always true; keeps a broken count from writing outside)
+            if (rank == 0) cnt[wave][digit] = base + __popcll(mask);
+        }
+        __syncthreads();                              // the next step reads what the group leaders stored
+    }
+}
+
+// As combine_runs, but returns the mask of run heads (every lane of the wave must call it).
+template <int F>
+__device__ __forceinline__ unsigned long long segment_sums(uint32_t key, float (&v)[F])
+{
+    const int lane = __lane_id();
+    const uint32_t prev = __shfl_up(key, 1);
+    const unsigned long long heads = __ballot(lane == 0 || prev != key);
+    if (heads == ~0ull) return heads;
+    const unsigned long long rest = lane == 63 ? 0ull : (heads >> (lane + 1));
+    const int end = rest ? lane + __ffsll(static_cast<long long>(rest)) - 1 : 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            const float o = __shfl_down(v[f], d);
+            if (lane + d <= end) v[f] += o;
+        }
+    }
+    return heads;
+}
+
+// Plain load - add - store by the one lane that owns the entry in this launch.
+template <int F>
+__device__ __forceinline__ void add_entry(float *table, uint32_t key, const float (&v)[F])
+{
+    float t[F];
+    float *dst = table + int64_t(key) * F;
+    load_feat<F>(dst, t);
+#pragma unroll
+    for (int f = 0; f < F; ++f) t[f] += v[f];
+    store_feat<F>(dst, t);
+}
+
+// Segmented sum over the sorted records: one wave per kGridSumRun consecutive records, 64 at a time.  A run of equal keys
+// inside a step is summed by segment_sums (a tree fixed by the lane positions); a run that goes on into the next step is
+// carried wave-uniformly and added in step order.  A run that lies strictly inside the wave's range is added to the table
+// here (no other wave sees its key); the run that starts at the range's first record and the one that ends at its last may
+// go on in the neighbouring waves, so they go to pkey / psum ([2 * wave]: first, [2 * wave + 1]: last, kInvalid: none) for
+// grid_sorted_fold_kernel.  A range that is one single run is its first partial.
+template <int F>
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_sum_kernel(const Rec *__restrict__ rec, uint32_t n_rec, const float *__restrict__ x,
+                                                                     const float *__restrict__ gl, float scale, uint32_t entries,
+                                                                     float *__restrict__ table, uint32_t *__restrict__ pkey,
+                                                                     float *__restrict__ psum)
+{
+    const int lane = __lane_id();
+    const uint32_t wave = blockIdx.x * kSortWaves + threadIdx.x / 64;
+    const uint32_t wbase = wave * kGridSumRun;
+    if (wbase >= n_rec) return;                       // (whole waves only; no workgroup barrier below)
+    uint32_t ckey = kInvalid, fkey = kInvalid;        // the open run at the end of the last step; the range's first run once closed
+    bool cfirst = false;                              // the open run started at the range's first record
+    float csum[F], fsum[F];
+#pragma unroll
+    for (int f = 0; f < F; ++f) csum[f] = fsum[f] = 0.0f;
+    for (int s = 0; s < kSumSteps; ++s) {
+        const uint32_t pos = wbase + s * 64 + lane;
+        uint32_t key = kInvalid;
+        float v[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) v[f] = 0.0f;
+        const Rec r = pos < n_rec ? rec[pos] : ~Rec(0);
+        const uint32_t src = uint32_t(r), i = src >> 3;
+        if (uint32_t(r >> 32) < entries && src < n_rec) key = uint32_t(r >> 32);   // (a record is followed only while in bounds)
+        if (key != kInvalid) {
+            float p[3], g[F];
+            load_point(x, i, p);
+            load_feat<F>(gl + int64_t(i) * F, g);
+            const float w = corner_weight(cell_of(p, scale), int(src & 7));
+#pragma unroll
+            for (int f = 0; f < F; ++f) v[f] = w * g[f];
+        }
+        const unsigned long long heads = segment_sums<F>(key, v);
+        const bool head = (heads >> lane) & 1;
+        const int last_head = 63 - __clzll(static_cast<long long>(heads));
+        const uint32_t key0 = __shfl(key, 0);
+        const bool first0 = s == 0 || (ckey == key0 && cfirst);           // lane 0's run started at the range's first record
+        if (ckey != kInvalid) {
+            if (ckey == key0) {
+                if (lane == 0) {
+#pragma unroll
+                    for (int f = 0; f < F; ++f) v[f] = csum[f] + v[f];
+                }
+            } else if (cfirst) {
+                fkey = ckey;
+#pragma unroll
+                for (int f = 0; f < F; ++f) fsum[f] = csum[f];
+            } else if (lane == 0) {
+                add_entry<F>(table, ckey, csum);
+            }
+        }
+        float v0[F], vl[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            v0[f] = __shfl(v[f], 0);
+            vl[f] = __shfl(v[f], last_head);
+        }
+        const uint32_t keyl = __shfl(key, last_head);
+        if (last_head != 0 && key0 != kInvalid && first0) {               // the first run closes in this step
+            fkey = key0;
+#pragma unroll
+            for (int f = 0; f < F; ++f) fsum[f] = v0[f];
+        }
+        if (head && lane != last_head && key != kInvalid && !(lane == 0 && first0)) add_entry<F>(table, key, v);
+        ckey = keyl;
+        cfirst = last_head == 0 && first0;
+#pragma unroll
+        for (int f = 0; f < F; ++f) csum[f] = vl[f];
+    }
+    if (ckey != kInvalid && cfirst) {
+        fkey = ckey;
+        ckey = kInvalid;
+#pragma unroll
+        for (int f = 0; f < F; ++f) fsum[f] = csum[f];
+    }
+    if (lane == 0) {
+        pkey[2 * wave] = fkey;
+        pkey[2 * wave + 1] = ckey;
+        store_feat<F>(psum + int64_t(2 * wave) * F, fsum);
+        store_feat<F>(psum + int64_t(2 * wave + 1) * F, csum);
+    }
+}
+
+// The boundary partials in wave order: the lane of an entry's first partial adds the entry's partials in that order.
+template <int F>
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_fold_kernel(const uint32_t *__restrict__ pkey, const float *__restrict__ psum,
+                                                                      uint32_t n_part, float *__restrict__ table)
+{
+    const uint32_t j = blockIdx.x * kSortBlock + threadIdx.x;
+    if (j >= n_part) return;
+    const uint32_t key = pkey[j];
+    if (key == kInvalid) return;
+    if (j > 0) {                                      // (a range's first partial always exists: no two kInvalid in a row)
+        uint32_t before = pkey[j - 1];
+        if (before == kInvalid && j > 1) before = pkey[j - 2];
+        if (before == key) return;
+    }
+    float sum[F];
+    load_feat<F>(psum + int64_t(j) * F, sum);
+    for (uint32_t k = j + 1; k < n_part; ++k) {
+        const uint32_t other = pkey[k];
+        if (other == kInvalid) continue;
+        if (other != key) break;
+        float t[F];
+        load_feat<F>(psum + int64_t(k) * F, t);
+#pragma unroll
+        for (int f = 0; f < F; ++f) sum[f] += t[f];
+    }
+    add_entry<F>(table, key, sum);
+}
+
+inline int key_bits(uint32_t entries)
+{
+    int bits = 1;
+    while (bits < 32 && (uint64_t(1) << bits) < entries) ++bits;
+    return bits;
+}
+
+#define TSAMD_GRID_LAUNCHED()                            \
+    do {                                                 \
+        const hipError_t e_ = hipGetLastError();         \
+        if (e_ != hipSuccess) return e_;                 \
+    } while (0)
+
+template <int F>
+hipError_t backward_sorted_f(const float *x, int64_t n, const float *params, const GridLevels &lv, const float *grad_out, float *grad_params,
+                             float *grad_x, void *workspace, hipStream_t stream)
+{
+    if (grad_params) {
+        const GridSortedWorkspace ws = grid_sorted_workspace(n, F);
+        char *base = static_cast<char *>(workspace);
+        Rec *rec_a = reinterpret_cast<Rec *>(base + ws.rec_a), *rec_b = reinterpret_cast<Rec *>(base + ws.rec_b);
+        float *gl = reinterpret_cast<float *>(base + ws.gl), *psum = reinterpret_cast<float *>(base + ws.psum);
+        uint32_t *hist = reinterpret_cast<uint32_t *>(base + ws.hist), *tot = reinterpret_cast<uint32_t *>(base + ws.tot);
+        uint32_t *pkey = reinterpret_cast<uint32_t *>(base + ws.pkey);
+        const int64_t row = int64_t(lv.n_levels) * F;
+        for (int64_t first = 0; first < n; first += kGridSortedChunk) {           // chunks in order: part of the summation order
+            const uint32_t nc = uint32_t(n - first < kGridSortedChunk ? n - first : kGridSortedChunk);
+            const uint32_t n_rec = nc * 8;
+            const uint32_t n_tiles = (n_rec + kGridSortTile - 1) / kGridSortTile, n_waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
+            const float *xc = x + first * 3, *gc = grad_out + first * row;
+            for (int l = 0; l < lv.n_levels; ++l) {
+                hipLaunchKernelGGL(grid_sorted_key_kernel<F>, dim3(n_tiles), dim3(kSortBlock), 0, stream, xc, nc, lv, l, gc, rec_a, gl, hist, n_tiles);
+                TSAMD_GRID_LAUNCHED();
+                Rec *src = rec_a, *dst = rec_b;
+                const int passes = (key_bits(lv.entries[l]) + 7) / 8;
+                for (int p = 0; p < passes; ++p) {
+                    if (p > 0) {
+                        hipLaunchKernelGGL(grid_sorted_hist_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, n_tiles);
+                        TSAMD_GRID_LAUNCHED();
+                    }
+                    hipLaunchKernelGGL(grid_sorted_scan_kernel, dim3(256), dim3(kSortBlock), 0, stream, hist, n_tiles, tot);
+                    TSAMD_GRID_LAUNCHED();
+                    hipLaunchKernelGGL(grid_sorted_scatter_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, tot, n_tiles,
+                                       dst);
+                    TSAMD_GRID_LAUNCHED();
+                    Rec *t = src;
+                    src = dst;
+                    dst = t;
+                }
+                float *table = grad_params + lv.offset[l] * F;
+                hipLaunchKernelGGL(grid_sorted_sum_kernel<F>, dim3((n_waves + kSortWaves - 1) / kSortWaves), dim3(kSortBlock), 0, stream, src, n_rec,
+                                   xc, gl, lv.scale[l], lv.entries[l], table, pkey, psum);
+                TSAMD_GRID_LAUNCHED();
+                hipLaunchKernelGGL(grid_sorted_fold_kernel<F>, dim3((2 * n_waves + kSortBlock - 1) / kSortBlock), dim3(kSortBlock), 0, stream, pkey,
+                                   psum, 2 * n_waves, table);
+                TSAMD_GRID_LAUNCHED();
+            }
+        }
+    }
+    if (grad_x) {
+        hipLaunchKernelGGL(grid_backward_x_kernel<F>, dim3(blocks_of(n)), dim3(kBlock), 0, stream, x, n, params, lv, grad_out, grad_x);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+#undef TSAMD_GRID_LAUNCHED
+
 }  // namespace
+
+hipError_t launch_grid_encode_backward_sorted(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features,
+                                              const float *grad_out, float *grad_params, float *grad_x, void *workspace, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    switch (n_features) {
+    case 1: return backward_sorted_f<1>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
+    case 2: return backward_sorted_f<2>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
+    case 4: return backward_sorted_f<4>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
+    case 8: return backward_sorted_f<8>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t launch_grid_encode(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features, float *out,
                               hipStream_t stream)

@@ -20,15 +20,20 @@ import torch
 from . import _capi
 from .tet_spheres_ext import _device_ctx, _stream_ptr
 
-__all__ = ["GridEncoding", "parse_grid_config", "grid_layout"]
+__all__ = ["GridEncoding", "parse_grid_config", "grid_layout", "sorted_workspace_bytes"]
 
 _lib = _capi.load()
 
 _OTYPES = {"hashgrid": "Hash", "densegrid": "Dense", "grid": None}
 
 
-def parse_grid_config(n_input_dims: int, config: dict) -> dict:
-    """The accepted ``tcnn.Encoding`` grid configs, normalised; ValueError on anything else."""
+PARAM_GRAD_MODES = ("atomic", "sorted")
+
+
+def parse_grid_config(n_input_dims: int, config: dict, param_grad: str | None = None) -> dict:
+    """The accepted ``tcnn.Encoding`` grid configs, normalised; ValueError on anything else.  ``param_grad`` (the keyword, else
+    the config key of that name, else ``"atomic"``) picks the route to dL/dparams: ``"atomic"`` (float atomics, last bits may
+    differ between runs) or ``"sorted"`` (radix sort + fixed-order sums, bitwise repeatable; csrc/grid.h states the contract)."""
     cfg = dict(config)
     otype = str(cfg.get("otype", "")).lower()
     if otype not in _OTYPES:
@@ -48,7 +53,10 @@ def parse_grid_config(n_input_dims: int, config: dict) -> dict:
         "base_resolution": int(cfg.get("base_resolution", 16)),
         "per_level_scale": float(cfg.get("per_level_scale", 2.0)),
         "dense": gtype == "Dense",
+        "param_grad": cfg.get("param_grad", "atomic") if param_grad is None else param_grad,
     }
+    if out["param_grad"] not in PARAM_GRAD_MODES:
+        raise ValueError(f"tssplat_amd encoding: param_grad = {out['param_grad']!r} ('atomic' or 'sorted' only)")
     if out["n_features_per_level"] not in (1, 2, 4, 8):
         raise ValueError(f"tssplat_amd encoding: n_features_per_level = {out['n_features_per_level']} (1, 2, 4 or 8 only)")
     return out
@@ -69,6 +77,13 @@ def grid_layout(cfg: dict) -> dict:
     n = C.c_int64(0)
     _capi.check(_lib.tsamd_grid_layout(*_args(cfg), off.ctypes.data, res.ctypes.data, hashed.ctypes.data, scale.ctypes.data, C.byref(n)))
     return {"offset": off, "res": res, "is_hash": hashed.astype(bool), "scale": scale, "n_params": int(n.value)}
+
+
+def sorted_workspace_bytes(cfg: dict, n_points: int) -> int:
+    """Bytes of workspace the sorted backward needs for ``n_points`` (tsamd_grid_backward_sorted_workspace_bytes; host only)."""
+    n = C.c_int64(0)
+    _capi.check(_lib.tsamd_grid_backward_sorted_workspace_bytes(int(n_points), *_args(cfg), C.byref(n)))
+    return int(n.value)
 
 
 def _check_input(x: torch.Tensor, n_input_dims: int) -> torch.Tensor:
@@ -102,19 +117,25 @@ class _GridEncodeFunc(torch.autograd.Function):
         N = int(x.shape[0])
         grad_p = torch.zeros_like(params) if need_p else None
         grad_x = torch.empty_like(x) if need_x else None
+        ptr = lambda t: None if t is None else t.data_ptr()
         with _device_ctx(x.device):
-            _capi.check(_lib.tsamd_grid_encode_backward(x.data_ptr(), N, params.data_ptr(), *_args(ctx.cfg), g.data_ptr(),
-                                                        None if grad_p is None else grad_p.data_ptr(),
-                                                        None if grad_x is None else grad_x.data_ptr(), _stream_ptr(x.device)))
+            if ctx.cfg["param_grad"] == "sorted" and need_p:
+                ws = torch.empty(sorted_workspace_bytes(ctx.cfg, N), dtype=torch.uint8, device=x.device)
+                _capi.check(_lib.tsamd_grid_encode_backward_sorted(x.data_ptr(), N, params.data_ptr(), *_args(ctx.cfg), g.data_ptr(),
+                                                                   ptr(grad_p), ptr(grad_x), ws.data_ptr(), ws.numel(),
+                                                                   _stream_ptr(x.device)))
+            else:
+                _capi.check(_lib.tsamd_grid_encode_backward(x.data_ptr(), N, params.data_ptr(), *_args(ctx.cfg), g.data_ptr(),
+                                                            ptr(grad_p), ptr(grad_x), _stream_ptr(x.device)))
         return grad_x, grad_p, None, None
 
 
 class GridEncoding(torch.nn.Module):
     """``tcnn.Encoding(3, grid_config)``: ``forward(x [N, 3] fp32 on the GPU) -> [N, n_levels * n_features_per_level]``."""
 
-    def __init__(self, n_input_dims: int, config: dict, seed: int = 1337):
+    def __init__(self, n_input_dims: int, config: dict, seed: int = 1337, param_grad: str | None = None):
         super().__init__()
-        self.cfg = parse_grid_config(n_input_dims, config)
+        self.cfg = parse_grid_config(n_input_dims, config, param_grad)
         self.layout = grid_layout(self.cfg)
         self.n_input_dims = n_input_dims
         self.n_output_dims = self.cfg["n_levels"] * self.cfg["n_features_per_level"]
@@ -133,5 +154,5 @@ class GridEncoding(torch.nn.Module):
         c = self.cfg
         return (f"{'Dense' if c['dense'] else 'Hash'}, n_levels={c['n_levels']}, F={c['n_features_per_level']}, "
                 f"log2_T={c['log2_hashmap_size']}, base={c['base_resolution']}, per_level_scale={c['per_level_scale']:.6g}, "
-                f"n_params={self.layout['n_params']}")
+                f"n_params={self.layout['n_params']}, param_grad={c['param_grad']}")
 

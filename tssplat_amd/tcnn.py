@@ -18,12 +18,13 @@ __all__ = ["Encoding", "Network", "NetworkWithInputEncoding"]
 
 class Encoding(GridEncoding):
     """``tcnn.Encoding(n_input_dims, encoding_config, seed=1337, dtype=None)`` for the grid encodings (HashGrid, DenseGrid,
-    Grid with type Hash / Dense); fp32 only."""
+    Grid with type Hash / Dense); fp32 only.  ``param_grad`` ("atomic" | "sorted", also a config key) is this package's own:
+    the route to dL/dparams (:func:`tssplat_amd.encoding.parse_grid_config`)."""
 
-    def __init__(self, n_input_dims: int, encoding_config: dict, seed: int = 1337, dtype=None):
+    def __init__(self, n_input_dims: int, encoding_config: dict, seed: int = 1337, dtype=None, param_grad: str | None = None):
         if dtype not in (None, torch.float32):
             raise ValueError(f"tssplat_amd.tcnn.Encoding: dtype {dtype} is not offered (float32 only)")
-        super().__init__(n_input_dims, encoding_config, seed=seed)
+        super().__init__(n_input_dims, encoding_config, seed=seed, param_grad=param_grad)
 
 
 def _check_network_otype(cls: str, network_config) -> None:
@@ -47,10 +48,11 @@ class NetworkWithInputEncoding(torch.nn.Module):
     encoding followed by the fused MLP.  ``params`` is one Parameter, ``[network params | encoding params]`` (tiny-cuda-nn's
     order, unpinned), split in two by views."""
 
-    def __init__(self, n_input_dims: int, n_output_dims: int, encoding_config: dict, network_config: dict = None, seed: int = 1337):
+    def __init__(self, n_input_dims: int, n_output_dims: int, encoding_config: dict, network_config: dict = None, seed: int = 1337,
+                 param_grad: str | None = None):
         super().__init__()
         _check_network_otype("NetworkWithInputEncoding", network_config)     # before the encoding config is parsed
-        enc = GridEncoding(n_input_dims, encoding_config, seed=seed)
+        enc = GridEncoding(n_input_dims, encoding_config, seed=seed, param_grad=param_grad)
         net = FusedMLP(enc.n_output_dims, n_output_dims, network_config, seed=seed)
         self.encoding_cfg, self.network_cfg = enc.cfg, net.cfg
         self.n_input_dims, self.n_output_dims = int(n_input_dims), int(n_output_dims)
