@@ -70,7 +70,8 @@ typedef struct tsamd_options {
                                 * (tets stay in Morton order).  Results do not depend on it beyond the order of fp32 sums. */
     int32_t host_only;         /* 1 = build the tiling plan only, never touch HIP (CPU tests)       */
     int32_t num_threads;       /* host threads used to build the plan; 0 = hardware concurrency     */
-    int32_t debug_flags;       /* bit1 = no LDS-conflict-aware ordering at all (measurements); other bits ignored */
+    int32_t debug_flags;       /* bit1 = no LDS-conflict-aware ordering at all (measurements); bit2 = no shared index planes: every
+                                * tile is its own index representative (tsamd_get_index_reps; same results, bit for bit); other bits ignored */
     int32_t slots_per_thread;  /* tets per lane: 0 = 2.  Lane layouts with a kernel: 2 (max_threads <= 768, two 80 KiB workgroups per
                                 * CU: the default, every operator variant); 3 (max_threads <= 512, or <= 1024 for one workgroup per
                                 * CU) and 4 (max_threads <= 768): fewer, fatter waves, built-in operator only -- with lds_budget_bytes
@@ -184,6 +185,10 @@ int tsamd_get_tile(const tsamd_handle *h, int64_t tile, tsamd_tile_view *out);
  * rows tsamd_tile_view.vdst names (off[n_finish] entries) */
 int tsamd_get_finish_lists(const tsamd_handle *h, int64_t *n_finish, const int32_t **vid,
                            const int32_t **off, const int32_t **idx);
+/* rep[t], one entry per tile = the tile whose index planes (planes 0-3) and row table the kernels read for tile t: the first tile
+ * of the plan that carries the same bytes (the same tile of an earlier copy of one template), t itself if there is none.  Tile t's
+ * own bytes (tsamd_get_tile) are byte-equal to its representative's. */
+int tsamd_get_index_reps(const tsamd_handle *h, const int32_t **rep);
 /* face adjacency computed at create time: 4 ints per tet, -1 = boundary face */
 int tsamd_get_adjacency(const tsamd_handle *h, const int32_t **nbr);
 

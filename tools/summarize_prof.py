@@ -26,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def short(name: str) -> str:
+    name = name.replace("tile_shared_index_kernel", "tile_energy_kernel")   # the tile kernel of plans with shared index planes
     for key in ("tile_energy_kernel", "finish_kernel", "scale_kernel", "absmax_kernel", "clamp_kernel"):
         if key in name:
             return key + ("<true>" if "<true" in name else "<false>" if "<false" in name else "")

@@ -116,7 +116,13 @@ int to_device(tsamd_handle *h, int device)
     h->host_only = false;
     const tsamd::Plan &P = h->plan;
     int rc;
-    if ((rc = upload(h->d_tiles, P.tiles.data(), P.tiles.size(), h->device_bytes))) return rc;
+    {
+        // the device copy of a descriptor names, in stage_off (host bookkeeping otherwise), where the kernels read the tile's index
+        // planes and row table: the blob offset of its index representative (plan.h: Plan::index_rep; its own offset if it has none)
+        std::vector<tsamd::TileDesc> dev_tiles(P.tiles);
+        for (size_t t = 0; t < dev_tiles.size(); ++t) dev_tiles[t].stage_off = int64_t(P.tiles[size_t(P.index_rep[t])].blob_off);
+        if ((rc = upload(h->d_tiles, dev_tiles.data(), dev_tiles.size(), h->device_bytes))) return rc;
+    }
     if (tsamd::planes_paired(P.spt) && !P.tiles.empty()) {
         // the device image interleaves the planes that are loaded together (plan.h: planes_paired); row tables, rest positions and
         // the padding between tiles are copied as they are
@@ -182,6 +188,7 @@ int create_common(const float *rest, int64_t n, const int32_t *tets, int64_t m, 
     po.target_owned = opt.target_owned;
     po.num_threads = opt.num_threads;
     po.conflict_aware = (opt.debug_flags & 2) ? 0 : 1;  // bit 1 of the debug word switches the LDS-aware neighbour ordering off
+    po.share_index = (opt.debug_flags & 4) ? 0 : 1;     // bit 2: every tile reads its own index planes (A/B of the shared planes)
     po.lane_search_sweeps = opt.lane_search_sweeps < 0 ? 0 : (opt.lane_search_sweeps == 0 ? 2 : opt.lane_search_sweeps);
     {
         const int spt = opt.slots_per_thread != 0 ? opt.slots_per_thread : tsamd::kSlotsPerLane;
@@ -294,6 +301,8 @@ tsamd::EvalArgs eval_args(tsamd_handle *h, const float *x, const float *grad_out
     a.n_planes = h->plan.n_planes;
     a.rebuild = h->plan.n_planes == tsamd::kPlanesRebuild;
     a.spt = h->plan.spt;
+    // cache-retaining index loads where most tiles read another tile's index planes, non-temporal ones where (almost) none does
+    a.index_nt = 2 * h->plan.n_index_shared < int64_t(h->plan.tiles.size());
     a.x = x;
     a.grad_out = grad_out;
     a.c1 = c1;
@@ -432,6 +441,13 @@ int tsamd_get_tile(const tsamd_handle *h, int64_t tile, tsamd_tile_view *out)
     out->rest = P.n_planes == tsamd::kPlanesRebuild
                     ? reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(out->planes) + tsamd::tile_rest_offset(P.n_planes, d.s_pad))
                     : nullptr;
+    return TSAMD_OK;
+}
+
+int tsamd_get_index_reps(const tsamd_handle *h, const int32_t **rep)
+{
+    if (!h || !rep) return fail(TSAMD_ERR_INVALID_ARGUMENT, "null argument");
+    *rep = h->plan.index_rep.data();
     return TSAMD_OK;
 }
 

@@ -22,6 +22,7 @@ struct EvalArgs {
     bool weighted = false;        // the plan carries an explicit element operator (22 planes per slot; 18 when it is symmetric)
     int32_t n_planes = 13;        // dword planes per slot of this plan (where a tile's incidence list starts)
     int32_t spt = kSlotsPerLane;  // slots per lane the plan is laid out for (selects the kernel instantiation)
+    bool index_nt = true;         // the plan shares (almost) no index planes: load them non-temporally (Plan::index_rep, kernels.hip: tile_body)
     // per evaluation
     const float *x;
     const float *grad_out;  // device scalar or nullptr

@@ -296,7 +296,7 @@ __device__ __forceinline__ uint32_t pos_hi(uint32_t w) { return ((w >> 16) & kVe
 // n_owned are the owned ones.
 // SPT slots per lane (the plan is laid out for it); the default, two, with launch bounds <768 threads, 6 waves per SIMD> gives
 // the 80-VGPR budget at which two workgroups share a CU.
-template <bool WITH_GRAD, bool WEIGHTED, bool REBUILD, int SPT>
+template <bool WITH_GRAD, bool WEIGHTED, bool REBUILD, int SPT, bool INDEX_NT>
 __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, int32_t gv0)
 {
     // named here, not passed in: a pointer parameter would be a generic pointer and every LDS access of the
@@ -340,7 +340,6 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
     // Non-temporal loads: a tile's planes are read once, by one CU -- kept out of the way of what IS re-read (positions shared with
     // the neighbouring tiles, the staging rows the finish kernel reads back).  Round 6, three scenes, same box each: tile kernel
     // -1.2 % (kuhn19), -1.3 % (a.veg), -1.7 % (Delaunay); finish kernel -5 % (round 1's kernel had measured +1.4 %).
-    auto plane_u = [&](int q) -> VU { return __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS PlaneU *>(pl + q * td.s_pad + SPT * lt)); };
     auto plane_f = [&](int q) -> VF { return __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS PlaneF *>(pl + q * td.s_pad + SPT * lt)); };
     // Two planes that are always loaded together are ONE load of twice the width (plan.h: planes_paired): in the device image
     // of the blob planes q and q + 1 are interleaved per lane -- [plane q: SPT dwords | plane q + 1: SPT dwords] -- so the
@@ -348,13 +347,26 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
     constexpr bool kPaired = planes_paired(SPT);
     typedef uint32_t VU2 __attribute__((ext_vector_type(2 * SPT)));
     typedef float VF2 __attribute__((ext_vector_type(2 * SPT)));
+    // The INDEX planes (0-3) and the row table are read at the tile's index representative (plan.h: Plan::index_rep; the device
+    // descriptor carries its blob offset in stage_off): every copy of a template reads the template's bytes, which hold tile-local
+    // quantities only.  For a plan whose tiles share (INDEX_NT == false: tile_shared_index_kernel) these are ordinary, cache-
+    // retaining loads -- the bytes ARE re-read, by the same tile of the next copy on this XCD, and one template's index planes
+    // (0.9 MB for a 41 k-tet sphere) stay in its 4 MiB L2; non-temporal loads do not keep them there (512 x kuhn19: tile kernel
+    // 0.330 ms, as without sharing, against 0.303).  A plan that shares nothing reads them once like everything else and keeps the
+    // non-temporal loads (plain ones cost it 2-4 % of the tile kernel and 10-15 % of the finish kernel).  The flavour is a template
+    // parameter: a run-time choice -- a scalar branch around each load -- was built and made the compiler drain the stream at
+    // every join (vmcnt(0) where the positions' wait is vmcnt(1)).
+    const GLOBAL_AS uint32_t *pli = reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + uint64_t(td.stage_off));
+    // (a macro, not a helper: the pointer types carry the alignment the addresses really have, which template deduction drops)
+#define INDEX_LOAD(p) (INDEX_NT ? __builtin_nontemporal_load(p) : *(p))
     auto pair_u = [&](int q, VU &lo, VU &hi) {
         if (kPaired) {
-            const VU2 t = __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS VU2 *>(pl + q * td.s_pad + 2 * SPT * lt));
+            const VU2 t = INDEX_LOAD(reinterpret_cast<const GLOBAL_AS VU2 *>(pli + q * td.s_pad + 2 * SPT * lt));
 #pragma unroll
             for (int p = 0; p < SPT; ++p) lo[p] = t[p], hi[p] = t[SPT + p];
         } else {
-            lo = plane_u(q), hi = plane_u(q + 1);
+            lo = INDEX_LOAD(reinterpret_cast<const GLOBAL_AS PlaneU *>(pli + q * td.s_pad + SPT * lt));
+            hi = INDEX_LOAD(reinterpret_cast<const GLOBAL_AS PlaneU *>(pli + (q + 1) * td.s_pad + SPT * lt));
         }
     };
     auto pair_f = [&](int q, VF &lo, VF &hi) {
@@ -379,9 +391,10 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
     pair_u(0, q_lv01, q_lv23);
     VF dm[9];
     const int kBasePlanes = REBUILD ? kPlanesRebuild : (WEIGHTED ? a.n_planes : kPlanes);   // (a compile-time constant unless WEIGHTED)
-    const GLOBAL_AS uint16_t *g_rowtab = reinterpret_cast<const GLOBAL_AS uint16_t *>(pl + size_t(kBasePlanes) * td.s_pad);
-    // rest positions of the tile's vertices (rebuild_dminv plans): one coalesced float4 per lane, staged behind the positions
-    const GLOBAL_AS v4f *g_rest = reinterpret_cast<const GLOBAL_AS v4f *>(g_rowtab + kRowTabEntries);
+    const GLOBAL_AS uint16_t *g_rowtab = reinterpret_cast<const GLOBAL_AS uint16_t *>(pli + size_t(kBasePlanes) * td.s_pad);   // (the representative's)
+    // rest positions of the tile's vertices (rebuild_dminv plans): one coalesced float4 per lane, staged behind the positions --
+    // the tile's OWN, behind its own row table
+    const GLOBAL_AS v4f *g_rest = reinterpret_cast<const GLOBAL_AS v4f *>(reinterpret_cast<const GLOBAL_AS uint16_t *>(pl + size_t(kBasePlanes) * td.s_pad) + kRowTabEntries);
     v4f rest0 = v4f{0.f, 0.f, 0.f, 0.f};
     if (REBUILD) rest0 = g_rest[tid < td.n_verts ? tid : 0];
     // the positions: unconditional loads (lanes beyond the tile's vertices hold vertex 0 and do not store), so that the
@@ -424,7 +437,7 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
     // join of a divergent branch the compiler waits for EVERY load in flight, and pass 1 would start behind the neighbour planes
     // (it did, for the first build of this layout: aveg x 952 0.4430 -> 0.4259 ms once the branch was gone).
     uint32_t row0 = 0;
-    if (WITH_GRAD) row0 = __builtin_nontemporal_load(&g_rowtab[tid < 65 ? tid : 64]);
+    if (WITH_GRAD) row0 = INDEX_LOAD(&g_rowtab[tid < 65 ? tid : 64]);
     __builtin_amdgcn_sched_barrier(0);
 
     // The smoothness coefficient is applied ONCE per vertex at the very end instead of nine times per slot:
@@ -734,10 +747,11 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
         }
     }
 #undef t_own
+#undef INDEX_LOAD
 }
 
-template <bool WITH_GRAD, int BLOCK, int WPE, bool WEIGHTED = false, bool REBUILD = false, int SPT = kSlotsPerLane>
-__global__ __launch_bounds__(BLOCK, WPE) void tile_energy_kernel(const KernelArgs a)
+template <bool WITH_GRAD, bool WEIGHTED, bool REBUILD, int SPT, bool INDEX_NT>
+__device__ __forceinline__ void tile_entry(const KernelArgs &a)
 {
     // XCD-aware tile order: workgroup b lands on XCD b % 8 (observed, speed only), so give each
     // XCD a contiguous run of tiles -- the tiles of one sphere then share one L2.
@@ -755,7 +769,22 @@ __global__ __launch_bounds__(BLOCK, WPE) void tile_energy_kernel(const KernelArg
     // re-read, the positions shared with neighbouring tiles and the staging rows; round 6: a.veg x 952 tile kernel -6 %, finish -8 %)
     const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);
     __builtin_amdgcn_sched_barrier(0);
-    tile_body<WITH_GRAD, WEIGHTED, REBUILD, SPT>(a, tile, gv0);
+    tile_body<WITH_GRAD, WEIGHTED, REBUILD, SPT, INDEX_NT>(a, tile, gv0);
+}
+
+template <bool WITH_GRAD, int BLOCK, int WPE, bool WEIGHTED = false, bool REBUILD = false, int SPT = kSlotsPerLane>
+__global__ __launch_bounds__(BLOCK, WPE) void tile_energy_kernel(const KernelArgs a)
+{
+    tile_entry<WITH_GRAD, WEIGHTED, REBUILD, SPT, true>(a);
+}
+
+// The same tile for plans whose tiles share index planes (Plan::index_rep): index planes and row table through cache-retaining
+// loads (tile_body: INDEX_LOAD).  Default lane layout only; the fat-wave layouts read their representative's planes through
+// tile_energy_kernel's non-temporal loads (same results, no L2 reuse).
+template <bool WITH_GRAD, int BLOCK, int WPE, bool WEIGHTED = false, bool REBUILD = false>
+__global__ __launch_bounds__(BLOCK, WPE) void tile_shared_index_kernel(const KernelArgs a)
+{
+    tile_entry<WITH_GRAD, WEIGHTED, REBUILD, kSlotsPerLane, false>(a);
 }
 
 struct FinishArgs {
@@ -1029,8 +1058,15 @@ namespace {
 //   4 x 768 @ 3 : 168 VGPRs, one workgroup per CU with up to 160 KiB: whole small tet-spheres as ONE tile, no halo, no
 //   3 x 1024 @ 4: 128 VGPRs, the same with more waves                   shared vertices (built-in operator)
 #define TSAMD_FN(...) reinterpret_cast<const void *>(&tile_energy_kernel<__VA_ARGS__>)
-const void *tile_kernel_for(int spt, int block_threads, bool grad, bool weighted, bool rebuild)
+#define TSAMD_FN_SHARED(...) reinterpret_cast<const void *>(&tile_shared_index_kernel<__VA_ARGS__>)
+// index_nt: the plan shares (almost) no index planes (EvalArgs::index_nt); false selects the cache-retaining twin where one is built
+const void *tile_kernel_for(int spt, int block_threads, bool grad, bool weighted, bool rebuild, bool index_nt)
 {
+    if (spt == 2 && block_threads <= 768 && !index_nt) {
+        if (weighted) return grad ? TSAMD_FN_SHARED(true, 768, 6, true, false) : TSAMD_FN_SHARED(false, 768, 6, true, false);
+        if (rebuild) return grad ? TSAMD_FN_SHARED(true, 768, 6, false, true) : TSAMD_FN_SHARED(false, 768, 6, false, true);
+        return grad ? TSAMD_FN_SHARED(true, 768, 6, false, false) : TSAMD_FN_SHARED(false, 768, 6, false, false);
+    }
     if (spt == 2 && block_threads <= 768) {
         if (weighted) return grad ? TSAMD_FN(true, 768, 6, true, false, 2) : TSAMD_FN(false, 768, 6, true, false, 2);
         if (rebuild) return grad ? TSAMD_FN(true, 768, 6, false, true, 2) : TSAMD_FN(false, 768, 6, false, true, 2);
@@ -1043,10 +1079,11 @@ const void *tile_kernel_for(int spt, int block_threads, bool grad, bool weighted
     return nullptr;
 }
 #undef TSAMD_FN
+#undef TSAMD_FN_SHARED
 
 }  // namespace
 
-bool lane_layout_supported(int spt, int max_threads) { return tile_kernel_for(spt, max_threads, true, false, false) != nullptr; }
+bool lane_layout_supported(int spt, int max_threads) { return tile_kernel_for(spt, max_threads, true, false, false, true) != nullptr; }
 
 hipError_t configure_kernels(int lds_bytes)
 {
@@ -1059,8 +1096,10 @@ hipError_t configure_kernels(int lds_bytes)
     // every tile kernel a plan can reach
     static const int layouts[][2] = {{2, 768}, {3, 512}, {4, 768}, {3, 1024}};
     for (const auto &lay : layouts)
-        for (int variant = 0; variant < 6; ++variant) {
-            const void *fn = tile_kernel_for(lay[0], lay[1], (variant & 1) != 0, variant / 2 == 1, variant / 2 == 2);
+        for (int variant = 0; variant < 12; ++variant) {
+            const int op = (variant % 6) / 2;
+            if (variant >= 6 && lay[0] != kSlotsPerLane) continue;   // (the cache-retaining twins exist for the default layout only)
+            const void *fn = tile_kernel_for(lay[0], lay[1], (variant & 1) != 0, op == 1, op == 2, variant < 6);
             if (!fn) continue;
             // lds_at() addresses the dynamic LDS array by absolute byte address: that is only right while the array starts
             // at LDS address 0, i.e. while the kernel has no static LDS object in front of it (a static __shared__ variable,
@@ -1127,7 +1166,7 @@ hipError_t make_recipe(const EvalArgs &e, LaunchRecipe &r)
         k.tiles_per_xcd = int((e.n_tiles + 7) / 8);
         k.vert_stride = e.vert_stride;
         k.n_planes = e.n_planes;
-        r.tile_fn = tile_kernel_for(e.spt, e.block_threads, e.grad != nullptr, e.weighted, e.rebuild);
+        r.tile_fn = tile_kernel_for(e.spt, e.block_threads, e.grad != nullptr, e.weighted, e.rebuild, e.index_nt);
         if (!r.tile_fn) return hipErrorInvalidConfiguration;
         r.tile_block = dim3(unsigned(e.block_threads));
         r.tile_grid = dim3(unsigned(8 * k.tiles_per_xcd));

@@ -719,23 +719,38 @@ int build_plan(const float *rest, int64_t n, const int32_t *tets, int64_t m, con
         n_models += model[g] == int64_t(g);
         n_refined += refined[size_t(model[g])];
     }
+    // The components that were cut themselves order their cells along the Morton curve of their own centroids ...
     parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int w) {
         Scratch &S = get_scratch(w);
         std::vector<int32_t> part;
         for (int64_t g = b; g < e; ++g) {
-            const int64_t r = model[size_t(g)];
-            if (r < 0 || !refined[size_t(r)]) continue;
-            int64_t cnt, cnt_r;
-            const int32_t *ids = comp_ids(g, cnt), *ids_r = comp_ids(r, cnt_r);
+            if (model[size_t(g)] != g || !refined[size_t(g)]) continue;
             auto &leaves = group_tiles[size_t(g)];
             leaves.clear();
             std::string unused_err;
             Splitter sp{M, lim, cen, S, leaves, unused_err};
-            for (const auto &c : cut[size_t(r)]) {
-                part.resize(c.size());
-                for (size_t i = 0; i < c.size(); ++i) part[i] = c[i] - ids_r[0] + ids[0];
+            for (const auto &c : cut[size_t(g)]) {
+                part.assign(c.begin(), c.end());
                 sp.emit(part.data(), int64_t(part.size()));
             }
+        }
+    });
+    // ... and their copies take the TILES over, tet for tet in the same order, not just the cut: a copy that sorted its cells by
+    // its own fp32 centroids (or kept its own bisection) broke a tie of the Morton codes differently in 2-3 % of its tiles, and
+    // everything behind the item order -- halo order, lanes, ranks, colouring, vertex numbering -- is a function of that order and
+    // of the connectivity alone.  With the order inherited a copy's index planes and row tables are the template's, byte for
+    // byte (Plan::index_rep, decided by comparison below).
+    parallel_chunks(int64_t(groups.size()), 1, nthreads, [&](int64_t b, int64_t e, int) {
+        for (int64_t g = b; g < e; ++g) {
+            const int64_t r = model[size_t(g)];
+            if (r < 0 || r == g) continue;
+            int64_t cnt, cnt_r;
+            const int32_t *ids = comp_ids(g, cnt), *ids_r = comp_ids(r, cnt_r);
+            const int32_t shift = ids[0] - ids_r[0];
+            auto &leaves = group_tiles[size_t(g)];
+            leaves = group_tiles[size_t(r)];
+            for (auto &l : leaves)
+                for (int32_t &el : l) el += shift;
         }
     });
     P.n_cut_components = n_cut;
@@ -1221,6 +1236,50 @@ int build_plan(const float *rest, int64_t n, const int32_t *tets, int64_t m, con
         err = "singular (zero-volume) rest tetrahedron";
         return ERR_BAD_MESH;
     }
+    // ---- shared index planes: which earlier tile carries the same index planes and row table? (Plan::index_rep) ----
+    // A hash of the descriptor's shape fields, planes 0-3 and the row table names a candidate -- the first tile of the plan with
+    // that hash --, the comparison in full decides.  Tile by tile over the finished bytes: independent of the thread count.
+    P.index_rep.resize(size_t(T));
+    for (int64_t t = 0; t < T; ++t) P.index_rep[size_t(t)] = int32_t(t);
+    if (opt.share_index && T > 1) {
+        const size_t rowtab_words = 2 * kRowTabEntries / 4;
+        auto rowtab_of = [&](const TileDesc &d) { return P.blob.data() + (d.blob_off + uint64_t(tile_rowtab_offset(n_planes, d.s_pad))) / 4; };
+        std::vector<std::pair<uint64_t, int32_t>> by_hash(static_cast<size_t>(T));
+        parallel_chunks(T, 16, nthreads, [&](int64_t b, int64_t e, int) {
+            for (int64_t t = b; t < e; ++t) {
+                const TileDesc &d = P.tiles[size_t(t)];
+                uint64_t h = 1469598103934665603ull;
+                auto mix = [&](uint64_t v) { h = (h ^ v) * 1099511628211ull; };
+                mix(uint64_t(d.s_pad));
+                mix(uint64_t(d.n_slots));
+                mix(uint64_t(d.n_owned));
+                mix(uint64_t(d.n_verts));
+                const uint32_t *pl = P.blob.data() + d.blob_off / 4, *rt = rowtab_of(d);
+                for (size_t i = 0; i < size_t(kPlanesRebuild) * size_t(d.s_pad); ++i) mix(pl[i]);
+                for (size_t i = 0; i < rowtab_words; ++i) mix(rt[i]);
+                by_hash[size_t(t)] = {h, int32_t(t)};
+            }
+        });
+        std::sort(by_hash.begin(), by_hash.end());
+        parallel_chunks(T, 16, nthreads, [&](int64_t b, int64_t e, int) {
+            for (int64_t i = b; i < e; ++i) {
+                const uint64_t h = by_hash[size_t(i)].first;
+                const auto first = std::lower_bound(by_hash.begin(), by_hash.end(), std::make_pair(h, int32_t(0)));
+                const int32_t t = by_hash[size_t(i)].second, r = first->second;
+                if (r == t) continue;
+                const TileDesc &d = P.tiles[size_t(t)], &dr = P.tiles[size_t(r)];
+                if (d.s_pad != dr.s_pad || d.n_slots != dr.n_slots || d.n_owned != dr.n_owned || d.n_verts != dr.n_verts || d.n_rows != dr.n_rows ||
+                    d.rec_base != dr.rec_base)
+                    continue;
+                if (std::memcmp(P.blob.data() + d.blob_off / 4, P.blob.data() + dr.blob_off / 4, size_t(kPlanesRebuild) * size_t(d.s_pad) * 4) != 0 ||
+                    std::memcmp(rowtab_of(d), rowtab_of(dr), 2 * kRowTabEntries) != 0)
+                    continue;
+                P.index_rep[size_t(t)] = r;
+            }
+        });
+        for (int64_t t = 0; t < T; ++t) P.n_index_shared += P.index_rep[size_t(t)] != t;
+    }
+    timer.lap("shared index planes");
     return OK;
 }
 

@@ -35,6 +35,7 @@ struct PlanOptions {
     int rebuild_dminv = 0;        // 1 = do not stream Dm^-1 (36 of the 52 bytes per slot): keep each tile's REST positions
                                   // (16 B per tile vertex) and invert Dm in registers, in fp32 (see kPlanesRebuild)
     int slots_per_lane = 0;       // 0 = kSlotsPerLane (2); 3 and 4 select the kernels built for fewer, fatter waves
+    int share_index = 1;          // 0 = every tile is its own index representative (Plan::index_rep): the A/B switch of the shared planes
 };
 
 // Device-visible tile descriptor (48 bytes, uniform loads in the kernel).
@@ -46,7 +47,8 @@ struct TileDesc {
     int32_t n_verts;     // local vertices (a vertex met by more than kMaxRank slots of the tile counts once per kMaxRank)
     int32_t n_excl;      // how many of them belong to this tile alone (statistics: the kernels read the sign of vdst[])
     int32_t vert_off;    // offset into gvid[] / vdst[] (= tile * vert_stride)
-    int64_t stage_off;   // host bookkeeping: the tile's first entry in fin_idx[]
+    int64_t stage_off;   // host: the tile's first entry in fin_idx[].  The DEVICE copy of the descriptor carries, in this field, the
+                         // blob offset of the tile whose index planes and row table the kernels read (Plan::index_rep)
     int32_t n_rows;      // rows of the tile's force array = the largest number of slots any of its vertices meets (<= kMaxRank)
     int32_t rec_base;    // LDS byte address of record 0 (tile_rec_base)
 };
@@ -209,6 +211,14 @@ struct Plan {
     int32_t max_slots = 0, max_verts = 0, block_threads = 64, lds_bytes = 0, spt = kSlotsPerLane;
     int32_t n_planes = kPlanes;      // kPlanes, or kPlanesWeighted when an explicit operator was given
     int32_t vert_stride = 64;        // gvid entries per tile (tile t's ids start at t * vert_stride = its TileDesc::vert_off)
+    // SHARED INDEX PLANES.  Planes 0-3 (lv01, lv23, nb01, nb23) and the row table hold tile-local quantities only -- local
+    // vertices, ranks, LDS record tokens, row starts -- so the same tile of every copy of one template carries the same bytes.
+    // index_rep[t] = the first tile of the plan whose descriptor (slots, vertices, rows, record base) and whose index planes and
+    // row table are byte-equal to tile t's, compared in full (t itself if there is none before it).  The kernels read these
+    // bytes at the representative's address: one copy per template stays in L2 instead of one per tile coming from HBM.
+    // Every tile keeps its own bytes in the blob all the same (tsamd_get_tile, and the device image is not compacted).
+    std::vector<int32_t> index_rep;
+    int64_t n_index_shared = 0;      // tiles with index_rep[t] != t
     std::vector<float> op_diag;      // explicit operator only: L[e,e] per tet
     std::vector<float> op_w;         // explicit operator only: L[e, nbr[4e+k]] per tet face (0 on boundary faces)
 };

@@ -189,6 +189,15 @@ class TetSpheres:
                 out[k] = getattr(cut, k)
         return out
 
+    def index_reps(self):
+        """Per tile, the tile whose index planes and row table the kernels read (tsamd_get_index_reps): itself, or the first tile
+        of the plan with the same bytes -- the same tile of an earlier copy of one template."""
+        import numpy as np
+        n = self.plan_info()["n_tiles"]
+        p = C.POINTER(C.c_int32)()
+        _capi.check(_lib.tsamd_get_index_reps(self._handle(), C.byref(p)))
+        return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+
     def set_timing(self, enable: bool) -> None:
         """Record HIP events around the kernels of every evaluation (bench.py roofline leg)."""
         _capi.check(_lib.tsamd_set_timing(self._handle(), int(enable)))
