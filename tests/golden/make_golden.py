@@ -19,6 +19,9 @@ exists on the GPU box, hence the outputs are committed:
 * aveg_mesh.npz -- a.veg converted to the extension's input layout
   (float32 [n,3], int32 [m,4], 0-based): the "real TetWild-quality mesh"
   fixture of SURVEY.md 8(d).
+
+`python tests/golden/make_golden.py plan_digests` is a section of its own (plan_digests() below): it needs the built
+library, not the reference, and writes plan_digests.json, the planner's recorded output for tests/test_plan_bytes.py.
 """
 import importlib.util
 import os
@@ -143,5 +146,30 @@ def surface_golden(mu):
     np.savez_compressed(os.path.join(HERE, "surface_golden.npz"), **out)
 
 
+def plan_digests(extra=False):
+    """plan_digests.json -- per case of tests/plan_digest.py::CASES the SHA-256 of the inputs and of everything the C ABI
+    shows of the plan built from them (tests/test_plan_bytes.py).  Needs the built library, not the reference:
+
+        python tests/golden/make_golden.py plan_digests            # rewrites the golden file
+        python tests/golden/make_golden.py plan_digests --extra    # prints CASES + EXTRA_CASES, writes nothing
+
+    Record it on the commit BEFORE a change of the planner and never afterwards: the file is what that change is held to."""
+    import json
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import plan_digest as PD
+    out = {}
+    for case in PD.CASES + (PD.EXTRA_CASES if extra else []):
+        out[PD.case_id(*case)] = PD.digests(*case)
+        print(PD.case_id(*case), out[PD.case_id(*case)]["inputs"][:16], out[PD.case_id(*case)]["plan"], flush=True)
+    if not extra:
+        with open(PD.GOLDEN, "w") as fh:
+            json.dump(out, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+        print("wrote", PD.GOLDEN)
+
+
 if __name__ == "__main__":
-    main()
+    if "plan_digests" in sys.argv[1:]:
+        plan_digests(extra="--extra" in sys.argv[1:])
+    else:
+        main()

@@ -347,5 +347,10 @@ def test_plan_does_not_depend_on_the_number_of_host_threads():
     for Ta, Tb in zip(TE.plan_tiles(a), TE.plan_tiles(b)):
         for k in ("planes", "gvid", "vdst", "slot_tet", "row_start"):
             assert np.array_equal(Ta[k], Tb[k]), k
+        for k in ("n_slots", "n_owned", "s_pad", "n_verts", "n_excl", "stage_off", "n_rows", "rec_base"):
+            assert Ta[k] == Tb[k], k
         n += 1
     assert n == a.plan_info()["n_tiles"] == b.plan_info()["n_tiles"] > 8
+    assert np.array_equal(a.index_reps(), b.index_reps())
+    for fa, fb in zip(TE.finish_lists(a), TE.finish_lists(b)):
+        assert np.array_equal(fa, fb)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Laboratory builds of the tile kernel WITHOUT touching the product source: every variant is a list of textual patches applied
-to a COPY of tssplat_amd/csrc/kernels.hip (and, optionally, plan.cpp), compiled into tssplat_amd/libtssplat_amd_<name>.so next to
+to a COPY of tssplat_amd/csrc/kernels.hip (and, optionally, any other file of _build.SOURCES), compiled into tssplat_amd/libtssplat_amd_<name>.so next to
 the product library and selected per process with TSSPLAT_AMD_LIB (tools/ab_variants.py does that).  The shipped kernels carry no
 experiment switches; pricing builds ("what does this phase cost?": results WRONG on purpose) and candidate
 changes live here, reproducible from this file.
@@ -18,7 +18,6 @@ sys.path.insert(0, ROOT)
 from tssplat_amd import _build  # noqa: E402
 
 K = "kernels.hip"
-P = "plan.cpp"
 
 # name -> (description, [(file, old, new), ...])
 VARIANTS = {

@@ -4,7 +4,7 @@
 Replays the addresses of the data-dependent LDS accesses (neighbour gathers of passes 2/3, position reads of pass 1, the
 scatter of the corner forces into the per-vertex force array) through the lane-group / bank rules of MI355X_MICROARCH.md (LDS
 section) and reports base cycles and extra (conflict) cycles per tile slot.  Used to compare ordering heuristics in
-csrc/plan.cpp offline (round 5: the scatter's ranks, 2.8x -> 1.5x the conflict-free cycles).  The per-vertex sums read
+csrc/plan_planes.cpp offline (round 5: the scatter's ranks, 2.8x -> 1.5x the conflict-free cycles).  The per-vertex sums read
 consecutive entries per lane and are conflict-free by construction.
 
     python tools/lds_conflicts.py [--scene kuhn19 --spheres 1] [--no-conflict-aware]

@@ -18,7 +18,7 @@
 // not depend on the number of host threads.  A cell's slot count and tile vertices (kMaxRank slots per tile vertex, as
 // measure() counts them) and the staged rows of the whole cut are kept exact under every move through per-(cell, vertex) slot
 // counts and per-vertex copy counts.
-#include "partition.h"
+#include "planner.h"
 
 #include <algorithm>
 #include <cmath>
