@@ -452,6 +452,39 @@ int tsamd_grid_encode_backward_sorted(const float *x_dev, int64_t n_points, cons
                                       float per_level_scale, int32_t dense, const float *grad_out_dev, float *grad_params_dev,
                                       float *grad_x_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* The planned backward: the sorted backward's dL/dparams for a FROZEN point set, with the sort done once.
+ * tsamd_grid_plan_build sorts the points' (entry, source) records as the sorted backward does and keeps, per chunk and level,
+ * the 4-byte source (8 * point_in_chunk + corner) of every record in sorted order: [chunk][level][8 * points_in_chunk] uint32,
+ * tsamd_grid_plan_bytes(n_points, config) bytes (>= n_points * 8 * n_levels * 4; a function of n_points and the config only,
+ * non-decreasing in n_points).  tsamd_grid_encode_backward_planned is then only the segmented sum over that stored order and
+ * its fold, every level of a chunk in one launch: no sort, no float atomics.
+ *   Same bits: for the same x, grad_out, config and initial contents of grad_params_dev, the result is bitwise equal to
+ *     tsamd_grid_encode_backward_sorted's; its repeatability and accuracy clauses carry over unchanged.
+ *   Placement: the result does not depend on where the plan or the workspace lie, nor on what the workspace (or, for the build,
+ *     the plan buffer) held on entry; nothing is written outside them and grad_params_dev.
+ *   Memory safety: any byte pattern in the plan keeps every access in bounds (a record is followed only while its source is
+ *     inside the chunk; its entry is recomputed from x_dev) -- a stale or foreign plan gives wrong numbers, nothing worse.
+ *   Caller's contract: x_dev, n_points and the config of a backward are those the plan was built with.
+ *   It ADDS into grad_params_dev (zero it first).  There is no dL/dx with a plan: a planned point set is frozen.
+ * Both calls run on `stream`, in chunks of tsamd_grid_sorted_chunk_points(), and make no allocation and no host
+ * synchronisation.  plan_dev and workspace_dev: 256-byte aligned.  The build's workspace is
+ * tsamd_grid_backward_sorted_workspace_bytes(n_points, config) bytes; the backward's is
+ * tsamd_grid_backward_planned_workspace_bytes(n_points, config) bytes (constant from one chunk on).  A null, misaligned or
+ * too-small plan or workspace, a null grad_out_dev / grad_params_dev, n_points < 0 or an unsupported config is
+ * TSAMD_ERR_INVALID_ARGUMENT before anything is launched; n_points == 0 succeeds without touching a device. */
+int tsamd_grid_plan_bytes(int64_t n_points, int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size,
+                          int32_t base_resolution, float per_level_scale, int32_t dense, int64_t *bytes_out);
+int tsamd_grid_plan_build(const float *x_dev, int64_t n_points, int32_t n_levels, int32_t n_features_per_level,
+                          int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, int32_t dense, void *plan_dev,
+                          int64_t plan_bytes, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int tsamd_grid_backward_planned_workspace_bytes(int64_t n_points, int32_t n_levels, int32_t n_features_per_level,
+                                                int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                                                int32_t dense, int64_t *bytes_out);
+int tsamd_grid_encode_backward_planned(const float *x_dev, int64_t n_points, int32_t n_levels, int32_t n_features_per_level,
+                                       int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, int32_t dense,
+                                       const float *grad_out_dev, float *grad_params_dev, const void *plan_dev, int64_t plan_bytes,
+                                       void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Fully fused MLP (the texture stage's colour MLP when its config names a tcnn network): tiny-cuda-nn's FullyFusedMLP,
  *   tsamd_mlp_forward  <- tcnn.Network(n_in, n_out, {"otype": "FullyFusedMLP" | "CutlassMLP" | "MLP", ...})(x)   models/networks.py:314-321

@@ -5,7 +5,11 @@ here from a known colour field on tests/golden/mario_mesh.npz under scenes.datas
 empty).
 
     python tools/train_texture.py [--views 16 --res 256 --iters 300 --lr 0.01 --mlp VanillaMLP|FullyFusedMLP
-                                    --param-grad atomic|sorted]
+                                    --param-grad atomic|sorted --plan-points]
+
+--plan-points: the views are fixed and the geometry frozen, so the renderer plans them once before the loop
+(MeshRasterizer.plan_views) and every iteration runs with view_plan=: no rasterise / interpolate / compaction, and the hash
+grid's dL/dparams by the planned route (no sort, no float atomics).
 
 One JSON line: the loss at the first and last iteration, ms per iteration, and the split of one iteration's forward + backward
 into encode (hash grid), MLP and the rest (rasterise, interpolate, antialias, loss), timed stage by stage on the same points."""
@@ -41,7 +45,7 @@ def timed(fn, reps=5):
     return a.elapsed_time(b) / reps
 
 
-def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_grad="atomic"):
+def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_grad="atomic", plan_points=False):
     from tssplat_amd import geometry, materials, renderers, scenes
     from tssplat_amd.utils.optimizer import AdamUniform
     torch.cuda.set_device(0)
@@ -65,8 +69,18 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_gra
     opt = AdamUniform(ren.parameters(), lr=lr)
     loss_fn = torch.nn.L1Loss()
 
+    view_plan, plan_build_ms = None, None
+    if plan_points:
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        view_plan = ren.plan_views(mvp, res)
+        b.record()
+        torch.cuda.synchronize()
+        plan_build_ms = a.elapsed_time(b)
+
     def step(it):
-        out = ren(mvp, only_alpha=False, iter_num=it, resolution=res, background=bg)
+        out = ren(mvp, only_alpha=False, iter_num=it, resolution=res, background=bg, view_plan=view_plan)
         loss = loss_fn(out["shaded"][..., :3], target[..., :3]) * 20           # trainer.py:102-104
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -97,17 +111,21 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_gra
     ge = torch.randn_like(e)
     gm = torch.randn(pts.shape[0], 3, device="cuda")
 
+    enc_in = mat.encoding.plan_points(pts) if plan_points else pts
+
     def enc_fb():
-        enc(pts).backward(ge)
+        enc(enc_in).backward(ge)
 
     def mlp_fb():
         mlp(e.requires_grad_(True)).backward(gm)
     ms_enc, ms_mlp = timed(enc_fb), timed(mlp_fb)
-    return {"views": views, "res": res, "iters": iters, "lr": lr, "mlp": mlp_otype, "param_grad": param_grad, "foreground_points": int(pts.shape[0]),
+    split_plan = {} if not plan_points else {"plan_build_ms": round(plan_build_ms, 3), "plan_bytes": view_plan.point_plan.nbytes}
+    return {"views": views, "res": res, "iters": iters, "lr": lr, "mlp": mlp_otype, "param_grad": "planned" if plan_points else param_grad,
+            "foreground_points": int(pts.shape[0]),
             "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)], "loss_ratio": round(losses[-1] / losses[0], 4),
             "ms_per_iter": round(ms_iter, 3),
             "split_ms": {"encode_fwd_bwd": round(ms_enc, 3), "mlp_fwd_bwd": round(ms_mlp, 3),
-                         "render_loss_optimizer_rest": round(ms_iter - ms_enc - ms_mlp, 3)}}
+                         "render_loss_optimizer_rest": round(ms_iter - ms_enc - ms_mlp, 3), **split_plan}}
 
 
 def main():
@@ -119,8 +137,10 @@ def main():
     ap.add_argument("--mlp", default="VanillaMLP", help="mlp_network_config otype (VanillaMLP or FullyFusedMLP)")
     ap.add_argument("--param-grad", choices=("atomic", "sorted"), default="atomic",
                     help="the hash grid's route to dL/dparams (sorted: bitwise repeatable)")
+    ap.add_argument("--plan-points", action="store_true",
+                    help="plan the fixed views once (MeshRasterizer.plan_views) and train with view_plan=")
     a = ap.parse_args()
-    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp, a.param_grad)))
+    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp, a.param_grad, a.plan_points)))
 
 
 if __name__ == "__main__":

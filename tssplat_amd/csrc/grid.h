@@ -82,4 +82,50 @@ inline GridSortedWorkspace grid_sorted_workspace(int64_t n, int32_t n_features)
 hipError_t launch_grid_encode_backward_sorted(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features,
                                               const float *grad_out, float *grad_params, float *grad_x, void *workspace, hipStream_t stream);
 
+// The planned route to dL/dparams: the sorted route with the sort taken out of the step.  A point plan is built once for a
+// frozen point set (x, n, config): per chunk and level it keeps the low word `src = 8 * point_in_chunk + corner` of every
+// sorted record, [chunk][level][8 * points_in_chunk] uint32 -- grid_plan_bytes(n, n_levels) bytes.  A planned backward is the
+// sorted route's segmented sum over that stored order (one device body for both; the entry of a record is rebuilt from the
+// point's cell, which the corner weight needs anyway) and its fold, every level of a chunk in one launch.  Contract:
+//  1. Same bits as the sorted route: for the same x, grad_out, config and initial grad_params, grad_params ends bitwise equal
+//     to launch_grid_encode_backward_sorted's.  Records, chunks, 512-record wave ranges, in-wave trees, carries and fold order
+//     are the same, so the sorted route's accuracy bound and repeatability clause carry over unchanged.
+//  2. The result does not depend on where the plan lies, nor on the planned workspace's contents or place; nothing is written
+//     outside the plan (build) and grad_params + workspace (backward).
+//  3. Memory safety: ANY byte pattern in the plan keeps every access in bounds.  A record is followed only while
+//     src < 8 * points_in_chunk, which bounds the point index; its entry is computed from x, so it is always < entries.  A stale
+//     or foreign plan gives wrong numbers, never an out-of-bounds access.
+//  4. Build and backward make no allocation and no host synchronisation; all launch geometry is a function of (n, config).
+// x, n and the config of a backward must be those the plan was built with.  It ADDS into grad_params.  There is no dL/dx with a
+// plan: a planned point set is frozen by definition.
+inline int64_t grid_plan_bytes(int64_t n, int32_t n_levels)
+{
+    const int64_t bytes = (n < 0 ? 0 : n) * 8 * n_levels * 4;
+    return (bytes + kGridWorkspaceAlign - 1) / kGridWorkspaceAlign * kGridWorkspaceAlign;
+}
+
+// The planned backward's workspace: the boundary partials of every level of one chunk, [level][2 * waves].
+struct GridPlannedWorkspace {
+    int64_t pkey, psum;        // [level][2 * waves] keys, [level][2 * waves, F] sums
+    int64_t bytes;
+};
+
+inline GridPlannedWorkspace grid_planned_workspace(int64_t n, int32_t n_features, int32_t n_levels)
+{
+    const int64_t nc = n < 0 ? 0 : (n < kGridSortedChunk ? n : kGridSortedChunk), n_rec = nc * 8;
+    const int64_t waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
+    const auto up = [](int64_t bytes) { return (bytes + kGridWorkspaceAlign - 1) / kGridWorkspaceAlign * kGridWorkspaceAlign; };
+    GridPlannedWorkspace ws{};
+    ws.pkey = 0;
+    ws.psum = up(int64_t(n_levels) * 2 * waves * 4);
+    ws.bytes = nc > 0 ? ws.psum + up(int64_t(n_levels) * 2 * waves * n_features * 4) : 0;
+    return ws;
+}
+
+// Build scratch: exactly grid_sorted_workspace(n, n_features).
+hipError_t launch_grid_plan_build(const float *x, int64_t n, const GridLevels &lv, int32_t n_features, void *plan, void *workspace,
+                                  hipStream_t stream);
+hipError_t launch_grid_encode_backward_planned(const float *x, int64_t n, const GridLevels &lv, int32_t n_features, const float *grad_out,
+                                               float *grad_params, const void *plan, void *workspace, hipStream_t stream);
+
 }  // namespace tsamd

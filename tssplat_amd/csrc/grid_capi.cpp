@@ -203,4 +203,101 @@ int tsamd_grid_encode_backward_sorted(const float *x_dev, int64_t n_points, cons
     return TSAMD_OK;
 }
 
+int tsamd_grid_plan_bytes(int64_t n_points, int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size, int32_t base_resolution,
+                          float per_level_scale, int32_t dense, int64_t *bytes_out)
+{
+    tsamd::GridLevels lv;
+    int64_t n_params = 0;
+    const int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
+    if (rc) return rc;
+    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
+    if (n_points > (int64_t(1) << 40)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points above 2^40");
+    if (!bytes_out) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: bytes_out is null");
+    *bytes_out = tsamd::grid_plan_bytes(n_points, n_levels);
+    return TSAMD_OK;
+}
+
+int tsamd_grid_backward_planned_workspace_bytes(int64_t n_points, int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size,
+                                                int32_t base_resolution, float per_level_scale, int32_t dense, int64_t *bytes_out)
+{
+    tsamd::GridLevels lv;
+    int64_t n_params = 0;
+    const int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
+    if (rc) return rc;
+    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
+    if (!bytes_out) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: bytes_out is null");
+    *bytes_out = tsamd::grid_planned_workspace(n_points, n_features_per_level, n_levels).bytes;
+    return TSAMD_OK;
+}
+
+namespace {
+
+// The plan's and a workspace's checks, shared by the plan build and the planned backward.
+int check_plan_buffers(int64_t n_points, int32_t n_levels, const void *plan_dev, int64_t plan_bytes, const void *workspace_dev,
+                       int64_t workspace_bytes, int64_t workspace_need, const char *workspace_query)
+{
+    const int64_t plan_need = tsamd::grid_plan_bytes(n_points, n_levels);
+    if (plan_need > 0 && !plan_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: plan_dev is null");
+    if (reinterpret_cast<uintptr_t>(plan_dev) % tsamd::kGridWorkspaceAlign)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: plan_dev is not aligned to 256 bytes");
+    if (plan_bytes < plan_need)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: plan_bytes = " + std::to_string(plan_bytes) + ", the plan needs " +
+                                                         std::to_string(plan_need) + " (tsamd_grid_plan_bytes)");
+    if (workspace_need > 0 && !workspace_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is null");
+    if (reinterpret_cast<uintptr_t>(workspace_dev) % tsamd::kGridWorkspaceAlign)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is not aligned to 256 bytes");
+    if (workspace_bytes < workspace_need)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_bytes = " + std::to_string(workspace_bytes) + ", needed: " +
+                                                         std::to_string(workspace_need) + " (" + workspace_query + ")");
+    return TSAMD_OK;
+}
+
+}  // namespace
+
+int tsamd_grid_plan_build(const float *x_dev, int64_t n_points, int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size,
+                          int32_t base_resolution, float per_level_scale, int32_t dense, void *plan_dev, int64_t plan_bytes, void *workspace_dev,
+                          int64_t workspace_bytes, void *stream)
+{
+    tsamd::GridLevels lv;
+    int64_t n_params = 0;
+    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
+    if (rc) return rc;
+    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
+    if (n_points > (int64_t(1) << 40)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points above 2^40");
+    if (n_points > 0 && !x_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is null");
+    if (reinterpret_cast<uintptr_t>(x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is not float-aligned");
+    rc = check_plan_buffers(n_points, n_levels, plan_dev, plan_bytes, workspace_dev, workspace_bytes,
+                            tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes, "tsamd_grid_backward_sorted_workspace_bytes");
+    if (rc) return rc;
+    TSAMD_HIP(tsamd::launch_grid_plan_build(x_dev, n_points, lv, n_features_per_level, plan_dev, workspace_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_grid_encode_backward_planned(const float *x_dev, int64_t n_points, int32_t n_levels, int32_t n_features_per_level,
+                                       int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, int32_t dense,
+                                       const float *grad_out_dev, float *grad_params_dev, const void *plan_dev, int64_t plan_bytes,
+                                       void *workspace_dev, int64_t workspace_bytes, void *stream)
+{
+    tsamd::GridLevels lv;
+    int64_t n_params = 0;
+    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
+    if (rc) return rc;
+    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
+    if (n_points > (int64_t(1) << 40)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points above 2^40");
+    if (n_points > 0 && !x_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is null");
+    if (reinterpret_cast<uintptr_t>(x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is not float-aligned");
+    if (n_points > 0 && !grad_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev is null");
+    if (n_points > 0 && !grad_params_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_params_dev is null");
+    const uintptr_t align = n_features_per_level == 1 ? 4 : (n_features_per_level == 2 ? 8 : 16);
+    if (reinterpret_cast<uintptr_t>(grad_out_dev) % align || reinterpret_cast<uintptr_t>(grad_params_dev) % align)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev / grad_params_dev not aligned to n_features_per_level floats (max 16 B)");
+    rc = check_plan_buffers(n_points, n_levels, plan_dev, plan_bytes, workspace_dev, workspace_bytes,
+                            tsamd::grid_planned_workspace(n_points, n_features_per_level, n_levels).bytes,
+                            "tsamd_grid_backward_planned_workspace_bytes");
+    if (rc) return rc;
+    TSAMD_HIP(tsamd::launch_grid_encode_backward_planned(x_dev, n_points, lv, n_features_per_level, grad_out_dev, grad_params_dev, plan_dev,
+                                                         workspace_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
 }  // extern "C"

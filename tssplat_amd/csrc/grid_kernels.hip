@@ -11,10 +11,14 @@
 //   grid_backward_x_kernel           dL/dx, one lane per point looping over the levels: plain stores, bitwise repeatable
 //   grid_sorted_*_kernel             the second route to dL/dparams (launch_grid_encode_backward_sorted), every level alike:
 //                                    (entry, source) records, a stable radix sort by entry, a segmented sum; no float atomics
+//   grid_plan_pack_kernel,           the third route (launch_grid_plan_build / launch_grid_encode_backward_planned): the sorted
+//   grid_planned_*_kernel            route's sort done once for a frozen point set, its low record words kept as the plan; a
+//                                    backward is then the sorted route's segmented sum (one device body for both) and fold over
+//                                    the stored order, every level of a chunk in one launch
 //
-// The forward and dL/dx are bitwise deterministic (fixed summation order).  dL/dparams has two routes: the default one is a
+// The forward and dL/dx are bitwise deterministic (fixed summation order).  dL/dparams has three routes: the default one is a
 // float-atomic sum and may differ in the last bits from run to run (tiny-cuda-nn's does too); the sorted one adds every entry's
-// contributions in a fixed order and is bitwise repeatable (contract: grid.h).
+// contributions in a fixed order and is bitwise repeatable, and the planned one gives the sorted one's bits (contracts: grid.h).
 #include <hip/hip_runtime.h>
 
 #include "grid.h"
@@ -353,8 +357,9 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *w
 }
 
 // One workgroup per sort tile (kGridSortTile records = kGridSortTile / 8 points): records in (point, corner) order, the level's
-// grad_out slice compacted into gl, and the tile's histogram of the first digit.  hist is [digit][tile].
-template <int F>
+// grad_out slice compacted into gl, and the tile's histogram of the first digit.  hist is [digit][tile].  kWithG = false (the
+// plan build: records only) reads no grad_out and writes no gl.
+template <int F, bool kWithG = true>
 __global__ __launch_bounds__(kSortBlock) void grid_sorted_key_kernel(const float *__restrict__ x, uint32_t n, GridLevels lv, int l,
                                                                      const float *__restrict__ grad_out, Rec *__restrict__ rec,
                                                                      float *__restrict__ gl, uint32_t *__restrict__ hist, uint32_t n_tiles)
@@ -370,10 +375,13 @@ __global__ __launch_bounds__(kSortBlock) void grid_sorted_key_kernel(const float
     for (int r = 0; r < kGridSortTile / (8 * kSortBlock); ++r) {
         const uint32_t i = blockIdx.x * (kGridSortTile / 8) + r * kSortBlock + threadIdx.x;
         if (i >= n) continue;
-        float p[3], g[F];
+        float p[3];
         load_point(x, i, p);
-        load_feat<F>(grad_out + i * row + int64_t(l) * F, g);
-        store_feat<F>(gl + int64_t(i) * F, g);
+        if constexpr (kWithG) {
+            float g[F];
+            load_feat<F>(grad_out + i * row + int64_t(l) * F, g);
+            store_feat<F>(gl + int64_t(i) * F, g);
+        }
         const Cell cl = cell_of(p, scale);
         ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(rec + int64_t(i) * 8);
 #pragma unroll
@@ -513,17 +521,51 @@ __device__ __forceinline__ void add_entry(float *table, uint32_t key, const floa
     store_feat<F>(dst, t);
 }
 
-// Segmented sum over the sorted records: one wave per kGridSumRun consecutive records, 64 at a time.  A run of equal keys
+// Where a lane's record comes from.  A source gives the record's 4-byte `src` (8 * point + corner, kInvalid past the end),
+// says whether the record may be followed at all, and names its entry once the point's cell is known.
+//   SortedRecords: the 8-byte records of the radix sort; the entry is the record's high word.
+//   PlannedRecords: the 4-byte src of a point plan; the entry is rebuilt from the cell, so it is < entries whatever the plan holds.
+// g_stride: floats between two points' g vectors (F: a compact level slice; n_levels * F: a row of grad_out).
+template <int F>
+struct SortedRecords {
+    const Rec *rec;
+    __device__ __forceinline__ uint32_t read(uint32_t pos, uint32_t n_rec, uint32_t &hi) const
+    {
+        const Rec r = pos < n_rec ? rec[pos] : ~Rec(0);
+        hi = uint32_t(r >> 32);
+        return uint32_t(r);
+    }
+    __device__ __forceinline__ bool follows(uint32_t hi, uint32_t entries) const { return hi < entries; }
+    __device__ __forceinline__ uint32_t key(uint32_t hi, const Cell &, int) const { return hi; }
+    __device__ __forceinline__ int64_t g_stride() const { return F; }
+};
+
+struct PlannedRecords {
+    const uint32_t *src;
+    uint32_t res, entries;
+    bool hashed;
+    int64_t stride;
+    __device__ __forceinline__ uint32_t read(uint32_t pos, uint32_t n_rec, uint32_t &hi) const
+    {
+        hi = 0;
+        return pos < n_rec ? src[pos] : kInvalid;
+    }
+    __device__ __forceinline__ bool follows(uint32_t, uint32_t) const { return true; }
+    __device__ __forceinline__ uint32_t key(uint32_t, const Cell &cl, int corner) const { return corner_index(cl, corner, res, entries, hashed); }
+    __device__ __forceinline__ int64_t g_stride() const { return stride; }
+};
+
+// Segmented sum over records in sorted order: one wave per kGridSumRun consecutive records, 64 at a time.  A run of equal keys
 // inside a step is summed by segment_sums (a tree fixed by the lane positions); a run that goes on into the next step is
 // carried wave-uniformly and added in step order.  A run that lies strictly inside the wave's range is added to the table
 // here (no other wave sees its key); the run that starts at the range's first record and the one that ends at its last may
 // go on in the neighbouring waves, so they go to pkey / psum ([2 * wave]: first, [2 * wave + 1]: last, kInvalid: none) for
-// grid_sorted_fold_kernel.  A range that is one single run is its first partial.
-template <int F>
-__global__ __launch_bounds__(kSortBlock) void grid_sorted_sum_kernel(const Rec *__restrict__ rec, uint32_t n_rec, const float *__restrict__ x,
-                                                                     const float *__restrict__ gl, float scale, uint32_t entries,
-                                                                     float *__restrict__ table, uint32_t *__restrict__ pkey,
-                                                                     float *__restrict__ psum)
+// the fold.  A range that is one single run is its first partial.  The one body of both routes: the same instructions
+// on the same values in the same order, whichever source the records come from.
+template <int F, class Source>
+__device__ __forceinline__ void segmented_sum(const Source &source, uint32_t n_rec, const float *__restrict__ x, const float *__restrict__ gl,
+                                              float scale, uint32_t entries, float *__restrict__ table, uint32_t *__restrict__ pkey,
+                                              float *__restrict__ psum)
 {
     const int lane = __lane_id();
     const uint32_t wave = blockIdx.x * kSortWaves + threadIdx.x / 64;
@@ -540,14 +582,15 @@ __global__ __launch_bounds__(kSortBlock) void grid_sorted_sum_kernel(const Rec *
         float v[F];
 #pragma unroll
         for (int f = 0; f < F; ++f) v[f] = 0.0f;
-        const Rec r = pos < n_rec ? rec[pos] : ~Rec(0);
-        const uint32_t src = uint32_t(r), i = src >> 3;
-        if (uint32_t(r >> 32) < entries && src < n_rec) key = uint32_t(r >> 32);   // (a record is followed only while in bounds)
-        if (key != kInvalid) {
+        uint32_t hi;
+        const uint32_t src = source.read(pos, n_rec, hi), i = src >> 3;
+        if (source.follows(hi, entries) && src < n_rec) {                 // (a record is followed only while in bounds)
             float p[3], g[F];
             load_point(x, i, p);
-            load_feat<F>(gl + int64_t(i) * F, g);
-            const float w = corner_weight(cell_of(p, scale), int(src & 7));
+            load_feat<F>(gl + int64_t(i) * source.g_stride(), g);
+            const Cell cl = cell_of(p, scale);
+            key = source.key(hi, cl, int(src & 7));
+            const float w = corner_weight(cl, int(src & 7));
 #pragma unroll
             for (int f = 0; f < F; ++f) v[f] = w * g[f];
         }
@@ -602,10 +645,35 @@ __global__ __launch_bounds__(kSortBlock) void grid_sorted_sum_kernel(const Rec *
     }
 }
 
+template <int F>
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_sum_kernel(const Rec *__restrict__ rec, uint32_t n_rec, const float *__restrict__ x,
+                                                                     const float *__restrict__ gl, float scale, uint32_t entries,
+                                                                     float *__restrict__ table, uint32_t *__restrict__ pkey,
+                                                                     float *__restrict__ psum)
+{
+    segmented_sum<F>(SortedRecords<F>{rec}, n_rec, x, gl, scale, entries, table, pkey, psum);
+}
+
+// The planned sum: every level of a chunk in one launch (blockIdx.y: the level).  plan: [level][n_rec] src; g: the first
+// point's g vector of level 0, g_level floats on to the next level's, g_stride floats on to the next point's; pkey / psum:
+// [level][2 * n_waves].
+template <int F>
+__global__ __launch_bounds__(kSortBlock) void grid_planned_sum_kernel(const uint32_t *__restrict__ plan, uint32_t n_rec,
+                                                                      const float *__restrict__ x, const float *__restrict__ g, int64_t g_level,
+                                                                      int64_t g_stride, GridLevels lv, float *__restrict__ grad_params,
+                                                                      uint32_t *__restrict__ pkey, float *__restrict__ psum, uint32_t n_waves)
+{
+    const int l = blockIdx.y;
+    const uint32_t entries = lv.entries[l];
+    const PlannedRecords source{plan + int64_t(l) * n_rec, lv.res[l], entries, lv.hashed[l] != 0, g_stride};
+    segmented_sum<F>(source, n_rec, x, g + int64_t(l) * g_level, lv.scale[l], entries, grad_params + lv.offset[l] * F,
+                     pkey + int64_t(l) * 2 * n_waves, psum + int64_t(l) * 2 * n_waves * F);
+}
+
 // The boundary partials in wave order: the lane of an entry's first partial adds the entry's partials in that order.
 template <int F>
-__global__ __launch_bounds__(kSortBlock) void grid_sorted_fold_kernel(const uint32_t *__restrict__ pkey, const float *__restrict__ psum,
-                                                                      uint32_t n_part, float *__restrict__ table)
+__device__ __forceinline__ void fold_partials(const uint32_t *__restrict__ pkey, const float *__restrict__ psum, uint32_t n_part,
+                                              float *__restrict__ table)
 {
     const uint32_t j = blockIdx.x * kSortBlock + threadIdx.x;
     if (j >= n_part) return;
@@ -628,6 +696,28 @@ __global__ __launch_bounds__(kSortBlock) void grid_sorted_fold_kernel(const uint
         for (int f = 0; f < F; ++f) sum[f] += t[f];
     }
     add_entry<F>(table, key, sum);
+}
+
+template <int F>
+__global__ __launch_bounds__(kSortBlock) void grid_sorted_fold_kernel(const uint32_t *__restrict__ pkey, const float *__restrict__ psum,
+                                                                      uint32_t n_part, float *__restrict__ table)
+{
+    fold_partials<F>(pkey, psum, n_part, table);
+}
+
+template <int F>
+__global__ __launch_bounds__(kSortBlock) void grid_planned_fold_kernel(const uint32_t *__restrict__ pkey, const float *__restrict__ psum,
+                                                                       uint32_t n_part, GridLevels lv, float *__restrict__ grad_params)
+{
+    const int l = blockIdx.y;
+    fold_partials<F>(pkey + int64_t(l) * n_part, psum + int64_t(l) * n_part * F, n_part, grad_params + lv.offset[l] * F);
+}
+
+// The low word of every sorted record (8 * point_in_chunk + corner): what a point plan keeps of the sort.
+__global__ __launch_bounds__(kSortBlock) void grid_plan_pack_kernel(const Rec *__restrict__ rec, uint32_t n_rec, uint32_t *__restrict__ plan)
+{
+    const uint32_t pos = blockIdx.x * kSortBlock + threadIdx.x;
+    if (pos < n_rec) plan[pos] = uint32_t(rec[pos]);
 }
 
 inline int key_bits(uint32_t entries)
@@ -696,9 +786,97 @@ hipError_t backward_sorted_f(const float *x, int64_t n, const float *params, con
     return hipSuccess;
 }
 
+// The plan of a frozen point set: per chunk and level, the records sorted as above with only their low word kept, laid out
+// [chunk][level][8 * points_in_chunk].  The workspace is the sorted route's.
+hipError_t plan_build(const float *x, int64_t n, const GridLevels &lv, int32_t n_features, uint32_t *plan, void *workspace, hipStream_t stream)
+{
+    const GridSortedWorkspace ws = grid_sorted_workspace(n, n_features);
+    char *base = static_cast<char *>(workspace);
+    Rec *rec_a = reinterpret_cast<Rec *>(base + ws.rec_a), *rec_b = reinterpret_cast<Rec *>(base + ws.rec_b);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(base + ws.hist), *tot = reinterpret_cast<uint32_t *>(base + ws.tot);
+    for (int64_t first = 0; first < n; first += kGridSortedChunk) {
+        const uint32_t nc = uint32_t(n - first < kGridSortedChunk ? n - first : kGridSortedChunk);
+        const uint32_t n_rec = nc * 8;
+        const uint32_t n_tiles = (n_rec + kGridSortTile - 1) / kGridSortTile;
+        const float *xc = x + first * 3;
+        uint32_t *pc = plan + first * 8 * lv.n_levels;
+        for (int l = 0; l < lv.n_levels; ++l) {
+            hipLaunchKernelGGL((grid_sorted_key_kernel<1, false>), dim3(n_tiles), dim3(kSortBlock), 0, stream, xc, nc, lv, l,
+                               static_cast<const float *>(nullptr), rec_a, static_cast<float *>(nullptr), hist, n_tiles);
+            TSAMD_GRID_LAUNCHED();
+            Rec *src = rec_a, *dst = rec_b;
+            const int passes = (key_bits(lv.entries[l]) + 7) / 8;
+            for (int p = 0; p < passes; ++p) {
+                if (p > 0) {
+                    hipLaunchKernelGGL(grid_sorted_hist_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, n_tiles);
+                    TSAMD_GRID_LAUNCHED();
+                }
+                hipLaunchKernelGGL(grid_sorted_scan_kernel, dim3(256), dim3(kSortBlock), 0, stream, hist, n_tiles, tot);
+                TSAMD_GRID_LAUNCHED();
+                hipLaunchKernelGGL(grid_sorted_scatter_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, tot, n_tiles,
+                                   dst);
+                TSAMD_GRID_LAUNCHED();
+                Rec *t = src;
+                src = dst;
+                dst = t;
+            }
+            hipLaunchKernelGGL(grid_plan_pack_kernel, dim3((n_rec + kSortBlock - 1) / kSortBlock), dim3(kSortBlock), 0, stream, src, n_rec,
+                               pc + int64_t(l) * n_rec);
+            TSAMD_GRID_LAUNCHED();
+        }
+    }
+    return hipSuccess;
+}
+
+template <int F>
+hipError_t backward_planned_f(const float *x, int64_t n, const GridLevels &lv, const float *grad_out, float *grad_params, const uint32_t *plan,
+                              void *workspace, hipStream_t stream)
+{
+    const GridPlannedWorkspace ws = grid_planned_workspace(n, F, lv.n_levels);
+    char *base = static_cast<char *>(workspace);
+    uint32_t *pkey = reinterpret_cast<uint32_t *>(base + ws.pkey);
+    float *psum = reinterpret_cast<float *>(base + ws.psum);
+    const int64_t row = int64_t(lv.n_levels) * F;
+    for (int64_t first = 0; first < n; first += kGridSortedChunk) {               // chunks in order: part of the summation order
+        const uint32_t nc = uint32_t(n - first < kGridSortedChunk ? n - first : kGridSortedChunk);
+        const uint32_t n_rec = nc * 8, n_waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
+        const float *xc = x + first * 3, *gc = grad_out + first * row;
+        const uint32_t *pc = plan + first * 8 * lv.n_levels;
+        // g is read straight from the rows of grad_out (level l at + l * F, the next point's a row on)
+        hipLaunchKernelGGL(grid_planned_sum_kernel<F>, dim3((n_waves + kSortWaves - 1) / kSortWaves, lv.n_levels), dim3(kSortBlock), 0, stream,
+                           pc, n_rec, xc, gc, int64_t(F), row, lv, grad_params, pkey, psum, n_waves);
+        TSAMD_GRID_LAUNCHED();
+        hipLaunchKernelGGL(grid_planned_fold_kernel<F>, dim3((2 * n_waves + kSortBlock - 1) / kSortBlock, lv.n_levels), dim3(kSortBlock), 0, stream,
+                           pkey, psum, 2 * n_waves, lv, grad_params);
+        TSAMD_GRID_LAUNCHED();
+    }
+    return hipSuccess;
+}
+
 #undef TSAMD_GRID_LAUNCHED
 
 }  // namespace
+
+hipError_t launch_grid_plan_build(const float *x, int64_t n, const GridLevels &lv, int32_t n_features, void *plan, void *workspace,
+                                  hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    return plan_build(x, n, lv, n_features, static_cast<uint32_t *>(plan), workspace, stream);
+}
+
+hipError_t launch_grid_encode_backward_planned(const float *x, int64_t n, const GridLevels &lv, int32_t n_features, const float *grad_out,
+                                               float *grad_params, const void *plan, void *workspace, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    const uint32_t *p = static_cast<const uint32_t *>(plan);
+    switch (n_features) {
+    case 1: return backward_planned_f<1>(x, n, lv, grad_out, grad_params, p, workspace, stream);
+    case 2: return backward_planned_f<2>(x, n, lv, grad_out, grad_params, p, workspace, stream);
+    case 4: return backward_planned_f<4>(x, n, lv, grad_out, grad_params, p, workspace, stream);
+    case 8: return backward_planned_f<8>(x, n, lv, grad_out, grad_params, p, workspace, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t launch_grid_encode_backward_sorted(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features,
                                               const float *grad_out, float *grad_params, float *grad_x, void *workspace, hipStream_t stream)

@@ -20,7 +20,8 @@ import torch
 from . import _capi
 from .tet_spheres_ext import _device_ctx, _stream_ptr
 
-__all__ = ["GridEncoding", "parse_grid_config", "grid_layout", "sorted_workspace_bytes"]
+__all__ = ["GridEncoding", "GridPointPlan", "parse_grid_config", "grid_layout", "sorted_workspace_bytes", "plan_bytes",
+           "planned_workspace_bytes"]
 
 _lib = _capi.load()
 
@@ -86,6 +87,55 @@ def sorted_workspace_bytes(cfg: dict, n_points: int) -> int:
     return int(n.value)
 
 
+def plan_bytes(cfg: dict, n_points: int) -> int:
+    """Bytes of a point plan for ``n_points`` (tsamd_grid_plan_bytes; host only)."""
+    n = C.c_int64(0)
+    _capi.check(_lib.tsamd_grid_plan_bytes(int(n_points), *_args(cfg), C.byref(n)))
+    return int(n.value)
+
+
+def planned_workspace_bytes(cfg: dict, n_points: int) -> int:
+    """Bytes of workspace the planned backward needs (tsamd_grid_backward_planned_workspace_bytes; host only)."""
+    n = C.c_int64(0)
+    _capi.check(_lib.tsamd_grid_backward_planned_workspace_bytes(int(n_points), *_args(cfg), C.byref(n)))
+    return int(n.value)
+
+
+PLAN_KEYS = ("n_levels", "n_features_per_level", "log2_hashmap_size", "base_resolution", "per_level_scale", "dense")
+
+
+class GridPointPlan:
+    """A frozen point set, sorted once for the planned dL/dparams (csrc/grid.h states the contract).  ``x``: the plan's own
+    contiguous copy of the points (no gradient: a planned point set is frozen); ``cfg``: the normalised config it was built
+    for; ``buffer``: the device plan; ``nbytes``: its size.  Build one with :meth:`GridEncoding.plan_points`."""
+
+    def __init__(self, x: torch.Tensor, cfg: dict):
+        self.x = x.detach().clone(memory_format=torch.contiguous_format)
+        self.x.requires_grad_(False)
+        self.n_points = int(self.x.shape[0])
+        self.cfg = {k: cfg[k] for k in PLAN_KEYS}
+        dev = self.x.device
+        self.buffer = torch.empty(plan_bytes(cfg, self.n_points), dtype=torch.uint8, device=dev)
+        with _device_ctx(dev):
+            ws = torch.empty(sorted_workspace_bytes(cfg, self.n_points), dtype=torch.uint8, device=dev)
+            _capi.check(_lib.tsamd_grid_plan_build(self.x.data_ptr(), self.n_points, *_args(cfg), self.buffer.data_ptr(), self.buffer.numel(),
+                                                   ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.buffer.numel())
+
+    @property
+    def device(self) -> torch.device:
+        return self.x.device
+
+    def check_cfg(self, cfg: dict) -> None:
+        """ValueError unless ``cfg`` (normalised) is the config this plan was built for."""
+        mine, theirs = self.cfg, {k: cfg[k] for k in PLAN_KEYS}
+        if mine != theirs:
+            raise ValueError(f"tssplat_amd encoding: this point plan was built for {mine}, not for {theirs}")
+
+
 def _check_input(x: torch.Tensor, n_input_dims: int) -> torch.Tensor:
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise RuntimeError("tssplat_amd encoding: x must be a GPU tensor (there is no CPU fallback)")
@@ -130,6 +180,50 @@ class _GridEncodeFunc(torch.autograd.Function):
         return grad_x, grad_p, None, None
 
 
+class _GridEncodePlannedFunc(torch.autograd.Function):
+    """The encode forward on ``plan.x`` (the same kernel: the same bits); dL/dparams by the planned route, whatever param_grad."""
+
+    @staticmethod
+    def forward(ctx, params, plan, cfg, n_output_dims):
+        x, N = plan.x, plan.n_points
+        out = torch.empty((N, n_output_dims), dtype=torch.float32, device=x.device)
+        with _device_ctx(x.device):
+            _capi.check(_lib.tsamd_grid_encode(x.data_ptr(), N, params.data_ptr(), *_args(cfg), out.data_ptr(), _stream_ptr(x.device)))
+        ctx.cfg, ctx.plan = cfg, plan
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        plan, cfg = ctx.plan, ctx.cfg
+        g = grad_out.contiguous()
+        dev = plan.x.device
+        grad_p = torch.zeros(grid_layout_n_params(cfg), dtype=torch.float32, device=dev)
+        with _device_ctx(dev):
+            ws = torch.empty(planned_workspace_bytes(cfg, plan.n_points), dtype=torch.uint8, device=dev)
+            _capi.check(_lib.tsamd_grid_encode_backward_planned(plan.x.data_ptr(), plan.n_points, *_args(cfg), g.data_ptr(), grad_p.data_ptr(),
+                                                                plan.buffer.data_ptr(), plan.buffer.numel(), ws.data_ptr(), ws.numel(),
+                                                                _stream_ptr(dev)))
+        return grad_p, None, None, None
+
+
+def grid_layout_n_params(cfg: dict) -> int:
+    n = C.c_int64(0)
+    _capi.check(_lib.tsamd_grid_layout(*_args(cfg), None, None, None, None, C.byref(n)))
+    return int(n.value)
+
+
+def encode_planned(plan: GridPointPlan, params: torch.Tensor, cfg: dict, n_output_dims: int) -> torch.Tensor:
+    """``encode(plan.x)`` with the planned backward; ValueError on a plan built for another config."""
+    if not isinstance(plan, GridPointPlan):
+        raise TypeError("tssplat_amd encoding: expected a GridPointPlan")
+    plan.check_cfg(cfg)
+    if not params.is_cuda or params.device != plan.x.device:
+        raise RuntimeError("tssplat_amd encoding: params and the plan's points must live on the same GPU")
+    return _GridEncodePlannedFunc.apply(params, plan, cfg, n_output_dims)
+
+
 class GridEncoding(torch.nn.Module):
     """``tcnn.Encoding(3, grid_config)``: ``forward(x [N, 3] fp32 on the GPU) -> [N, n_levels * n_features_per_level]``."""
 
@@ -144,7 +238,15 @@ class GridEncoding(torch.nn.Module):
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.params = torch.nn.Parameter(init.to(dev))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def plan_points(self, x: torch.Tensor) -> GridPointPlan:
+        """Sorts a frozen point set once (``x``: as for ``forward``).  ``forward(plan)`` then gives ``forward(plan.x)``'s bits,
+        and its dL/dparams is the sorted route's, bit for bit, without the sort: no float atomics, a few launches.  The plan
+        owns a copy of ``x``; it carries no gradient to any ``x``.  It costs ``8 * n_levels * 4`` bytes per point."""
+        return GridPointPlan(_check_input(x, self.n_input_dims), self.cfg)
+
+    def forward(self, x) -> torch.Tensor:
+        if isinstance(x, GridPointPlan):
+            return encode_planned(x, self.params, self.cfg, self.n_output_dims)
         x = _check_input(x, self.n_input_dims)
         if not self.params.is_cuda or self.params.device != x.device:
             raise RuntimeError("tssplat_amd encoding: params and x must live on the same GPU")

@@ -14,6 +14,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
+from .encoding import GridPointPlan
 from .models import get_activation, get_encoding, get_mlp, scale_tensor, _rank
 
 __all__ = ["ExplicitMaterial", "contract_to_unisphere", "load_material"]
@@ -65,7 +66,18 @@ class ExplicitMaterial(torch.nn.Module):
         self.feature_network = get_mlp(self.encoding.n_output_dims, self.cfg.n_output_dims, self.cfg.mlp_network_config)
         self.to(self.device)
 
+    def plan_points(self, positions) -> GridPointPlan:
+        """A point plan for a frozen set of surface points: ``positions`` contracted exactly as ``forward`` does, flattened to
+        ``[-1, 3]`` and planned through the grid encoding.  ``forward(positions=plan)`` then returns the colour of those
+        points, ``[n_points, 3]``, with the planned (sort-free, atomic-free) dL/dparams of the grid."""
+        with torch.no_grad():
+            x = contract_to_unisphere(positions, self.bbox)
+            return self.encoding.plan_points(x.reshape(-1, 3))
+
     def forward(self, positions, **kwargs) -> Dict[str, Any]:
+        if isinstance(positions, GridPointPlan):
+            features = self.feature_network(self.encoding(positions)).view(positions.n_points, 3)
+            return {"color": get_activation(self.cfg.material_activation)(features)}
         positions = contract_to_unisphere(positions, self.bbox)          # points normalised to (0, 1)
         enc = self.encoding(positions.view(-1, 3))
         features = self.feature_network(enc).view(*positions.shape[:-1], 3)

@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import tcnn
+from .encoding import GridPointPlan
 
 __all__ = ["get_activation", "get_encoding", "get_mlp", "scale_tensor", "TCNNEncoding", "ProgressiveBandHashGrid",
            "ProgressiveBandFrequency", "CompositeEncoding", "VanillaMLP", "SphereInitVanillaMLP", "TCNNNetwork",
@@ -117,6 +118,10 @@ class TCNNEncoding(nn.Module):
     def forward(self, x):
         return self.encoding(x)
 
+    def plan_points(self, x):
+        """A point plan of the grid encoding (:meth:`tssplat_amd.encoding.GridEncoding.plan_points`); ``forward`` takes it."""
+        return self.encoding.plan_points(x)
+
 
 class ProgressiveBandHashGrid(nn.Module):
     """networks.py:109-148."""
@@ -139,6 +144,10 @@ class ProgressiveBandHashGrid(nn.Module):
     def forward(self, x):
         return self.encoding(x) * self.mask
 
+    def plan_points(self, x):
+        """A point plan of the grid encoding (:meth:`tssplat_amd.encoding.GridEncoding.plan_points`); ``forward`` takes it."""
+        return self.encoding.plan_points(x)
+
     def update_step(self, epoch, global_step, on_load_weights=False):
         current_level = min(self.start_level + max(global_step - self.start_step, 0) // self.update_steps, self.n_level)
         self.current_level = current_level
@@ -157,7 +166,14 @@ class CompositeEncoding(nn.Module):
     def forward(self, x, *args):
         if not self.include_xyz:
             return self.encoding(x, *args)
-        return torch.cat([x * self.xyz_scale + self.xyz_offset, self.encoding(x, *args)], dim=-1)
+        xyz = x.x if isinstance(x, GridPointPlan) else x            # (a plan's xyz columns come from its own points)
+        return torch.cat([xyz * self.xyz_scale + self.xyz_offset, self.encoding(x, *args)], dim=-1)
+
+    def plan_points(self, x):
+        """A point plan of the wrapped grid encoding; ``forward(plan)`` takes it in place of ``x``."""
+        if not hasattr(self.encoding, "plan_points"):
+            raise NotImplementedError(f"{type(self.encoding).__name__} offers no point plan (grid encodings only)")
+        return self.encoding.plan_points(x)
 
 
 def get_encoding(n_input_dims: int, config) -> nn.Module:

@@ -18,7 +18,21 @@ import torch
 
 from . import dr
 
-__all__ = ["MeshRasterizer"]
+__all__ = ["MeshRasterizer", "ViewPlan"]
+
+
+class ViewPlan:
+    """What the colour branch of :meth:`MeshRasterizer.forward` derives from a frozen surface under a fixed batch of views:
+    ``pos_clip``, ``rast_out``, the foreground ``selector`` and the material's point plan for the foreground points, in the
+    selector's order.  Built by :meth:`MeshRasterizer.plan_views`."""
+
+    def __init__(self, mvp, resolution: int, pos_clip, rast_out, selector, point_plan):
+        self.mvp, self.resolution = mvp, int(resolution)
+        self.pos_clip, self.rast_out, self.selector, self.point_plan = pos_clip, rast_out, selector, point_plan
+
+    @property
+    def n_points(self) -> int:
+        return self.point_plan.n_points
 
 
 class MeshRasterizer(torch.nn.Module):
@@ -46,9 +60,37 @@ class MeshRasterizer(torch.nn.Module):
             res[..., 2] /= 6
         return res
 
+    def plan_views(self, mvp: torch.Tensor, resolution: int, iter_num: int = 0) -> ViewPlan:
+        """Plans the texture stage's colour branch for one batch of views over FROZEN geometry: geometry, ``transform_pos``,
+        ``dr.rasterize`` and ``dr.interpolate`` run once, without gradients, and the material sorts the foreground points once
+        (``materials.plan_points``).  ``forward(..., view_plan=plan)`` then skips all four and the boolean compaction, and the
+        grid's dL/dparams is the planned route's: no sort, no float atomics.
+
+        A plan belongs to one point set in one order: these views, in this order, at this resolution.  A trainer whose loader
+        reshuffles the views every iteration keeps one plan per batch composition, or feeds the views in a fixed order.
+        Raises unless the geometry is frozen (``geometry.tet_v`` a buffer, not a Parameter) and the material offers
+        ``plan_points``."""
+        if isinstance(getattr(self.geometry, "tet_v", None), torch.nn.Parameter):
+            raise RuntimeError("MeshRasterizer.plan_views: the geometry is being optimised (tet_v is a Parameter); a view plan "
+                               "needs a frozen surface (optimize_geo=False)")
+        if self.materials is None or not hasattr(self.materials, "plan_points"):
+            raise RuntimeError("MeshRasterizer.plan_views: materials must offer plan_points (ExplicitMaterial does)")
+        with torch.no_grad():
+            data = self.geometry(iter_num=iter_num)
+            tri = data.t_pos_idx
+            pos_clip = self.transform_pos(mvp, data.v_pos).contiguous()
+            rast_out, _ = dr.rasterize(self.glctx, pos_clip, tri, resolution=[resolution, resolution], grad_db=False)
+            selector = rast_out[..., -1] > 0
+            positions_all, _ = dr.interpolate(data.v_pos[None, ...], rast_out, tri)
+            point_plan = self.materials.plan_points(positions_all[selector])
+        return ViewPlan(mvp, resolution, pos_clip, rast_out, selector, point_plan)
+
     def forward(self, mvp: torch.Tensor, only_alpha: bool, iter_num: int, resolution: int, permute_surface_scheduler=None,
                 fit_normal: bool = False, fit_depth: bool = False, background: Optional[torch.Tensor] = None,
-                campos: Optional[torch.Tensor] = None):
+                campos: Optional[torch.Tensor] = None, view_plan: Optional[ViewPlan] = None):
+        if view_plan is not None:
+            return self._forward_planned(view_plan, only_alpha, iter_num, resolution, permute_surface_scheduler, fit_normal, fit_depth,
+                                         background, campos)
         geo_input = {"iter_num": iter_num}
         if permute_surface_scheduler is not None:                    # mesh_rasterizer.py:90-94
             permute_dev = permute_surface_scheduler(iter_num)
@@ -89,6 +131,43 @@ class MeshRasterizer(torch.nn.Module):
             out["n"] = v_n
 
         if fit_depth:                                                # mesh_rasterizer.py:150-161
+            assert campos is not None
+            world_pos, _ = dr.interpolate(data.v_pos[None, ...], rast_out, tri)
+            out["d"] = torch.norm(world_pos - campos[:, None, None, :], dim=-1, keepdim=True)
+        return out
+
+    def _forward_planned(self, plan: ViewPlan, only_alpha, iter_num, resolution, permute_surface_scheduler, fit_normal, fit_depth,
+                         background, campos):
+        """``forward`` with a :class:`ViewPlan`: the geometry forward still runs (``geo_regularization``), alpha and both
+        ``antialias`` calls are as without a plan, the colour comes from the material's point plan."""
+        if only_alpha:
+            raise RuntimeError("MeshRasterizer.forward: view_plan with only_alpha=True (a view plan is the colour branch's)")
+        if permute_surface_scheduler is not None and permute_surface_scheduler(iter_num) is not None:
+            raise RuntimeError("MeshRasterizer.forward: view_plan while permute_surface_scheduler perturbs the surface at "
+                               f"iteration {iter_num}: the surface would move under the plan")
+        if int(resolution) != plan.resolution:
+            raise RuntimeError(f"MeshRasterizer.forward: view_plan was built at resolution {plan.resolution}, not {resolution}")
+        assert self.materials is not None
+        assert background is not None
+        data = self.geometry(iter_num=iter_num)
+        tri = data.t_pos_idx
+        pos_clip, rast_out = plan.pos_clip, plan.rast_out
+        alpha = torch.clamp(rast_out[..., -1:], 0, 1)
+        alpha = dr.antialias(alpha.contiguous(), rast_out, pos_clip, tri, topology_hash=self.tri_hash, pos_gradient_boost=1.0)
+
+        color = self.materials(positions=plan.point_plan)["color"]
+        gb_fg = torch.zeros(rast_out.shape[0], plan.resolution, plan.resolution, 3, device=self.device)
+        gb_fg[plan.selector] = color
+        gb_mat = torch.lerp(background, gb_fg, plan.selector[..., None].float())
+        shaded = dr.antialias(gb_mat.contiguous(), rast_out, pos_clip, tri, topology_hash=self.tri_hash, pos_gradient_boost=1.0)
+        out = {"shaded": shaded, "geo_regularization": data.smooth_barrier_energy}
+
+        if fit_normal:
+            v_s = data._compute_vertex_normal()[None, ...]
+            scale = torch.tensor([1, 1, -1], dtype=torch.float32, device=self.device)[None, None, :]
+            v_n, _ = dr.interpolate((v_s * scale).contiguous(), rast_out, tri)
+            out["n"] = v_n
+        if fit_depth:
             assert campos is not None
             world_pos, _ = dr.interpolate(data.v_pos[None, ...], rast_out, tri)
             out["d"] = torch.norm(world_pos - campos[:, None, None, :], dim=-1, keepdim=True)

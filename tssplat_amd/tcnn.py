@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import torch
 
-from .encoding import GridEncoding, _GridEncodeFunc, _check_input
+from .encoding import GridEncoding, GridPointPlan, _GridEncodeFunc, _check_input, encode_planned
 from .network import FusedMLP, fused_mlp, is_network_otype
 
 __all__ = ["Encoding", "Network", "NetworkWithInputEncoding"]
@@ -67,7 +67,14 @@ class NetworkWithInputEncoding(torch.nn.Module):
     def encoding_params(self) -> torch.Tensor:
         return self.params[self.n_network_params:]
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def plan_points(self, x: torch.Tensor) -> GridPointPlan:
+        """:meth:`tssplat_amd.encoding.GridEncoding.plan_points` for this module's encoding; ``forward(plan)`` takes it."""
+        return GridPointPlan(_check_input(x, self.n_input_dims), self.encoding_cfg)
+
+    def forward(self, x) -> torch.Tensor:
+        if isinstance(x, GridPointPlan):
+            features = encode_planned(x, self.encoding_params, self.encoding_cfg, self.network_cfg["n_input_dims"])
+            return fused_mlp(features, self.network_params, self.network_cfg)
         x = _check_input(x, self.n_input_dims)
         if not self.params.is_cuda or self.params.device != x.device:
             raise RuntimeError("tssplat_amd network: params and x must live on the same GPU")
