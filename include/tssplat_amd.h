@@ -521,6 +521,60 @@ int tsamd_mlp_backward(const float *x_dev, int64_t n_rows, const float *params_d
                        int32_t n_neurons, int32_t n_hidden_layers, int32_t activation, int32_t output_activation,
                        const float *grad_y_dev, float *grad_params_dev, float *grad_x_dev, void *workspace_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Texture atlas and texture sampling: the last step of the texture stage, a textured mesh,
+ *   tsamd_atlas_bake_positions <- what renderer.export(path, "material") bakes (renderers/mesh_rasterizer.py:165; the reference
+ *                                 goes through trimesh / pymeshlab / xatlas, none of which is used here)
+ *   tsamd_texture              <- dr.texture(tex, uv, filter_mode, boundary_mode) of nvdiffrast, without mipmaps and cube maps
+ * Semantics are fixed by tests/atlas_oracle.py and tests/texture_oracle.py; PARITY UNPINNED against pymeshlab's and
+ * nvdiffrast's own results.  Stateless; the caller owns all buffers and the current HIP device is used.
+ *
+ * The atlas is closed form, no packer.  T triangles in a square texture of R texels: n = ceil(sqrt(ceil(T / 2))) cells per
+ * row, c = R / n (integer) texels per cell, legs of L = c - 5 texels; c >= 6 is required.  Cell k = t / 2 has its origin at
+ * ((k % n) c, (k / n) c) and holds triangle 2 k as half A and 2 k + 1 as half B, two mirrored right triangles of the same
+ * orientation.  Texel (i, j) is column i, row j, its centre (i + 0.5, j + 0.5); uv = texel / R, no flip.  Corners relative
+ * to the cell origin, A: (1.5, 1.5), (1.5 + L, 1.5), (1.5, 1.5 + L); B: (c - 1.5, c - 1.5), (c - 1.5 - L, c - 1.5),
+ * (c - 1.5, c - 1.5 - L).  Ownership with local i, j in 0 .. c - 1: A owns i + j <= L + 3, B owns i + j >= 2 c - L - 5, the
+ * band between them, the texels outside the n c square and the halves of triangles >= T are unowned.  Every bilinear tap of
+ * non-zero weight of a point inside a UV triangle is a texel that triangle owns.  Barycentrics of an owned texel, extrapolated
+ * into the gutter so that bilinear sampling reproduces a linear function up to the edge: A: b1 = (i - 1) / L, b2 = (j - 1) / L;
+ * B: b1 = (c - 2 - i) / L, b2 = (c - 2 - j) / L; b0 = 1 - b1 - b2.
+ *
+ * tsamd_atlas_layout (host only): n, c and L.  The outputs (each may be NULL) are written whenever n_triangles is 1 .. 2^31
+ * and texture_res 1 .. 32768, also when c < 6 makes the call fail with TSAMD_ERR_INVALID_ARGUMENT: 6 n is then the smallest
+ * workable resolution, and the error text names it.
+ * tsamd_atlas_bake_positions: one lane per texel; positions_out_dev [R, R, 3] f32 = b0 v0 + b1 v1 + b2 v2 of the owning
+ * triangle in fp32, owner_out_dev [R, R] i32 = its index; an unowned texel gets owner -1 and position 0.  A triangle with a
+ * vertex index outside [0, n_vertices) is unowned; nothing is read or written out of bounds.  v_pos_dev: [n_vertices, 3] f32;
+ * tri_dev: [n_triangles, 3] i32. */
+int tsamd_atlas_layout(int64_t n_triangles, int32_t texture_res, int32_t *cells_per_row_out, int32_t *cell_out, int32_t *leg_out);
+int tsamd_atlas_bake_positions(const float *v_pos_dev, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                               int32_t texture_res, float *positions_out_dev, int32_t *owner_out_dev, void *stream);
+
+/* tex_dev: [tex_batch (1 or batch), tex_height, tex_width, n_channels] f32; uv_dev: [batch, height, width, 2] f32, 8-byte
+ * aligned; out_dev / grad_out_dev: [batch, height, width, n_channels] f32.  tex_height, tex_width 1 .. 32768.
+ * LINEAR: x = u W - 0.5, y = v H - 0.5 (a rounded product, then the difference; no flip), taps at floor(x), floor(x) + 1 and
+ * likewise in y, weights from the fractional parts.  NEAREST: the texel floor(u W), floor(v H).  WRAP reduces tap indices
+ * modulo the size (a true modulo: negative indices work), CLAMP clamps them, ZERO gives out-of-range taps the value 0.
+ * Indices are formed from coordinates kept within +-1e9; a non-finite uv gives a non-finite output, never an access out of
+ * bounds.
+ * tsamd_texture_backward: grad_tex_dev (tex's shape; NULL: not computed) is zero-filled by the call and accumulated with
+ * float atomics, summed over the batch when tex_batch is 1: not bitwise repeatable.  grad_uv_dev ([batch, height, width, 2],
+ * 8-byte aligned; NULL: not computed; LINEAR only, with NEAREST it must be NULL) is written: dL/du = W sum_c g_c ((t10 - t00)
+ * (1 - fy) + (t11 - t01) fy) and likewise dL/dv with H, from the taps actually used, so two clamped taps that coincide give 0.
+ * tex_dev may be NULL when grad_uv_dev is. */
+#define TSAMD_TEX_FILTER_NEAREST 0
+#define TSAMD_TEX_FILTER_LINEAR 1
+#define TSAMD_TEX_BOUNDARY_WRAP 0
+#define TSAMD_TEX_BOUNDARY_CLAMP 1
+#define TSAMD_TEX_BOUNDARY_ZERO 2
+int tsamd_texture(const float *tex_dev, int64_t tex_batch, int32_t tex_height, int32_t tex_width, int32_t n_channels,
+                  const float *uv_dev, int64_t batch, int32_t height, int32_t width, int32_t filter_mode, int32_t boundary_mode,
+                  float *out_dev, void *stream);
+int tsamd_texture_backward(const float *tex_dev, int64_t tex_batch, int32_t tex_height, int32_t tex_width, int32_t n_channels,
+                           const float *uv_dev, int64_t batch, int32_t height, int32_t width, int32_t filter_mode,
+                           int32_t boundary_mode, const float *grad_out_dev, float *grad_tex_dev, float *grad_uv_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

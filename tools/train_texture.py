@@ -5,11 +5,14 @@ here from a known colour field on tests/golden/mario_mesh.npz under scenes.datas
 empty).
 
     python tools/train_texture.py [--views 16 --res 256 --iters 300 --lr 0.01 --mlp VanillaMLP|FullyFusedMLP
-                                    --param-grad atomic|sorted --plan-points]
+                                    --param-grad atomic|sorted --plan-points --export DIR]
 
 --plan-points: the views are fixed and the geometry frozen, so the renderer plans them once before the loop
 (MeshRasterizer.plan_views) and every iteration runs with view_plan=: no rasterise / interpolate / compaction, and the hash
 grid's dL/dparams by the planned route (no sort, no float atomics).
+
+--export DIR: after the fit, renderer.export(DIR, "material") (trainer.py's last step) writes DIR/material/exported_surface.obj,
+.mtl and .png; the JSON line gains "export": the bake and the whole export in ms at texture_res = 1024.
 
 One JSON line: the loss at the first and last iteration, ms per iteration, and the split of one iteration's forward + backward
 into encode (hash grid), MLP and the rest (rasterise, interpolate, antialias, loss), timed stage by stage on the same points."""
@@ -45,7 +48,7 @@ def timed(fn, reps=5):
     return a.elapsed_time(b) / reps
 
 
-def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_grad="atomic", plan_points=False):
+def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_grad="atomic", plan_points=False, export_dir=None):
     from tssplat_amd import geometry, materials, renderers, scenes
     from tssplat_amd.utils.optimizer import AdamUniform
     torch.cuda.set_device(0)
@@ -119,13 +122,25 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_gra
     def mlp_fb():
         mlp(e.requires_grad_(True)).backward(gm)
     ms_enc, ms_mlp = timed(enc_fb), timed(mlp_fb)
+    export = {}
+    if export_dir is not None:
+        import time
+        from tssplat_amd import atlas
+        texture_res = 1024
+        bake_ms = timed(lambda: atlas.bake_material(mat, geo.tet_v[geo.surface_vid.long()], geo.surface_fid, texture_res), reps=3)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ren.export(export_dir, "material", texture_res=texture_res)
+        torch.cuda.synchronize()
+        export = {"export": {"dir": os.path.join(export_dir, "material"), "texture_res": texture_res, "triangles": int(f.shape[0]),
+                             "bake_material_ms": round(bake_ms, 3), "export_ms": round((time.perf_counter() - t0) * 1e3, 1)}}
     split_plan = {} if not plan_points else {"plan_build_ms": round(plan_build_ms, 3), "plan_bytes": view_plan.point_plan.nbytes}
     return {"views": views, "res": res, "iters": iters, "lr": lr, "mlp": mlp_otype, "param_grad": "planned" if plan_points else param_grad,
             "foreground_points": int(pts.shape[0]),
             "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)], "loss_ratio": round(losses[-1] / losses[0], 4),
             "ms_per_iter": round(ms_iter, 3),
             "split_ms": {"encode_fwd_bwd": round(ms_enc, 3), "mlp_fwd_bwd": round(ms_mlp, 3),
-                         "render_loss_optimizer_rest": round(ms_iter - ms_enc - ms_mlp, 3), **split_plan}}
+                         "render_loss_optimizer_rest": round(ms_iter - ms_enc - ms_mlp, 3), **split_plan}, **export}
 
 
 def main():
@@ -139,8 +154,10 @@ def main():
                     help="the hash grid's route to dL/dparams (sorted: bitwise repeatable)")
     ap.add_argument("--plan-points", action="store_true",
                     help="plan the fixed views once (MeshRasterizer.plan_views) and train with view_plan=")
+    ap.add_argument("--export", metavar="DIR", default=None,
+                    help="after the fit, write DIR/material/exported_surface.{obj,mtl,png} (MeshRasterizer.export)")
     a = ap.parse_args()
-    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp, a.param_grad, a.plan_points)))
+    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp, a.param_grad, a.plan_points, a.export)))
 
 
 if __name__ == "__main__":

@@ -9,14 +9,16 @@
 
 This module offers all four under the same names and argument order (``import tssplat_amd.dr as dr``), differentiable
 where nvdiffrast is: ``rasterize`` w.r.t. ``pos`` through ``(u, v)``, ``interpolate`` w.r.t. ``attr`` and ``rast``,
-``antialias`` w.r.t. ``color`` and ``pos``.  nvdiffrast is a separate library, not vendored by the reference and not
+``antialias`` w.r.t. ``color`` and ``pos``.  ``texture`` (which the reference's renderer does not call, but a textured mesh
+exported by ``MeshRasterizer.export`` needs to be rendered again) is offered without mipmaps and cube maps, differentiable
+w.r.t. ``tex`` and ``uv``; its semantics are pinned down in tests/texture_oracle.py, PARITY UNPINNED likewise.  nvdiffrast is a separate library, not vendored by the reference and not
 installed here: the semantics are a restatement of its published algorithm, pinned down in oracle/raster_oracle.py --
 PARITY UNPINNED against the library itself.
 
 What it does not do, loudly: ``grad_db=True``, ``ranges`` (range mode) and ``rast_db`` / ``diff_attrs`` are
 rejected (``RasterizeGLContext`` is an alias of the HIP context); clipping is against the NEAR plane only (a triangle with vertices at ``w <= 0`` is clipped there; one with a vertex
-beyond the +-16384-pixel guard band is dropped; the silhouette of a clipped triangle is not antialiased); no depth peeling,
-no texture sampling.
+beyond the +-16384-pixel guard band is dropped; the silhouette of a clipped triangle is not antialiased); no depth peeling; ``texture`` rejects ``uv_da``,
+``mip_level_bias``, ``mip``, ``max_mip_level``, the ``linear-mipmap-*`` filters and ``boundary_mode='cube'``.
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ import torch
 from . import _capi
 from .tet_spheres_ext import _device_ctx, _stream_ptr
 
-__all__ = ["RasterizeCudaContext", "rasterize", "interpolate", "antialias", "antialias_construct_topology_hash"]
+__all__ = ["RasterizeCudaContext", "rasterize", "interpolate", "antialias", "antialias_construct_topology_hash", "texture"]
 
 _lib = _capi.load()
 
@@ -334,3 +336,72 @@ def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: t
     if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != rast.device:
         raise RuntimeError("tssplat_amd.dr.antialias: topology_hash does not belong to this triangle list")
     return _AntialiasFunc.apply(color, rast, pos, tri, topo.opp, float(pos_gradient_boost), pair_masks)
+
+
+_TEX_FILTERS = {"nearest": 0, "linear": 1}                  # TSAMD_TEX_FILTER_* of include/tssplat_amd.h
+_TEX_BOUNDARIES = {"wrap": 0, "clamp": 1, "zero": 2}        # TSAMD_TEX_BOUNDARY_*
+
+
+class _TextureFunc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uv, filter_mode, boundary_mode):
+        TB, TH, TW, Cn = (int(k) for k in tex.shape)
+        B, H, W = int(uv.shape[0]), int(uv.shape[1]), int(uv.shape[2])
+        out = torch.empty((B, H, W, Cn), dtype=torch.float32, device=uv.device)
+        with _device_ctx(uv.device):
+            _capi.check(_lib.tsamd_texture(tex.data_ptr(), TB, TH, TW, Cn, uv.data_ptr(), B, H, W, filter_mode, boundary_mode, out.data_ptr(),
+                                           _stream_ptr(uv.device)))
+        ctx.save_for_backward(tex, uv)
+        ctx.modes = (filter_mode, boundary_mode)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        tex, uv = ctx.saved_tensors
+        filter_mode, boundary_mode = ctx.modes
+        TB, TH, TW, Cn = (int(k) for k in tex.shape)
+        B, H, W = int(uv.shape[0]), int(uv.shape[1]), int(uv.shape[2])
+        g = grad_out.contiguous()
+        grad_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None          # (zero-filled by the call)
+        grad_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] and filter_mode == _TEX_FILTERS["linear"] else None
+        if grad_tex is not None or grad_uv is not None:
+            with _device_ctx(uv.device):
+                _capi.check(_lib.tsamd_texture_backward(tex.data_ptr(), TB, TH, TW, Cn, uv.data_ptr(), B, H, W, filter_mode, boundary_mode, g.data_ptr(),
+                                                        None if grad_tex is None else grad_tex.data_ptr(),
+                                                        None if grad_uv is None else grad_uv.data_ptr(), _stream_ptr(uv.device)))
+        return grad_tex, grad_uv, None, None
+
+
+def texture(tex: torch.Tensor, uv: torch.Tensor, uv_da=None, mip_level_bias=None, mip=None, filter_mode: str = "auto",
+            boundary_mode: str = "wrap", max_mip_level=None):
+    """``dr.texture``: ``out[B, h, w, C]`` = ``tex[1 or B, H, W, C]`` sampled at ``uv[B, h, w, 2]``, nvdiffrast's names and
+    argument order.  ``filter_mode`` ``'nearest'`` or ``'linear'`` (``'auto'`` = ``'linear'``: there are no mipmaps to choose);
+    ``boundary_mode`` ``'wrap'`` (a true modulo), ``'clamp'`` or ``'zero'``.  ``x = u W - 0.5``, ``y = v H - 0.5``, no flip;
+    linear filtering takes the taps at ``floor(x)``, ``floor(x) + 1`` and likewise in ``y`` with the fractional parts as
+    weights, nearest takes texel ``floor(u W)``, ``floor(v H)`` (tests/texture_oracle.py; PARITY UNPINNED against nvdiffrast).
+
+    Differentiable w.r.t. ``tex`` (summed over the batch when ``tex`` has batch 1; float atomics, so the last bits are not
+    repeatable from run to run) and, for ``'linear'``, w.r.t. ``uv`` from the taps actually used; ``'nearest'`` gives ``uv``
+    no gradient (``None``).  ``uv_da``, ``mip_level_bias``, ``mip``, ``max_mip_level``, the ``'linear-mipmap-*'`` filters and
+    ``boundary_mode='cube'`` are not part of this slice and raise."""
+    if uv_da is not None or mip_level_bias is not None or mip is not None or max_mip_level is not None:
+        raise NotImplementedError("tssplat_amd.dr.texture: uv_da / mip_level_bias / mip / max_mip_level (mipmaps) are not part of this slice")
+    if filter_mode == "auto":
+        filter_mode = "linear"
+    if filter_mode in ("linear-mipmap-nearest", "linear-mipmap-linear"):
+        raise NotImplementedError(f"tssplat_amd.dr.texture: filter_mode={filter_mode!r} (mipmaps) is not part of this slice")
+    if boundary_mode == "cube":
+        raise NotImplementedError("tssplat_amd.dr.texture: boundary_mode='cube' (cube maps) is not part of this slice")
+    if filter_mode not in _TEX_FILTERS:
+        raise ValueError(f"tssplat_amd.dr.texture: unknown filter_mode {filter_mode!r}")
+    if boundary_mode not in _TEX_BOUNDARIES:
+        raise ValueError(f"tssplat_amd.dr.texture: unknown boundary_mode {boundary_mode!r}")
+    tex = _check_cuda_f32("tex", tex)
+    uv = _check_cuda_f32("uv", uv)
+    if uv.dim() != 4 or uv.shape[3] != 2:
+        raise RuntimeError("tssplat_amd.dr.texture: uv must be [B, h, w, 2]")
+    if tex.dim() != 4 or tex.shape[0] not in (1, uv.shape[0]) or min(tex.shape[1:]) < 1:
+        raise RuntimeError("tssplat_amd.dr.texture: tex must be [1 or B, H, W, C] with H, W, C >= 1")
+    if tex.device != uv.device:
+        raise RuntimeError("tssplat_amd.dr.texture: tex and uv must live on the same device")
+    return _TextureFunc.apply(tex, uv, _TEX_FILTERS[filter_mode], _TEX_BOUNDARIES[boundary_mode])

@@ -196,8 +196,12 @@ class TetMeshGeometry(torch.nn.Module):
 
     The reference reads its configuration with omegaconf and its mesh with pypgo (``TetrahedronMesh(veg_file_path=...)``);
     neither is part of the hot path, so the constructor takes the arrays (``from_veg`` reads a ``.veg`` file with this
-    package's own reader) and the reference's ``Config`` fields as keyword arguments.  Remeshing / export / uv are not
-    mirrored (offline tools)."""
+    package's own reader) and the reference's ``Config`` fields as keyword arguments.  ``uv`` / ``uv_idx`` (the reference's
+    names, tetmesh_geometry.py:150-153, there filled by xatlas) are the per-wedge UVs of this package's closed-form atlas
+    (tssplat_amd/atlas.py) at ``uv_resolution`` texels, built on first access.  Remeshing / geometry export are not mirrored
+    (offline tools)."""
+
+    uv_resolution = 1024
 
     def __init__(self, vtx_init, elem, use_smooth_barrier: bool = True, smooth_barrier_param=None, optimize_geo: bool = True,
                  device=None, surface_vid=None, surface_fid=None, **energy_kwargs):
@@ -231,6 +235,22 @@ class TetMeshGeometry(torch.nn.Module):
             with torch.cuda.device(self.device):
                 self.mesh_smooth_barrier = SmoothnessBarrierEnergy(vtx, elem, flags, **energy_kwargs)
         self._surface_ops = _ops_for(self.surface_vid, self.surface_fid, int(tet_v.shape[0]))
+
+    def _atlas_uv(self):
+        if getattr(self, "_uv", None) is None:
+            from . import atlas
+            self._uv = atlas.atlas_uv(int(self.surface_fid.shape[0]), self.uv_resolution, device=self.device)
+        return self._uv
+
+    @property
+    def uv(self) -> torch.Tensor:
+        """``[3 T, 2]`` float32 per-wedge texture coordinates of the surface triangles (atlas.atlas_uv)."""
+        return self._atlas_uv()[0]
+
+    @property
+    def uv_idx(self) -> torch.Tensor:
+        """``[T, 3]`` int32 indices into ``uv``, one row per triangle of ``surface_fid``."""
+        return self._atlas_uv()[1]
 
     @classmethod
     def from_veg(cls, path, **kwargs):

@@ -4,19 +4,20 @@ caller of SURVEY 8(f) rows 2 and 4: geometry forward (energy + surface gather), 
 
 Same ``forward`` arguments and output keys (``"shaded"``, ``"geo_regularization"``, ``"n"``, ``"d"``) as the reference, so that
 trainer.py:81-130 reads the same against either.  Host logic only: every tensor operation that is not one of this package's
-kernels is the torch call the reference itself makes (clamp, lerp, masked assignment, norm).  Not mirrored: ``export``
-(xatlas / pymeshlab / cv2, an offline tool) and the reference's structured-config plumbing (``context_type="gl"`` is served
-by the same HIP kernels as ``"cuda"``; the two
-``Config`` fields are keyword arguments).
+kernels is the torch call the reference itself makes (clamp, lerp, masked assignment, norm).  ``export`` keeps the reference's
+signature and file names but not its route (trimesh / pymeshlab / xatlas): the colour field is baked into this package's own
+closed-form atlas (tssplat_amd/atlas.py).  Not mirrored: the reference's structured-config plumbing (``context_type="gl"`` is
+served by the same HIP kernels as ``"cuda"``; the two ``Config`` fields are keyword arguments).
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import numpy as np
 import torch
 
-from . import dr
+from . import atlas, dr
 
 __all__ = ["MeshRasterizer", "ViewPlan"]
 
@@ -172,3 +173,19 @@ class MeshRasterizer(torch.nn.Module):
             world_pos, _ = dr.interpolate(data.v_pos[None, ...], rast_out, tri)
             out["d"] = torch.norm(world_pos - campos[:, None, None, :], dim=-1, keepdim=True)
         return out
+
+    def export(self, path: str, folder: str, texture_res: int = 1024):
+        """``renderer.export(f"{cfg.output_path}/final", "material")`` (trainer.py, mesh_rasterizer.py:165): writes
+        ``exported_surface.obj``, ``.mtl`` and ``.png`` under ``path/folder`` -- the surface ``tet_v[surface_vid]`` /
+        ``surface_fid`` with per-wedge UVs of the closed-form atlas at ``texture_res`` and ``self.materials`` baked into it
+        (:mod:`tssplat_amd.atlas`; unowned texels stay black, there is no inpainting)."""
+        assert self.materials is not None
+        out_dir = os.path.join(path, folder)
+        os.makedirs(out_dir, exist_ok=True)
+        with torch.no_grad():
+            v_pos = self.geometry.tet_v.detach()[self.geometry.surface_vid.long()].contiguous()
+            t_pos_idx = self.geometry.surface_fid
+            # (geometry.uv / uv_idx are this atlas at the geometry's default resolution; the atlas depends on texture_res)
+            v_tex, t_tex_idx = atlas.atlas_uv(int(t_pos_idx.shape[0]), texture_res)
+            tex = atlas.bake_material(self.materials, v_pos, t_pos_idx, texture_res)
+        atlas.write_textured_obj(out_dir, "exported_surface", v_pos, t_pos_idx, v_tex, t_tex_idx, tex)
