@@ -48,6 +48,19 @@ constexpr int kGridSortTile = 4096;                        // records per workgr
 constexpr int kGridSumRun = 512;                           // records per wave of the segmented sum
 constexpr int64_t kGridWorkspaceAlign = 256;
 
+inline int64_t grid_align_up(int64_t bytes) { return (bytes + kGridWorkspaceAlign - 1) / kGridWorkspaceAlign * kGridWorkspaceAlign; }
+
+// Of n points still to go, the next chunk's points (at most kGridSortedChunk), its records, sort tiles and sum waves.
+struct GridChunk {
+    int64_t points, records, tiles, waves;
+};
+
+inline GridChunk grid_chunk(int64_t n)
+{
+    const int64_t nc = n < 0 ? 0 : (n < kGridSortedChunk ? n : kGridSortedChunk), n_rec = nc * 8;
+    return {nc, n_rec, (n_rec + kGridSortTile - 1) / kGridSortTile, (n_rec + kGridSumRun - 1) / kGridSumRun};
+}
+
 // Byte offsets of the workspace's parts (each kGridWorkspaceAlign-aligned) and its size: a function of min(n, chunk) and F.
 struct GridSortedWorkspace {
     int64_t rec_a, rec_b;      // 8-byte records (entry << 32 | 8 * point + corner), ping and pong
@@ -59,23 +72,15 @@ struct GridSortedWorkspace {
 
 inline GridSortedWorkspace grid_sorted_workspace(int64_t n, int32_t n_features)
 {
-    const int64_t nc = n < 0 ? 0 : (n < kGridSortedChunk ? n : kGridSortedChunk), n_rec = nc * 8;
-    const int64_t tiles = (n_rec + kGridSortTile - 1) / kGridSortTile, waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
-    GridSortedWorkspace ws{};
-    int64_t at = 0;
-    const auto take = [&at](int64_t bytes) {
-        const int64_t here = at;
-        at += (bytes + kGridWorkspaceAlign - 1) / kGridWorkspaceAlign * kGridWorkspaceAlign;
-        return here;
-    };
-    ws.rec_a = take(n_rec * 8);
-    ws.rec_b = take(n_rec * 8);
-    ws.gl = take(nc * n_features * 4);
-    ws.hist = take(256 * tiles * 4);
-    ws.tot = take(256 * 4);
-    ws.pkey = take(2 * waves * 4);
-    ws.psum = take(2 * waves * n_features * 4);
-    ws.bytes = nc > 0 ? at : 0;
+    const GridChunk c = grid_chunk(n);
+    GridSortedWorkspace ws{};                      // (rec_a = 0)
+    ws.rec_b = ws.rec_a + grid_align_up(c.records * 8);
+    ws.gl = ws.rec_b + grid_align_up(c.records * 8);
+    ws.hist = ws.gl + grid_align_up(c.points * n_features * 4);
+    ws.tot = ws.hist + grid_align_up(256 * c.tiles * 4);
+    ws.pkey = ws.tot + grid_align_up(256 * 4);
+    ws.psum = ws.pkey + grid_align_up(2 * c.waves * 4);
+    ws.bytes = c.points > 0 ? ws.psum + grid_align_up(2 * c.waves * n_features * 4) : 0;
     return ws;
 }
 
@@ -98,11 +103,7 @@ hipError_t launch_grid_encode_backward_sorted(const float *x, int64_t n, const f
 //  4. Build and backward make no allocation and no host synchronisation; all launch geometry is a function of (n, config).
 // x, n and the config of a backward must be those the plan was built with.  It ADDS into grad_params.  There is no dL/dx with a
 // plan: a planned point set is frozen by definition.
-inline int64_t grid_plan_bytes(int64_t n, int32_t n_levels)
-{
-    const int64_t bytes = (n < 0 ? 0 : n) * 8 * n_levels * 4;
-    return (bytes + kGridWorkspaceAlign - 1) / kGridWorkspaceAlign * kGridWorkspaceAlign;
-}
+inline int64_t grid_plan_bytes(int64_t n, int32_t n_levels) { return grid_align_up((n < 0 ? 0 : n) * 8 * n_levels * 4); }
 
 // The planned backward's workspace: the boundary partials of every level of one chunk, [level][2 * waves].
 struct GridPlannedWorkspace {
@@ -112,13 +113,10 @@ struct GridPlannedWorkspace {
 
 inline GridPlannedWorkspace grid_planned_workspace(int64_t n, int32_t n_features, int32_t n_levels)
 {
-    const int64_t nc = n < 0 ? 0 : (n < kGridSortedChunk ? n : kGridSortedChunk), n_rec = nc * 8;
-    const int64_t waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
-    const auto up = [](int64_t bytes) { return (bytes + kGridWorkspaceAlign - 1) / kGridWorkspaceAlign * kGridWorkspaceAlign; };
-    GridPlannedWorkspace ws{};
-    ws.pkey = 0;
-    ws.psum = up(int64_t(n_levels) * 2 * waves * 4);
-    ws.bytes = nc > 0 ? ws.psum + up(int64_t(n_levels) * 2 * waves * n_features * 4) : 0;
+    const GridChunk c = grid_chunk(n);
+    GridPlannedWorkspace ws{};                     // (pkey = 0)
+    ws.psum = grid_align_up(n_levels * 2 * c.waves * 4);
+    ws.bytes = c.points > 0 ? ws.psum + grid_align_up(n_levels * 2 * c.waves * n_features * 4) : 0;
     return ws;
 }
 

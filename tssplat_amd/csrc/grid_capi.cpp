@@ -73,30 +73,88 @@ bool grid_layout(int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size
 
 namespace {
 
-int layout_or_fail(int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
-                   int32_t dense, tsamd::GridLevels &lv, int64_t &n_params)
+int fail(const std::string &what) { return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: " + what); }
+
+#define TSAMD_GRID_CHECK(check)                  \
+    do {                                         \
+        if (const int rc_ = (check)) return rc_; \
+    } while (0)
+
+// The config's level table, as the kernels take it.
+int check_config(int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, int32_t dense,
+                 tsamd::GridLevels &lv, int64_t *n_params_out = nullptr)
 {
     std::string err;
-    if (!tsamd::grid_layout(n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params, err))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: " + err);
+    int64_t n_params = 0;
+    if (!tsamd::grid_layout(n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params, err)) return fail(err);
     // the coarse levels whose table fits in LDS (a prefix: entries never decrease with the level)
     lv.lds_levels = 0;
     while (lv.lds_levels < n_levels && int64_t(lv.entries[lv.lds_levels]) * n_features * 4 <= tsamd::kGridLdsBytes) ++lv.lds_levels;
+    if (n_params_out) *n_params_out = n_params;
     return TSAMD_OK;
 }
 
-int check_pointers(int64_t n_points, const float *x_dev, const float *params_dev, int32_t n_features)
+// `limited`: whether the entry point bounds n_points by 2^40.  The two workspace size queries (sorted and planned) never did
+// and still do not (their answer is constant from one chunk on); every other entry point does.
+int check_count(int64_t n_points, bool limited)
 {
-    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
-    if (n_points > (int64_t(1) << 40)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points above 2^40");
-    if (!params_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: params_dev is null");
-    if (n_points > 0 && !x_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is null");
-    // one vector load / store per entry: float2 for F = 2, float4 for F >= 4
-    const uintptr_t align = n_features == 1 ? 4 : (n_features == 2 ? 8 : 16);
-    if (reinterpret_cast<uintptr_t>(params_dev) % align)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: params_dev is not aligned to n_features_per_level floats (max 16 B)");
-    if (reinterpret_cast<uintptr_t>(x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is not float-aligned");
+    if (n_points < 0) return fail("n_points < 0");
+    if (limited && n_points > (int64_t(1) << 40)) return fail("n_points above 2^40");
     return TSAMD_OK;
+}
+
+int check_float_aligned(const void *p, const char *name)
+{
+    if (reinterpret_cast<uintptr_t>(p) % 4) return fail(std::string(name) + " is not float-aligned");
+    return TSAMD_OK;
+}
+
+int check_points(int64_t n_points, const float *x_dev)
+{
+    TSAMD_GRID_CHECK(check_count(n_points, true));
+    if (n_points > 0 && !x_dev) return fail("x_dev is null");
+    return check_float_aligned(x_dev, "x_dev");
+}
+
+// A size query's own arguments (`limited`: check_count).
+int check_query(int64_t n_points, bool limited, const int64_t *bytes_out)
+{
+    TSAMD_GRID_CHECK(check_count(n_points, limited));
+    return bytes_out ? TSAMD_OK : fail("bytes_out is null");
+}
+
+// One vector load / store per entry: float2 for F = 2, float4 for F >= 4.
+int check_feature_aligned(const void *p, const char *name, int32_t n_features)
+{
+    const uintptr_t align = n_features == 1 ? 4 : (n_features == 2 ? 8 : 16);
+    if (reinterpret_cast<uintptr_t>(p) % align) return fail(std::string(name) + " is not aligned to n_features_per_level floats (max 16 B)");
+    return TSAMD_OK;
+}
+
+// A caller-owned device buffer `<name>_dev` of `<name>_bytes` bytes, sized by the query function `query`.
+int check_buffer(const char *name, const void *p, int64_t bytes, int64_t need, const char *query)
+{
+    if (need > 0 && !p) return fail(std::string(name) + "_dev is null");
+    if (reinterpret_cast<uintptr_t>(p) % tsamd::kGridWorkspaceAlign) return fail(std::string(name) + "_dev is not aligned to 256 bytes");
+    if (bytes < need) return fail(std::string(name) + "_bytes = " + std::to_string(bytes) + ", needed: " + std::to_string(need) + " (" + query + ")");
+    return TSAMD_OK;
+}
+
+// The points and the table, as the forward and the two backwards that differentiate through x take them.
+int check_inputs(int64_t n_points, const float *x_dev, const float *params_dev, int32_t n_features)
+{
+    TSAMD_GRID_CHECK(check_points(n_points, x_dev));
+    if (!params_dev) return fail("params_dev is null");
+    return check_feature_aligned(params_dev, "params_dev", n_features);
+}
+
+// grad_out and the two gradients of the atomic and the sorted backward.
+int check_gradients(int64_t n_points, const float *grad_out_dev, const float *grad_params_dev, const float *grad_x_dev, int32_t n_features)
+{
+    if (n_points > 0 && !grad_out_dev) return fail("grad_out_dev is null");
+    TSAMD_GRID_CHECK(check_feature_aligned(grad_out_dev, "grad_out_dev", n_features));
+    TSAMD_GRID_CHECK(check_feature_aligned(grad_params_dev, "grad_params_dev", n_features));
+    return check_float_aligned(grad_x_dev, "grad_x_dev");
 }
 
 }  // namespace
@@ -109,8 +167,7 @@ int tsamd_grid_layout(int32_t n_levels, int32_t n_features_per_level, int32_t lo
 {
     tsamd::GridLevels lv;
     int64_t n_params = 0;
-    const int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, &n_params));
     for (int l = 0; l < n_levels; ++l) {
         if (offsets_out) offsets_out[l] = lv.offset[l];
         if (resolution_out) resolution_out[l] = int32_t(lv.res[l]);
@@ -126,14 +183,10 @@ int tsamd_grid_encode(const float *x_dev, int64_t n_points, const float *params_
                       int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, int32_t dense, float *out_dev, void *stream)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    rc = check_pointers(n_points, x_dev, params_dev, n_features_per_level);
-    if (rc) return rc;
-    if (n_points > 0 && !out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: out_dev is null");
-    if (reinterpret_cast<uintptr_t>(out_dev) % (n_features_per_level == 1 ? 4 : (n_features_per_level == 2 ? 8 : 16)))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: out_dev is not aligned to n_features_per_level floats (max 16 B)");
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_inputs(n_points, x_dev, params_dev, n_features_per_level));
+    if (n_points > 0 && !out_dev) return fail("out_dev is null");
+    TSAMD_GRID_CHECK(check_feature_aligned(out_dev, "out_dev", n_features_per_level));
     TSAMD_HIP(tsamd::launch_grid_encode(x_dev, n_points, params_dev, lv, n_features_per_level, out_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
 }
@@ -143,16 +196,9 @@ int tsamd_grid_encode_backward(const float *x_dev, int64_t n_points, const float
                                const float *grad_out_dev, float *grad_params_dev, float *grad_x_dev, void *stream)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    rc = check_pointers(n_points, x_dev, params_dev, n_features_per_level);
-    if (rc) return rc;
-    if (n_points > 0 && !grad_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev is null");
-    const uintptr_t align = n_features_per_level == 1 ? 4 : (n_features_per_level == 2 ? 8 : 16);
-    if (reinterpret_cast<uintptr_t>(grad_out_dev) % align || reinterpret_cast<uintptr_t>(grad_params_dev) % align)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev / grad_params_dev not aligned to n_features_per_level floats (max 16 B)");
-    if (reinterpret_cast<uintptr_t>(grad_x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_x_dev is not float-aligned");
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_inputs(n_points, x_dev, params_dev, n_features_per_level));
+    TSAMD_GRID_CHECK(check_gradients(n_points, grad_out_dev, grad_params_dev, grad_x_dev, n_features_per_level));
     TSAMD_HIP(tsamd::launch_grid_encode_backward(x_dev, n_points, params_dev, lv, n_features_per_level, grad_out_dev, grad_params_dev, grad_x_dev,
                                                  static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -164,11 +210,8 @@ int tsamd_grid_backward_sorted_workspace_bytes(int64_t n_points, int32_t n_level
                                                int32_t base_resolution, float per_level_scale, int32_t dense, int64_t *bytes_out)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    const int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
-    if (!bytes_out) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: bytes_out is null");
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_query(n_points, false, bytes_out));
     *bytes_out = tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes;
     return TSAMD_OK;
 }
@@ -179,25 +222,12 @@ int tsamd_grid_encode_backward_sorted(const float *x_dev, int64_t n_points, cons
                                       int64_t workspace_bytes, void *stream)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    rc = check_pointers(n_points, x_dev, params_dev, n_features_per_level);
-    if (rc) return rc;
-    if (n_points > 0 && !grad_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev is null");
-    const uintptr_t align = n_features_per_level == 1 ? 4 : (n_features_per_level == 2 ? 8 : 16);
-    if (reinterpret_cast<uintptr_t>(grad_out_dev) % align || reinterpret_cast<uintptr_t>(grad_params_dev) % align)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev / grad_params_dev not aligned to n_features_per_level floats (max 16 B)");
-    if (reinterpret_cast<uintptr_t>(grad_x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_x_dev is not float-aligned");
-    if (grad_params_dev) {                            // (dL/dx only needs no workspace)
-        const int64_t need = tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes;
-        if (need > 0 && !workspace_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is null");
-        if (reinterpret_cast<uintptr_t>(workspace_dev) % tsamd::kGridWorkspaceAlign)
-            return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is not aligned to 256 bytes");
-        if (workspace_bytes < need)
-            return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_bytes = " + std::to_string(workspace_bytes) + ", the sorted backward needs " +
-                                                             std::to_string(need) + " (tsamd_grid_backward_sorted_workspace_bytes)");
-    }
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_inputs(n_points, x_dev, params_dev, n_features_per_level));
+    TSAMD_GRID_CHECK(check_gradients(n_points, grad_out_dev, grad_params_dev, grad_x_dev, n_features_per_level));
+    if (grad_params_dev)                              // (dL/dx only needs no workspace)
+        TSAMD_GRID_CHECK(check_buffer("workspace", workspace_dev, workspace_bytes, tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes,
+                                      "tsamd_grid_backward_sorted_workspace_bytes"));
     TSAMD_HIP(tsamd::launch_grid_encode_backward_sorted(x_dev, n_points, params_dev, lv, n_features_per_level, grad_out_dev, grad_params_dev,
                                                         grad_x_dev, workspace_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -207,12 +237,8 @@ int tsamd_grid_plan_bytes(int64_t n_points, int32_t n_levels, int32_t n_features
                           float per_level_scale, int32_t dense, int64_t *bytes_out)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    const int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
-    if (n_points > (int64_t(1) << 40)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points above 2^40");
-    if (!bytes_out) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: bytes_out is null");
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_query(n_points, true, bytes_out));
     *bytes_out = tsamd::grid_plan_bytes(n_points, n_levels);
     return TSAMD_OK;
 }
@@ -221,54 +247,22 @@ int tsamd_grid_backward_planned_workspace_bytes(int64_t n_points, int32_t n_leve
                                                 int32_t base_resolution, float per_level_scale, int32_t dense, int64_t *bytes_out)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    const int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
-    if (!bytes_out) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: bytes_out is null");
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_query(n_points, false, bytes_out));
     *bytes_out = tsamd::grid_planned_workspace(n_points, n_features_per_level, n_levels).bytes;
     return TSAMD_OK;
 }
-
-namespace {
-
-// The plan's and a workspace's checks, shared by the plan build and the planned backward.
-int check_plan_buffers(int64_t n_points, int32_t n_levels, const void *plan_dev, int64_t plan_bytes, const void *workspace_dev,
-                       int64_t workspace_bytes, int64_t workspace_need, const char *workspace_query)
-{
-    const int64_t plan_need = tsamd::grid_plan_bytes(n_points, n_levels);
-    if (plan_need > 0 && !plan_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: plan_dev is null");
-    if (reinterpret_cast<uintptr_t>(plan_dev) % tsamd::kGridWorkspaceAlign)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: plan_dev is not aligned to 256 bytes");
-    if (plan_bytes < plan_need)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: plan_bytes = " + std::to_string(plan_bytes) + ", the plan needs " +
-                                                         std::to_string(plan_need) + " (tsamd_grid_plan_bytes)");
-    if (workspace_need > 0 && !workspace_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is null");
-    if (reinterpret_cast<uintptr_t>(workspace_dev) % tsamd::kGridWorkspaceAlign)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_dev is not aligned to 256 bytes");
-    if (workspace_bytes < workspace_need)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: workspace_bytes = " + std::to_string(workspace_bytes) + ", needed: " +
-                                                         std::to_string(workspace_need) + " (" + workspace_query + ")");
-    return TSAMD_OK;
-}
-
-}  // namespace
 
 int tsamd_grid_plan_build(const float *x_dev, int64_t n_points, int32_t n_levels, int32_t n_features_per_level, int32_t log2_hashmap_size,
                           int32_t base_resolution, float per_level_scale, int32_t dense, void *plan_dev, int64_t plan_bytes, void *workspace_dev,
                           int64_t workspace_bytes, void *stream)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
-    if (n_points > (int64_t(1) << 40)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points above 2^40");
-    if (n_points > 0 && !x_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is null");
-    if (reinterpret_cast<uintptr_t>(x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is not float-aligned");
-    rc = check_plan_buffers(n_points, n_levels, plan_dev, plan_bytes, workspace_dev, workspace_bytes,
-                            tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes, "tsamd_grid_backward_sorted_workspace_bytes");
-    if (rc) return rc;
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_points(n_points, x_dev));
+    TSAMD_GRID_CHECK(check_buffer("plan", plan_dev, plan_bytes, tsamd::grid_plan_bytes(n_points, n_levels), "tsamd_grid_plan_bytes"));
+    TSAMD_GRID_CHECK(check_buffer("workspace", workspace_dev, workspace_bytes, tsamd::grid_sorted_workspace(n_points, n_features_per_level).bytes,
+                                  "tsamd_grid_backward_sorted_workspace_bytes"));
     TSAMD_HIP(tsamd::launch_grid_plan_build(x_dev, n_points, lv, n_features_per_level, plan_dev, workspace_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
 }
@@ -279,22 +273,16 @@ int tsamd_grid_encode_backward_planned(const float *x_dev, int64_t n_points, int
                                        void *workspace_dev, int64_t workspace_bytes, void *stream)
 {
     tsamd::GridLevels lv;
-    int64_t n_params = 0;
-    int rc = layout_or_fail(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv, n_params);
-    if (rc) return rc;
-    if (n_points < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points < 0");
-    if (n_points > (int64_t(1) << 40)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: n_points above 2^40");
-    if (n_points > 0 && !x_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is null");
-    if (reinterpret_cast<uintptr_t>(x_dev) % 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: x_dev is not float-aligned");
-    if (n_points > 0 && !grad_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev is null");
-    if (n_points > 0 && !grad_params_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_params_dev is null");
-    const uintptr_t align = n_features_per_level == 1 ? 4 : (n_features_per_level == 2 ? 8 : 16);
-    if (reinterpret_cast<uintptr_t>(grad_out_dev) % align || reinterpret_cast<uintptr_t>(grad_params_dev) % align)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid encoding: grad_out_dev / grad_params_dev not aligned to n_features_per_level floats (max 16 B)");
-    rc = check_plan_buffers(n_points, n_levels, plan_dev, plan_bytes, workspace_dev, workspace_bytes,
-                            tsamd::grid_planned_workspace(n_points, n_features_per_level, n_levels).bytes,
-                            "tsamd_grid_backward_planned_workspace_bytes");
-    if (rc) return rc;
+    TSAMD_GRID_CHECK(check_config(n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale, dense, lv));
+    TSAMD_GRID_CHECK(check_points(n_points, x_dev));
+    if (n_points > 0 && !grad_out_dev) return fail("grad_out_dev is null");
+    if (n_points > 0 && !grad_params_dev) return fail("grad_params_dev is null");
+    TSAMD_GRID_CHECK(check_feature_aligned(grad_out_dev, "grad_out_dev", n_features_per_level));
+    TSAMD_GRID_CHECK(check_feature_aligned(grad_params_dev, "grad_params_dev", n_features_per_level));
+    TSAMD_GRID_CHECK(check_buffer("plan", plan_dev, plan_bytes, tsamd::grid_plan_bytes(n_points, n_levels), "tsamd_grid_plan_bytes"));
+    TSAMD_GRID_CHECK(check_buffer("workspace", workspace_dev, workspace_bytes,
+                                  tsamd::grid_planned_workspace(n_points, n_features_per_level, n_levels).bytes,
+                                  "tsamd_grid_backward_planned_workspace_bytes"));
     TSAMD_HIP(tsamd::launch_grid_encode_backward_planned(x_dev, n_points, lv, n_features_per_level, grad_out_dev, grad_params_dev, plan_dev,
                                                          workspace_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;

@@ -7,7 +7,8 @@
 //                                    loop, then add the table into global memory with contiguous 256-B atomic wave-instructions
 //   grid_backward_params_kernel      dL/dparams of the other levels: one global_atomic_add_f32 per feature, after the lanes of
 //                                    a wave that hit the same entry with the same corner (neighbouring pixels in one cell)
-//                                    summed their adds on chip
+//                                    summed their adds on chip (backward_params_point: one body for both atomic kernels,
+//                                    which differ in where the add lands)
 //   grid_backward_x_kernel           dL/dx, one lane per point looping over the levels: plain stores, bitwise repeatable
 //   grid_sorted_*_kernel             the second route to dL/dparams (launch_grid_encode_backward_sorted), every level alike:
 //                                    (entry, source) records, a stable radix sort by entry, a segmented sum; no float atomics
@@ -16,10 +17,16 @@
 //                                    backward is then the sorted route's segmented sum (one device body for both) and fold over
 //                                    the stored order, every level of a chunk in one launch
 //
+// What the routes share is written once: segment_sums (the run scan of all three), sort_records (the radix-sort driver of the
+// sorted backward and the plan build, over sort_buffers' typed view of the workspace), grid_chunk (grid.h: a chunk's points,
+// records, tiles and waves) and with_features (n_features -> the template argument F of every launch_* entry point).
+//
 // The forward and dL/dx are bitwise deterministic (fixed summation order).  dL/dparams has three routes: the default one is a
 // float-atomic sum and may differ in the last bits from run to run (tiny-cuda-nn's does too); the sorted one adds every entry's
 // contributions in a fixed order and is bitwise repeatable, and the planned one gives the sorted one's bits (contracts: grid.h).
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "grid.h"
 
@@ -106,17 +113,23 @@ __device__ __forceinline__ void load_point(const float *x, int64_t i, float (&p)
     p[2] = x[3 * i + 2];
 }
 
-// Sums v over the run of consecutive lanes holding the same key; returns true on the run's first lane, which then holds the
-// run's sum.  Every lane of the wave must call it (inactive lanes pass kInvalid and zeros).  Hillis-Steele suffix scan
-// restricted to the run; skipped (one ballot) when no two neighbouring lanes share a key.
+// Sums v over the run of consecutive lanes holding the same key: the run's first lane then holds the run's sum.  Every lane of
+// the wave must call it (inactive lanes pass kInvalid and zeros).  Hillis-Steele suffix scan restricted to the run; skipped (one
+// ballot) when no two neighbouring lanes share a key.  The one run scan of all three routes to dL/dparams: the "same bits"
+// contract of grid.h rests on it.
+struct Runs {
+    unsigned long long heads;       // the runs' first lanes
+    bool head;                      // this lane is one of them
+};
+
 template <int F>
-__device__ __forceinline__ bool combine_runs(uint32_t key, float (&v)[F])
+__device__ __forceinline__ Runs segment_sums(uint32_t key, float (&v)[F])
 {
     const int lane = __lane_id();
     const uint32_t prev = __shfl_up(key, 1);
     const bool head = lane == 0 || prev != key;
     const unsigned long long heads = __ballot(head);
-    if (heads == ~0ull) return true;
+    if (heads == ~0ull) return {heads, true};
     const unsigned long long rest = lane == 63 ? 0ull : (heads >> (lane + 1));
     const int end = rest ? lane + __ffsll(static_cast<long long>(rest)) - 1 : 63;   // last lane of this lane's run
 #pragma unroll
@@ -127,7 +140,7 @@ __device__ __forceinline__ bool combine_runs(uint32_t key, float (&v)[F])
             if (lane + d <= end) v[f] += o;
         }
     }
-    return head;
+    return {heads, head};
 }
 
 template <int F>
@@ -157,13 +170,14 @@ __global__ __launch_bounds__(kBlock) void grid_encode_kernel(const float *__rest
     store_feat<F>(out + i * (int64_t(lv.n_levels) * F) + int64_t(l) * F, acc);
 }
 
-template <int F>
-__global__ __launch_bounds__(kBlock) void grid_backward_params_kernel(const float *__restrict__ x, int64_t n, GridLevels lv,
-                                                                      const float *__restrict__ grad_out, float *__restrict__ grad_params)
+// The atomic route's work for point i of level l: w * g of its 8 corners, summed on chip over the lanes of the wave that hit
+// the same entry with the same corner, then one add(table, key, sum) per run (table: the level's slice of grad_params; the LDS
+// kernel's add ignores it, its sums land in LDS first).  No early return here or in the callers: every lane of the wave takes
+// part in segment_sums, so a lane past the end comes here with valid = false.
+template <int F, class Add>
+__device__ __forceinline__ void backward_params_point(const float *__restrict__ x, const float *__restrict__ grad_out, float *__restrict__ grad_params,
+                                                      const GridLevels &lv, int l, int64_t i, bool valid, const Add &add)
 {
-    const int l = lv.lds_levels + blockIdx.y;
-    const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-    const bool valid = i < n;                       // no early return: the whole wave takes part in combine_runs
     float p[3] = {0.0f, 0.0f, 0.0f}, g[F];
 #pragma unroll
     for (int f = 0; f < F; ++f) g[f] = 0.0f;
@@ -182,12 +196,21 @@ __global__ __launch_bounds__(kBlock) void grid_backward_params_kernel(const floa
         float v[F];
 #pragma unroll
         for (int f = 0; f < F; ++f) v[f] = w * g[f];
-        if (combine_runs<F>(key, v) && valid) {
-            float *dst = table + int64_t(key) * F;
-#pragma unroll
-            for (int f = 0; f < F; ++f) atomicAdd(dst + f, v[f]);
-        }
+        if (segment_sums<F>(key, v).head && valid) add(table, key, v);
     }
+}
+
+template <int F>
+__global__ __launch_bounds__(kBlock) void grid_backward_params_kernel(const float *__restrict__ x, int64_t n, GridLevels lv,
+                                                                      const float *__restrict__ grad_out, float *__restrict__ grad_params)
+{
+    const int l = lv.lds_levels + blockIdx.y;
+    const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    backward_params_point<F>(x, grad_out, grad_params, lv, l, i, i < n, [](float *table, uint32_t key, const float (&v)[F]) {
+        float *dst = table + int64_t(key) * F;
+#pragma unroll
+        for (int f = 0; f < F; ++f) atomicAdd(dst + f, v[f]);
+    });
 }
 
 template <int F>
@@ -199,36 +222,14 @@ __global__ __launch_bounds__(kLdsBlock) void grid_backward_params_lds_kernel(con
     const uint32_t n_floats = lv.entries[l] * F;
     for (uint32_t j = threadIdx.x; j < n_floats; j += kLdsBlock) acc[j] = 0.0f;
     __syncthreads();
-    const float scale = lv.scale[l];
-    const uint32_t res = lv.res[l], entries = lv.entries[l];
-    const bool hashed = lv.hashed[l] != 0;
-    const int64_t row = int64_t(lv.n_levels) * F;
     const int64_t stride = int64_t(gridDim.x) * kLdsBlock;
-    // the loop bound is the same for the whole wave (n rounded up to the stride's multiple of 64): combine_runs needs every lane
+    // the loop bound is the same for the whole wave (n rounded up to the stride's multiple of 64)
     const int64_t n_wave = (n + 63) & ~int64_t(63);
-    for (int64_t i = int64_t(blockIdx.x) * kLdsBlock + threadIdx.x; i < n_wave; i += stride) {
-        const bool valid = i < n;
-        float p[3] = {0.0f, 0.0f, 0.0f}, g[F];
+    for (int64_t i = int64_t(blockIdx.x) * kLdsBlock + threadIdx.x; i < n_wave; i += stride)
+        backward_params_point<F>(x, grad_out, grad_params, lv, l, i, i < n, [](float *, uint32_t key, const float (&v)[F]) {
 #pragma unroll
-        for (int f = 0; f < F; ++f) g[f] = 0.0f;
-        if (valid) {
-            load_point(x, i, p);
-            load_feat<F>(grad_out + i * row + int64_t(l) * F, g);
-        }
-        const Cell cl = cell_of(p, scale);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t key = valid ? corner_index(cl, c, res, entries, hashed) : kInvalid;
-            const float w = corner_weight(cl, c);
-            float v[F];
-#pragma unroll
-            for (int f = 0; f < F; ++f) v[f] = w * g[f];
-            if (combine_runs<F>(key, v) && valid) {
-#pragma unroll
-                for (int f = 0; f < F; ++f) atomicAdd(&acc[key * F + f], v[f]);
-            }
-        }
-    }
+            for (int f = 0; f < F; ++f) atomicAdd(&acc[key * F + f], v[f]);
+        });
     __syncthreads();
     float *dst = grad_params + lv.offset[l] * F;
     for (uint32_t j = threadIdx.x; j < n_floats; j += kLdsBlock) {
@@ -488,27 +489,6 @@ __global__ __launch_bounds__(kSortBlock) void grid_sorted_scatter_kernel(const R
     }
 }
 
-// As combine_runs, but returns the mask of run heads (every lane of the wave must call it).
-template <int F>
-__device__ __forceinline__ unsigned long long segment_sums(uint32_t key, float (&v)[F])
-{
-    const int lane = __lane_id();
-    const uint32_t prev = __shfl_up(key, 1);
-    const unsigned long long heads = __ballot(lane == 0 || prev != key);
-    if (heads == ~0ull) return heads;
-    const unsigned long long rest = lane == 63 ? 0ull : (heads >> (lane + 1));
-    const int end = rest ? lane + __ffsll(static_cast<long long>(rest)) - 1 : 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const float o = __shfl_down(v[f], d);
-            if (lane + d <= end) v[f] += o;
-        }
-    }
-    return heads;
-}
-
 // Plain load - add - store by the one lane that owns the entry in this launch.
 template <int F>
 __device__ __forceinline__ void add_entry(float *table, uint32_t key, const float (&v)[F])
@@ -594,7 +574,7 @@ __device__ __forceinline__ void segmented_sum(const Source &source, uint32_t n_r
 #pragma unroll
             for (int f = 0; f < F; ++f) v[f] = w * g[f];
         }
-        const unsigned long long heads = segment_sums<F>(key, v);
+        const unsigned long long heads = segment_sums<F>(key, v).heads;
         const bool head = (heads >> lane) & 1;
         const int last_head = 63 - __clzll(static_cast<long long>(heads));
         const uint32_t key0 = __shfl(key, 0);
@@ -733,48 +713,69 @@ inline int key_bits(uint32_t entries)
         if (e_ != hipSuccess) return e_;                 \
     } while (0)
 
+// The sorted route's workspace (grid.h: GridSortedWorkspace) as typed pointers.
+struct SortBuffers {
+    Rec *rec_a, *rec_b;
+    float *gl, *psum;
+    uint32_t *hist, *tot, *pkey;
+};
+
+inline SortBuffers sort_buffers(void *workspace, const GridSortedWorkspace &ws)
+{
+    char *base = static_cast<char *>(workspace);
+    return {reinterpret_cast<Rec *>(base + ws.rec_a), reinterpret_cast<Rec *>(base + ws.rec_b), reinterpret_cast<float *>(base + ws.gl),
+            reinterpret_cast<float *>(base + ws.psum), reinterpret_cast<uint32_t *>(base + ws.hist), reinterpret_cast<uint32_t *>(base + ws.tot),
+            reinterpret_cast<uint32_t *>(base + ws.pkey)};
+}
+
+// Sorts a level's records by entry, after the key kernel left them in rec_a and the first digit's histogram in hist: one
+// stable pass per 8-bit digit of the bits the entry count needs, ping-pong between rec_a and rec_b.  *sorted: the buffer that
+// holds the result.
+hipError_t sort_records(const GridChunk &ch, uint32_t entries, const SortBuffers &b, hipStream_t stream, Rec **sorted)
+{
+    Rec *src = b.rec_a, *dst = b.rec_b;
+    const int passes = (key_bits(entries) + 7) / 8;
+    for (int p = 0; p < passes; ++p) {
+        if (p > 0) {
+            hipLaunchKernelGGL(grid_sorted_hist_kernel, dim3(ch.tiles), dim3(kSortBlock), 0, stream, src, ch.records, 8 * p, b.hist, ch.tiles);
+            TSAMD_GRID_LAUNCHED();
+        }
+        hipLaunchKernelGGL(grid_sorted_scan_kernel, dim3(256), dim3(kSortBlock), 0, stream, b.hist, ch.tiles, b.tot);
+        TSAMD_GRID_LAUNCHED();
+        hipLaunchKernelGGL(grid_sorted_scatter_kernel, dim3(ch.tiles), dim3(kSortBlock), 0, stream, src, ch.records, 8 * p, b.hist, b.tot, ch.tiles,
+                           dst);
+        TSAMD_GRID_LAUNCHED();
+        Rec *t = src;
+        src = dst;
+        dst = t;
+    }
+    *sorted = src;
+    return hipSuccess;
+}
+
 template <int F>
 hipError_t backward_sorted_f(const float *x, int64_t n, const float *params, const GridLevels &lv, const float *grad_out, float *grad_params,
                              float *grad_x, void *workspace, hipStream_t stream)
 {
     if (grad_params) {
-        const GridSortedWorkspace ws = grid_sorted_workspace(n, F);
-        char *base = static_cast<char *>(workspace);
-        Rec *rec_a = reinterpret_cast<Rec *>(base + ws.rec_a), *rec_b = reinterpret_cast<Rec *>(base + ws.rec_b);
-        float *gl = reinterpret_cast<float *>(base + ws.gl), *psum = reinterpret_cast<float *>(base + ws.psum);
-        uint32_t *hist = reinterpret_cast<uint32_t *>(base + ws.hist), *tot = reinterpret_cast<uint32_t *>(base + ws.tot);
-        uint32_t *pkey = reinterpret_cast<uint32_t *>(base + ws.pkey);
+        const SortBuffers b = sort_buffers(workspace, grid_sorted_workspace(n, F));
         const int64_t row = int64_t(lv.n_levels) * F;
         for (int64_t first = 0; first < n; first += kGridSortedChunk) {           // chunks in order: part of the summation order
-            const uint32_t nc = uint32_t(n - first < kGridSortedChunk ? n - first : kGridSortedChunk);
-            const uint32_t n_rec = nc * 8;
-            const uint32_t n_tiles = (n_rec + kGridSortTile - 1) / kGridSortTile, n_waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
+            const GridChunk ch = grid_chunk(n - first);
             const float *xc = x + first * 3, *gc = grad_out + first * row;
             for (int l = 0; l < lv.n_levels; ++l) {
-                hipLaunchKernelGGL(grid_sorted_key_kernel<F>, dim3(n_tiles), dim3(kSortBlock), 0, stream, xc, nc, lv, l, gc, rec_a, gl, hist, n_tiles);
+                hipLaunchKernelGGL(grid_sorted_key_kernel<F>, dim3(ch.tiles), dim3(kSortBlock), 0, stream, xc, ch.points, lv, l, gc, b.rec_a, b.gl,
+                                   b.hist, ch.tiles);
                 TSAMD_GRID_LAUNCHED();
-                Rec *src = rec_a, *dst = rec_b;
-                const int passes = (key_bits(lv.entries[l]) + 7) / 8;
-                for (int p = 0; p < passes; ++p) {
-                    if (p > 0) {
-                        hipLaunchKernelGGL(grid_sorted_hist_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, n_tiles);
-                        TSAMD_GRID_LAUNCHED();
-                    }
-                    hipLaunchKernelGGL(grid_sorted_scan_kernel, dim3(256), dim3(kSortBlock), 0, stream, hist, n_tiles, tot);
-                    TSAMD_GRID_LAUNCHED();
-                    hipLaunchKernelGGL(grid_sorted_scatter_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, tot, n_tiles,
-                                       dst);
-                    TSAMD_GRID_LAUNCHED();
-                    Rec *t = src;
-                    src = dst;
-                    dst = t;
-                }
+                Rec *sorted = nullptr;
+                const hipError_t e = sort_records(ch, lv.entries[l], b, stream, &sorted);
+                if (e != hipSuccess) return e;
                 float *table = grad_params + lv.offset[l] * F;
-                hipLaunchKernelGGL(grid_sorted_sum_kernel<F>, dim3((n_waves + kSortWaves - 1) / kSortWaves), dim3(kSortBlock), 0, stream, src, n_rec,
-                                   xc, gl, lv.scale[l], lv.entries[l], table, pkey, psum);
+                hipLaunchKernelGGL(grid_sorted_sum_kernel<F>, dim3((ch.waves + kSortWaves - 1) / kSortWaves), dim3(kSortBlock), 0, stream, sorted,
+                                   ch.records, xc, b.gl, lv.scale[l], lv.entries[l], table, b.pkey, b.psum);
                 TSAMD_GRID_LAUNCHED();
-                hipLaunchKernelGGL(grid_sorted_fold_kernel<F>, dim3((2 * n_waves + kSortBlock - 1) / kSortBlock), dim3(kSortBlock), 0, stream, pkey,
-                                   psum, 2 * n_waves, table);
+                hipLaunchKernelGGL(grid_sorted_fold_kernel<F>, dim3((2 * ch.waves + kSortBlock - 1) / kSortBlock), dim3(kSortBlock), 0, stream, b.pkey,
+                                   b.psum, 2 * ch.waves, table);
                 TSAMD_GRID_LAUNCHED();
             }
         }
@@ -790,38 +791,20 @@ hipError_t backward_sorted_f(const float *x, int64_t n, const float *params, con
 // [chunk][level][8 * points_in_chunk].  The workspace is the sorted route's.
 hipError_t plan_build(const float *x, int64_t n, const GridLevels &lv, int32_t n_features, uint32_t *plan, void *workspace, hipStream_t stream)
 {
-    const GridSortedWorkspace ws = grid_sorted_workspace(n, n_features);
-    char *base = static_cast<char *>(workspace);
-    Rec *rec_a = reinterpret_cast<Rec *>(base + ws.rec_a), *rec_b = reinterpret_cast<Rec *>(base + ws.rec_b);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(base + ws.hist), *tot = reinterpret_cast<uint32_t *>(base + ws.tot);
+    const SortBuffers b = sort_buffers(workspace, grid_sorted_workspace(n, n_features));
     for (int64_t first = 0; first < n; first += kGridSortedChunk) {
-        const uint32_t nc = uint32_t(n - first < kGridSortedChunk ? n - first : kGridSortedChunk);
-        const uint32_t n_rec = nc * 8;
-        const uint32_t n_tiles = (n_rec + kGridSortTile - 1) / kGridSortTile;
+        const GridChunk ch = grid_chunk(n - first);
         const float *xc = x + first * 3;
         uint32_t *pc = plan + first * 8 * lv.n_levels;
         for (int l = 0; l < lv.n_levels; ++l) {
-            hipLaunchKernelGGL((grid_sorted_key_kernel<1, false>), dim3(n_tiles), dim3(kSortBlock), 0, stream, xc, nc, lv, l,
-                               static_cast<const float *>(nullptr), rec_a, static_cast<float *>(nullptr), hist, n_tiles);
+            hipLaunchKernelGGL((grid_sorted_key_kernel<1, false>), dim3(ch.tiles), dim3(kSortBlock), 0, stream, xc, ch.points, lv, l,
+                               static_cast<const float *>(nullptr), b.rec_a, static_cast<float *>(nullptr), b.hist, ch.tiles);
             TSAMD_GRID_LAUNCHED();
-            Rec *src = rec_a, *dst = rec_b;
-            const int passes = (key_bits(lv.entries[l]) + 7) / 8;
-            for (int p = 0; p < passes; ++p) {
-                if (p > 0) {
-                    hipLaunchKernelGGL(grid_sorted_hist_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, n_tiles);
-                    TSAMD_GRID_LAUNCHED();
-                }
-                hipLaunchKernelGGL(grid_sorted_scan_kernel, dim3(256), dim3(kSortBlock), 0, stream, hist, n_tiles, tot);
-                TSAMD_GRID_LAUNCHED();
-                hipLaunchKernelGGL(grid_sorted_scatter_kernel, dim3(n_tiles), dim3(kSortBlock), 0, stream, src, n_rec, 8 * p, hist, tot, n_tiles,
-                                   dst);
-                TSAMD_GRID_LAUNCHED();
-                Rec *t = src;
-                src = dst;
-                dst = t;
-            }
-            hipLaunchKernelGGL(grid_plan_pack_kernel, dim3((n_rec + kSortBlock - 1) / kSortBlock), dim3(kSortBlock), 0, stream, src, n_rec,
-                               pc + int64_t(l) * n_rec);
+            Rec *sorted = nullptr;
+            const hipError_t e = sort_records(ch, lv.entries[l], b, stream, &sorted);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(grid_plan_pack_kernel, dim3((ch.records + kSortBlock - 1) / kSortBlock), dim3(kSortBlock), 0, stream, sorted,
+                               ch.records, pc + l * ch.records);
             TSAMD_GRID_LAUNCHED();
         }
     }
@@ -838,22 +821,34 @@ hipError_t backward_planned_f(const float *x, int64_t n, const GridLevels &lv, c
     float *psum = reinterpret_cast<float *>(base + ws.psum);
     const int64_t row = int64_t(lv.n_levels) * F;
     for (int64_t first = 0; first < n; first += kGridSortedChunk) {               // chunks in order: part of the summation order
-        const uint32_t nc = uint32_t(n - first < kGridSortedChunk ? n - first : kGridSortedChunk);
-        const uint32_t n_rec = nc * 8, n_waves = (n_rec + kGridSumRun - 1) / kGridSumRun;
+        const GridChunk ch = grid_chunk(n - first);
         const float *xc = x + first * 3, *gc = grad_out + first * row;
         const uint32_t *pc = plan + first * 8 * lv.n_levels;
         // g is read straight from the rows of grad_out (level l at + l * F, the next point's a row on)
-        hipLaunchKernelGGL(grid_planned_sum_kernel<F>, dim3((n_waves + kSortWaves - 1) / kSortWaves, lv.n_levels), dim3(kSortBlock), 0, stream,
-                           pc, n_rec, xc, gc, int64_t(F), row, lv, grad_params, pkey, psum, n_waves);
+        hipLaunchKernelGGL(grid_planned_sum_kernel<F>, dim3((ch.waves + kSortWaves - 1) / kSortWaves, lv.n_levels), dim3(kSortBlock), 0, stream, pc,
+                           ch.records, xc, gc, int64_t(F), row, lv, grad_params, pkey, psum, ch.waves);
         TSAMD_GRID_LAUNCHED();
-        hipLaunchKernelGGL(grid_planned_fold_kernel<F>, dim3((2 * n_waves + kSortBlock - 1) / kSortBlock, lv.n_levels), dim3(kSortBlock), 0, stream,
-                           pkey, psum, 2 * n_waves, lv, grad_params);
+        hipLaunchKernelGGL(grid_planned_fold_kernel<F>, dim3((2 * ch.waves + kSortBlock - 1) / kSortBlock, lv.n_levels), dim3(kSortBlock), 0, stream,
+                           pkey, psum, 2 * ch.waves, lv, grad_params);
         TSAMD_GRID_LAUNCHED();
     }
     return hipSuccess;
 }
 
 #undef TSAMD_GRID_LAUNCHED
+
+// Calls fn with n_features as a compile-time constant (fn(std::integral_constant<int, F>{})), for the F the kernels are built for.
+template <class Fn>
+hipError_t with_features(int32_t n_features, Fn fn)
+{
+    switch (n_features) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 8: return fn(std::integral_constant<int, 8>{});
+    default: return hipErrorInvalidValue;
+    }
+}
 
 }  // namespace
 
@@ -868,53 +863,31 @@ hipError_t launch_grid_encode_backward_planned(const float *x, int64_t n, const 
                                                float *grad_params, const void *plan, void *workspace, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    const uint32_t *p = static_cast<const uint32_t *>(plan);
-    switch (n_features) {
-    case 1: return backward_planned_f<1>(x, n, lv, grad_out, grad_params, p, workspace, stream);
-    case 2: return backward_planned_f<2>(x, n, lv, grad_out, grad_params, p, workspace, stream);
-    case 4: return backward_planned_f<4>(x, n, lv, grad_out, grad_params, p, workspace, stream);
-    case 8: return backward_planned_f<8>(x, n, lv, grad_out, grad_params, p, workspace, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return with_features(n_features, [&](auto f) {
+        return backward_planned_f<f()>(x, n, lv, grad_out, grad_params, static_cast<const uint32_t *>(plan), workspace, stream);
+    });
 }
 
 hipError_t launch_grid_encode_backward_sorted(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features,
                                               const float *grad_out, float *grad_params, float *grad_x, void *workspace, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    switch (n_features) {
-    case 1: return backward_sorted_f<1>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
-    case 2: return backward_sorted_f<2>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
-    case 4: return backward_sorted_f<4>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
-    case 8: return backward_sorted_f<8>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return with_features(n_features,
+                         [&](auto f) { return backward_sorted_f<f()>(x, n, params, lv, grad_out, grad_params, grad_x, workspace, stream); });
 }
 
 hipError_t launch_grid_encode(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features, float *out,
                               hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    switch (n_features) {
-    case 1: return encode_f<1>(x, n, params, lv, out, stream);
-    case 2: return encode_f<2>(x, n, params, lv, out, stream);
-    case 4: return encode_f<4>(x, n, params, lv, out, stream);
-    case 8: return encode_f<8>(x, n, params, lv, out, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return with_features(n_features, [&](auto f) { return encode_f<f()>(x, n, params, lv, out, stream); });
 }
 
 hipError_t launch_grid_encode_backward(const float *x, int64_t n, const float *params, const GridLevels &lv, int32_t n_features,
                                        const float *grad_out, float *grad_params, float *grad_x, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    switch (n_features) {
-    case 1: return backward_f<1>(x, n, params, lv, grad_out, grad_params, grad_x, stream);
-    case 2: return backward_f<2>(x, n, params, lv, grad_out, grad_params, grad_x, stream);
-    case 4: return backward_f<4>(x, n, params, lv, grad_out, grad_params, grad_x, stream);
-    case 8: return backward_f<8>(x, n, params, lv, grad_out, grad_params, grad_x, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return with_features(n_features, [&](auto f) { return backward_f<f()>(x, n, params, lv, grad_out, grad_params, grad_x, stream); });
 }
 
 }  // namespace tsamd

@@ -80,25 +80,31 @@ def grid_layout(cfg: dict) -> dict:
     return {"offset": off, "res": res, "is_hash": hashed.astype(bool), "scale": scale, "n_params": int(n.value)}
 
 
+def grid_layout_n_params(cfg: dict) -> int:
+    n = C.c_int64(0)
+    _capi.check(_lib.tsamd_grid_layout(*_args(cfg), None, None, None, None, C.byref(n)))
+    return int(n.value)
+
+
+def _bytes_query(query, cfg: dict, n_points: int) -> int:
+    n = C.c_int64(0)
+    _capi.check(query(int(n_points), *_args(cfg), C.byref(n)))
+    return int(n.value)
+
+
 def sorted_workspace_bytes(cfg: dict, n_points: int) -> int:
     """Bytes of workspace the sorted backward needs for ``n_points`` (tsamd_grid_backward_sorted_workspace_bytes; host only)."""
-    n = C.c_int64(0)
-    _capi.check(_lib.tsamd_grid_backward_sorted_workspace_bytes(int(n_points), *_args(cfg), C.byref(n)))
-    return int(n.value)
+    return _bytes_query(_lib.tsamd_grid_backward_sorted_workspace_bytes, cfg, n_points)
 
 
 def plan_bytes(cfg: dict, n_points: int) -> int:
     """Bytes of a point plan for ``n_points`` (tsamd_grid_plan_bytes; host only)."""
-    n = C.c_int64(0)
-    _capi.check(_lib.tsamd_grid_plan_bytes(int(n_points), *_args(cfg), C.byref(n)))
-    return int(n.value)
+    return _bytes_query(_lib.tsamd_grid_plan_bytes, cfg, n_points)
 
 
 def planned_workspace_bytes(cfg: dict, n_points: int) -> int:
     """Bytes of workspace the planned backward needs (tsamd_grid_backward_planned_workspace_bytes; host only)."""
-    n = C.c_int64(0)
-    _capi.check(_lib.tsamd_grid_backward_planned_workspace_bytes(int(n_points), *_args(cfg), C.byref(n)))
-    return int(n.value)
+    return _bytes_query(_lib.tsamd_grid_backward_planned_workspace_bytes, cfg, n_points)
 
 
 PLAN_KEYS = ("n_levels", "n_features_per_level", "log2_hashmap_size", "base_resolution", "per_level_scale", "dense")
@@ -146,16 +152,20 @@ def _check_input(x: torch.Tensor, n_input_dims: int) -> torch.Tensor:
     return x.contiguous()
 
 
+def _encode(x: torch.Tensor, params: torch.Tensor, cfg: dict, n_output_dims: int) -> torch.Tensor:
+    N = int(x.shape[0])
+    out = torch.empty((N, n_output_dims), dtype=torch.float32, device=x.device)
+    with _device_ctx(x.device):
+        _capi.check(_lib.tsamd_grid_encode(x.data_ptr(), N, params.data_ptr(), *_args(cfg), out.data_ptr(), _stream_ptr(x.device)))
+    return out
+
+
 class _GridEncodeFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, params, cfg, n_output_dims):
-        N = int(x.shape[0])
-        out = torch.empty((N, n_output_dims), dtype=torch.float32, device=x.device)
-        with _device_ctx(x.device):
-            _capi.check(_lib.tsamd_grid_encode(x.data_ptr(), N, params.data_ptr(), *_args(cfg), out.data_ptr(), _stream_ptr(x.device)))
         ctx.cfg = cfg
         ctx.save_for_backward(x, params)
-        return out
+        return _encode(x, params, cfg, n_output_dims)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -185,12 +195,8 @@ class _GridEncodePlannedFunc(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, params, plan, cfg, n_output_dims):
-        x, N = plan.x, plan.n_points
-        out = torch.empty((N, n_output_dims), dtype=torch.float32, device=x.device)
-        with _device_ctx(x.device):
-            _capi.check(_lib.tsamd_grid_encode(x.data_ptr(), N, params.data_ptr(), *_args(cfg), out.data_ptr(), _stream_ptr(x.device)))
         ctx.cfg, ctx.plan = cfg, plan
-        return out
+        return _encode(plan.x, params, cfg, n_output_dims)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -206,12 +212,6 @@ class _GridEncodePlannedFunc(torch.autograd.Function):
                                                                 plan.buffer.data_ptr(), plan.buffer.numel(), ws.data_ptr(), ws.numel(),
                                                                 _stream_ptr(dev)))
         return grad_p, None, None, None
-
-
-def grid_layout_n_params(cfg: dict) -> int:
-    n = C.c_int64(0)
-    _capi.check(_lib.tsamd_grid_layout(*_args(cfg), None, None, None, None, C.byref(n)))
-    return int(n.value)
 
 
 def encode_planned(plan: GridPointPlan, params: torch.Tensor, cfg: dict, n_output_dims: int) -> torch.Tensor:
