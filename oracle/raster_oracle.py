@@ -329,6 +329,10 @@ def rasterize_backward(pos_clip: np.ndarray, tri: np.ndarray, rast: np.ndarray, 
 # same undirected vertex pair; an edge whose partner's far vertex has w <= 0 counts as a silhouette; every qualifying
 # edge of the triangle contributes (normally one).  All decisions are single float64 operations in a fixed order, which
 # the GPU kernel repeats -- the SET of blends is identical, their float32 sums are compared with a tolerance.
+#
+# Foreign ids (a `rast` image made with another triangle list, or a corrupt index buffer): a pair whose winning triangle id
+# lies outside [0, T) is skipped, so is a pair whose triangle has a vertex index outside [0, V), and a partner entry of `opp`
+# outside [0, V) counts as "no partner" (like -1: the edge is a silhouette).  Nothing is read through such an index.
 # ---------------------------------------------------------------------------------------------------------------------
 def edge_partners(tri: np.ndarray) -> np.ndarray:
     """``opp[3 t + e]`` = the vertex opposite edge ``e`` (the edge not touching local vertex ``e``) in the partner triangle
@@ -361,8 +365,12 @@ def _window(p4, height, width):
 
 def _antialias_events(rast_b, pos_b, tri, opp, pixel_gradient=False):
     """The blends of one view: tuples ``(dst (j, i), src (j, i), weight, sign, axis, (va, vb), (dA, dB))`` where ``dA / dB``
-    are the derivatives of ``t`` w.r.t. the window coordinates of the edge's two vertices."""
+    are the derivatives of ``t`` w.r.t. the window coordinates of the edge's two vertices.
+
+    Ids that do not belong to this mesh blend nothing: a pair whose winning triangle id is outside ``[0, T)`` or whose triangle
+    has a vertex index outside ``[0, V)`` is skipped, and an ``opp`` entry outside ``[0, V)`` is treated like -1 (no partner)."""
     height, width = rast_b.shape[:2]
+    n_tri, n_vertices = len(tri), len(pos_b)
     ids = rast_b[..., 3].astype(np.int64) - 1
     zw = rast_b[..., 2]
     events = []
@@ -377,9 +385,13 @@ def _antialias_events(rast_b, pos_b, tri, opp, pixel_gradient=False):
             else:
                 first = a0 >= 0
             t = a0 if first else a1
+            if not 0 <= t < n_tri:
+                continue
             P = (j, i) if first else (j + dj, i + di)
             Q = (j + dj, i + di) if first else (j, i)
             vid = [int(k) for k in tri[t]]
+            if not all(0 <= k < n_vertices for k in vid):
+                continue
             win = [_window(pos_b[k], height, width) for k in vid]
             if any(q is None for q in win):
                 continue
@@ -390,7 +402,7 @@ def _antialias_events(rast_b, pos_b, tri, opp, pixel_gradient=False):
                 (Ax, Ay), (Bx, By), (Ox, Oy) = win[ka], win[kb], win[e]
                 ex, ey = Bx - Ax, By - Ay
                 o2 = int(opp[3 * t + e])
-                if o2 >= 0:
+                if 0 <= o2 < n_vertices:
                     w2 = _window(pos_b[o2], height, width)
                     if w2 is not None:
                         s1 = ex * (Oy - Ay) - ey * (Ox - Ax)
@@ -428,7 +440,19 @@ def _antialias_events(rast_b, pos_b, tri, opp, pixel_gradient=False):
     return events
 
 
-def antialias(color: np.ndarray, rast: np.ndarray, pos_clip: np.ndarray, tri: np.ndarray, opp: np.ndarray | None = None) -> np.ndarray:
+def antialias_events(rast: np.ndarray, pos_clip: np.ndarray, tri: np.ndarray, opp: np.ndarray | None = None) -> list:
+    """``_antialias_events`` of every view, from the inputs as ``antialias`` / ``antialias_backward`` prepare them: a caller
+    that wants the image, the gradients and the events themselves hands the list back as ``events=`` and pays for one analysis."""
+    rast = np.asarray(rast, dtype=np.float32).astype(np.float64)
+    p = np.asarray(pos_clip, dtype=np.float32).astype(np.float64)
+    if p.ndim == 2:
+        p = p[None]
+    tri = np.asarray(tri, dtype=np.int64).reshape(-1, 3)
+    opp = edge_partners(tri) if opp is None else opp
+    return [_antialias_events(rast[b], p[b], tri, opp) for b in range(rast.shape[0])]
+
+
+def antialias(color: np.ndarray, rast: np.ndarray, pos_clip: np.ndarray, tri: np.ndarray, opp: np.ndarray | None = None, events: list | None = None) -> np.ndarray:
     """``dr.antialias(color, rast, pos, tri)`` (mesh_rasterizer.py:107,128): ``[B, H, W, C]`` float64."""
     color = np.asarray(color, dtype=np.float32).astype(np.float64)
     rast = np.asarray(rast, dtype=np.float32).astype(np.float64)
@@ -436,15 +460,15 @@ def antialias(color: np.ndarray, rast: np.ndarray, pos_clip: np.ndarray, tri: np
     if p.ndim == 2:
         p = p[None]
     tri = np.asarray(tri, dtype=np.int64).reshape(-1, 3)
-    opp = edge_partners(tri) if opp is None else opp
+    events = antialias_events(rast, p, tri, opp) if events is None else events
     out = color.copy()
     for b in range(rast.shape[0]):
-        for dst, src, wgt, _, _, _, _ in _antialias_events(rast[b], p[b], tri, opp):
+        for dst, src, wgt, _, _, _, _ in events[b]:
             out[b][dst] += wgt * (color[b][src] - color[b][dst])
     return out
 
 
-def antialias_backward(color, rast, pos_clip, tri, grad_out, opp=None, pos_gradient_boost: float = 1.0):
+def antialias_backward(color, rast, pos_clip, tri, grad_out, opp=None, pos_gradient_boost: float = 1.0, events: list | None = None):
     """Gradients of ``antialias`` w.r.t. ``color`` and ``pos_clip`` (float64)."""
     color = np.asarray(color, dtype=np.float32).astype(np.float64)
     rast = np.asarray(rast, dtype=np.float32).astype(np.float64)
@@ -453,12 +477,12 @@ def antialias_backward(color, rast, pos_clip, tri, grad_out, opp=None, pos_gradi
         p = p[None]
     g = np.asarray(grad_out, dtype=np.float64)
     tri = np.asarray(tri, dtype=np.int64).reshape(-1, 3)
-    opp = edge_partners(tri) if opp is None else opp
+    events = antialias_events(rast, p, tri, opp) if events is None else events
     height, width = rast.shape[1:3]
     grad_color = g.copy()
     grad_pos = np.zeros_like(p)
     for b in range(rast.shape[0]):
-        for dst, src, wgt, sign, _, (va, vb), (dA, dB) in _antialias_events(rast[b], p[b], tri, opp):
+        for dst, src, wgt, sign, _, (va, vb), (dA, dB) in events[b]:
             gd = g[b][dst]
             grad_color[b][src] += wgt * gd
             grad_color[b][dst] -= wgt * gd

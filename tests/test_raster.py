@@ -419,6 +419,35 @@ def test_interpolate_forward_backward(attr_batch_is_one):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("channels", [1, 2, 4, 5])
+def test_interpolate_channel_counts(channels):
+    """Channel counts other than 3 (the texture stage interpolates 2-channel uv), on views that end inside a wave (33 x 50):
+    the assertions of test_interpolate_forward_backward."""
+    import torch
+    import tssplat_amd.dr as dr
+    views, res = 2, (33, 50)
+    pos_clip, tri, v = _surface_scene("kuhn8", 5, views)
+    tri_d = torch.from_numpy(tri).cuda()
+    rast, _ = dr.rasterize(dr.RasterizeCudaContext(), torch.from_numpy(pos_clip).cuda(), tri_d, resolution=list(res), grad_db=False)
+    rng = np.random.default_rng(channels)
+    attr_np = rng.standard_normal((views, v.shape[0], channels)).astype(np.float32)
+    attr = torch.from_numpy(attr_np).cuda().requires_grad_(True)
+    rast_in = rast.clone().requires_grad_(True)
+    out, da = dr.interpolate(attr, rast_in, tri_d)
+    assert out.shape == (views, res[0], res[1], channels) and da.shape[-1] == 0
+    rast_np = rast.cpu().numpy()
+    assert (rast_np[..., 3] > 0).mean() > 0.02
+    ref = R.interpolate(attr_np, rast_np, tri)
+    assert np.abs(out.detach().cpu().numpy() - ref).max() <= 2e-6 * max(1.0, np.abs(ref).max())
+    g = rng.standard_normal(ref.shape).astype(np.float32)
+    out.backward(torch.from_numpy(g).cuda())
+    ga, gr = R.interpolate_backward(attr_np, rast_np, tri, g)
+    assert np.abs(attr.grad.cpu().numpy() - ga).max() <= 2e-5 * np.abs(ga).max()            # fp32 atomics, arbitrary order
+    assert np.abs(rast_in.grad.cpu().numpy() - gr).max() <= 2e-5 * max(np.abs(gr).max(), 1e-30)
+    assert (rast_in.grad[..., 2:] == 0).all()
+
+
+@pytest.mark.gpu
 def test_topology_table_matches_the_oracle():
     import torch
     import tssplat_amd.dr as dr
