@@ -401,6 +401,32 @@ int tsamd_antialias_backward(const float *color_dev, const float *rast_dev, cons
                              int32_t n_channels, const float *grad_out_dev, float pos_gradient_boost, float *grad_color_dev, float *grad_pos_dev,
                              void *stream);
 
+/* The alpha stage (the reference's trainer.py fits the geometry with only_alpha=True: loss = MSE(antialias(clamp(rast[..., -1:], 0, 1)))),
+ * without a rast image.  With colours in {0, 1} a pair of two covered pixels blends w (1 - 1) = 0, so only pairs with exactly one
+ * background pixel are analysed, and the covered pixel's triangle always wins them: results equal tsamd_antialias of the clamp image
+ * up to the rounding of its float32 sums.
+ * tsamd_silhouette: ids_out_dev [batch, height, width] i32 = triangle + 1, 0 on background (what tsamd_rasterize puts into rast's
+ * fourth channel); alpha_out_dev [batch, height, width, 1] f32 = coverage 0 / 1 with the silhouette pixels blended (all zero without
+ * triangles); cover_masks_out_dev (tsamd_pair_masks_bytes, the layout of the pair masks): bit l = exactly one pixel of the pair is
+ * background.  workspace_dev: tsamd_rasterize_workspace_bytes.  ids and cover masks are the inputs of the two backward calls.
+ * tsamd_silhouette_backward: grad_pos_dev [batch, n_vertices, 4] (zero-filled first) from grad_alpha_dev [batch, height, width, 1].
+ * tsamd_silhouette_mse: loss_out_dev[0] = mean((alpha - target)^2) over n floats (0 for n = 0), bitwise repeatable for the same
+ * inputs; workspace_dev: tsamd_silhouette_mse_workspace_bytes(n).  tsamd_silhouette_mse_backward: the gradient of that loss of the
+ * alpha image w.r.t. pos_clip without a gradient image -- alpha_dev as tsamd_silhouette wrote it, grad_loss_dev one f32 in device
+ * memory (d objective / d loss).  Limits and messages are tsamd_rasterize's; nothing synchronises with the host. */
+int tsamd_silhouette(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                     const int32_t *edge_partner_dev, int32_t height, int32_t width, void *workspace_dev, int32_t *ids_out_dev,
+                     void *cover_masks_out_dev, float *alpha_out_dev, void *stream);
+int tsamd_silhouette_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                              const int32_t *edge_partner_dev, int32_t height, int32_t width, const int32_t *ids_dev, const void *cover_masks_dev,
+                              const float *grad_alpha_dev, float pos_gradient_boost, float *grad_pos_dev, void *stream);
+int64_t tsamd_silhouette_mse_workspace_bytes(int64_t n);
+int tsamd_silhouette_mse(const float *alpha_dev, const float *target_dev, int64_t n, void *workspace_dev, float *loss_out_dev, void *stream);
+int tsamd_silhouette_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                                  const int32_t *edge_partner_dev, int32_t height, int32_t width, const int32_t *ids_dev, const void *cover_masks_dev,
+                                  const float *alpha_dev, const float *target_dev, const float *grad_loss_dev, float pos_gradient_boost,
+                                  float *grad_pos_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Hash-grid encoding (the texture stage's colour field): tiny-cuda-nn's `Grid` encoding, 3-D input, trilinear,
  *   tsamd_grid_encode          <- tcnn.Encoding(3, {"otype": "HashGrid" | "DenseGrid" | "Grid", ...})(x)   models/networks.py:97-106

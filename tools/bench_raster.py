@@ -79,6 +79,33 @@ def main():
         dr.antialias(alpha, rast, pos_g, tri, topology_hash=topo).backward(ga)
 
     t_aa_fb = timed(aa_fwd_bwd, args.reps)
+
+    # the same alpha image and its gradient without a rast image (rasterisation included), and with the mean squared error fused in
+    def ops_fwd_bwd():
+        pos_g.grad = None
+        r, _ = dr.rasterize(ctx, pos_g, tri, resolution=res, grad_db=False)
+        a = torch.clamp(r[..., -1:].detach(), 0, 1).contiguous()
+        dr.antialias(a, r, pos_g, tri, topology_hash=topo).backward(ga)
+
+    def sil_fwd_bwd():
+        pos_g.grad = None
+        dr.silhouette(ctx, pos_g, tri, res, topology_hash=topo).backward(ga)
+
+    target = torch.rand(args.views, args.res, args.res, device="cuda")
+    mse = torch.nn.MSELoss()
+
+    def ops_mse_fwd_bwd():
+        pos_g.grad = None
+        r, _ = dr.rasterize(ctx, pos_g, tri, resolution=res, grad_db=False)
+        a = torch.clamp(r[..., -1:].detach(), 0, 1).contiguous()
+        mse(dr.antialias(a, r, pos_g, tri, topology_hash=topo)[..., -1], target).backward()
+
+    def sil_mse_fwd_bwd():
+        pos_g.grad = None
+        dr.silhouette_mse(ctx, pos_g, tri, res, target, topology_hash=topo).backward()
+
+    t_ops_fb, t_sil_fb = timed(ops_fwd_bwd, args.reps), timed(sil_fwd_bwd, args.reps)
+    t_ops_mse_fb, t_sil_mse_fb = timed(ops_mse_fwd_bwd, args.reps), timed(sil_mse_fwd_bwd, args.reps)
     aa = dr.antialias(alpha, rast, pos, tri, topology_hash=topo)
     blended = int(((aa - alpha).abs().sum(-1) > 0).sum())
 
@@ -96,6 +123,8 @@ def main():
         "rasterize_ms": t_rast, "interpolate_ms": t_interp, "interpolate_fwd_bwd_ms": t_fb,
         "antialias_ms": t_aa, "antialias_fwd_bwd_ms": t_aa_fb, "antialias_topology_ms": t_topo, "antialias_blended_pixels": blended,
         "rasterize_interpolate_fwd_bwd_to_pos_ms": t_rb,
+        "rasterize_clamp_antialias_fwd_bwd_ms": t_ops_fb, "silhouette_fwd_bwd_ms": t_sil_fb,
+        "rasterize_clamp_antialias_mse_fwd_bwd_ms": t_ops_mse_fb, "silhouette_mse_fwd_bwd_ms": t_sil_mse_fb,
         "triangle_views_per_s": args.views * T / (t_rast * 1e-3),
         "config": {"workload": f"{args.spheres} x {args.scene} surface: {T} triangles, {V} vertices; {args.views} views x {args.res}^2, "
                                f"coverage {cover:.3f}", "dtype": "f32 (coverage / depth test: int64 + f64)"},

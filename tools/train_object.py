@@ -13,7 +13,11 @@ absent):
 * everything else is the reference's loop: `img_loss = MSE(alpha) * 20`, `loss = img_loss * 100 + reg`, `AdamUniform(lr 0.2,
   grad_limit 0.01)`, cosine schedule, order 2 -> 4 at iteration 1 000, smooth_eng_coeff / n_spheres (tetmesh_geometry.py:242).
 
-    python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500]
+    python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
+
+--silhouette: how the loop renders alpha and takes the image loss -- `operators` (the default: rasterize, clamp, antialias, MSELoss),
+`fused` (MeshRasterizer(fused_silhouette=True): dr.silhouette, then MSELoss) or `fused-loss` (MeshRasterizer.silhouette_loss:
+dr.silhouette_mse, no gradient image).  --no-stages: leave out the stand-alone stage timings (`stages_ms`).
 
 One JSON line: silhouette IoU over all views, inverted tets, seconds per iteration and the stand-alone stage times."""
 import argparse
@@ -88,13 +92,15 @@ def build_spheres(centres, radii, k):
     return np.concatenate(rest), np.concatenate(tets).astype(np.int32)
 
 
-def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False):
+def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators"):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
     from tssplat_amd import geometry, renderers, scenes
     from tssplat_amd.utils.optimizer import AdamUniform
 
+    if silhouette not in ("operators", "fused", "fused-loss"):
+        raise ValueError(f"unknown --silhouette mode {silhouette!r}")
     target_npz = target_npz or os.path.join(ROOT, "tests", "golden", "mario_mesh.npz")
     tgt = np.load(target_npz)
     tv = torch.from_numpy(tgt["vertices"].astype(np.float32)).cuda()
@@ -108,7 +114,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     rest, tets = build_spheres(centres, radii, k)
     flags = types.SimpleNamespace(smooth_eng_coeff=2e-4 / S, barrier_coeff=2e-4, increase_order_iter=1000)   # gso.yaml:8-11, tetmesh_geometry.py:242-243
     geo = geometry.TetMeshGeometry(rest, tets, smooth_barrier_param=flags)
-    ren = renderers.MeshRasterizer(geo)
+    ren = renderers.MeshRasterizer(geo, fused_silhouette=silhouette != "operators")
     opt = AdamUniform(ren.parameters(), lr=0.2, grad_limit=True, grad_limit_values=[0.01, 0.01], grad_limit_iters=[1500])   # gso.yaml:37-41
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, iters, eta_min=1e-4)                                           # trainer.py:57-58
     shade_loss = torch.nn.MSELoss()
@@ -124,8 +130,12 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(iters):
-        out = ren(mvp, only_alpha=True, iter_num=it, resolution=res)
-        img_loss = shade_loss(out["shaded"][..., -1], target[..., -1]) * 20            # trainer.py:99-101
+        if silhouette == "fused-loss":
+            out = ren.silhouette_loss(mvp, target, iter_num=it, resolution=res)
+            img_loss = out["img_loss"] * 20
+        else:
+            out = ren(mvp, only_alpha=True, iter_num=it, resolution=res)
+            img_loss = shade_loss(out["shaded"][..., -1], target[..., -1]) * 20        # trainer.py:99-101
         loss = img_loss * 100 + out["geo_regularization"]                              # trainer.py:115
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -145,7 +155,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     inverted = int((np.sign(dets(x)) != np.sign(dets(rest.astype(np.float64)))).sum())
     rec = {
         "metric": "s per iteration, geometry-fitting loop on the reference's object (BASELINE config 5)", "value": dt / iters, "unit": "s/iteration",
-        "higher_is_better": False, "iterations": iters, "wall_s": dt, "ms_per_iteration": 1e3 * dt / iters,
+        "higher_is_better": False, "silhouette": silhouette, "iterations": iters, "wall_s": dt, "ms_per_iteration": 1e3 * dt / iters,
         "silhouette_iou": iou, "silhouette_iou_at_start": iou0, "inverted_tets": inverted, "tets": int(tets.shape[0]),
         "img_loss_first_last": [log[0][1], log[-1][1]], "reg_first_last": [log[0][2], log[-1][2]],
         "spheres": {"placed": S, "asked": n_spheres, "radii_min_max": [float(radii.min()), float(radii.max())], "visual_hull_fraction_of_cube": hull_frac,
@@ -184,10 +194,20 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         def aa_fb(j):
             pos_g.grad = None
             dr.antialias(alpha, rast, pos_g, tri).backward(ga)
+
+        def sil_fb(j):
+            pos_g.grad = None
+            dr.silhouette(ren.glctx, pos_g, tri, [res, res]).backward(ga)
+
+        def sil_mse_fb(j):
+            pos_g.grad = None
+            dr.silhouette_mse(ren.glctx, pos_g, tri, [res, res], target).backward()
         rec["stages_ms"] = {
             "energy_and_surface_forward_backward": timed(geo_fb),
             "rasterize": timed(lambda j: dr.rasterize(ren.glctx, pos, tri, resolution=[res, res], grad_db=False)),
             "antialias_forward_backward": timed(aa_fb),
+            "silhouette_forward_backward": timed(sil_fb),
+            "silhouette_mse_forward_backward": timed(sil_mse_fb),
             "optimizer_step": timed(lambda j: opt.step()),
         }
     return rec
@@ -202,8 +222,11 @@ def main():
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--iters", type=int, default=1500)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--silhouette", choices=["operators", "fused", "fused-loss"], default="operators")
+    ap.add_argument("--no-stages", action="store_true", help="skip the stand-alone stage timings")
     args = ap.parse_args()
-    print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose)))
+    print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
+                         stages=not args.no_stages)))
 
 
 if __name__ == "__main__":

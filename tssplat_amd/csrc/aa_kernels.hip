@@ -11,7 +11,11 @@
 //                        with two different triangle ids are compacted in LDS and analysed in float64 with the oracle's
 //                        operations, so the SET of blends is identical; the blends themselves are float32 atomics (compared
 //                        with a tolerance).
+//   silhouette kernels   the alpha stage: the same analysis over the coverage masks of the cover pass, no `rast`; and the mean
+//                        squared error of the alpha image against a target, whose backward needs no gradient image
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "raster.h"
 
@@ -166,18 +170,13 @@ struct Blend {
 };
 
 // oracle/raster_oracle.py::_antialias_events for ONE pair of pixels -- (j, i) with its right (axis 0) or its upper (axis 1)
-// neighbour, which the caller has found to carry two different triangle ids; `emit` is called per blend.  `n_vertices`
-// bounds every index read from `tri` / `opp` (a corrupt index skips the pair).
+// neighbour -- once the caller has chosen the pair's triangle: `t`, shown by the pair's first pixel (`first`) or by its second.
+// `emit` is called per blend.  `n_vertices` bounds every index read from `tri` / `opp` (a corrupt index skips the pair).
 template <bool TABLE, class Emit>
-__device__ __forceinline__ void pair_blends(const float4 *rast_view, const float4 *pos_view, const double2 *win_view, const uint8_t *flag_view, const int32_t *tri, const int32_t *opp, int64_t n_vertices,
-                                            int64_t n_tri, int height, int width, int j, int i, int axis, Emit &&emit)
+__device__ __forceinline__ void triangle_blends(int64_t t, bool first, const float4 *pos_view, const double2 *win_view, const uint8_t *flag_view, const int32_t *tri,
+                                                const int32_t *opp, int64_t n_vertices, int64_t n_tri, int height, int width, int j, int i, int axis, Emit &&emit)
 {
     const int dj = axis, di = 1 - axis;
-    const float4 r0 = rast_view[int64_t(j) * width + i];
-    const float4 r1 = rast_view[int64_t(j + dj) * width + (i + di)];
-    const int64_t t0 = int64_t(r0.w) - 1, t1 = int64_t(r1.w) - 1;
-    const bool first = (t0 >= 0 && t1 >= 0) ? (r0.z < r1.z) : (t0 >= 0);
-    const int64_t t = first ? t0 : t1;
     if (t < 0 || t >= n_tri) return;
     uint32_t may_blend = 7u;
     if (TABLE) {
@@ -250,6 +249,37 @@ __device__ __forceinline__ void pair_blends(const float4 *rast_view, const float
         b.dBx = axis == 0 ? along_b : across_b;
         b.dBy = axis == 0 ? across_b : along_b;
         emit(b);
+    }
+}
+
+// The pair as dr.antialias meets it: two pixels of `rast` that the caller has found to carry two different triangle ids.  The
+// triangle closer to the camera wins (ties to the second pixel's, background never).
+template <bool TABLE, class Emit>
+__device__ __forceinline__ void pair_blends(const float4 *rast_view, const float4 *pos_view, const double2 *win_view, const uint8_t *flag_view, const int32_t *tri, const int32_t *opp, int64_t n_vertices,
+                                            int64_t n_tri, int height, int width, int j, int i, int axis, Emit &&emit)
+{
+    const int dj = axis, di = 1 - axis;
+    const float4 r0 = rast_view[int64_t(j) * width + i];
+    const float4 r1 = rast_view[int64_t(j + dj) * width + (i + di)];
+    const int64_t t0 = int64_t(r0.w) - 1, t1 = int64_t(r1.w) - 1;
+    const bool first = (t0 >= 0 && t1 >= 0) ? (r0.z < r1.z) : (t0 >= 0);
+    triangle_blends<TABLE>(first ? t0 : t1, first, pos_view, win_view, flag_view, tri, opp, n_vertices, n_tri, height, width, j, i, axis, emit);
+}
+
+// d loss / d clip-space position of a blend's two edge vertices, from dt = d loss / d t of the blend (fp32 atomics into the view's grad_pos)
+__device__ __forceinline__ void scatter_blend_gradient(const Blend &e, double dt, const float4 *pos_view, float4 *grad_pos_view, int height, int width)
+{
+    const int32_t vtx[2] = {e.va, e.vb};
+    const double dx[2] = {e.dAx, e.dBx}, dy[2] = {e.dAy, e.dBy};
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+        const float4 p = pos_view[vtx[k2]];
+        const double x = double(p.x), y = double(p.y), iw = 1.0 / double(p.w);
+        const double gx = dt * dx[k2] * (0.5 * double(width) * iw), gy = dt * dy[k2] * (0.5 * double(height) * iw);   // d loss / d (x, y)
+        float *gp = reinterpret_cast<float *>(grad_pos_view + vtx[k2]);
+        atomicAdd(gp + 0, float(gx));
+        atomicAdd(gp + 1, float(gy));
+        atomicAdd(gp + 3, float(-(gx * x + gy * y) * iw));
     }
 }
 
@@ -428,21 +458,7 @@ __device__ __forceinline__ void antialias_backward_body(const float *color, cons
                     atomicAdd(gc + e.dst * channels + c, -e.weight * g);
                 }
             }
-            if (grad_pos) {
-                const double dt = double(e.sign) * double(dot) * double(boost);
-                const int32_t vtx[2] = {e.va, e.vb};
-                const double dx[2] = {e.dAx, e.dBx}, dy[2] = {e.dAy, e.dBy};
-#pragma unroll
-                for (int k2 = 0; k2 < 2; ++k2) {
-                    const float4 p = pv[vtx[k2]];
-                    const double x = double(p.x), y = double(p.y), iw = 1.0 / double(p.w);
-                    const double gx = dt * dx[k2] * (0.5 * double(width) * iw), gy = dt * dy[k2] * (0.5 * double(height) * iw);   // d loss / d (x, y)
-                    float *gp = reinterpret_cast<float *>(grad_pos + b * n_vertices + vtx[k2]);
-                    atomicAdd(gp + 0, float(gx));
-                    atomicAdd(gp + 1, float(gy));
-                    atomicAdd(gp + 3, float(-(gx * x + gy * y) * iw));
-                }
-            }
+            if (grad_pos) scatter_blend_gradient(e, double(e.sign) * double(dot) * double(boost), pv, grad_pos + b * n_vertices, height, width);
         });
     };
     if (TABLE) {
@@ -476,6 +492,125 @@ __global__ __launch_bounds__(kAaBlock) __attribute__((amdgpu_waves_per_eu(8, 8))
 __global__ __launch_bounds__(kAaBlock) void antialias_backward_masked_kernel(TSAMD_AA_ARGS, const float *grad_out, float boost, float *grad_color, float4 *grad_pos)
 {
     antialias_backward_body<true>(TSAMD_AA_PASS, grad_out, boost, grad_color, grad_pos);
+}
+
+// ---- the alpha stage (tsamd_silhouette*): antialias of the 0 / 1 coverage image without a `rast` image ----
+// A pair of two covered pixels blends w (1 - 1) = 0 and its gradient term is g 0: only pairs with exactly one background pixel
+// matter, the covered pixel's triangle always wins them (z/w is never consulted), and the cover pass (raster_kernels.hip) has
+// marked exactly those pairs in the coverage masks.  The analysis is triangle_blends in its table-free form.
+//
+// work(view, triangle of the covered pixel, covered pixel is the pair's first, j, i, axis) for every pair of the coverage masks
+template <class Work>
+__device__ __forceinline__ void for_cover_pairs(const int32_t *ids, const unsigned long long *masks, int64_t batch, int height, int width, int group, Work &&work)
+{
+    __shared__ uint16_t stacks[(kAaBlock / 64) * kPairStack];
+    const int64_t hw = int64_t(height) * width, total = batch * hw;
+    for_pairs_masked(masks, (total + 63) / 64, group, stacks + (threadIdx.x >> 6) * kPairStack, [&](int64_t gid, int axis) {
+        if (gid >= total) return;                              // (masks are the caller's: a bit beyond the image is ignored)
+        const int64_t b = gid / hw, pix = gid - b * hw;
+        const int j = int(pix / width), i = int(pix - int64_t(j) * width);
+        if (axis == 0 ? i + 1 >= width : j + 1 >= height) return;
+        const int32_t id0 = ids[gid], id1 = ids[gid + (axis == 0 ? 1 : width)];
+        if ((id0 > 0) == (id1 > 0)) return;
+        work(b, int64_t(id0 > 0 ? id0 : id1) - 1, id0 > 0, j, i, axis);
+    });
+}
+
+__global__ __launch_bounds__(kAaBlock) void silhouette_blend_kernel(const int32_t *ids, const unsigned long long *masks, const float4 *pos, const int32_t *tri, const int32_t *opp,
+                                                                    int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int group, float *alpha)
+{
+    const int64_t hw = int64_t(height) * width;
+    for_cover_pairs(ids, masks, batch, height, width, group, [&](int64_t b, int64_t t, bool first, int j, int i, int axis) {
+        const int32_t *iv = ids + b * hw;
+        float *av = alpha + b * hw;
+        triangle_blends<false>(t, first, pos + b * n_vertices, nullptr, nullptr, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
+            atomicAdd(av + e.dst, e.weight * (float(iv[e.src] > 0) - float(iv[e.dst] > 0)));
+        });
+    });
+}
+
+// MSE = false: grad_alpha is the gradient image.  MSE = true: there is none -- g[dst] = 2 (alpha[dst] - target[dst]) grad_loss / n
+// is formed per blend in float64, grad_loss read from device memory.
+template <bool MSE>
+__device__ __forceinline__ void silhouette_backward_body(const int32_t *ids, const unsigned long long *masks, const float4 *pos, const int32_t *tri, const int32_t *opp, int64_t batch,
+                                                         int64_t n_vertices, int64_t n_tri, int height, int width, int group, const float *grad_alpha, const float *alpha,
+                                                         const float *target, const float *grad_loss, float boost, float4 *grad_pos)
+{
+    const int64_t hw = int64_t(height) * width;
+    for_cover_pairs(ids, masks, batch, height, width, group, [&](int64_t b, int64_t t, bool first, int j, int i, int axis) {
+        const int32_t *iv = ids + b * hw;
+        const float4 *pv = pos + b * n_vertices;
+        triangle_blends<false>(t, first, pv, nullptr, nullptr, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
+            const float dc = float(iv[e.src] > 0) - float(iv[e.dst] > 0);
+            double dot;
+            if (MSE)
+                dot = 2.0 * (double(alpha[b * hw + e.dst]) - double(target[b * hw + e.dst])) * double(*grad_loss) / double(batch * hw) * double(dc);
+            else
+                dot = double(grad_alpha[b * hw + e.dst] * dc);
+            scatter_blend_gradient(e, double(e.sign) * dot * double(boost), pv, grad_pos + b * n_vertices, height, width);
+        });
+    });
+}
+
+#define TSAMD_SIL_ARGS                                                                                                                                       \
+    const int32_t *ids, const unsigned long long *masks, const float4 *pos, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, \
+        int height, int width, int group
+#define TSAMD_SIL_PASS ids, masks, pos, tri, opp, batch, n_vertices, n_tri, height, width, group
+
+__global__ __launch_bounds__(kAaBlock) void silhouette_backward_kernel(TSAMD_SIL_ARGS, const float *grad_alpha, float boost, float4 *grad_pos)
+{
+    silhouette_backward_body<false>(TSAMD_SIL_PASS, grad_alpha, nullptr, nullptr, nullptr, boost, grad_pos);
+}
+__global__ __launch_bounds__(kAaBlock) void silhouette_mse_backward_kernel(TSAMD_SIL_ARGS, const float *alpha, const float *target, const float *grad_loss, float boost,
+                                                                           float4 *grad_pos)
+{
+    silhouette_backward_body<true>(TSAMD_SIL_PASS, nullptr, alpha, target, grad_loss, boost, grad_pos);
+}
+
+// ---- loss = mean((alpha - target)^2), bitwise repeatable: no atomics, fixed grid, fixed trees ----
+// d = a - t in float32, d * d accumulated in float64.  A workgroup strides over the 16-byte groups (n4 of them; 0 when a pointer is
+// not 16-byte aligned) and over the scalar rest [4 n4, n), sums its lanes in a fixed tree and stores one double; the final
+// workgroup adds the partials in a fixed order and stores float(sum / n).
+constexpr int kMseBlock = 256;
+constexpr int kMseMaxBlocks = 1024;
+
+int mse_blocks(int64_t n) { return int(std::min<int64_t>(kMseMaxBlocks, std::max<int64_t>(1, (n + 4 * kMseBlock - 1) / (4 * kMseBlock)))); }
+
+__device__ __forceinline__ double block_sum(double v, double *lds)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((lds[0] + lds[1]) + (lds[2] + lds[3]));
+}
+
+__global__ __launch_bounds__(kMseBlock) void silhouette_mse_kernel(const float *alpha, const float *target, int64_t n, int64_t n4, double *partials)
+{
+    __shared__ double lds[kMseBlock / 64];
+    const int64_t first = int64_t(blockIdx.x) * kMseBlock + threadIdx.x, stride = int64_t(gridDim.x) * kMseBlock;
+    double acc = 0.0;
+    const float4 *a4 = reinterpret_cast<const float4 *>(alpha), *t4 = reinterpret_cast<const float4 *>(target);
+    for (int64_t k = first; k < n4; k += stride) {
+        const float4 a = a4[k], t = t4[k];
+        const float d0 = a.x - t.x, d1 = a.y - t.y, d2 = a.z - t.z, d3 = a.w - t.w;
+        acc += (double(d0) * double(d0) + double(d1) * double(d1)) + (double(d2) * double(d2) + double(d3) * double(d3));
+    }
+    for (int64_t k = 4 * n4 + first; k < n; k += stride) {
+        const float d = alpha[k] - target[k];
+        acc += double(d) * double(d);
+    }
+    const double sum = block_sum(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(kMseBlock) void silhouette_mse_final_kernel(const double *partials, int n_partials, int64_t n, float *loss)
+{
+    __shared__ double lds[kMseBlock / 64];
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < n_partials; k += kMseBlock) acc += partials[k];
+    const double sum = block_sum(acc, lds);
+    if (threadIdx.x == 0) *loss = float(sum / double(n));
 }
 
 unsigned blocks_for(int64_t n) { return unsigned((n + 255) / 256); }
@@ -604,6 +739,55 @@ hipError_t launch_antialias_backward(const float *color, const float *rast, cons
                        reinterpret_cast<const float4 *>(pos_clip), static_cast<const double2 *>(prepared), masks, flags, tri, opp, batch, n_vertices, n_tri, height, width,
                        channels, group, grad_out, boost, grad_color,
                        reinterpret_cast<float4 *>(grad_pos));
+    return hipGetLastError();
+}
+
+hipError_t launch_silhouette_blend(const float *pos_clip, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width,
+                                   const int32_t *ids, const void *cover_masks, float *alpha, hipStream_t stream)
+{
+    const int64_t pixels = batch * int64_t(height) * width;
+    if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
+    const int group = masked_group((pixels + 63) / 64);
+    const int64_t waves = ((pixels + 63) / 64 + group - 1) / group;
+    hipLaunchKernelGGL(silhouette_blend_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, ids, static_cast<const unsigned long long *>(cover_masks),
+                       reinterpret_cast<const float4 *>(pos_clip), tri, opp, batch, n_vertices, n_tri, height, width, group, alpha);
+    return hipGetLastError();
+}
+
+hipError_t launch_silhouette_backward(const float *pos_clip, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width,
+                                      const int32_t *ids, const void *cover_masks, const float *grad_alpha, const float *alpha, const float *target,
+                                      const float *grad_loss, float boost, float *grad_pos, hipStream_t stream)
+{
+    if (batch * n_vertices > 0) {
+        const hipError_t e = hipMemsetAsync(grad_pos, 0, size_t(batch) * size_t(n_vertices) * 4 * sizeof(float), stream);
+        if (e != hipSuccess) return e;
+    }
+    const int64_t pixels = batch * int64_t(height) * width;
+    if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
+    const int group = masked_group((pixels + 63) / 64);
+    const int64_t waves = ((pixels + 63) / 64 + group - 1) / group;
+    const unsigned long long *masks = static_cast<const unsigned long long *>(cover_masks);
+    const float4 *pos = reinterpret_cast<const float4 *>(pos_clip);
+    if (grad_alpha)
+        hipLaunchKernelGGL(silhouette_backward_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, ids, masks, pos, tri, opp, batch, n_vertices, n_tri, height,
+                           width, group, grad_alpha, boost, reinterpret_cast<float4 *>(grad_pos));
+    else
+        hipLaunchKernelGGL(silhouette_mse_backward_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, ids, masks, pos, tri, opp, batch, n_vertices, n_tri,
+                           height, width, group, alpha, target, grad_loss, boost, reinterpret_cast<float4 *>(grad_pos));
+    return hipGetLastError();
+}
+
+int64_t silhouette_mse_workspace_bytes(int64_t n) { return (int64_t(mse_blocks(n)) * 8 + 255) / 256 * 256; }
+
+hipError_t launch_silhouette_mse(const float *alpha, const float *target, int64_t n, void *workspace, float *loss, hipStream_t stream)
+{
+    if (n <= 0) return hipMemsetAsync(loss, 0, sizeof(float), stream);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(alpha) | reinterpret_cast<uintptr_t>(target)) & 15u) == 0;
+    const int blocks = mse_blocks(n);
+    hipLaunchKernelGGL(silhouette_mse_kernel, dim3(blocks), dim3(kMseBlock), 0, stream, alpha, target, n, aligned ? n / 4 : 0, static_cast<double *>(workspace));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(silhouette_mse_final_kernel, dim3(1), dim3(kMseBlock), 0, stream, static_cast<const double *>(workspace), blocks, n, loss);
     return hipGetLastError();
 }
 

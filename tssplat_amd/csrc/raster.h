@@ -30,6 +30,20 @@ hipError_t launch_antialias(const float *color, const float *rast, const float *
 hipError_t launch_antialias_backward(const float *color, const float *rast, const float *pos_clip, const void *prepared, const int32_t *tri,
                                      const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int channels, const float *grad_out, float boost,
                                      float *grad_color, float *grad_pos, hipStream_t stream);
+// The alpha stage (tsamd_silhouette*).  cover (raster_kernels.hip): the depth keys of launch_rasterize, then per pixel ids (triangle + 1,
+// 0 = background), alpha = 0 / 1 and the coverage masks (pair_masks_bytes; bit = exactly one pixel of the pair is background).
+// blend / backward (aa_kernels.hip): the antialias analysis over those masks; backward takes grad_alpha, or (grad_alpha null) alpha,
+// target and the device scalar grad_loss of the mean squared error; grad_pos is zero-filled by the launch.
+hipError_t launch_silhouette_cover(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                   void *workspace, int32_t *ids, void *cover_masks, float *alpha, hipStream_t stream);
+hipError_t launch_silhouette_blend(const float *pos_clip, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width,
+                                   const int32_t *ids, const void *cover_masks, float *alpha, hipStream_t stream);
+hipError_t launch_silhouette_backward(const float *pos_clip, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width,
+                                      const int32_t *ids, const void *cover_masks, const float *grad_alpha, const float *alpha, const float *target,
+                                      const float *grad_loss, float boost, float *grad_pos, hipStream_t stream);
+// loss = mean((alpha - target)^2) over n floats, bitwise repeatable; n = 0 stores 0
+int64_t silhouette_mse_workspace_bytes(int64_t n);
+hipError_t launch_silhouette_mse(const float *alpha, const float *target, int64_t n, void *workspace, float *loss, hipStream_t stream);
 hipError_t launch_interpolate(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels, const float *rast, const int32_t *tri,
                               int64_t n_tri, int64_t batch, int height, int width, float *out, hipStream_t stream);
 // grad_attr is zero-filled by the launch; grad_rast may be null

@@ -1,6 +1,7 @@
 // C ABI of the renderer slice (include/tssplat_amd.h, "renderer" section): stateless entry points, the caller owns
 // every buffer (positions, triangles, the depth-key workspace, outputs) and names the device by making it current.
 #include <climits>
+#include <initializer_list>
 #include <string>
 
 #include "capi_common.h"
@@ -176,6 +177,110 @@ int tsamd_antialias_backward(const float *color_dev, const float *rast_dev, cons
     TSAMD_HIP(tsamd::launch_antialias_backward(color_dev, rast_dev, pos_clip_dev, prepared_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height,
                                                width, n_channels, grad_out_dev, pos_gradient_boost, grad_color_dev, grad_pos_dev,
                                                static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+namespace {
+// the first null pointer of a list of (pointer, name) pairs, named on its own
+struct NamedPtr {
+    const void *ptr;
+    const char *name;
+};
+int check_not_null(std::initializer_list<NamedPtr> args)
+{
+    for (const NamedPtr &a : args)
+        if (!a.ptr) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(a.name) + " is null");
+    return TSAMD_OK;
+}
+
+// the arguments tsamd_silhouette and its two backward calls share, with the limits and the words of tsamd_rasterize
+int check_silhouette(int64_t batch, int64_t n_vertices, int64_t n_triangles, int32_t height, int32_t width)
+{
+    int rc = check_image(batch, height, width);
+    if (rc) return rc;
+    if (n_vertices < 0 || n_triangles < 0 || n_triangles > (int64_t(1) << 24) - 1)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "negative size or more than 2^24 - 1 triangles (the id + 1 is returned as a float32, exact up to 2^24)");
+    if ((batch + 7) / 8 * 8 * ((n_triangles + 255) / 256) > int64_t(INT32_MAX))
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch x triangles / 256 exceeds the grid limit (2^31 - 1 workgroups)");
+    return TSAMD_OK;
+}
+
+int check_silhouette_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                              const int32_t *edge_partner_dev, int32_t height, int32_t width, const int32_t *ids_dev, const void *cover_masks_dev,
+                              const float *grad_pos_dev)
+{
+    int rc = check_silhouette(batch, n_vertices, n_triangles, height, width);
+    if (rc) return rc;
+    const int64_t pixels = batch * int64_t(height) * width;
+    if (batch * n_vertices > 0 && !grad_pos_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_pos_dev is null");
+    if (pixels <= 0 || batch * n_triangles <= 0) return TSAMD_OK;
+    return check_not_null({{ids_dev, "ids_dev"}, {cover_masks_dev, "cover_masks_dev"}, {pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"},
+                           {edge_partner_dev, "edge_partner_dev"}});
+}
+}  // namespace
+
+int tsamd_silhouette(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                     const int32_t *edge_partner_dev, int32_t height, int32_t width, void *workspace_dev, int32_t *ids_out_dev, void *cover_masks_out_dev,
+                     float *alpha_out_dev, void *stream)
+{
+    int rc = check_silhouette(batch, n_vertices, n_triangles, height, width);
+    if (rc) return rc;
+    const int64_t pixels = batch * int64_t(height) * width;
+    if (pixels > 0 && (rc = check_not_null({{workspace_dev, "workspace_dev"}, {ids_out_dev, "ids_out_dev"}, {cover_masks_out_dev, "cover_masks_out_dev"},
+                                            {alpha_out_dev, "alpha_out_dev"}})))
+        return rc;
+    if (batch * n_triangles > 0 && (rc = check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {edge_partner_dev, "edge_partner_dev"}}))) return rc;
+    TSAMD_HIP(tsamd::launch_silhouette_cover(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, workspace_dev, ids_out_dev,
+                                             cover_masks_out_dev, alpha_out_dev, static_cast<hipStream_t>(stream)));
+    TSAMD_HIP(tsamd::launch_silhouette_blend(pos_clip_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width, ids_out_dev,
+                                             cover_masks_out_dev, alpha_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_silhouette_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                              const int32_t *edge_partner_dev, int32_t height, int32_t width, const int32_t *ids_dev, const void *cover_masks_dev,
+                              const float *grad_alpha_dev, float pos_gradient_boost, float *grad_pos_dev, void *stream)
+{
+    int rc = check_silhouette_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, edge_partner_dev, height, width, ids_dev, cover_masks_dev,
+                                       grad_pos_dev);
+    if (rc) return rc;
+    if (batch * int64_t(height) * width > 0 && batch * n_triangles > 0 && !grad_alpha_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_alpha_dev is null");
+    TSAMD_HIP(tsamd::launch_silhouette_backward(pos_clip_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width, ids_dev, cover_masks_dev,
+                                                grad_alpha_dev, nullptr, nullptr, nullptr, pos_gradient_boost, grad_pos_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int64_t tsamd_silhouette_mse_workspace_bytes(int64_t n)
+{
+    if (n < 0) return -1;
+    return tsamd::silhouette_mse_workspace_bytes(n);
+}
+
+int tsamd_silhouette_mse(const float *alpha_dev, const float *target_dev, int64_t n, void *workspace_dev, float *loss_out_dev, void *stream)
+{
+    if (n < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "negative size");
+    if (!loss_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "loss_out_dev is null");
+    if (n > 0) {
+        const int rc = check_not_null({{alpha_dev, "alpha_dev"}, {target_dev, "target_dev"}, {workspace_dev, "workspace_dev"}});
+        if (rc) return rc;
+    }
+    TSAMD_HIP(tsamd::launch_silhouette_mse(alpha_dev, target_dev, n, workspace_dev, loss_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_silhouette_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
+                                  const int32_t *edge_partner_dev, int32_t height, int32_t width, const int32_t *ids_dev, const void *cover_masks_dev,
+                                  const float *alpha_dev, const float *target_dev, const float *grad_loss_dev, float pos_gradient_boost, float *grad_pos_dev,
+                                  void *stream)
+{
+    int rc = check_silhouette_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, edge_partner_dev, height, width, ids_dev, cover_masks_dev,
+                                       grad_pos_dev);
+    if (rc) return rc;
+    if (batch * int64_t(height) * width > 0 && batch * n_triangles > 0 &&
+        (rc = check_not_null({{alpha_dev, "alpha_dev"}, {target_dev, "target_dev"}, {grad_loss_dev, "grad_loss_dev"}})))
+        return rc;
+    TSAMD_HIP(tsamd::launch_silhouette_backward(pos_clip_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width, ids_dev, cover_masks_dev,
+                                                nullptr, alpha_dev, target_dev, grad_loss_dev, pos_gradient_boost, grad_pos_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
 }
 

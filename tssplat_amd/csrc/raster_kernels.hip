@@ -14,6 +14,7 @@
 //   rasterize_clip_kernel  the rare path: triangles with a vertex at w <= 0, clipped against the near plane, same integer rules
 //   rasterize_resolve_kernel  one lane per pixel: winning triangle -> (u, v, z/w, id + 1); optional by-product: the pair masks
 //                          (which pixels differ from their right / upper neighbour) that the antialias kernels start from
+//   silhouette_cover_kernel  the alpha stage's resolve pass: id, coverage 0 / 1 and the coverage masks per pixel, from the keys alone
 //   interpolate_kernel / interpolate_backward_kernel  one lane per pixel
 //
 // Bound: the depth image -- L2 atomics and the reads in front of them (pricing builds, profiles/r04_raster_experiments.md: walk
@@ -488,6 +489,67 @@ __global__ __launch_bounds__(256) void rasterize_resolve_kernel(const float4 *po
     }
 }
 
+// The alpha stage's resolve pass (tsamd_silhouette): per pixel the id the pass above would write (triangle + 1, 0 on background) as
+// an int32, its coverage as a float 0 / 1, and the coverage masks -- the layout, chunking and guards of the pair masks above, but
+// bit l says that exactly ONE pixel of the pair is background.  Nothing is read but the keys: no vertex, no barycentric, no z/w.
+__global__ __launch_bounds__(256) void silhouette_cover_kernel(int64_t batch, int height, int width, const unsigned long long *keys, int32_t *ids,
+                                                               unsigned long long *cover_masks, float *alpha)
+{
+    constexpr int K = kResolvePixels;
+    const int64_t hw = int64_t(height) * width, total = batch * hw;
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t gid0 = (int64_t(blockIdx.x) * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6))) * (64 * K);
+    int64_t gid[K];
+    int px[K], py[K];
+    bool have[K];
+    const int64_t b0 = hw >= 64 * K ? gid0 / hw : 0;   // (as in the resolve pass: the view of the wave's first pixel on the scalar unit)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        gid[k] = gid0 + 64 * k + lane;
+        have[k] = gid[k] < total;
+        uint32_t pix;
+        if (hw >= 64 * K) {
+            const int64_t off = gid[k] - b0 * hw;
+            pix = uint32_t(off >= hw ? off - hw : off);
+        } else {
+            pix = uint32_t(gid[k] % hw);
+        }
+        py[k] = int(pix / uint32_t(width));
+        px[k] = int(pix - uint32_t(py[k]) * uint32_t(width));
+    }
+    unsigned long long key[K], key_up[K], key_right = kNoFragment;
+    bool want_up[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        want_up[k] = have[k] && py[k] + 1 < height;
+        key[k] = have[k] ? keys[gid[k]] : kNoFragment;
+        key_up[k] = want_up[k] ? keys[gid[k] + width] : kNoFragment;
+    }
+    const bool want_right = have[K - 1] && px[K - 1] + 1 < width && lane == 63 && gid[K - 1] + 1 < total;
+    if (want_right) key_right = keys[gid[K - 1] + 1];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const bool cov = key[k] != kNoFragment;
+        const unsigned long long covered = __ballot(cov);
+        // lane 63's right neighbour: the next chunk's first pixel (lane 0 of this wave), behind the last chunk the extra load
+        bool beyond = key_right != kNoFragment;
+        if (k + 1 < K) beyond = __builtin_amdgcn_readfirstlane(int(key[k + 1 < K ? k + 1 : k] != kNoFragment)) != 0;
+        const bool right = lane == 63 ? beyond : ((covered >> ((lane + 1) & 63)) & 1ull) != 0ull;
+        const bool up = want_up[k] ? key_up[k] != kNoFragment : cov;
+        const bool c0 = have[k] && px[k] + 1 < width && right != cov;
+        const bool c1 = have[k] && py[k] + 1 < height && up != cov;
+        const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1);
+        if (lane == 0 && have[k]) {
+            cover_masks[2 * (gid[k] >> 6)] = m0;
+            cover_masks[2 * (gid[k] >> 6) + 1] = m1;
+        }
+        if (have[k]) {
+            ids[gid[k]] = cov ? int32_t(uint32_t(key[k])) + 1 : 0;
+            alpha[gid[k]] = cov ? 1.f : 0.f;
+        }
+    }
+}
+
 // ---- scatter with runs ----
 // The backward scatters add one value per pixel to the three vertices of the pixel's triangle.  Consecutive pixels of a row
 // mostly belong to the same triangle (a 41 k-tet object at 512^2: runs of ~5), so the lanes of a run are summed inside the wave
@@ -668,13 +730,13 @@ __global__ __launch_bounds__(256) void interpolate_backward_kernel(const float *
 
 unsigned blocks_for(int64_t n) { return unsigned((n + 255) / 256); }
 
-}  // namespace
-
-hipError_t launch_rasterize(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
-                            void *workspace, float *rast, void *pair_masks, hipStream_t stream)
+// The stages every rasterisation starts with -- depth keys cleared, vertices snapped, triangles binned, the rare ones clipped: after
+// them keys[batch * height * width] (the head of `workspace`) holds (depth32 << 32 | triangle) of the winning fragment per pixel,
+// kNoFragment on background.  pixels = batch * height * width > 0.
+hipError_t launch_depth_keys(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                             void *workspace, hipStream_t stream)
 {
     const int64_t pixels = batch * int64_t(height) * width;
-    if (pixels <= 0) return hipSuccess;
     unsigned long long *keys = static_cast<unsigned long long *>(workspace);
     SnapRec *snapped = reinterpret_cast<SnapRec *>(keys + ((size_t(pixels) + 1) & ~size_t(1)));   // 16-byte aligned
     uint32_t *view_flags = reinterpret_cast<uint32_t *>(snapped + size_t(batch) * size_t(n_vertices));
@@ -698,8 +760,32 @@ hipError_t launch_rasterize(const float *pos_clip, int64_t batch, int64_t n_vert
                            reinterpret_cast<const float4 *>(pos_clip), snapped, tri, view_flags, batch, n_vertices, n_tri, height, width, keys);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_rasterize(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                            void *workspace, float *rast, void *pair_masks, hipStream_t stream)
+{
+    const int64_t pixels = batch * int64_t(height) * width;
+    if (pixels <= 0) return hipSuccess;
+    const hipError_t e = launch_depth_keys(pos_clip, batch, n_vertices, tri, n_tri, height, width, workspace, stream);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rasterize_resolve_kernel, dim3(blocks_for((pixels + kResolvePixels - 1) / kResolvePixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri,
-                       n_vertices, batch, height, width, keys, reinterpret_cast<float4 *>(rast), static_cast<unsigned long long *>(pair_masks));
+                       n_vertices, batch, height, width, static_cast<const unsigned long long *>(workspace), reinterpret_cast<float4 *>(rast), static_cast<unsigned long long *>(pair_masks));
+    return hipGetLastError();
+}
+
+hipError_t launch_silhouette_cover(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                   void *workspace, int32_t *ids, void *cover_masks, float *alpha, hipStream_t stream)
+{
+    const int64_t pixels = batch * int64_t(height) * width;
+    if (pixels <= 0) return hipSuccess;
+    const hipError_t e = launch_depth_keys(pos_clip, batch, n_vertices, tri, n_tri, height, width, workspace, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(silhouette_cover_kernel, dim3(blocks_for((pixels + kResolvePixels - 1) / kResolvePixels)), dim3(256), 0, stream, batch, height, width,
+                       static_cast<const unsigned long long *>(workspace), ids, static_cast<unsigned long long *>(cover_masks), alpha);
     return hipGetLastError();
 }
 

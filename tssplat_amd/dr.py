@@ -19,6 +19,10 @@ What it does not do, loudly: ``grad_db=True``, ``ranges`` (range mode) and ``ras
 rejected (``RasterizeGLContext`` is an alias of the HIP context); clipping is against the NEAR plane only (a triangle with vertices at ``w <= 0`` is clipped there; one with a vertex
 beyond the +-16384-pixel guard band is dropped; the silhouette of a clipped triangle is not antialiased); no depth peeling; ``texture`` rejects ``uv_da``,
 ``mip_level_bias``, ``mip``, ``max_mip_level``, the ``linear-mipmap-*`` filters and ``boundary_mode='cube'``.
+
+``silhouette`` and ``silhouette_mse`` are this package's own: the alpha stage of the reference's trainer (``only_alpha=True``:
+``MSE(antialias(clamp(rast[..., -1:], 0, 1)))``) without the ``rast`` image, the clamp, the antialias copy and the dense loss
+gradient -- the same blends as the three operators above give on the 0 / 1 coverage image.
 """
 from __future__ import annotations
 
@@ -31,7 +35,8 @@ import torch
 from . import _capi
 from .tet_spheres_ext import _device_ctx, _stream_ptr
 
-__all__ = ["RasterizeCudaContext", "rasterize", "interpolate", "antialias", "antialias_construct_topology_hash", "texture"]
+__all__ = ["RasterizeCudaContext", "rasterize", "interpolate", "antialias", "antialias_construct_topology_hash", "texture", "silhouette",
+           "silhouette_mse"]
 
 _lib = _capi.load()
 
@@ -336,6 +341,107 @@ def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: t
     if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != rast.device:
         raise RuntimeError("tssplat_amd.dr.antialias: topology_hash does not belong to this triangle list")
     return _AntialiasFunc.apply(color, rast, pos, tri, topo.opp, float(pos_gradient_boost), pair_masks)
+
+
+# ---- the alpha stage without a rast image ----
+
+def _silhouette_args(name: str, pos, tri, resolution, topology_hash):
+    pos = _check_cuda_f32("pos", pos)
+    if pos.dim() != 3 or pos.shape[2] != 4:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: pos must be [B, V, 4] clip-space positions (instanced mode)")
+    tri = _check_tri(tri, pos.device)
+    height, width = int(resolution[0]), int(resolution[1])
+    if int(tri.shape[0]) > (1 << 24) - 1:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: more than 2^24 - 1 triangles")
+    if not (0 <= height <= 8192 and 0 <= width <= 8192):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: resolution out of range (0 .. 8192 pixels per side)")
+    topo = _topology_for(tri) if topology_hash is None else topology_hash
+    if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != pos.device:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: topology_hash does not belong to this triangle list")
+    return pos, tri, height, width, topo
+
+
+def _silhouette_forward(pos, tri, opp, glctx, height, width):
+    """(alpha [B, H, W, 1], ids [B, H, W] int32, coverage masks) of tsamd_silhouette."""
+    B, V = int(pos.shape[0]), int(pos.shape[1])
+    alpha = torch.empty((B, height, width, 1), dtype=torch.float32, device=pos.device)
+    ids = torch.empty((B, height, width), dtype=torch.int32, device=pos.device)
+    masks = torch.empty((max(int(_lib.tsamd_pair_masks_bytes(B, height, width)), 8),), dtype=torch.uint8, device=pos.device)
+    ws = glctx.workspace(B, V, height, width, pos.device)
+    with _device_ctx(pos.device):
+        _capi.check(_lib.tsamd_silhouette(pos.data_ptr(), B, V, tri.data_ptr(), int(tri.shape[0]), opp.data_ptr(), height, width, ws.data_ptr(),
+                                          ids.data_ptr(), masks.data_ptr(), alpha.data_ptr(), _stream_ptr(pos.device)))
+    return alpha, ids, masks
+
+
+class _SilhouetteFunc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, tri, opp, glctx, height, width, boost):
+        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
+        ctx.save_for_backward(pos, tri, opp, ids, masks)
+        ctx.boost = float(boost)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        pos, tri, opp, ids, masks = ctx.saved_tensors
+        B, V, H, W = int(pos.shape[0]), int(pos.shape[1]), int(ids.shape[1]), int(ids.shape[2])
+        g = grad_alpha.contiguous()
+        grad_pos = torch.empty_like(pos)
+        with _device_ctx(pos.device):
+            _capi.check(_lib.tsamd_silhouette_backward(pos.data_ptr(), B, V, tri.data_ptr(), int(tri.shape[0]), opp.data_ptr(), H, W, ids.data_ptr(),
+                                                       masks.data_ptr(), g.data_ptr(), ctx.boost, grad_pos.data_ptr(), _stream_ptr(pos.device)))
+        return grad_pos, None, None, None, None, None, None
+
+
+def silhouette(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor, resolution, topology_hash=None, pos_gradient_boost: float = 1.0):
+    """``alpha[B, H, W, 1]``: what ``antialias(clamp(rast[..., -1:], 0, 1), rast, pos, tri)`` of ``rasterize(glctx, pos, tri, resolution)``
+    gives -- coverage 0 / 1 with the silhouette pixels blended -- without the ``rast`` image; differentiable w.r.t. ``pos``."""
+    pos, tri, height, width, topo = _silhouette_args("silhouette", pos, tri, resolution, topology_hash)
+    return _SilhouetteFunc.apply(pos, tri, topo.opp, glctx, height, width, float(pos_gradient_boost))
+
+
+class _SilhouetteMseFunc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, tri, opp, glctx, height, width, target, boost):
+        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
+        n = alpha.numel()
+        loss = torch.empty((), dtype=torch.float32, device=pos.device)
+        ws = torch.empty((int(_lib.tsamd_silhouette_mse_workspace_bytes(n)),), dtype=torch.uint8, device=pos.device)
+        with _device_ctx(pos.device):
+            _capi.check(_lib.tsamd_silhouette_mse(alpha.data_ptr(), target.data_ptr(), n, ws.data_ptr(), loss.data_ptr(), _stream_ptr(pos.device)))
+        ctx.save_for_backward(pos, tri, opp, ids, masks, alpha, target)
+        ctx.boost = float(boost)
+        ctx.mark_non_differentiable(alpha)
+        return loss, alpha
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_alpha):
+        pos, tri, opp, ids, masks, alpha, target = ctx.saved_tensors
+        B, V, H, W = int(pos.shape[0]), int(pos.shape[1]), int(ids.shape[1]), int(ids.shape[2])
+        g = grad_loss.to(torch.float32).contiguous()           # stays on the device: the kernel reads it there
+        grad_pos = torch.empty_like(pos)
+        with _device_ctx(pos.device):
+            _capi.check(_lib.tsamd_silhouette_mse_backward(pos.data_ptr(), B, V, tri.data_ptr(), int(tri.shape[0]), opp.data_ptr(), H, W, ids.data_ptr(),
+                                                           masks.data_ptr(), alpha.data_ptr(), target.data_ptr(), g.data_ptr(), ctx.boost,
+                                                           grad_pos.data_ptr(), _stream_ptr(pos.device)))
+        return grad_pos, None, None, None, None, None, None, None
+
+
+def silhouette_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor, resolution, target: torch.Tensor, topology_hash=None,
+                   pos_gradient_boost: float = 1.0, return_alpha: bool = False):
+    """``mean((silhouette(...) - target) ** 2)`` as a 0-dim tensor (bitwise repeatable), differentiable w.r.t. ``pos`` without a
+    gradient image; ``target`` is ``[B, H, W]`` or ``[B, H, W, 1]`` float32 and carries no gradient.  ``return_alpha=True``:
+    ``(loss, alpha.detach())``."""
+    pos, tri, height, width, topo = _silhouette_args("silhouette_mse", pos, tri, resolution, topology_hash)
+    target = _check_cuda_f32("target", target)
+    if target.device != pos.device:
+        raise RuntimeError("tssplat_amd.dr.silhouette_mse: target and pos must live on the same device")
+    shape = (int(pos.shape[0]), height, width)
+    if tuple(target.shape) not in (shape, shape + (1,)):
+        raise RuntimeError("tssplat_amd.dr.silhouette_mse: target must be [B, H, W] or [B, H, W, 1] of the image size")
+    loss, alpha = _SilhouetteMseFunc.apply(pos, tri, topo.opp, glctx, height, width, target.detach(), float(pos_gradient_boost))
+    return (loss, alpha.detach()) if return_alpha else loss
 
 
 _TEX_FILTERS = {"nearest": 0, "linear": 1}                  # TSAMD_TEX_FILTER_* of include/tssplat_amd.h

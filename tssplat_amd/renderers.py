@@ -37,8 +37,11 @@ class ViewPlan:
 
 
 class MeshRasterizer(torch.nn.Module):
-    def __init__(self, geometry: torch.nn.Module, materials: Optional[torch.nn.Module] = None, context_type: str = "cuda", is_orhto: bool = False):
+    def __init__(self, geometry: torch.nn.Module, materials: Optional[torch.nn.Module] = None, context_type: str = "cuda", is_orhto: bool = False,
+                 fused_silhouette: bool = False):
         super().__init__()
+        # opt-in: forward(only_alpha=True) without fit_normal / fit_depth takes alpha from dr.silhouette (no rast image)
+        self.fused_silhouette = bool(fused_silhouette)
         if context_type not in ("cuda", "gl"):                       # mesh_rasterizer.py:33-38
             raise ValueError("Invalid context type")
         self.is_orhto = bool(is_orhto)                               # (the reference's spelling, mesh_rasterizer.py:24)
@@ -86,23 +89,30 @@ class MeshRasterizer(torch.nn.Module):
             point_plan = self.materials.plan_points(positions_all[selector])
         return ViewPlan(mvp, resolution, pos_clip, rast_out, selector, point_plan)
 
+    def _geometry_forward(self, iter_num: int, permute_surface_scheduler=None):
+        """The geometry forward of one iteration, with the surface permutation the scheduler asks for (mesh_rasterizer.py:90-94)."""
+        geo_input = {"iter_num": iter_num}
+        if permute_surface_scheduler is not None:
+            permute_dev = permute_surface_scheduler(iter_num)
+            if permute_dev is not None:
+                geo_input["permute_surface_v"] = True
+                geo_input["permute_surface_v_dev"] = permute_dev
+        return self.geometry(**geo_input)
+
     def forward(self, mvp: torch.Tensor, only_alpha: bool, iter_num: int, resolution: int, permute_surface_scheduler=None,
                 fit_normal: bool = False, fit_depth: bool = False, background: Optional[torch.Tensor] = None,
                 campos: Optional[torch.Tensor] = None, view_plan: Optional[ViewPlan] = None):
         if view_plan is not None:
             return self._forward_planned(view_plan, only_alpha, iter_num, resolution, permute_surface_scheduler, fit_normal, fit_depth,
                                          background, campos)
-        geo_input = {"iter_num": iter_num}
-        if permute_surface_scheduler is not None:                    # mesh_rasterizer.py:90-94
-            permute_dev = permute_surface_scheduler(iter_num)
-            if permute_dev is not None:
-                geo_input["permute_surface_v"] = True
-                geo_input["permute_surface_v_dev"] = permute_dev
-        data = self.geometry(**geo_input)
+        data = self._geometry_forward(iter_num, permute_surface_scheduler)
         res = [resolution, resolution]
         tri = data.t_pos_idx
 
         pos_clip = self.transform_pos(mvp, data.v_pos).contiguous()
+        if self.fused_silhouette and only_alpha and not fit_normal and not fit_depth:      # (either of the two needs rast_out)
+            shaded = dr.silhouette(self.glctx, pos_clip, tri, res, topology_hash=self.tri_hash, pos_gradient_boost=1.0)
+            return {"shaded": shaded, "geo_regularization": data.smooth_barrier_energy}
         rast_out, _ = dr.rasterize(self.glctx, pos_clip, tri, resolution=res, grad_db=False)
         # mesh_rasterizer.py:106-108.  The id channel carries no gradient (a triangle id + 1 is >= 1: the clamp is flat there, and
         # rasterize's backward ignores that channel anyway), so it is detached here: autograd would otherwise run the clamp's and
@@ -136,6 +146,17 @@ class MeshRasterizer(torch.nn.Module):
             world_pos, _ = dr.interpolate(data.v_pos[None, ...], rast_out, tri)
             out["d"] = torch.norm(world_pos - campos[:, None, None, :], dim=-1, keepdim=True)
         return out
+
+    def silhouette_loss(self, mvp: torch.Tensor, target_alpha: torch.Tensor, iter_num: int, resolution: int, permute_surface_scheduler=None):
+        """The alpha stage's render and image loss in one: ``{"img_loss", "geo_regularization", "shaded"}`` with ``img_loss`` the
+        plain mean squared error of ``forward(mvp, only_alpha=True, ...)["shaded"]`` against ``target_alpha`` (``[B, H, W]`` or
+        ``[B, H, W, 1]``; the caller applies the trainer's weights) through ``dr.silhouette_mse`` -- no ``rast`` image, no
+        gradient image -- and ``shaded`` detached."""
+        data = self._geometry_forward(iter_num, permute_surface_scheduler)
+        pos_clip = self.transform_pos(mvp, data.v_pos).contiguous()
+        loss, shaded = dr.silhouette_mse(self.glctx, pos_clip, data.t_pos_idx, [resolution, resolution], target_alpha, topology_hash=self.tri_hash,
+                                         pos_gradient_boost=1.0, return_alpha=True)
+        return {"img_loss": loss, "geo_regularization": data.smooth_barrier_energy, "shaded": shaded}
 
     def _forward_planned(self, plan: ViewPlan, only_alpha, iter_num, resolution, permute_surface_scheduler, fit_normal, fit_depth,
                          background, campos):
