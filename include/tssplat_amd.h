@@ -427,6 +427,65 @@ int tsamd_silhouette_mse_backward(const float *pos_clip_dev, int64_t batch, int6
                                   const float *alpha_dev, const float *target_dev, const float *grad_loss_dev, float pos_gradient_boost,
                                   float *grad_pos_dev, void *stream);
 
+/* The texture stage's image side under frozen geometry and fixed views (the reference's trainer.py with optimize_geo = False:
+ * loss = L1(antialias(lerp(background, scatter(color), mask))[..., :3], target[..., :3])).  Which triangle wins a pixel pair, which
+ * silhouette edge crosses between the two centres and the weight |t - 1/2| depend on rast / pos_clip only, so antialiasing is a
+ * fixed sparse linear operator on the per-pixel colours: out_p = c_p + sum_e w_e (c_src(e) - c_p) over the blends e with
+ * destination p, c_p = color[pix_point[p]] on foreground, background[p] elsewhere.  Its transpose is its whole backward.
+ *
+ * tsamd_shade_plan_count / _fill extract the blends of tsamd_antialias on (rast_dev, pos_clip_dev, prepared_dev of
+ * tsamd_antialias_prepare -- required) as records: _count writes counts_out_dev[2 pixel + axis] = blends of the pixel's pair with
+ * its right (axis 0) / upper (axis 1) neighbour; the caller scans the counts exclusively into offsets_dev and _fill stores
+ * (destination pixel, source pixel, weight = f32(|t - 1/2|)) of every pair from its offset on, pixel indices batch-wide: the
+ * order of the records is the order of the pair slots.  batch * height * width must stay below 2^30 and n_blends below 2^31.
+ *
+ * tsamd_blend_plan names the device arrays the hot calls read (all i32 unless noted):
+ *   pix_point [pixels]    index of the pixel's row in color_dev, -1 on background      pix_dst [pixels]   destination slot or -1
+ *   dst_ptr [n_dst + 1]   record range of a destination slot in the arrays grouped by destination:
+ *                         dst_src_pix (source pixel), dst_src_point (pix_point of the source pixel), dst_weight (f32)
+ *   src_ptr [n_src + 1]   record range of a source slot in the arrays grouped by source:
+ *                         src_dst_pix (destination pixel), src_dst_slot (its destination slot), src_weight (f32)
+ *   point_pix / point_dst / point_src [n_points]   pixel, destination slot or -1, source slot or -1 of a point
+ * Every index is checked against its array before use (an index out of range reads as background / contributes nothing).
+ *
+ * tsamd_shade: out_dev [batch, height, width, 3] f32 from color_dev [n_points, 3] and background_dev [batch, height, width, 3],
+ * float32, out = ((c_p + w_0 (c_src0 - c_p)) + w_1 (c_src1 - c_p)) + ... in the order of the destination's records, every
+ * difference, product and sum rounded on its own.  tsamd_shade_backward: grad_color_dev [n_points, 3] from the gradient image,
+ * grad_color[k] = (g_p (1 - ((w_0 + w_1) + ...)) + w'_0 g_dst0) + w'_1 g_dst1 ..., w over the records with destination p, w' over
+ * those with source p; no atomics.
+ * tsamd_shade_l1: loss_out_dev[0] = mean |out[..., c] - target[..., c]|, c < 3 (0 without pixels), target_dev [batch, height, width,
+ * target_channels] with target_channels 3 or 4; float32 difference, float64 absolute values and sums in a fixed order: bitwise
+ * repeatable.  image_out_dev (optional) receives out; point_sign_out_dev [n_points, 3] and dst_sign_out_dev [n_dst, 3] (optional,
+ * both or neither) receive sign(out - target) in {-1, 0, 1} per point and per destination slot for tsamd_shade_l1_backward, which
+ * forms g = sign * (grad_loss_dev[0] / (3 pixels)) and applies the formula of tsamd_shade_backward.  workspace_dev:
+ * tsamd_shade_l1_workspace_bytes(pixels).  Nothing synchronises with the host. */
+typedef struct tsamd_blend_plan {
+    int32_t struct_size; /* sizeof(tsamd_blend_plan) */
+    int32_t height, width;
+    int32_t reserved;
+    int64_t batch, n_points, n_blends, n_dst, n_src;
+    const int32_t *pix_point_dev, *pix_dst_dev;
+    const int32_t *dst_ptr_dev, *dst_src_pix_dev, *dst_src_point_dev;
+    const float *dst_weight_dev;
+    const int32_t *src_ptr_dev, *src_dst_pix_dev, *src_dst_slot_dev;
+    const float *src_weight_dev;
+    const int32_t *point_pix_dev, *point_dst_dev, *point_src_dev;
+} tsamd_blend_plan;
+
+int tsamd_shade_plan_count(const float *rast_dev, const float *pos_clip_dev, const void *prepared_dev, const int32_t *tri_dev,
+                           const int32_t *edge_partner_dev, int64_t batch, int64_t n_vertices, int64_t n_triangles, int32_t height, int32_t width,
+                           int32_t *counts_out_dev, void *stream);
+int tsamd_shade_plan_fill(const float *rast_dev, const float *pos_clip_dev, const void *prepared_dev, const int32_t *tri_dev,
+                          const int32_t *edge_partner_dev, int64_t batch, int64_t n_vertices, int64_t n_triangles, int32_t height, int32_t width,
+                          const int32_t *offsets_dev, int64_t n_blends, int32_t *dst_out_dev, int32_t *src_out_dev, float *weight_out_dev, void *stream);
+int tsamd_shade(const tsamd_blend_plan *plan, const float *color_dev, const float *background_dev, float *out_dev, void *stream);
+int tsamd_shade_backward(const tsamd_blend_plan *plan, const float *grad_out_dev, float *grad_color_dev, void *stream);
+int64_t tsamd_shade_l1_workspace_bytes(int64_t pixels);
+int tsamd_shade_l1(const tsamd_blend_plan *plan, const float *color_dev, const float *background_dev, const float *target_dev, int32_t target_channels,
+                   void *workspace_dev, float *loss_out_dev, float *image_out_dev, float *point_sign_out_dev, float *dst_sign_out_dev, void *stream);
+int tsamd_shade_l1_backward(const tsamd_blend_plan *plan, const float *point_sign_dev, const float *dst_sign_dev, const float *grad_loss_dev,
+                            float *grad_color_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Hash-grid encoding (the texture stage's colour field): tiny-cuda-nn's `Grid` encoding, 3-D input, trilinear,
  *   tsamd_grid_encode          <- tcnn.Encoding(3, {"otype": "HashGrid" | "DenseGrid" | "Grid", ...})(x)   models/networks.py:97-106

@@ -5,11 +5,16 @@ here from a known colour field on tests/golden/mario_mesh.npz under scenes.datas
 empty).
 
     python tools/train_texture.py [--views 16 --res 256 --iters 300 --lr 0.01 --mlp VanillaMLP|FullyFusedMLP
-                                    --param-grad atomic|sorted --plan-points --export DIR]
+                                    --param-grad atomic|sorted --plan-points --shade operators|fused|fused-loss --export DIR]
 
 --plan-points: the views are fixed and the geometry frozen, so the renderer plans them once before the loop
 (MeshRasterizer.plan_views) and every iteration runs with view_plan=: no rasterise / interpolate / compaction, and the hash
 grid's dL/dparams by the planned route (no sort, no float atomics).
+
+--shade: the image side of an iteration.  `operators` (default): the reference's chain -- antialias of alpha, zero image, masked
+scatter, lerp, antialias, slices, L1Loss.  `fused` (MeshRasterizer(fused_shade=True): dr.shade on the view plan's blend plan, then
+L1Loss) or `fused-loss` (MeshRasterizer.shade_loss: dr.shade_l1; the only image it writes is the `shaded` it returns); both need --plan-points.  The JSON line
+names the mode and, for the fused ones, the blend plan's size ("n_blends", "blend_plan_build_ms", "blend_plan_bytes").
 
 --export DIR: after the fit, renderer.export(DIR, "material") (trainer.py's last step) writes DIR/material/exported_surface.obj,
 .mtl and .png; the JSON line gains "export": the bake and the whole export in ms at texture_res = 1024.
@@ -48,7 +53,9 @@ def timed(fn, reps=5):
     return a.elapsed_time(b) / reps
 
 
-def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_grad="atomic", plan_points=False, export_dir=None):
+def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_grad="atomic", plan_points=False, export_dir=None, shade="operators"):
+    if shade != "operators" and not plan_points:
+        raise SystemExit("--shade fused / fused-loss needs --plan-points (the blend plan belongs to a view plan)")
     from tssplat_amd import geometry, materials, renderers, scenes
     from tssplat_amd.utils.optimizer import AdamUniform
     torch.cuda.set_device(0)
@@ -68,7 +75,7 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_gra
     if param_grad != "atomic":                         # the encoding's route to dL/dparams, as a key of its config
         cfg["pos_encoding_config"] = dict(materials.ExplicitMaterial.Config(**cfg).pos_encoding_config, param_grad=param_grad)
     mat = materials.ExplicitMaterial(cfg)
-    ren = renderers.MeshRasterizer(geo, mat)
+    ren = renderers.MeshRasterizer(geo, mat, fused_shade=shade == "fused")
     opt = AdamUniform(ren.parameters(), lr=lr)
     loss_fn = torch.nn.L1Loss()
 
@@ -81,10 +88,21 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_gra
         b.record()
         torch.cuda.synchronize()
         plan_build_ms = a.elapsed_time(b)
+    blend_info = {}
+    if shade != "operators":
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        blend_plan = view_plan.blend_plan
+        b.record()
+        torch.cuda.synchronize()
+        blend_info = {"n_blends": blend_plan.n_blends, "blend_plan_build_ms": round(a.elapsed_time(b), 3), "blend_plan_bytes": blend_plan.nbytes}
 
     def step(it):
-        out = ren(mvp, only_alpha=False, iter_num=it, resolution=res, background=bg, view_plan=view_plan)
-        loss = loss_fn(out["shaded"][..., :3], target[..., :3]) * 20           # trainer.py:102-104
+        if shade == "fused-loss":
+            loss = ren.shade_loss(view_plan, bg, target, it)["img_loss"] * 20
+        else:
+            out = ren(mvp, only_alpha=False, iter_num=it, resolution=res, background=bg, view_plan=view_plan)
+            loss = loss_fn(out["shaded"][..., :3], target[..., :3]) * 20           # trainer.py:102-104
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -136,7 +154,7 @@ def run(views=16, res=256, iters=300, lr=0.01, mlp_otype="VanillaMLP", param_gra
                              "bake_material_ms": round(bake_ms, 3), "export_ms": round((time.perf_counter() - t0) * 1e3, 1)}}
     split_plan = {} if not plan_points else {"plan_build_ms": round(plan_build_ms, 3), "plan_bytes": view_plan.point_plan.nbytes}
     return {"views": views, "res": res, "iters": iters, "lr": lr, "mlp": mlp_otype, "param_grad": "planned" if plan_points else param_grad,
-            "foreground_points": int(pts.shape[0]),
+            "shade": shade, **blend_info, "foreground_points": int(pts.shape[0]),
             "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)], "loss_ratio": round(losses[-1] / losses[0], 4),
             "ms_per_iter": round(ms_iter, 3),
             "split_ms": {"encode_fwd_bwd": round(ms_enc, 3), "mlp_fwd_bwd": round(ms_mlp, 3),
@@ -154,10 +172,12 @@ def main():
                     help="the hash grid's route to dL/dparams (sorted: bitwise repeatable)")
     ap.add_argument("--plan-points", action="store_true",
                     help="plan the fixed views once (MeshRasterizer.plan_views) and train with view_plan=")
+    ap.add_argument("--shade", choices=("operators", "fused", "fused-loss"), default="operators",
+                    help="the image side of an iteration (fused / fused-loss: dr.shade / dr.shade_l1 on the view plan's blend plan; need --plan-points)")
     ap.add_argument("--export", metavar="DIR", default=None,
                     help="after the fit, write DIR/material/exported_surface.{obj,mtl,png} (MeshRasterizer.export)")
     a = ap.parse_args()
-    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp, a.param_grad, a.plan_points, a.export)))
+    print(json.dumps(run(a.views, a.res, a.iters, a.lr, a.mlp, a.param_grad, a.plan_points, a.export, a.shade)))
 
 
 if __name__ == "__main__":

@@ -22,8 +22,8 @@ ARCH = "gfx950"
 
 SOURCES = ["plan.cpp", "plan_mesh.cpp", "plan_tiling.cpp", "plan_layout.cpp", "plan_planes.cpp", "partition.cpp", "conflict_opt.cpp", "capi.cpp", "kernels.hip", "surface.cpp", "surface_capi.cpp", "surface_kernels.hip",
            "raster_capi.cpp", "raster_kernels.hip", "aa_kernels.hip", "grid_capi.cpp", "grid_kernels.hip",
-           "mlp_capi.cpp", "mlp_kernels.hip", "texture_capi.cpp", "texture_kernels.hip"]
-HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "surface.h", "raster.h", "grid.h", "mlp.h", "texture.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
+           "mlp_capi.cpp", "mlp_kernels.hip", "texture_capi.cpp", "texture_kernels.hip", "shade_capi.cpp", "shade_kernels.hip"]
+HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "surface.h", "raster.h", "grid.h", "mlp.h", "texture.h", "shade.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
 
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-pthread"]
 # -fno-slp-vectorize: SLP packs the 3x3 algebra into v_pk_*_f32, which runs at the scalar-fp32 rate on
@@ -35,9 +35,10 @@ DEVICE_FLAGS = [f"--offload-arch={ARCH}", "-ffp-contract=fast", "-fno-slp-vector
 # The renderer kernels repeat the oracle's float32 / float64 operations one by one (bit-exact triangle ids, identical
 # silhouette decisions): a multiply and an add must round separately.  The __fmul_rn / __dmul_rn family are plain operators
 # in this toolchain's headers, so the only reliable switch is the flag (appended last: it overrides the one above).
-# (texture_kernels.hip: dr.texture's x = u W - 0.5 is a rounded product and a difference, as tests/texture_oracle.py states it)
+# (texture_kernels.hip: dr.texture's x = u W - 0.5 is a rounded product and a difference, as tests/texture_oracle.py states it;
+# shade_kernels.hip: out + w (c_src - c) in the operation order tests/shade_oracle.py derives its rounding bound from)
 SOURCE_FLAGS = {"raster_kernels.hip": ["-ffp-contract=off"], "aa_kernels.hip": ["-ffp-contract=off"],
-                "texture_kernels.hip": ["-ffp-contract=off"]}
+                "texture_kernels.hip": ["-ffp-contract=off"], "shade_kernels.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -70,6 +70,18 @@ class TileView(C.Structure):
     ]
 
 
+class BlendPlanStruct(C.Structure):
+    """``tsamd_blend_plan``: device pointers and sizes of a blend plan (tssplat_amd/dr.py: BlendPlan)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+        ("batch", C.c_int64), ("n_points", C.c_int64), ("n_blends", C.c_int64), ("n_dst", C.c_int64), ("n_src", C.c_int64),
+        ("pix_point_dev", C.c_void_p), ("pix_dst_dev", C.c_void_p),
+        ("dst_ptr_dev", C.c_void_p), ("dst_src_pix_dev", C.c_void_p), ("dst_src_point_dev", C.c_void_p), ("dst_weight_dev", C.c_void_p),
+        ("src_ptr_dev", C.c_void_p), ("src_dst_pix_dev", C.c_void_p), ("src_dst_slot_dev", C.c_void_p), ("src_weight_dev", C.c_void_p),
+        ("point_pix_dev", C.c_void_p), ("point_dst_dev", C.c_void_p), ("point_src_dev", C.c_void_p),
+    ]
+
+
 ABI_VERSION = 3          # include/tssplat_amd.h: TSAMD_ABI_VERSION
 
 # every symbol include/tssplat_amd.h declares: name -> (restype, argtypes)
@@ -144,6 +156,17 @@ SIGNATURES = {
     "tsamd_silhouette_mse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsamd_silhouette_mse_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    # the texture stage's image side under a blend plan
+    "tsamd_shade_plan_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p]),
+    "tsamd_shade_plan_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_shade": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_shade_backward": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_shade_l1_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "tsamd_shade_l1": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_shade_l1_backward": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # surface glue
     "tsamd_extract_surface": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
                                       C.POINTER(C.c_int64)]),

@@ -13,6 +13,7 @@
 //                        with a tolerance).
 //   silhouette kernels   the alpha stage: the same analysis over the coverage masks of the cover pass, no `rast`; and the mean
 //                        squared error of the alpha image against a target, whose backward needs no gradient image
+//   blend plan kernels   the blends of a frozen image as (dst, src, weight) records: count per pair, (scan by the caller), fill
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -494,6 +495,54 @@ __global__ __launch_bounds__(kAaBlock) void antialias_backward_masked_kernel(TSA
     antialias_backward_body<true>(TSAMD_AA_PASS, grad_out, boost, grad_color, grad_pos);
 }
 
+// ---- the blend plan (tsamd_shade_plan_*): the blends of a FROZEN rast / pos_clip as records, for csrc/shade_kernels.hip ----
+// The masked pair walk and pair_blends<true> of antialias_masked_kernel, with an emit that counts (FILL = false: counts[2 pixel +
+// axis] = blends of that pair, at most one per edge of the winning triangle) or stores (FILL = true: the pair's blends from record
+// offsets[2 pixel + axis] on, in edge order).  The caller scans the counts in between, so the order of the records is the order of
+// the pair slots whatever the schedule: no append counter.  Pixel indices are batch-wide.
+template <bool FILL>
+__device__ __forceinline__ void blend_plan_body(const float4 *rast, const float4 *pos, const double2 *windows, const unsigned long long *masks, const uint8_t *flags, const int32_t *tri,
+                                                const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int group, int32_t *counts,
+                                                const int32_t *offsets, int64_t n_blends, int32_t *rec_dst, int32_t *rec_src, float *rec_weight)
+{
+    __shared__ uint16_t stacks[(kAaBlock / 64) * kPairStack];
+    const int64_t hw = int64_t(height) * width, total = batch * hw;
+    for_pairs_masked(masks, (total + 63) / 64, group, stacks + (threadIdx.x >> 6) * kPairStack, [&](int64_t gid, int axis) {
+        if (gid >= total) return;
+        const int64_t b = gid / hw, pix = gid - b * hw;
+        const int j = int(pix / width), i = int(pix - int64_t(j) * width);
+        if (axis == 0 ? i + 1 >= width : j + 1 >= height) return;
+        int n = 0;
+        const int64_t first = FILL ? int64_t(offsets[2 * gid + axis]) : 0;
+        pair_blends<true>(rast + b * hw, pos + b * n_vertices, windows + b * n_vertices, flags + b * n_tri, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
+            if (FILL) {
+                const int64_t k = first + n;
+                if (k >= 0 && k < n_blends) {
+                    rec_dst[k] = int32_t(b * hw + e.dst);
+                    rec_src[k] = int32_t(b * hw + e.src);
+                    rec_weight[k] = e.weight;
+                }
+            }
+            ++n;
+        });
+        if (!FILL) counts[2 * gid + axis] = n;
+    });
+}
+
+#define TSAMD_PLAN_ARGS                                                                                                                                            \
+    const float4 *rast, const float4 *pos, const double2 *windows, const unsigned long long *masks, const uint8_t *flags, const int32_t *tri, const int32_t *opp, \
+        int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int group
+#define TSAMD_PLAN_PASS rast, pos, windows, masks, flags, tri, opp, batch, n_vertices, n_tri, height, width, group
+
+__global__ __launch_bounds__(kAaBlock) void blend_plan_count_kernel(TSAMD_PLAN_ARGS, int32_t *counts)
+{
+    blend_plan_body<false>(TSAMD_PLAN_PASS, counts, nullptr, 0, nullptr, nullptr, nullptr);
+}
+__global__ __launch_bounds__(kAaBlock) void blend_plan_fill_kernel(TSAMD_PLAN_ARGS, const int32_t *offsets, int64_t n_blends, int32_t *rec_dst, int32_t *rec_src, float *rec_weight)
+{
+    blend_plan_body<true>(TSAMD_PLAN_PASS, nullptr, offsets, n_blends, rec_dst, rec_src, rec_weight);
+}
+
 // ---- the alpha stage (tsamd_silhouette*): antialias of the 0 / 1 coverage image without a `rast` image ----
 // A pair of two covered pixels blends w (1 - 1) = 0 and its gradient term is g 0: only pairs with exactly one background pixel
 // matter, the covered pixel's triangle always wins them (z/w is never consulted), and the cover pass (raster_kernels.hip) has
@@ -739,6 +788,32 @@ hipError_t launch_antialias_backward(const float *color, const float *rast, cons
                        reinterpret_cast<const float4 *>(pos_clip), static_cast<const double2 *>(prepared), masks, flags, tri, opp, batch, n_vertices, n_tri, height, width,
                        channels, group, grad_out, boost, grad_color,
                        reinterpret_cast<float4 *>(grad_pos));
+    return hipGetLastError();
+}
+
+hipError_t launch_blend_plan(const float *rast, const float *pos_clip, const void *prepared, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices,
+                             int64_t n_tri, int height, int width, int32_t *counts, const int32_t *offsets, int64_t n_blends, int32_t *rec_dst, int32_t *rec_src,
+                             float *rec_weight, hipStream_t stream)
+{
+    const int64_t pixels = batch * int64_t(height) * width;
+    if (counts && pixels > 0) {
+        const hipError_t e = hipMemsetAsync(counts, 0, size_t(pixels) * 2 * sizeof(int32_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0 || (!counts && n_blends <= 0)) return hipSuccess;
+    const Prepared lay = prepared_layout(batch, n_vertices, n_tri, height, width);
+    const unsigned long long *masks = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(prepared) + lay.masks);
+    const uint8_t *flags = reinterpret_cast<const uint8_t *>(static_cast<const char *>(prepared) + lay.flags);
+    const int group = masked_group((pixels + 63) / 64);
+    const int64_t waves = ((pixels + 63) / 64 + group - 1) / group;
+    const float4 *r4 = reinterpret_cast<const float4 *>(rast), *p4 = reinterpret_cast<const float4 *>(pos_clip);
+    const double2 *windows = static_cast<const double2 *>(prepared);
+    if (counts)
+        hipLaunchKernelGGL(blend_plan_count_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, r4, p4, windows, masks, flags, tri, opp, batch, n_vertices, n_tri,
+                           height, width, group, counts);
+    else
+        hipLaunchKernelGGL(blend_plan_fill_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, r4, p4, windows, masks, flags, tri, opp, batch, n_vertices, n_tri,
+                           height, width, group, offsets, n_blends, rec_dst, rec_src, rec_weight);
     return hipGetLastError();
 }
 

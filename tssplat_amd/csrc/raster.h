@@ -30,6 +30,12 @@ hipError_t launch_antialias(const float *color, const float *rast, const float *
 hipError_t launch_antialias_backward(const float *color, const float *rast, const float *pos_clip, const void *prepared, const int32_t *tri,
                                      const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int channels, const float *grad_out, float boost,
                                      float *grad_color, float *grad_pos, hipStream_t stream);
+// The blend plan (tsamd_shade_plan_*, aa_kernels.hip): the blends tsamd_antialias would apply to `rast`, as records.  counts non-null:
+// counts[2 pixel + axis] = blends of the pair (zero-filled first).  counts null: the records of every pair from offsets[2 pixel + axis]
+// on (the exclusive scan of the counts), pixel indices batch-wide; records at or beyond n_blends are not written.
+hipError_t launch_blend_plan(const float *rast, const float *pos_clip, const void *prepared, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices,
+                             int64_t n_tri, int height, int width, int32_t *counts, const int32_t *offsets, int64_t n_blends, int32_t *rec_dst, int32_t *rec_src,
+                             float *rec_weight, hipStream_t stream);
 // The alpha stage (tsamd_silhouette*).  cover (raster_kernels.hip): the depth keys of launch_rasterize, then per pixel ids (triangle + 1,
 // 0 = background), alpha = 0 / 1 and the coverage masks (pair_masks_bytes; bit = exactly one pixel of the pair is background).
 // blend / backward (aa_kernels.hip): the antialias analysis over those masks; backward takes grad_alpha, or (grad_alpha null) alpha,

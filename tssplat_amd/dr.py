@@ -23,6 +23,11 @@ beyond the +-16384-pixel guard band is dropped; the silhouette of a clipped tria
 ``silhouette`` and ``silhouette_mse`` are this package's own: the alpha stage of the reference's trainer (``only_alpha=True``:
 ``MSE(antialias(clamp(rast[..., -1:], 0, 1)))``) without the ``rast`` image, the clamp, the antialias copy and the dense loss
 gradient -- the same blends as the three operators above give on the 0 / 1 coverage image.
+
+``plan_blends``, ``shade`` and ``shade_l1`` are this package's own too: the colour stage under frozen geometry and fixed views.
+There the blends of ``antialias`` do not depend on what is being trained, so they are extracted once into a :class:`BlendPlan`,
+and ``L1(antialias(lerp(background, scatter(color), mask)))`` becomes a fixed sparse operator on the ``[N, 3]`` point colours:
+no image-sized temporary in either direction (``shade_l1`` writes an image only when asked to return it), no atomics, bitwise repeatable.
 """
 from __future__ import annotations
 
@@ -36,7 +41,7 @@ from . import _capi
 from .tet_spheres_ext import _device_ctx, _stream_ptr
 
 __all__ = ["RasterizeCudaContext", "rasterize", "interpolate", "antialias", "antialias_construct_topology_hash", "texture", "silhouette",
-           "silhouette_mse"]
+           "silhouette_mse", "BlendPlan", "plan_blends", "shade", "shade_l1"]
 
 _lib = _capi.load()
 
@@ -442,6 +447,215 @@ def silhouette_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Te
         raise RuntimeError("tssplat_amd.dr.silhouette_mse: target must be [B, H, W] or [B, H, W, 1] of the image size")
     loss, alpha = _SilhouetteMseFunc.apply(pos, tri, topo.opp, glctx, height, width, target.detach(), float(pos_gradient_boost))
     return (loss, alpha.detach()) if return_alpha else loss
+
+
+# ---- the colour stage under a blend plan ----
+
+class BlendPlan:
+    """The blends ``antialias(., rast, pos, tri)`` applies, for a FROZEN ``rast`` / ``pos`` / ``tri``, as data (:func:`plan_blends`).
+
+    ``pix_point[B * H * W]`` int32: the row of a pixel's colour in ``color[N, 3]`` -- the order of ``positions_all[rast[..., 3] > 0]``
+    -- or -1 on background; ``n_points = N``.  ``rec_dst / rec_src / rec_weight[n_blends]``: the blend records in extraction order
+    (pair slot order: pixel-major, the pair with the right neighbour before the one with the upper neighbour, edges 0, 1, 2), pixel
+    indices batch-wide.  ``dst_perm`` / ``src_perm``: the stable permutations that group the records by destination / by source;
+    ``dst_pix[n_dst]`` and ``dst_ptr[n_dst + 1]`` (``src_pix``, ``src_ptr`` likewise) are the two CSR views, ``pix_dst[B * H * W]``
+    the destination slot of a pixel or -1.  The remaining arrays are those views with the indices the kernels need next to them
+    (include/tssplat_amd.h: tsamd_blend_plan)."""
+
+    _STRUCT_FIELDS = ("pix_point", "pix_dst", "dst_ptr", "dst_src_pix", "dst_src_point", "dst_weight", "src_ptr", "src_dst_pix", "src_dst_slot",
+                      "src_weight", "point_pix", "point_dst", "point_src")
+    _OTHER_FIELDS = ("rec_dst", "rec_src", "rec_weight", "dst_perm", "src_perm", "dst_pix", "src_pix")
+
+    def __init__(self, shape, n_points: int, **tensors):
+        self.batch, self.height, self.width = (int(k) for k in shape)
+        self.n_points = int(n_points)
+        for name in self._STRUCT_FIELDS + self._OTHER_FIELDS:
+            setattr(self, name, tensors[name])
+        self.n_blends, self.n_dst, self.n_src = int(self.rec_dst.shape[0]), int(self.dst_pix.shape[0]), int(self.src_pix.shape[0])
+        self.device = self.pix_point.device
+        st = _capi.BlendPlanStruct()
+        st.struct_size = _capi.C.sizeof(_capi.BlendPlanStruct)
+        st.height, st.width, st.batch = self.height, self.width, self.batch
+        st.n_points, st.n_blends, st.n_dst, st.n_src = self.n_points, self.n_blends, self.n_dst, self.n_src
+        for name in self._STRUCT_FIELDS:
+            t = getattr(self, name)
+            setattr(st, name + "_dev", t.data_ptr() if t.numel() else None)
+        self._struct = st
+
+    def tensors(self) -> dict:
+        return {name: getattr(self, name) for name in self._STRUCT_FIELDS + self._OTHER_FIELDS}
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors().values())
+
+    @property
+    def shape(self):
+        return (self.batch, self.height, self.width)
+
+
+def _csr(keys: torch.Tensor, n_pixels: int):
+    """Stable grouping of the records by ``keys`` (pixel indices): (perm, group pixels, ptr[n + 1] int32, slot per pixel or -1)."""
+    dev = keys.device
+    perm = torch.sort(keys, stable=True).indices
+    pix, counts = torch.unique_consecutive(keys[perm], return_counts=True)
+    ptr = torch.zeros(pix.shape[0] + 1, dtype=torch.int32, device=dev)
+    ptr[1:] = torch.cumsum(counts, 0)
+    slot = torch.full((n_pixels,), -1, dtype=torch.int32, device=dev)
+    slot[pix.long()] = torch.arange(pix.shape[0], dtype=torch.int32, device=dev)
+    return perm, pix, ptr, slot
+
+
+def plan_blends(rast: torch.Tensor, pos: torch.Tensor, tri: torch.Tensor, topology_hash=None) -> BlendPlan:
+    """The :class:`BlendPlan` of ``rast[B, H, W, 4]`` (as ``rasterize`` returned it), ``pos[B, V, 4]`` and ``tri``: the blends are
+    exactly those ``antialias`` analyses on the same inputs (oracle/raster_oracle.py::antialias_events), weights
+    ``float32(|t - 1/2|)``.  Runs once per plan: the records come from a count / scan / fill pass of the antialias analysis, the
+    two groupings from stable sorts; it synchronises with the host (two sizes are read back)."""
+    rast = _check_cuda_f32("rast", rast.detach())
+    pos = _check_cuda_f32("pos", pos.detach())
+    if rast.dim() != 4 or rast.shape[3] != 4:
+        raise RuntimeError("tssplat_amd.dr.plan_blends: rast must be [B, H, W, 4]")
+    if pos.dim() != 3 or pos.shape[2] != 4 or pos.shape[0] != rast.shape[0]:
+        raise RuntimeError("tssplat_amd.dr.plan_blends: pos must be [B, V, 4] clip-space positions (instanced mode)")
+    if pos.device != rast.device:
+        raise RuntimeError("tssplat_amd.dr.plan_blends: rast and pos must live on the same device")
+    tri = _check_tri(tri, rast.device)
+    topo = _topology_for(tri) if topology_hash is None else topology_hash
+    if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != rast.device:
+        raise RuntimeError("tssplat_amd.dr.plan_blends: topology_hash does not belong to this triangle list")
+    B, H, W = (int(k) for k in rast.shape[:3])
+    V, T, P = int(pos.shape[1]), int(tri.shape[0]), B * H * W
+    if P >= 1 << 30:
+        raise RuntimeError("tssplat_amd.dr.plan_blends: batch x height x width must stay below 2^30 pixels")
+    dev = rast.device
+    fg = rast[..., 3].reshape(-1) > 0
+    rank = torch.cumsum(fg, 0, dtype=torch.int32)
+    pix_point = torch.where(fg, rank - 1, torch.full_like(rank, -1))
+    point_pix = torch.nonzero(fg).reshape(-1).to(torch.int32)
+    n_points = int(point_pix.shape[0])
+    counts = torch.empty(2 * P, dtype=torch.int32, device=dev)             # (zero-filled by the count call)
+    prepared = torch.empty((max(int(_lib.tsamd_antialias_prepared_bytes(B, V, T, H, W)), 8),), dtype=torch.uint8, device=dev)
+    args = (rast.data_ptr(), pos.data_ptr(), prepared.data_ptr(), tri.data_ptr(), topo.opp.data_ptr(), B, V, T, H, W)
+    with _device_ctx(dev):
+        stream = _stream_ptr(dev)
+        _capi.check(_lib.tsamd_antialias_prepare(rast.data_ptr(), pos.data_ptr(), tri.data_ptr(), topo.opp.data_ptr(), None, B, V, T, H, W, prepared.data_ptr(),
+                                                 stream))
+        _capi.check(_lib.tsamd_shade_plan_count(*args, counts.data_ptr(), stream))
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)        # (scanned in 64 bits: the total is checked before it is narrowed)
+        n_blends = int(ends[-1]) if P else 0
+        if n_blends >= 1 << 31:
+            raise RuntimeError(f"tssplat_amd.dr.plan_blends: {n_blends} blends; record offsets are 32-bit (at most 2^31 - 1)")
+        offsets = (ends - counts).to(torch.int32)
+        rec_dst = torch.empty(n_blends, dtype=torch.int32, device=dev)
+        rec_src = torch.empty(n_blends, dtype=torch.int32, device=dev)
+        rec_weight = torch.empty(n_blends, dtype=torch.float32, device=dev)
+        _capi.check(_lib.tsamd_shade_plan_fill(*args, offsets.data_ptr(), n_blends, rec_dst.data_ptr(), rec_src.data_ptr(), rec_weight.data_ptr(), stream))
+    dst_perm, dst_pix, dst_ptr, pix_dst = _csr(rec_dst, P)
+    src_perm, src_pix, src_ptr, pix_src = _csr(rec_src, P)
+    dst_src_pix, src_dst_pix = rec_src[dst_perm], rec_dst[src_perm]
+    return BlendPlan((B, H, W), n_points, pix_point=pix_point, pix_dst=pix_dst, dst_ptr=dst_ptr, dst_src_pix=dst_src_pix,
+                     dst_src_point=pix_point[dst_src_pix.long()], dst_weight=rec_weight[dst_perm], src_ptr=src_ptr, src_dst_pix=src_dst_pix,
+                     src_dst_slot=pix_dst[src_dst_pix.long()], src_weight=rec_weight[src_perm], point_pix=point_pix,
+                     point_dst=pix_dst[point_pix.long()], point_src=pix_src[point_pix.long()], rec_dst=rec_dst, rec_src=rec_src, rec_weight=rec_weight,
+                     dst_perm=dst_perm, src_perm=src_perm, dst_pix=dst_pix, src_pix=src_pix)
+
+
+def _shade_args(name: str, color, plan, background, target=None):
+    if not isinstance(plan, BlendPlan):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: blend_plan must be a BlendPlan (dr.plan_blends)")
+    color = _check_cuda_f32("color", color)
+    background = _check_cuda_f32("background", background)
+    if color.dim() != 2 or color.shape[1] != 3 or int(color.shape[0]) != plan.n_points:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: color must be [n_points, 3] with n_points = {plan.n_points} (the plan's foreground pixels), "
+                           f"not {list(color.shape)}")
+    if tuple(background.shape) != plan.shape + (3,):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: background must be [B, H, W, 3] = {list(plan.shape + (3,))} (the plan's batch and resolution), "
+                           f"not {list(background.shape)}")
+    if color.device != plan.device or background.device != plan.device:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: color, background and the plan must live on the same device")
+    if target is None:
+        return color, background
+    if not isinstance(target, torch.Tensor) or not target.is_cuda or target.dtype != torch.float32 or target.device != plan.device:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: target must be a float32 GPU tensor on the plan's device")
+    if tuple(target.shape[:3]) != plan.shape or target.dim() != 4 or target.shape[3] not in (3, 4):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: target must be [B, H, W, 3 or 4] of the plan's batch and resolution {list(plan.shape)}, "
+                           f"not {list(target.shape)}")
+    if not target.is_contiguous():
+        raise RuntimeError(f"tssplat_amd.dr.{name}: target must be contiguous (a four-channel target is read with its channel stride: pass it whole, "
+                           "not a slice)")
+    return color, background, target.detach()
+
+
+class _ShadeFunc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, plan, background):
+        out = torch.empty(plan.shape + (3,), dtype=torch.float32, device=color.device)
+        with _device_ctx(color.device):
+            _capi.check(_lib.tsamd_shade(plan._struct, color.data_ptr(), background.data_ptr(), out.data_ptr(), _stream_ptr(color.device)))
+        ctx.plan = plan
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        plan = ctx.plan
+        g = grad_out.contiguous()
+        grad_color = torch.empty((plan.n_points, 3), dtype=torch.float32, device=g.device)
+        with _device_ctx(g.device):
+            _capi.check(_lib.tsamd_shade_backward(plan._struct, g.data_ptr(), grad_color.data_ptr(), _stream_ptr(g.device)))
+        return grad_color, None, None
+
+
+def shade(color: torch.Tensor, blend_plan: BlendPlan, background: torch.Tensor) -> torch.Tensor:
+    """``[B, H, W, 3]``: ``antialias(lerp(background, scatter(color), mask), rast, pos, tri)`` of the plan's ``rast`` / ``pos`` /
+    ``tri`` -- ``color[N, 3]`` in the order of ``positions_all[rast[..., 3] > 0]``, ``background[B, H, W, 3]`` -- in one pass, one
+    lane per pixel: ``out = c_p + sum w (c_src - c_p)`` over the pixel's blends in the plan's order.  Differentiable w.r.t.
+    ``color`` only (the plan is frozen: there is no gradient w.r.t. positions); the backward writes ``[N, 3]`` without atomics."""
+    color, background = _shade_args("shade", color, blend_plan, background)
+    return _ShadeFunc.apply(color, blend_plan, background.detach())
+
+
+class _ShadeL1Func(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, plan, background, target, want_image):
+        dev = color.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        image = torch.empty(plan.shape + (3,) if want_image else (0,), dtype=torch.float32, device=dev)
+        need_grad = ctx.needs_input_grad[0]
+        point_sign = torch.empty((plan.n_points, 3), dtype=torch.float32, device=dev) if need_grad else None
+        dst_sign = torch.empty((plan.n_dst, 3), dtype=torch.float32, device=dev) if need_grad else None
+        ws = torch.empty((int(_lib.tsamd_shade_l1_workspace_bytes(plan.batch * plan.height * plan.width)),), dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        with _device_ctx(dev):
+            _capi.check(_lib.tsamd_shade_l1(plan._struct, color.data_ptr(), background.data_ptr(), target.data_ptr(), int(target.shape[3]), ws.data_ptr(),
+                                            loss.data_ptr(), ptr(image), ptr(point_sign), ptr(dst_sign), _stream_ptr(dev)))
+        ctx.plan = plan
+        if need_grad:
+            ctx.save_for_backward(point_sign, dst_sign)
+        ctx.mark_non_differentiable(image)
+        return loss, image
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_image):
+        plan = ctx.plan
+        point_sign, dst_sign = ctx.saved_tensors
+        g = grad_loss.to(torch.float32).contiguous()            # stays on the device: the kernel reads it there
+        grad_color = torch.empty((plan.n_points, 3), dtype=torch.float32, device=g.device)
+        with _device_ctx(g.device):
+            _capi.check(_lib.tsamd_shade_l1_backward(plan._struct, point_sign.data_ptr() if point_sign.numel() else None,
+                                                     dst_sign.data_ptr() if dst_sign.numel() else None, g.data_ptr(), grad_color.data_ptr(),
+                                                     _stream_ptr(g.device)))
+        return grad_color, None, None, None, None
+
+
+def shade_l1(color: torch.Tensor, blend_plan: BlendPlan, background: torch.Tensor, target: torch.Tensor, return_image: bool = False):
+    """``torch.nn.L1Loss()(shade(color, blend_plan, background)[..., :3], target[..., :3])`` as a 0-dim float32 tensor, bitwise
+    repeatable, without the image: ``target`` is ``[B, H, W, 3]`` or ``[B, H, W, 4]`` (contiguous; of four channels the first three
+    are read in place) and carries no gradient.  Differentiable w.r.t. ``color``: the forward keeps ``sign(out - target)`` per point
+    and per blended pixel (``sign(0) = 0``), the backward scales them by the device-side ``grad_loss / n`` -- no gradient image.
+    ``return_image=True``: ``(loss, image)`` with the detached image the loss was taken of."""
+    color, background, target = _shade_args("shade_l1", color, blend_plan, background, target)
+    loss, image = _ShadeL1Func.apply(color, blend_plan, background.detach(), target, bool(return_image))
+    return (loss, image.detach()) if return_image else loss
 
 
 _TEX_FILTERS = {"nearest": 0, "linear": 1}                  # TSAMD_TEX_FILTER_* of include/tssplat_amd.h

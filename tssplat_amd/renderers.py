@@ -27,9 +27,21 @@ class ViewPlan:
     ``pos_clip``, ``rast_out``, the foreground ``selector`` and the material's point plan for the foreground points, in the
     selector's order.  Built by :meth:`MeshRasterizer.plan_views`."""
 
-    def __init__(self, mvp, resolution: int, pos_clip, rast_out, selector, point_plan):
+    def __init__(self, mvp, resolution: int, pos_clip, rast_out, selector, point_plan, tri=None):
         self.mvp, self.resolution = mvp, int(resolution)
         self.pos_clip, self.rast_out, self.selector, self.point_plan = pos_clip, rast_out, selector, point_plan
+        self.tri = tri
+        self._blend_plan = None
+
+    @property
+    def blend_plan(self) -> "dr.BlendPlan":
+        """The blends of ``dr.antialias`` on this plan's ``rast_out`` / ``pos_clip`` (``dr.plan_blends``), built on first use: what
+        ``MeshRasterizer(fused_shade=True)`` and ``MeshRasterizer.shade_loss`` run on."""
+        if self._blend_plan is None:
+            if self.tri is None:
+                raise RuntimeError("ViewPlan.blend_plan: the plan carries no triangle list (build it with MeshRasterizer.plan_views)")
+            self._blend_plan = dr.plan_blends(self.rast_out, self.pos_clip, self.tri)
+        return self._blend_plan
 
     @property
     def n_points(self) -> int:
@@ -38,8 +50,11 @@ class ViewPlan:
 
 class MeshRasterizer(torch.nn.Module):
     def __init__(self, geometry: torch.nn.Module, materials: Optional[torch.nn.Module] = None, context_type: str = "cuda", is_orhto: bool = False,
-                 fused_silhouette: bool = False):
+                 fused_silhouette: bool = False, fused_shade: bool = False):
         super().__init__()
+        # opt-in: forward(only_alpha=False, view_plan=plan) takes the image from dr.shade on the plan's blend plan (no alpha
+        # antialias, no zero image, no masked scatter, no lerp, no per-call pair analysis); without a view plan it changes nothing
+        self.fused_shade = bool(fused_shade)
         # opt-in: forward(only_alpha=True) without fit_normal / fit_depth takes alpha from dr.silhouette (no rast image)
         self.fused_silhouette = bool(fused_silhouette)
         if context_type not in ("cuda", "gl"):                       # mesh_rasterizer.py:33-38
@@ -87,7 +102,7 @@ class MeshRasterizer(torch.nn.Module):
             selector = rast_out[..., -1] > 0
             positions_all, _ = dr.interpolate(data.v_pos[None, ...], rast_out, tri)
             point_plan = self.materials.plan_points(positions_all[selector])
-        return ViewPlan(mvp, resolution, pos_clip, rast_out, selector, point_plan)
+        return ViewPlan(mvp, resolution, pos_clip, rast_out, selector, point_plan, tri=tri)
 
     def _geometry_forward(self, iter_num: int, permute_surface_scheduler=None):
         """The geometry forward of one iteration, with the surface permutation the scheduler asks for (mesh_rasterizer.py:90-94)."""
@@ -158,10 +173,20 @@ class MeshRasterizer(torch.nn.Module):
                                          pos_gradient_boost=1.0, return_alpha=True)
         return {"img_loss": loss, "geo_regularization": data.smooth_barrier_energy, "shaded": shaded}
 
-    def _forward_planned(self, plan: ViewPlan, only_alpha, iter_num, resolution, permute_surface_scheduler, fit_normal, fit_depth,
-                         background, campos):
-        """``forward`` with a :class:`ViewPlan`: the geometry forward still runs (``geo_regularization``), alpha and both
-        ``antialias`` calls are as without a plan, the colour comes from the material's point plan."""
+    def shade_loss(self, view_plan: ViewPlan, background: torch.Tensor, target: torch.Tensor, iter_num: int, permute_surface_scheduler=None):
+        """The colour stage's render and image loss in one, under a view plan: ``{"img_loss", "geo_regularization", "shaded"}`` with
+        ``img_loss`` the plain ``L1Loss`` of ``forward(..., view_plan=view_plan)["shaded"][..., :3]`` against ``target[..., :3]``
+        (``[B, H, W, 3]`` or ``[B, H, W, 4]``; the caller applies the trainer's weights) through ``dr.shade_l1`` -- no image-sized
+        temporary besides ``shaded`` itself, which is detached."""
+        self._check_planned(view_plan, False, iter_num, view_plan.resolution, permute_surface_scheduler)
+        assert self.materials is not None
+        data = self.geometry(iter_num=iter_num)
+        color = self.materials(positions=view_plan.point_plan)["color"].float()
+        loss, shaded = dr.shade_l1(color, view_plan.blend_plan, background, target, return_image=True)
+        return {"img_loss": loss, "geo_regularization": data.smooth_barrier_energy, "shaded": shaded}
+
+    @staticmethod
+    def _check_planned(plan: ViewPlan, only_alpha, iter_num, resolution, permute_surface_scheduler):
         if only_alpha:
             raise RuntimeError("MeshRasterizer.forward: view_plan with only_alpha=True (a view plan is the colour branch's)")
         if permute_surface_scheduler is not None and permute_surface_scheduler(iter_num) is not None:
@@ -169,19 +194,29 @@ class MeshRasterizer(torch.nn.Module):
                                f"iteration {iter_num}: the surface would move under the plan")
         if int(resolution) != plan.resolution:
             raise RuntimeError(f"MeshRasterizer.forward: view_plan was built at resolution {plan.resolution}, not {resolution}")
+
+    def _forward_planned(self, plan: ViewPlan, only_alpha, iter_num, resolution, permute_surface_scheduler, fit_normal, fit_depth,
+                         background, campos):
+        """``forward`` with a :class:`ViewPlan`: the geometry forward still runs (``geo_regularization``), alpha and both
+        ``antialias`` calls are as without a plan, the colour comes from the material's point plan.  ``fused_shade``: the image
+        comes from ``dr.shade`` on the plan's blend plan instead."""
+        self._check_planned(plan, only_alpha, iter_num, resolution, permute_surface_scheduler)
         assert self.materials is not None
         assert background is not None
         data = self.geometry(iter_num=iter_num)
         tri = data.t_pos_idx
         pos_clip, rast_out = plan.pos_clip, plan.rast_out
-        alpha = torch.clamp(rast_out[..., -1:], 0, 1)
-        alpha = dr.antialias(alpha.contiguous(), rast_out, pos_clip, tri, topology_hash=self.tri_hash, pos_gradient_boost=1.0)
+        if self.fused_shade:
+            shaded = dr.shade(self.materials(positions=plan.point_plan)["color"].float(), plan.blend_plan, background)
+        else:
+            alpha = torch.clamp(rast_out[..., -1:], 0, 1)
+            alpha = dr.antialias(alpha.contiguous(), rast_out, pos_clip, tri, topology_hash=self.tri_hash, pos_gradient_boost=1.0)
 
-        color = self.materials(positions=plan.point_plan)["color"]
-        gb_fg = torch.zeros(rast_out.shape[0], plan.resolution, plan.resolution, 3, device=self.device)
-        gb_fg[plan.selector] = color
-        gb_mat = torch.lerp(background, gb_fg, plan.selector[..., None].float())
-        shaded = dr.antialias(gb_mat.contiguous(), rast_out, pos_clip, tri, topology_hash=self.tri_hash, pos_gradient_boost=1.0)
+            color = self.materials(positions=plan.point_plan)["color"]
+            gb_fg = torch.zeros(rast_out.shape[0], plan.resolution, plan.resolution, 3, device=self.device)
+            gb_fg[plan.selector] = color
+            gb_mat = torch.lerp(background, gb_fg, plan.selector[..., None].float())
+            shaded = dr.antialias(gb_mat.contiguous(), rast_out, pos_clip, tri, topology_hash=self.tri_hash, pos_gradient_boost=1.0)
         out = {"shaded": shaded, "geo_regularization": data.smooth_barrier_energy}
 
         if fit_normal:
