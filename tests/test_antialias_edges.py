@@ -17,7 +17,7 @@ EPS = 2.0 ** -24     # unit round-off of float32
 
 
 def masked_group(n_chunks):
-    """Chunks per wave of the prepared kernels (``masked_group`` in aa_kernels.hip, restated: a property of the launch, not of
+    """Chunks per wave of the prepared kernels (``masked_launch`` in aa_kernels.hip, restated: a property of the launch, not of
     the result).  Group 64 needs 2^20 chunks -- 67 M pixels -- and stays uncovered by this file."""
     g = 1
     while g < 64 and n_chunks // (2 * g) >= 16384:
@@ -322,11 +322,11 @@ def check_antialias(monkeypatch, pos_np, tri_np, res, channels, condition, min_c
             assert np.all(np.abs(out - first[0]) <= tol_out) and np.all(np.abs(gcol - first[1]) <= tol_gc) and np.all(np.abs(gpos - first[2]) <= tol_gp), route
 
 
-def _ragged(res):
+def _ragged(res, views=None):
     H, W = res
     if (H, W) == (33, 50):
-        return S.merge(S.checker(H, W, 27, 3, 6, 47, views=3), S.open_sheet(H, W, views=3, box=(2, -1, 48, 25)))
-    return S.merge(S.checker(H, W, 0, 0, 3, 191, views=2), S.open_sheet(H, W, nu=30, nv=5, views=2, box=(1, 3.5, 191, 7.5)))
+        return S.merge(S.checker(H, W, 27, 3, 6, 47, views=views or 3), S.open_sheet(H, W, views=views or 3, box=(2, -1, 48, 25)))
+    return S.merge(S.checker(H, W, 0, 0, 3, 191, views=views or 2), S.open_sheet(H, W, nu=30, nv=5, views=views or 2, box=(1, 3.5, 191, 7.5)))
 
 
 @pytest.mark.gpu
@@ -472,3 +472,63 @@ def test_antialias_default_choice_of_form(prepared, monkeypatch):
     assert dr.PREPARE_ANTIALIAS is None
     check_antialias(monkeypatch, pos, tri, (H, W), 3, lambda rast, events, opp: None, 200, dense=False,
                     routes=("default:resolve-masks" if prepared else "default:per-pair",))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("res", [(7, 192), (33, 50)])
+def test_antialias_skips_mask_bits_outside_the_image(res):
+    """``pair_masks_dev`` is the caller's memory: through tsamd_antialias_prepare -> tsamd_antialias -> tsamd_antialias_backward, a
+    bit for a pair that does not exist -- axis 0 in the last column, axis 1 in the last row (its second pixel lies past the end of
+    the one view), any bit of a pixel past the end of the image -- is skipped by the pair driver, so the results are those of the
+    rasteriser's own masks within the route-to-route tolerances of tests/test_raster.py::test_antialias_forward_backward.
+    One view of 7 x 192 is 21 full chunks: its masks hold no pixel past the end, the last row's pairs are the ones that reach
+    there.  One view of 33 x 50 ends inside a chunk, whose bits 50 .. 63 are set too."""
+    import torch
+    import tssplat_amd.dr as dr
+    from tssplat_amd import _capi
+    lib = _capi.load()
+    H, W = res
+    pos_np, tri_np = _ragged(res, views=1)
+    pos, tri = torch.from_numpy(pos_np).cuda(), torch.from_numpy(tri_np).cuda()
+    V, T, Cn = int(pos.shape[1]), int(tri.shape[0]), 3
+    opp = dr.antialias_construct_topology_hash(tri).opp
+    ws = torch.empty(int(lib.tsamd_rasterize_workspace_bytes(1, V, H, W)), dtype=torch.uint8, device="cuda")
+    rast = torch.empty((1, H, W, 4), dtype=torch.float32, device="cuda")
+    masks = torch.zeros(int(lib.tsamd_pair_masks_bytes(1, H, W)), dtype=torch.uint8, device="cuda")
+    _capi.check(lib.tsamd_rasterize(pos.data_ptr(), 1, V, tri.data_ptr(), T, H, W, ws.data_ptr(), rast.data_ptr(), masks.data_ptr(), None))
+    clean = masks.cpu().numpy().view(np.uint64).reshape(-1, 2).copy()
+    assert len(clean) == (H * W + 63) // 64 and ((H * W) % 64 == 0) == (res == (7, 192))
+
+    pix = np.arange(H * W)
+    past = np.arange(H * W, 64 * len(clean))
+    outside = (np.concatenate([pix[pix % W == W - 1], past]), np.concatenate([pix[pix // W == H - 1], past]))
+    bad = clean.copy()
+    for axis, idx in enumerate(outside):
+        bit = np.uint64(1) << (idx & 63).astype(np.uint64)
+        assert not (clean[idx >> 6, axis] & bit).any()                        # the rasteriser never names such a pair
+        np.bitwise_or.at(bad[:, axis], idx >> 6, bit)
+    assert len(outside[0]) >= H and len(outside[1]) >= W and (len(past) > 0) == (res == (33, 50))
+    assert int(np.sum(clean != 0)) > 10                                       # and the image has pairs of its own
+
+    rng = np.random.default_rng(7)
+    col = torch.from_numpy(rng.random((1, H, W, Cn), dtype=np.float32)).cuda()
+    g = torch.from_numpy(rng.standard_normal((1, H, W, Cn), dtype=np.float32)).cuda()
+    prepared = torch.empty(int(lib.tsamd_antialias_prepared_bytes(1, V, T, H, W)), dtype=torch.uint8, device="cuda")
+
+    def run(mask_words):
+        m = torch.from_numpy(mask_words.view(np.uint8).reshape(-1).copy()).cuda()
+        out, gc, gp = torch.empty_like(col), torch.empty_like(col), torch.empty_like(pos)
+        _capi.check(lib.tsamd_antialias_prepare(None, pos.data_ptr(), tri.data_ptr(), opp.data_ptr(), m.data_ptr(), 1, V, T, H, W, prepared.data_ptr(), None))
+        _capi.check(lib.tsamd_antialias(col.data_ptr(), rast.data_ptr(), pos.data_ptr(), prepared.data_ptr(), tri.data_ptr(), opp.data_ptr(), 1, V, T, H, W, Cn,
+                                        out.data_ptr(), None))
+        _capi.check(lib.tsamd_antialias_backward(col.data_ptr(), rast.data_ptr(), pos.data_ptr(), prepared.data_ptr(), tri.data_ptr(), opp.data_ptr(), 1, V, T, H, W,
+                                                 Cn, g.data_ptr(), 2.0, gc.data_ptr(), gp.data_ptr(), None))
+        torch.cuda.synchronize()
+        return out.cpu().numpy(), gc.cpu().numpy(), gp.cpu().numpy()
+
+    out0, gc0, gp0 = run(clean)
+    out1, gc1, gp1 = run(bad)
+    assert int((out0 != col.cpu().numpy()).any(axis=-1).sum()) > 100 and np.abs(gp0).max() > 0      # the clean run blends
+    assert np.abs(out1 - out0).max() <= 1e-6
+    assert np.abs(gc1 - gc0).max() <= 1e-5 * max(1.0, np.abs(gc0).max())
+    assert np.abs(gp1 - gp0).max() <= 2e-5 * np.abs(gp0).max()

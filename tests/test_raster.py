@@ -297,6 +297,36 @@ def test_c_abi_checks_antialias_arguments():
     assert b"null" in lib.tsamd_last_error()
 
 
+def test_c_abi_names_every_null_pointer():
+    """rasterize, interpolate, rasterize_backward and the antialias calls report the FIRST null pointer they need by its name in
+    include/tssplat_amd.h, as the newer entry points do (sizes non-zero; the optional pointers -- pair_masks_out_dev, prepared_dev of
+    the two antialias calls, grad_rast_dev of interpolate_backward, one of grad_color_dev / grad_pos_dev -- may stay null)."""
+    lib = _capi.load()
+    p = C.c_void_p(256)                                            # non-null, never dereferenced: every call below fails first
+    calls = {
+        "tsamd_rasterize": (("pos_clip_dev", 1, 3, "tri_dev", 1, 4, 4, "workspace_dev", "rast_out_dev", None, None), {}),
+        "tsamd_interpolate": (("attr_dev", 1, 3, 3, "rast_dev", "tri_dev", 1, 1, 4, 4, "out_dev", None), {}),
+        "tsamd_interpolate_backward": (("attr_dev", 1, 3, 3, "rast_dev", "tri_dev", 1, 1, 4, 4, "grad_out_dev", "grad_attr_dev", None, None), {}),
+        "tsamd_rasterize_backward": (("pos_clip_dev", 1, 3, "tri_dev", 1, 4, 4, "rast_dev", "grad_rast_dev", "grad_pos_dev", None), {}),
+        "tsamd_antialias_topology": (("tri_dev", 5, "workspace_dev", "edge_partner_dev", None), {}),
+        "tsamd_antialias_prepare": (("rast_dev", "pos_clip_dev", "tri_dev", "edge_partner_dev", None, 1, 3, 1, 4, 4, "prepared_dev", None), {}),
+        "tsamd_antialias": (("color_dev", "rast_dev", "pos_clip_dev", None, "tri_dev", "edge_partner_dev", 1, 3, 1, 4, 4, 1, "out_dev", None), {}),
+        "tsamd_antialias_backward": (("color_dev", "rast_dev", "pos_clip_dev", None, "tri_dev", "edge_partner_dev", 1, 3, 1, 4, 4, 1, "grad_out_dev", 1.0,
+                                      None, "grad_pos_dev", None), {"grad_pos_dev": "grad_color_dev and grad_pos_dev are both null"}),
+    }
+    for fn, (args, other) in calls.items():
+        names = [a for a in args if isinstance(a, str)]
+        assert len(names) >= 3, fn
+        for missing in names:
+            rc = getattr(lib, fn)(*[(None if a == missing else p) if isinstance(a, str) else a for a in args])
+            assert rc == 1, (fn, missing)
+            assert lib.tsamd_last_error().decode().endswith(other.get(missing, missing + " is null")), (fn, missing, lib.tsamd_last_error())
+    # with the rasteriser's pair masks, prepare does not need rast_dev: the next pointer is the one reported
+    prepare = calls["tsamd_antialias_prepare"][0]
+    rc = lib.tsamd_antialias_prepare(*[(None if a in ("rast_dev", "tri_dev") else p) if isinstance(a, str) else (p if k == 4 else a) for k, a in enumerate(prepare)])
+    assert rc == 1 and lib.tsamd_last_error().decode().endswith("tri_dev is null")
+
+
 # ------------------------------------------------------------------ GPU parity ------------------------------------------------------------------
 
 def _surface_scene(kind, spheres, n_views, seed=0):

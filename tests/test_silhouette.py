@@ -20,7 +20,7 @@ EPS = 2.0 ** -24     # unit round-off of float32
 
 
 def masked_group(n_chunks):
-    """Chunks per wave of the masked kernels (``masked_group`` in aa_kernels.hip, restated: a property of the launch)."""
+    """Chunks per wave of the masked kernels (``masked_launch`` in aa_kernels.hip, restated: a property of the launch)."""
     g = 1
     while g < 64 and n_chunks // (2 * g) >= 16384:
         g *= 2

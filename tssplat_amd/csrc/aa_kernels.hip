@@ -16,8 +16,7 @@
 //   blend plan kernels   the blends of a frozen image as (dst, src, weight) records: count per pair, (scan by the caller), fill
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
+#include "det_mean.h"
 #include "raster.h"
 
 // Coverage, depth and silhouette decisions repeat the oracle's operations one by one: a multiply and an add must round
@@ -163,6 +162,21 @@ __global__ __launch_bounds__(256) void antialias_edge_flags_kernel(const double2
     flags[gid] = uint8_t(f);
 }
 
+// What every pair kernel is given, ahead of its own arguments: the mesh, the image and the chunks per wave of the masked walk (masked_launch).
+struct MeshImage {
+    const float4 *pos;
+    const int32_t *tri, *opp;
+    int64_t batch, n_vertices, n_tri;
+    int height, width, group;
+};
+
+// The three parts of tsamd_antialias_prepare's buffer (prepared_view); all null in the table-free form.
+struct Prepared {
+    double2 *windows;
+    unsigned long long *masks;
+    uint8_t *flags;
+};
+
 struct Blend {
     int64_t dst, src;      // pixel indices inside the view
     float weight, sign;
@@ -174,14 +188,18 @@ struct Blend {
 // neighbour -- once the caller has chosen the pair's triangle: `t`, shown by the pair's first pixel (`first`) or by its second.
 // `emit` is called per blend.  `n_vertices` bounds every index read from `tri` / `opp` (a corrupt index skips the pair).
 template <bool TABLE, class Emit>
-__device__ __forceinline__ void triangle_blends(int64_t t, bool first, const float4 *pos_view, const double2 *win_view, const uint8_t *flag_view, const int32_t *tri,
-                                                const int32_t *opp, int64_t n_vertices, int64_t n_tri, int height, int width, int j, int i, int axis, Emit &&emit)
+__device__ __forceinline__ void triangle_blends(int64_t t, bool first, const MeshImage &m, const Prepared &prep, int64_t b, int j, int i, int axis, Emit &&emit)
 {
+    const float4 *pos_view = m.pos + b * m.n_vertices;
+    const double2 *win_view = TABLE ? prep.windows + b * m.n_vertices : nullptr;
+    const int32_t *tri = m.tri, *opp = m.opp;
+    const int64_t n_vertices = m.n_vertices;
+    const int height = m.height, width = m.width;
     const int dj = axis, di = 1 - axis;
-    if (t < 0 || t >= n_tri) return;
+    if (t < 0 || t >= m.n_tri) return;
     uint32_t may_blend = 7u;
     if (TABLE) {
-        may_blend = flag_view[t];
+        may_blend = prep.flags[b * m.n_tri + t];
         if (may_blend == 0u) return;   // (also: a vertex out of range or behind the camera)
     }
     const int pj = first ? j : j + dj, pi = first ? i : i + di;
@@ -256,15 +274,15 @@ __device__ __forceinline__ void triangle_blends(int64_t t, bool first, const flo
 // The pair as dr.antialias meets it: two pixels of `rast` that the caller has found to carry two different triangle ids.  The
 // triangle closer to the camera wins (ties to the second pixel's, background never).
 template <bool TABLE, class Emit>
-__device__ __forceinline__ void pair_blends(const float4 *rast_view, const float4 *pos_view, const double2 *win_view, const uint8_t *flag_view, const int32_t *tri, const int32_t *opp, int64_t n_vertices,
-                                            int64_t n_tri, int height, int width, int j, int i, int axis, Emit &&emit)
+__device__ __forceinline__ void pair_blends(const float4 *rast, const MeshImage &m, const Prepared &prep, int64_t b, int j, int i, int axis, Emit &&emit)
 {
     const int dj = axis, di = 1 - axis;
-    const float4 r0 = rast_view[int64_t(j) * width + i];
-    const float4 r1 = rast_view[int64_t(j + dj) * width + (i + di)];
+    const float4 *rast_view = rast + b * (int64_t(m.height) * m.width);
+    const float4 r0 = rast_view[int64_t(j) * m.width + i];
+    const float4 r1 = rast_view[int64_t(j + dj) * m.width + (i + di)];
     const int64_t t0 = int64_t(r0.w) - 1, t1 = int64_t(r1.w) - 1;
     const bool first = (t0 >= 0 && t1 >= 0) ? (r0.z < r1.z) : (t0 >= 0);
-    triangle_blends<TABLE>(first ? t0 : t1, first, pos_view, win_view, flag_view, tri, opp, n_vertices, n_tri, height, width, j, i, axis, emit);
+    triangle_blends<TABLE>(first ? t0 : t1, first, m, prep, b, j, i, axis, emit);
 }
 
 // d loss / d clip-space position of a blend's two edge vertices, from dt = d loss / d t of the blend (fp32 atomics into the view's grad_pos)
@@ -404,51 +422,53 @@ __device__ __forceinline__ void for_pairs_masked(const unsigned long long *masks
     }
 }
 
-// chunks per wave of the masked form: enough waves to fill the chip (>= ~16 k) before a wave takes more than one chunk
-int masked_group(int64_t n_chunks)
+// ---- the pair driver: work(view b, j, i, axis) for every pair of an image -- pixel (j, i) of view b with its right (axis 0) or its
+// upper (axis 1) neighbour.  MASKED: the pairs are the bits of `masks` (tsamd_antialias_prepare's, or the cover pass's); else they
+// are detected in `rast`.  The driver owns the LDS of either walk, the decode of a pair and its guards: the masks are the caller's
+// memory, so a bit beyond the image, in the last column (axis 0) or in the last row (axis 1) is skipped.  (The detect form never
+// produces such a pair -- differing_neighbours -- and is compiled without the guards: its kernels are held to 64 VGPRs.)
+template <bool MASKED, class Work>
+__device__ __forceinline__ void for_image_pairs(const float4 *rast, const unsigned long long *masks, const MeshImage &m, Work &&work)
 {
-    int g = 1;
-    while (g < 64 && n_chunks / (2 * g) >= 16384) g *= 2;
-    return g;
-}
-
-template <bool TABLE>
-__device__ __forceinline__ void antialias_body(const float *color, const float4 *rast, const float4 *pos, const double2 *windows, const unsigned long long *masks, const uint8_t *flags, const int32_t *tri, const int32_t *opp,
-                                                        int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int channels, int group, float *out)
-{
-    const int64_t hw = int64_t(height) * width;
-    auto work = [&](int64_t gid, int axis) {
+    const int64_t hw = int64_t(m.height) * m.width, total = m.batch * hw;
+    auto pair = [&](int64_t gid, int axis) {
+        if (MASKED && gid >= total) return;
         const int64_t b = gid / hw, pix = gid - b * hw;
-        const int j = int(pix / width), i = int(pix - int64_t(j) * width);
-        const float *cv = color + b * hw * channels;
-        float *ov = out + b * hw * channels;
-        pair_blends<TABLE>(rast + b * hw, pos + b * n_vertices, TABLE ? windows + b * n_vertices : nullptr, TABLE ? flags + b * n_tri : nullptr, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
-            for (int c = 0; c < channels; ++c) atomicAdd(ov + e.dst * channels + c, e.weight * (cv[e.src * channels + c] - cv[e.dst * channels + c]));
-        });
+        const int j = int(pix / m.width), i = int(pix - int64_t(j) * m.width);
+        if (MASKED && (axis == 0 ? i + 1 >= m.width : j + 1 >= m.height)) return;
+        work(b, j, i, axis);
     };
-    if (TABLE) {
+    if constexpr (MASKED) {
         __shared__ uint16_t stacks[(kAaBlock / 64) * kPairStack];
-        for_pairs_masked(masks, (batch * hw + 63) / 64, group, stacks + (threadIdx.x >> 6) * kPairStack, work);
+        for_pairs_masked(masks, (total + 63) / 64, m.group, stacks + (threadIdx.x >> 6) * kPairStack, pair);
     } else {
         __shared__ PairList L;
-        for_pairs_detected(rast, batch * hw, hw, height, width, L, work);
+        for_pairs_detected(rast, total, hw, m.height, m.width, L, pair);
     }
 }
 
 template <bool TABLE>
-__device__ __forceinline__ void antialias_backward_body(const float *color, const float4 *rast, const float4 *pos, const double2 *windows, const unsigned long long *masks, const uint8_t *flags, const int32_t *tri,
-                                                                 const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height,
-                                                                 int width, int channels, int group, const float *grad_out, float boost, float *grad_color,
-                                                                 float4 *grad_pos)
+__device__ __forceinline__ void antialias_body(const MeshImage &m, const Prepared &prep, const float *color, const float4 *rast, int channels, float *out)
 {
-    const int64_t hw = int64_t(height) * width;
-    auto work = [&](int64_t gid, int axis) {
-        const int64_t b = gid / hw, pix = gid - b * hw;
-        const int j = int(pix / width), i = int(pix - int64_t(j) * width);
+    const int64_t hw = int64_t(m.height) * m.width;
+    for_image_pairs<TABLE>(rast, prep.masks, m, [&](int64_t b, int j, int i, int axis) {
+        const float *cv = color + b * hw * channels;
+        float *ov = out + b * hw * channels;
+        pair_blends<TABLE>(rast, m, prep, b, j, i, axis, [&](const Blend &e) {
+            for (int c = 0; c < channels; ++c) atomicAdd(ov + e.dst * channels + c, e.weight * (cv[e.src * channels + c] - cv[e.dst * channels + c]));
+        });
+    });
+}
+
+template <bool TABLE>
+__device__ __forceinline__ void antialias_backward_body(const MeshImage &m, const Prepared &prep, const float *color, const float4 *rast, int channels, const float *grad_out,
+                                                        float boost, float *grad_color, float4 *grad_pos)
+{
+    const int64_t hw = int64_t(m.height) * m.width;
+    for_image_pairs<TABLE>(rast, prep.masks, m, [&](int64_t b, int j, int i, int axis) {
         const float *cv = color + b * hw * channels;
         const float *gv = grad_out + b * hw * channels;
-        const float4 *pv = pos + b * n_vertices;
-        pair_blends<TABLE>(rast + b * hw, pv, TABLE ? windows + b * n_vertices : nullptr, TABLE ? flags + b * n_tri : nullptr, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
+        pair_blends<TABLE>(rast, m, prep, b, j, i, axis, [&](const Blend &e) {
             float dot = 0.f;
             for (int c = 0; c < channels; ++c) {
                 const float g = gv[e.dst * channels + c];
@@ -459,40 +479,32 @@ __device__ __forceinline__ void antialias_backward_body(const float *color, cons
                     atomicAdd(gc + e.dst * channels + c, -e.weight * g);
                 }
             }
-            if (grad_pos) scatter_blend_gradient(e, double(e.sign) * double(dot) * double(boost), pv, grad_pos + b * n_vertices, height, width);
+            if (grad_pos) scatter_blend_gradient(e, double(e.sign) * double(dot) * double(boost), m.pos + b * m.n_vertices, grad_pos + b * m.n_vertices, m.height, m.width);
         });
-    };
-    if (TABLE) {
-        __shared__ uint16_t stacks[(kAaBlock / 64) * kPairStack];
-        for_pairs_masked(masks, (batch * hw + 63) / 64, group, stacks + (threadIdx.x >> 6) * kPairStack, work);
-    } else {
-        __shared__ PairList L;
-        for_pairs_detected(rast, batch * hw, hw, height, width, L, work);
-    }
+    });
 }
 
 // The table-free kernels have a lane per pixel in their detect phase and are held to 64 VGPRs (8 waves per SIMD; the analysis
 // spills a little); the masked kernels have no such phase -- few waves, all of them in the analysis -- and take the registers
 // the analysis wants.
+// (The four antialias kernels keep their arguments flat and in this order, with the tuple built inside: the kernel-argument
+// layout is part of what the two 64-VGPR kernels compile to.)
 #define TSAMD_AA_ARGS                                                                                                                       \
-    const float *color, const float4 *rast, const float4 *pos, const double2 *windows, const unsigned long long *masks, const uint8_t *flags, \
-        const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int channels, int group
-#define TSAMD_AA_PASS color, rast, pos, windows, masks, flags, tri, opp, batch, n_vertices, n_tri, height, width, channels, group
+    const float *color, const float4 *rast, const float4 *pos, double2 *windows, unsigned long long *masks, uint8_t *flags, const int32_t *tri, \
+        const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int channels, int group
+#define TSAMD_AA_TUPLE MeshImage{pos, tri, opp, batch, n_vertices, n_tri, height, width, group}, Prepared{windows, masks, flags}, color, rast, channels
 
-__global__ __launch_bounds__(kAaBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void antialias_kernel(TSAMD_AA_ARGS, float *out)
-{
-    antialias_body<false>(TSAMD_AA_PASS, out);
-}
-__global__ __launch_bounds__(kAaBlock) void antialias_masked_kernel(TSAMD_AA_ARGS, float *out) { antialias_body<true>(TSAMD_AA_PASS, out); }
+__global__ __launch_bounds__(kAaBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void antialias_kernel(TSAMD_AA_ARGS, float *out) { antialias_body<false>(TSAMD_AA_TUPLE, out); }
+__global__ __launch_bounds__(kAaBlock) void antialias_masked_kernel(TSAMD_AA_ARGS, float *out) { antialias_body<true>(TSAMD_AA_TUPLE, out); }
 
 __global__ __launch_bounds__(kAaBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void antialias_backward_kernel(TSAMD_AA_ARGS, const float *grad_out, float boost,
                                                                                                                 float *grad_color, float4 *grad_pos)
 {
-    antialias_backward_body<false>(TSAMD_AA_PASS, grad_out, boost, grad_color, grad_pos);
+    antialias_backward_body<false>(TSAMD_AA_TUPLE, grad_out, boost, grad_color, grad_pos);
 }
 __global__ __launch_bounds__(kAaBlock) void antialias_backward_masked_kernel(TSAMD_AA_ARGS, const float *grad_out, float boost, float *grad_color, float4 *grad_pos)
 {
-    antialias_backward_body<true>(TSAMD_AA_PASS, grad_out, boost, grad_color, grad_pos);
+    antialias_backward_body<true>(TSAMD_AA_TUPLE, grad_out, boost, grad_color, grad_pos);
 }
 
 // ---- the blend plan (tsamd_shade_plan_*): the blends of a FROZEN rast / pos_clip as records, for csrc/shade_kernels.hip ----
@@ -501,20 +513,15 @@ __global__ __launch_bounds__(kAaBlock) void antialias_backward_masked_kernel(TSA
 // offsets[2 pixel + axis] on, in edge order).  The caller scans the counts in between, so the order of the records is the order of
 // the pair slots whatever the schedule: no append counter.  Pixel indices are batch-wide.
 template <bool FILL>
-__device__ __forceinline__ void blend_plan_body(const float4 *rast, const float4 *pos, const double2 *windows, const unsigned long long *masks, const uint8_t *flags, const int32_t *tri,
-                                                const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int group, int32_t *counts,
-                                                const int32_t *offsets, int64_t n_blends, int32_t *rec_dst, int32_t *rec_src, float *rec_weight)
+__device__ __forceinline__ void blend_plan_body(const MeshImage &m, const Prepared &prep, const float4 *rast, int32_t *counts, const int32_t *offsets, int64_t n_blends, int32_t *rec_dst,
+                                                int32_t *rec_src, float *rec_weight)
 {
-    __shared__ uint16_t stacks[(kAaBlock / 64) * kPairStack];
-    const int64_t hw = int64_t(height) * width, total = batch * hw;
-    for_pairs_masked(masks, (total + 63) / 64, group, stacks + (threadIdx.x >> 6) * kPairStack, [&](int64_t gid, int axis) {
-        if (gid >= total) return;
-        const int64_t b = gid / hw, pix = gid - b * hw;
-        const int j = int(pix / width), i = int(pix - int64_t(j) * width);
-        if (axis == 0 ? i + 1 >= width : j + 1 >= height) return;
+    const int64_t hw = int64_t(m.height) * m.width;
+    for_image_pairs<true>(rast, prep.masks, m, [&](int64_t b, int j, int i, int axis) {
+        const int64_t slot = 2 * (b * hw + int64_t(j) * m.width + i) + axis;
         int n = 0;
-        const int64_t first = FILL ? int64_t(offsets[2 * gid + axis]) : 0;
-        pair_blends<true>(rast + b * hw, pos + b * n_vertices, windows + b * n_vertices, flags + b * n_tri, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
+        const int64_t first = FILL ? int64_t(offsets[slot]) : 0;
+        pair_blends<true>(rast, m, prep, b, j, i, axis, [&](const Blend &e) {
             if (FILL) {
                 const int64_t k = first + n;
                 if (k >= 0 && k < n_blends) {
@@ -525,22 +532,18 @@ __device__ __forceinline__ void blend_plan_body(const float4 *rast, const float4
             }
             ++n;
         });
-        if (!FILL) counts[2 * gid + axis] = n;
+        if (!FILL) counts[slot] = n;
     });
 }
 
-#define TSAMD_PLAN_ARGS                                                                                                                                            \
-    const float4 *rast, const float4 *pos, const double2 *windows, const unsigned long long *masks, const uint8_t *flags, const int32_t *tri, const int32_t *opp, \
-        int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int group
-#define TSAMD_PLAN_PASS rast, pos, windows, masks, flags, tri, opp, batch, n_vertices, n_tri, height, width, group
-
-__global__ __launch_bounds__(kAaBlock) void blend_plan_count_kernel(TSAMD_PLAN_ARGS, int32_t *counts)
+__global__ __launch_bounds__(kAaBlock) void blend_plan_count_kernel(MeshImage m, Prepared prep, const float4 *rast, int32_t *counts)
 {
-    blend_plan_body<false>(TSAMD_PLAN_PASS, counts, nullptr, 0, nullptr, nullptr, nullptr);
+    blend_plan_body<false>(m, prep, rast, counts, nullptr, 0, nullptr, nullptr, nullptr);
 }
-__global__ __launch_bounds__(kAaBlock) void blend_plan_fill_kernel(TSAMD_PLAN_ARGS, const int32_t *offsets, int64_t n_blends, int32_t *rec_dst, int32_t *rec_src, float *rec_weight)
+__global__ __launch_bounds__(kAaBlock) void blend_plan_fill_kernel(MeshImage m, Prepared prep, const float4 *rast, const int32_t *offsets, int64_t n_blends, int32_t *rec_dst,
+                                                                   int32_t *rec_src, float *rec_weight)
 {
-    blend_plan_body<true>(TSAMD_PLAN_PASS, nullptr, offsets, n_blends, rec_dst, rec_src, rec_weight);
+    blend_plan_body<true>(m, prep, rast, nullptr, offsets, n_blends, rec_dst, rec_src, rec_weight);
 }
 
 // ---- the alpha stage (tsamd_silhouette*): antialias of the 0 / 1 coverage image without a `rast` image ----
@@ -550,29 +553,23 @@ __global__ __launch_bounds__(kAaBlock) void blend_plan_fill_kernel(TSAMD_PLAN_AR
 //
 // work(view, triangle of the covered pixel, covered pixel is the pair's first, j, i, axis) for every pair of the coverage masks
 template <class Work>
-__device__ __forceinline__ void for_cover_pairs(const int32_t *ids, const unsigned long long *masks, int64_t batch, int height, int width, int group, Work &&work)
+__device__ __forceinline__ void for_cover_pairs(const MeshImage &m, const int32_t *ids, const unsigned long long *masks, Work &&work)
 {
-    __shared__ uint16_t stacks[(kAaBlock / 64) * kPairStack];
-    const int64_t hw = int64_t(height) * width, total = batch * hw;
-    for_pairs_masked(masks, (total + 63) / 64, group, stacks + (threadIdx.x >> 6) * kPairStack, [&](int64_t gid, int axis) {
-        if (gid >= total) return;                              // (masks are the caller's: a bit beyond the image is ignored)
-        const int64_t b = gid / hw, pix = gid - b * hw;
-        const int j = int(pix / width), i = int(pix - int64_t(j) * width);
-        if (axis == 0 ? i + 1 >= width : j + 1 >= height) return;
-        const int32_t id0 = ids[gid], id1 = ids[gid + (axis == 0 ? 1 : width)];
+    for_image_pairs<true>(nullptr, masks, m, [&](int64_t b, int j, int i, int axis) {
+        const int32_t *pair = ids + b * (int64_t(m.height) * m.width) + int64_t(j) * m.width + i;
+        const int32_t id0 = pair[0], id1 = pair[axis == 0 ? 1 : m.width];
         if ((id0 > 0) == (id1 > 0)) return;
         work(b, int64_t(id0 > 0 ? id0 : id1) - 1, id0 > 0, j, i, axis);
     });
 }
 
-__global__ __launch_bounds__(kAaBlock) void silhouette_blend_kernel(const int32_t *ids, const unsigned long long *masks, const float4 *pos, const int32_t *tri, const int32_t *opp,
-                                                                    int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int group, float *alpha)
+__global__ __launch_bounds__(kAaBlock) void silhouette_blend_kernel(MeshImage m, const int32_t *ids, const unsigned long long *masks, float *alpha)
 {
-    const int64_t hw = int64_t(height) * width;
-    for_cover_pairs(ids, masks, batch, height, width, group, [&](int64_t b, int64_t t, bool first, int j, int i, int axis) {
+    const int64_t hw = int64_t(m.height) * m.width;
+    for_cover_pairs(m, ids, masks, [&](int64_t b, int64_t t, bool first, int j, int i, int axis) {
         const int32_t *iv = ids + b * hw;
         float *av = alpha + b * hw;
-        triangle_blends<false>(t, first, pos + b * n_vertices, nullptr, nullptr, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
+        triangle_blends<false>(t, first, m, Prepared{}, b, j, i, axis, [&](const Blend &e) {
             atomicAdd(av + e.dst, e.weight * (float(iv[e.src] > 0) - float(iv[e.dst] > 0)));
         });
     });
@@ -581,63 +578,45 @@ __global__ __launch_bounds__(kAaBlock) void silhouette_blend_kernel(const int32_
 // MSE = false: grad_alpha is the gradient image.  MSE = true: there is none -- g[dst] = 2 (alpha[dst] - target[dst]) grad_loss / n
 // is formed per blend in float64, grad_loss read from device memory.
 template <bool MSE>
-__device__ __forceinline__ void silhouette_backward_body(const int32_t *ids, const unsigned long long *masks, const float4 *pos, const int32_t *tri, const int32_t *opp, int64_t batch,
-                                                         int64_t n_vertices, int64_t n_tri, int height, int width, int group, const float *grad_alpha, const float *alpha,
+__device__ __forceinline__ void silhouette_backward_body(const MeshImage &m, const int32_t *ids, const unsigned long long *masks, const float *grad_alpha, const float *alpha,
                                                          const float *target, const float *grad_loss, float boost, float4 *grad_pos)
 {
-    const int64_t hw = int64_t(height) * width;
-    for_cover_pairs(ids, masks, batch, height, width, group, [&](int64_t b, int64_t t, bool first, int j, int i, int axis) {
+    const int64_t hw = int64_t(m.height) * m.width;
+    for_cover_pairs(m, ids, masks, [&](int64_t b, int64_t t, bool first, int j, int i, int axis) {
         const int32_t *iv = ids + b * hw;
-        const float4 *pv = pos + b * n_vertices;
-        triangle_blends<false>(t, first, pv, nullptr, nullptr, tri, opp, n_vertices, n_tri, height, width, j, i, axis, [&](const Blend &e) {
+        triangle_blends<false>(t, first, m, Prepared{}, b, j, i, axis, [&](const Blend &e) {
             const float dc = float(iv[e.src] > 0) - float(iv[e.dst] > 0);
             double dot;
             if (MSE)
-                dot = 2.0 * (double(alpha[b * hw + e.dst]) - double(target[b * hw + e.dst])) * double(*grad_loss) / double(batch * hw) * double(dc);
+                dot = 2.0 * (double(alpha[b * hw + e.dst]) - double(target[b * hw + e.dst])) * double(*grad_loss) / double(m.batch * hw) * double(dc);
             else
                 dot = double(grad_alpha[b * hw + e.dst] * dc);
-            scatter_blend_gradient(e, double(e.sign) * dot * double(boost), pv, grad_pos + b * n_vertices, height, width);
+            scatter_blend_gradient(e, double(e.sign) * dot * double(boost), m.pos + b * m.n_vertices, grad_pos + b * m.n_vertices, m.height, m.width);
         });
     });
 }
 
-#define TSAMD_SIL_ARGS                                                                                                                                       \
-    const int32_t *ids, const unsigned long long *masks, const float4 *pos, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, \
-        int height, int width, int group
-#define TSAMD_SIL_PASS ids, masks, pos, tri, opp, batch, n_vertices, n_tri, height, width, group
-
-__global__ __launch_bounds__(kAaBlock) void silhouette_backward_kernel(TSAMD_SIL_ARGS, const float *grad_alpha, float boost, float4 *grad_pos)
+__global__ __launch_bounds__(kAaBlock) void silhouette_backward_kernel(MeshImage m, const int32_t *ids, const unsigned long long *masks, const float *grad_alpha, float boost,
+                                                                       float4 *grad_pos)
 {
-    silhouette_backward_body<false>(TSAMD_SIL_PASS, grad_alpha, nullptr, nullptr, nullptr, boost, grad_pos);
+    silhouette_backward_body<false>(m, ids, masks, grad_alpha, nullptr, nullptr, nullptr, boost, grad_pos);
 }
-__global__ __launch_bounds__(kAaBlock) void silhouette_mse_backward_kernel(TSAMD_SIL_ARGS, const float *alpha, const float *target, const float *grad_loss, float boost,
-                                                                           float4 *grad_pos)
+__global__ __launch_bounds__(kAaBlock) void silhouette_mse_backward_kernel(MeshImage m, const int32_t *ids, const unsigned long long *masks, const float *alpha, const float *target,
+                                                                           const float *grad_loss, float boost, float4 *grad_pos)
 {
-    silhouette_backward_body<true>(TSAMD_SIL_PASS, nullptr, alpha, target, grad_loss, boost, grad_pos);
+    silhouette_backward_body<true>(m, ids, masks, nullptr, alpha, target, grad_loss, boost, grad_pos);
 }
 
-// ---- loss = mean((alpha - target)^2), bitwise repeatable: no atomics, fixed grid, fixed trees ----
+// ---- loss = mean((alpha - target)^2), bitwise repeatable (det_mean.h) ----
 // d = a - t in float32, d * d accumulated in float64.  A workgroup strides over the 16-byte groups (n4 of them; 0 when a pointer is
-// not 16-byte aligned) and over the scalar rest [4 n4, n), sums its lanes in a fixed tree and stores one double; the final
-// workgroup adds the partials in a fixed order and stores float(sum / n).
-constexpr int kMseBlock = 256;
+// not 16-byte aligned) and over the scalar rest [4 n4, n), and stores one double.
+constexpr int kMsePerBlock = 4 * kMeanBlock;
 constexpr int kMseMaxBlocks = 1024;
 
-int mse_blocks(int64_t n) { return int(std::min<int64_t>(kMseMaxBlocks, std::max<int64_t>(1, (n + 4 * kMseBlock - 1) / (4 * kMseBlock)))); }
-
-__device__ __forceinline__ double block_sum(double v, double *lds)
+__global__ __launch_bounds__(kMeanBlock) void silhouette_mse_kernel(const float *alpha, const float *target, int64_t n, int64_t n4, double *partials)
 {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + (lds[2] + lds[3]));
-}
-
-__global__ __launch_bounds__(kMseBlock) void silhouette_mse_kernel(const float *alpha, const float *target, int64_t n, int64_t n4, double *partials)
-{
-    __shared__ double lds[kMseBlock / 64];
-    const int64_t first = int64_t(blockIdx.x) * kMseBlock + threadIdx.x, stride = int64_t(gridDim.x) * kMseBlock;
+    __shared__ double lds[kMeanBlock / 64];
+    const int64_t first = int64_t(blockIdx.x) * kMeanBlock + threadIdx.x, stride = int64_t(gridDim.x) * kMeanBlock;
     double acc = 0.0;
     const float4 *a4 = reinterpret_cast<const float4 *>(alpha), *t4 = reinterpret_cast<const float4 *>(target);
     for (int64_t k = first; k < n4; k += stride) {
@@ -653,16 +632,21 @@ __global__ __launch_bounds__(kMseBlock) void silhouette_mse_kernel(const float *
     if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
-__global__ __launch_bounds__(kMseBlock) void silhouette_mse_final_kernel(const double *partials, int n_partials, int64_t n, float *loss)
-{
-    __shared__ double lds[kMseBlock / 64];
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < n_partials; k += kMseBlock) acc += partials[k];
-    const double sum = block_sum(acc, lds);
-    if (threadIdx.x == 0) *loss = float(sum / double(n));
-}
-
 unsigned blocks_for(int64_t n) { return unsigned((n + 255) / 256); }
+
+// The launch geometry of the masked walk over `pixels` pixels: a wave takes `group` (<= 64) consecutive 64-pixel chunks -- enough
+// waves to fill the chip (>= ~16 k) before a wave takes more than one -- and `grid` workgroups of kAaBlock lanes hold the waves.
+struct MaskedLaunch {
+    int group;
+    unsigned grid;
+};
+MaskedLaunch masked_launch(int64_t pixels)
+{
+    const int64_t n_chunks = (pixels + 63) / 64;
+    int g = 1;
+    while (g < 64 && n_chunks / (2 * g) >= 16384) g *= 2;
+    return {g, blocks_for((n_chunks + g - 1) / g * 64)};
+}
 
 uint64_t table_slots(int64_t n_tri)
 {
@@ -699,21 +683,34 @@ hipError_t launch_antialias_topology(const int32_t *tri, int64_t n_tri, void *wo
 
 // prepared = [batch * n_vertices] double2 window coordinates | two 64-bit pair masks per 64 pixels | [batch * n_tri] edge flags,
 // every part 256-byte aligned
-struct Prepared {
+struct PreparedLayout {
     int64_t masks, flags, bytes;
 };
 
-static Prepared prepared_layout(int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width)
+static PreparedLayout prepared_layout(int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width)
 {
-    const int64_t pixels = batch * int64_t(height) * width;
-    Prepared p;
+    PreparedLayout p;
     p.masks = (batch * n_vertices * 16 + 255) / 256 * 256;
-    p.flags = p.masks + ((pixels + 63) / 64 * 16 + 255) / 256 * 256;
+    p.flags = p.masks + (pair_masks_bytes(batch, height, width) + 255) / 256 * 256;
     p.bytes = p.flags + (batch * n_tri + 255) / 256 * 256;
     return p;
 }
 
-int64_t pair_masks_bytes(int64_t batch, int height, int width) { return (batch * int64_t(height) * width + 63) / 64 * 16; }
+// the three typed parts of a `prepared` buffer (null stays null: the table-free form); only launch_antialias_prepare writes through them
+static Prepared prepared_view(const void *prepared, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width)
+{
+    if (!prepared) return Prepared{};
+    const PreparedLayout lay = prepared_layout(batch, n_vertices, n_tri, height, width);
+    char *base = static_cast<char *>(const_cast<void *>(prepared));
+    return {reinterpret_cast<double2 *>(base), reinterpret_cast<unsigned long long *>(base + lay.masks), reinterpret_cast<uint8_t *>(base + lay.flags)};
+}
+
+static MeshImage mesh_image(const float *pos_clip, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int group)
+{
+    return {reinterpret_cast<const float4 *>(pos_clip), tri, opp, batch, n_vertices, n_tri, height, width, group};
+}
+
+int64_t pair_masks_bytes(int64_t batch, int height, int width) { return (pixel_count(batch, height, width) + 63) / 64 * 16; }
 
 int64_t antialias_prepared_bytes(int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width)
 {
@@ -723,44 +720,39 @@ int64_t antialias_prepared_bytes(int64_t batch, int64_t n_vertices, int64_t n_tr
 hipError_t launch_antialias_prepare(const float *rast, const float *pos_clip, const int32_t *tri, const int32_t *opp, const void *pair_masks, int64_t batch,
                                     int64_t n_vertices, int64_t n_tri, int height, int width, void *prepared, hipStream_t stream)
 {
-    const int64_t n = batch * n_vertices, pixels = batch * int64_t(height) * width;
-    const Prepared lay = prepared_layout(batch, n_vertices, n_tri, height, width);
-    char *base = static_cast<char *>(prepared);
+    const int64_t n = batch * n_vertices, pixels = pixel_count(batch, height, width);
+    const Prepared prep = prepared_view(prepared, batch, n_vertices, n_tri, height, width);
     hipError_t e;
     if (n > 0) {
         hipLaunchKernelGGL(antialias_windows_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), n, double(width),
-                           double(height), reinterpret_cast<double2 *>(base));
+                           double(height), prep.windows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (batch * n_tri > 0) {
-        hipLaunchKernelGGL(antialias_edge_flags_kernel, dim3(blocks_for(batch * n_tri)), dim3(256), 0, stream, reinterpret_cast<const double2 *>(base), tri, opp,
-                           batch, n_vertices, n_tri, reinterpret_cast<uint8_t *>(base + lay.flags));
+        hipLaunchKernelGGL(antialias_edge_flags_kernel, dim3(blocks_for(batch * n_tri)), dim3(256), 0, stream, prep.windows, tri, opp, batch, n_vertices, n_tri, prep.flags);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (pixels <= 0) return hipSuccess;
     if (pair_masks)   // the rasteriser found them while it resolved the image
-        return hipMemcpyAsync(base + lay.masks, pair_masks, size_t(pair_masks_bytes(batch, height, width)), hipMemcpyDeviceToDevice, stream);
+        return hipMemcpyAsync(prep.masks, pair_masks, size_t(pair_masks_bytes(batch, height, width)), hipMemcpyDeviceToDevice, stream);
     hipLaunchKernelGGL(antialias_detect_kernel, dim3(blocks_for(pixels)), dim3(kAaBlock), 0, stream, reinterpret_cast<const float4 *>(rast), pixels,
-                       int64_t(height) * width, height, width, reinterpret_cast<unsigned long long *>(base + lay.masks));
+                       int64_t(height) * width, height, width, prep.masks);
     return hipGetLastError();
 }
 
 hipError_t launch_antialias(const float *color, const float *rast, const float *pos_clip, const void *prepared, const int32_t *tri, const int32_t *opp,
                             int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int channels, float *out, hipStream_t stream)
 {
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     if (pixels <= 0 || channels <= 0) return hipSuccess;
     hipError_t e = hipMemcpyAsync(out, color, size_t(pixels) * size_t(channels) * sizeof(float), hipMemcpyDeviceToDevice, stream);
     if (e != hipSuccess) return e;
     if (n_tri <= 0) return hipSuccess;
-    const Prepared lay = prepared_layout(batch, n_vertices, n_tri, height, width);
-    const unsigned long long *masks = prepared ? reinterpret_cast<const unsigned long long *>(static_cast<const char *>(prepared) + lay.masks) : nullptr;
-    const uint8_t *flags = prepared ? reinterpret_cast<const uint8_t *>(static_cast<const char *>(prepared) + lay.flags) : nullptr;
-    const int group = masked_group((pixels + 63) / 64);
-    const int64_t masked_waves = ((pixels + 63) / 64 + group - 1) / group;
-    hipLaunchKernelGGL(prepared ? antialias_masked_kernel : antialias_kernel, dim3(prepared ? blocks_for(masked_waves * 64) : blocks_for(pixels)), dim3(kAaBlock), 0, stream, color, reinterpret_cast<const float4 *>(rast),
-                       reinterpret_cast<const float4 *>(pos_clip), static_cast<const double2 *>(prepared), masks, flags, tri, opp, batch, n_vertices, n_tri, height, width,
-                       channels, group, out);
+    const MaskedLaunch geo = masked_launch(pixels);
+    const Prepared prep = prepared_view(prepared, batch, n_vertices, n_tri, height, width);
+    hipLaunchKernelGGL(prepared ? antialias_masked_kernel : antialias_kernel, dim3(prepared ? geo.grid : blocks_for(pixels)), dim3(kAaBlock), 0, stream,
+                       color, reinterpret_cast<const float4 *>(rast), reinterpret_cast<const float4 *>(pos_clip), prep.windows, prep.masks, prep.flags, tri, opp, batch, n_vertices, n_tri,
+                       height, width, channels, geo.group, out);
     return hipGetLastError();
 }
 
@@ -768,7 +760,7 @@ hipError_t launch_antialias_backward(const float *color, const float *rast, cons
                                      const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width, int channels, const float *grad_out, float boost,
                                      float *grad_color, float *grad_pos, hipStream_t stream)
 {
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     hipError_t e;
     if (grad_color && pixels > 0 && channels > 0) {
         e = hipMemcpyAsync(grad_color, grad_out, size_t(pixels) * size_t(channels) * sizeof(float), hipMemcpyDeviceToDevice, stream);
@@ -779,15 +771,11 @@ hipError_t launch_antialias_backward(const float *color, const float *rast, cons
         if (e != hipSuccess) return e;
     }
     if (pixels <= 0 || channels <= 0 || n_tri <= 0) return hipSuccess;
-    const Prepared lay = prepared_layout(batch, n_vertices, n_tri, height, width);
-    const unsigned long long *masks = prepared ? reinterpret_cast<const unsigned long long *>(static_cast<const char *>(prepared) + lay.masks) : nullptr;
-    const uint8_t *flags = prepared ? reinterpret_cast<const uint8_t *>(static_cast<const char *>(prepared) + lay.flags) : nullptr;
-    const int group = masked_group((pixels + 63) / 64);
-    const int64_t masked_waves = ((pixels + 63) / 64 + group - 1) / group;
-    hipLaunchKernelGGL(prepared ? antialias_backward_masked_kernel : antialias_backward_kernel, dim3(prepared ? blocks_for(masked_waves * 64) : blocks_for(pixels)), dim3(kAaBlock), 0, stream, color, reinterpret_cast<const float4 *>(rast),
-                       reinterpret_cast<const float4 *>(pos_clip), static_cast<const double2 *>(prepared), masks, flags, tri, opp, batch, n_vertices, n_tri, height, width,
-                       channels, group, grad_out, boost, grad_color,
-                       reinterpret_cast<float4 *>(grad_pos));
+    const MaskedLaunch geo = masked_launch(pixels);
+    const Prepared prep = prepared_view(prepared, batch, n_vertices, n_tri, height, width);
+    hipLaunchKernelGGL(prepared ? antialias_backward_masked_kernel : antialias_backward_kernel, dim3(prepared ? geo.grid : blocks_for(pixels)), dim3(kAaBlock), 0, stream,
+                       color, reinterpret_cast<const float4 *>(rast), reinterpret_cast<const float4 *>(pos_clip), prep.windows, prep.masks, prep.flags, tri, opp, batch, n_vertices, n_tri,
+                       height, width, channels, geo.group, grad_out, boost, grad_color, reinterpret_cast<float4 *>(grad_pos));
     return hipGetLastError();
 }
 
@@ -795,37 +783,31 @@ hipError_t launch_blend_plan(const float *rast, const float *pos_clip, const voi
                              int64_t n_tri, int height, int width, int32_t *counts, const int32_t *offsets, int64_t n_blends, int32_t *rec_dst, int32_t *rec_src,
                              float *rec_weight, hipStream_t stream)
 {
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     if (counts && pixels > 0) {
         const hipError_t e = hipMemsetAsync(counts, 0, size_t(pixels) * 2 * sizeof(int32_t), stream);
         if (e != hipSuccess) return e;
     }
     if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0 || (!counts && n_blends <= 0)) return hipSuccess;
-    const Prepared lay = prepared_layout(batch, n_vertices, n_tri, height, width);
-    const unsigned long long *masks = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(prepared) + lay.masks);
-    const uint8_t *flags = reinterpret_cast<const uint8_t *>(static_cast<const char *>(prepared) + lay.flags);
-    const int group = masked_group((pixels + 63) / 64);
-    const int64_t waves = ((pixels + 63) / 64 + group - 1) / group;
-    const float4 *r4 = reinterpret_cast<const float4 *>(rast), *p4 = reinterpret_cast<const float4 *>(pos_clip);
-    const double2 *windows = static_cast<const double2 *>(prepared);
+    const MaskedLaunch geo = masked_launch(pixels);
+    const MeshImage m = mesh_image(pos_clip, tri, opp, batch, n_vertices, n_tri, height, width, geo.group);
+    const Prepared prep = prepared_view(prepared, batch, n_vertices, n_tri, height, width);
+    const float4 *r4 = reinterpret_cast<const float4 *>(rast);
     if (counts)
-        hipLaunchKernelGGL(blend_plan_count_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, r4, p4, windows, masks, flags, tri, opp, batch, n_vertices, n_tri,
-                           height, width, group, counts);
+        hipLaunchKernelGGL(blend_plan_count_kernel, dim3(geo.grid), dim3(kAaBlock), 0, stream, m, prep, r4, counts);
     else
-        hipLaunchKernelGGL(blend_plan_fill_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, r4, p4, windows, masks, flags, tri, opp, batch, n_vertices, n_tri,
-                           height, width, group, offsets, n_blends, rec_dst, rec_src, rec_weight);
+        hipLaunchKernelGGL(blend_plan_fill_kernel, dim3(geo.grid), dim3(kAaBlock), 0, stream, m, prep, r4, offsets, n_blends, rec_dst, rec_src, rec_weight);
     return hipGetLastError();
 }
 
 hipError_t launch_silhouette_blend(const float *pos_clip, const int32_t *tri, const int32_t *opp, int64_t batch, int64_t n_vertices, int64_t n_tri, int height, int width,
                                    const int32_t *ids, const void *cover_masks, float *alpha, hipStream_t stream)
 {
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
-    const int group = masked_group((pixels + 63) / 64);
-    const int64_t waves = ((pixels + 63) / 64 + group - 1) / group;
-    hipLaunchKernelGGL(silhouette_blend_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, ids, static_cast<const unsigned long long *>(cover_masks),
-                       reinterpret_cast<const float4 *>(pos_clip), tri, opp, batch, n_vertices, n_tri, height, width, group, alpha);
+    const MaskedLaunch geo = masked_launch(pixels);
+    hipLaunchKernelGGL(silhouette_blend_kernel, dim3(geo.grid), dim3(kAaBlock), 0, stream, mesh_image(pos_clip, tri, opp, batch, n_vertices, n_tri, height, width, geo.group), ids,
+                       static_cast<const unsigned long long *>(cover_masks), alpha);
     return hipGetLastError();
 }
 
@@ -837,33 +819,28 @@ hipError_t launch_silhouette_backward(const float *pos_clip, const int32_t *tri,
         const hipError_t e = hipMemsetAsync(grad_pos, 0, size_t(batch) * size_t(n_vertices) * 4 * sizeof(float), stream);
         if (e != hipSuccess) return e;
     }
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
-    const int group = masked_group((pixels + 63) / 64);
-    const int64_t waves = ((pixels + 63) / 64 + group - 1) / group;
+    const MaskedLaunch geo = masked_launch(pixels);
+    const MeshImage m = mesh_image(pos_clip, tri, opp, batch, n_vertices, n_tri, height, width, geo.group);
     const unsigned long long *masks = static_cast<const unsigned long long *>(cover_masks);
-    const float4 *pos = reinterpret_cast<const float4 *>(pos_clip);
     if (grad_alpha)
-        hipLaunchKernelGGL(silhouette_backward_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, ids, masks, pos, tri, opp, batch, n_vertices, n_tri, height,
-                           width, group, grad_alpha, boost, reinterpret_cast<float4 *>(grad_pos));
+        hipLaunchKernelGGL(silhouette_backward_kernel, dim3(geo.grid), dim3(kAaBlock), 0, stream, m, ids, masks, grad_alpha, boost, reinterpret_cast<float4 *>(grad_pos));
     else
-        hipLaunchKernelGGL(silhouette_mse_backward_kernel, dim3(blocks_for(waves * 64)), dim3(kAaBlock), 0, stream, ids, masks, pos, tri, opp, batch, n_vertices, n_tri,
-                           height, width, group, alpha, target, grad_loss, boost, reinterpret_cast<float4 *>(grad_pos));
+        hipLaunchKernelGGL(silhouette_mse_backward_kernel, dim3(geo.grid), dim3(kAaBlock), 0, stream, m, ids, masks, alpha, target, grad_loss, boost, reinterpret_cast<float4 *>(grad_pos));
     return hipGetLastError();
 }
 
-int64_t silhouette_mse_workspace_bytes(int64_t n) { return (int64_t(mse_blocks(n)) * 8 + 255) / 256 * 256; }
+int64_t silhouette_mse_workspace_bytes(int64_t n) { return mean_workspace_bytes(mean_blocks(n, kMsePerBlock, kMseMaxBlocks)); }
 
 hipError_t launch_silhouette_mse(const float *alpha, const float *target, int64_t n, void *workspace, float *loss, hipStream_t stream)
 {
     if (n <= 0) return hipMemsetAsync(loss, 0, sizeof(float), stream);
     const bool aligned = ((reinterpret_cast<uintptr_t>(alpha) | reinterpret_cast<uintptr_t>(target)) & 15u) == 0;
-    const int blocks = mse_blocks(n);
-    hipLaunchKernelGGL(silhouette_mse_kernel, dim3(blocks), dim3(kMseBlock), 0, stream, alpha, target, n, aligned ? n / 4 : 0, static_cast<double *>(workspace));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(silhouette_mse_final_kernel, dim3(1), dim3(kMseBlock), 0, stream, static_cast<const double *>(workspace), blocks, n, loss);
-    return hipGetLastError();
+    const int blocks = mean_blocks(n, kMsePerBlock, kMseMaxBlocks);
+    hipLaunchKernelGGL(silhouette_mse_kernel, dim3(blocks), dim3(kMeanBlock), 0, stream, alpha, target, n, aligned ? n / 4 : 0, static_cast<double *>(workspace));
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, n, loss, stream);
 }
 
 }  // namespace tsamd

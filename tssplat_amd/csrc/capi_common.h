@@ -1,8 +1,10 @@
-// Shared by the translation units that implement the C ABI (capi.cpp, surface_capi.cpp).
+// Shared by the translation units that implement the C ABI (capi.cpp and every *_capi.cpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
+#include <climits>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/tssplat_amd.h"
@@ -32,6 +34,43 @@ struct DeviceGuard {
         if (active) (void)hipSetDevice(prev);
     }
 };
+
+// The first null pointer of a list of (pointer, name as in the header) pairs, named on its own: "<name> is null".
+struct NamedPtr {
+    const void *ptr;
+    const char *name;
+};
+inline int check_not_null(std::initializer_list<NamedPtr> args)
+{
+    for (const NamedPtr &a : args)
+        if (!a.ptr) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(a.name) + " is null");
+    return TSAMD_OK;
+}
+
+// ---- the renderer's argument checks (raster_capi.cpp, shade_capi.cpp) ----
+constexpr int64_t kMaxPixels = int64_t(1) << 30;   // pixel and pair-slot (2 per pixel) indices are 32-bit
+
+// cap_pixels: the entry points that index pixels and pair slots with 32 bits (the blend plan and everything under it)
+inline int check_image(int64_t batch, int32_t height, int32_t width, bool cap_pixels)
+{
+    // 8192: snapped window coordinates are kept within +-2^22 sub-pixel units (1/256 pixel) = +-16384 pixels and a triangle with a
+    // vertex beyond that is dropped (there is no clipping), so the cap leaves a guard band of at least one screen on every side
+    if (batch < 0 || height < 0 || width < 0 || height > 8192 || width > 8192)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch / height / width out of range (0 .. 8192 pixels per side)");
+    if (cap_pixels && (batch > kMaxPixels || batch * int64_t(height) * width >= kMaxPixels))
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch x height x width must stay below 2^30 pixels (32-bit pixel and pair indices)");
+    return TSAMD_OK;
+}
+
+// grid_limit: the entry points that bin triangles (one workgroup per 8 views x 256 triangles)
+inline int check_mesh_sizes(int64_t n_vertices, int64_t n_triangles, int64_t batch, bool grid_limit)
+{
+    if (n_vertices < 0 || n_triangles < 0 || n_triangles > (int64_t(1) << 24) - 1)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "negative size or more than 2^24 - 1 triangles (the id + 1 is returned as a float32, exact up to 2^24)");
+    if (grid_limit && (batch + 7) / 8 * 8 * ((n_triangles + 255) / 256) > int64_t(INT32_MAX))
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch x triangles / 256 exceeds the grid limit (2^31 - 1 workgroups)");
+    return TSAMD_OK;
+}
 
 }  // namespace tsamd
 

@@ -7,6 +7,8 @@
 
 namespace tsamd {
 
+inline int64_t pixel_count(int64_t batch, int height, int width) { return batch * int64_t(height) * width; }
+
 // workspace: batch * height * width 64-bit depth keys, then batch * n_vertices 16-byte snapped vertices
 // pair_masks (optional output, 16 bytes per 64 pixels): see antialias_prepare
 hipError_t launch_rasterize(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,

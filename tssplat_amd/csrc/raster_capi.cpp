@@ -1,23 +1,21 @@
 // C ABI of the renderer slice (include/tssplat_amd.h, "renderer" section): stateless entry points, the caller owns
 // every buffer (positions, triangles, the depth-key workspace, outputs) and names the device by making it current.
-#include <climits>
-#include <initializer_list>
-#include <string>
-
 #include "capi_common.h"
 #include "raster.h"
 
 using tsamd::capi_fail;
+using tsamd::check_not_null;
+using tsamd::pixel_count;
 
 namespace {
 
-int check_image(int64_t batch, int32_t height, int32_t width)
+int check_image(int64_t batch, int32_t height, int32_t width) { return tsamd::check_image(batch, height, width, false); }
+
+// the sizes of tsamd_rasterize and of the alpha stage, which bins triangles the same way
+int check_render(int64_t batch, int64_t n_vertices, int64_t n_triangles, int32_t height, int32_t width)
 {
-    // 8192: snapped window coordinates are kept within +-2^22 sub-pixel units (1/256 pixel) = +-16384 pixels and a triangle with a
-    // vertex beyond that is dropped (there is no clipping), so the cap leaves a guard band of at least one screen on every side
-    if (batch < 0 || height < 0 || width < 0 || height > 8192 || width > 8192)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch / height / width out of range (0 .. 8192 pixels per side)");
-    return TSAMD_OK;
+    const int rc = check_image(batch, height, width);
+    return rc ? rc : tsamd::check_mesh_sizes(n_vertices, n_triangles, batch, true);
 }
 
 }  // namespace
@@ -28,7 +26,7 @@ int64_t tsamd_rasterize_workspace_bytes(int64_t batch, int64_t n_vertices, int32
 {
     if (batch < 0 || n_vertices < 0 || height < 0 || width < 0) return -1;
     // depth keys (padded to 16 B) + snapped vertices + one flag per view (has a vertex at w <= 0: near-plane clipping needed)
-    return ((batch * int64_t(height) * int64_t(width) + 1) & ~int64_t(1)) * 8 + batch * n_vertices * 16 + ((batch * 4 + 15) & ~int64_t(15));
+    return ((pixel_count(batch, height, width) + 1) & ~int64_t(1)) * 8 + batch * n_vertices * 16 + ((batch * 4 + 15) & ~int64_t(15));
 }
 
 int64_t tsamd_pair_masks_bytes(int64_t batch, int32_t height, int32_t width)
@@ -40,15 +38,10 @@ int64_t tsamd_pair_masks_bytes(int64_t batch, int32_t height, int32_t width)
 int tsamd_rasterize(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height,
                     int32_t width, void *workspace_dev, float *rast_out_dev, void *pair_masks_out_dev, void *stream)
 {
-    int rc = check_image(batch, height, width);
+    int rc = check_render(batch, n_vertices, n_triangles, height, width);
     if (rc) return rc;
-    if (n_vertices < 0 || n_triangles < 0 || n_triangles > (int64_t(1) << 24) - 1)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "negative size or more than 2^24 - 1 triangles (the id + 1 is returned as a float32, exact up to 2^24)");
-    if ((batch + 7) / 8 * 8 * ((n_triangles + 255) / 256) > int64_t(INT32_MAX))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch x triangles / 256 exceeds the grid limit (2^31 - 1 workgroups)");
-    const int64_t pixels = batch * int64_t(height) * width;
-    if (pixels > 0 && (!workspace_dev || !rast_out_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "workspace_dev / rast_out_dev is null");
-    if (batch * n_triangles > 0 && (!pos_clip_dev || !tri_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "pos_clip_dev / tri_dev is null");
+    if (pixel_count(batch, height, width) > 0 && (rc = check_not_null({{workspace_dev, "workspace_dev"}, {rast_out_dev, "rast_out_dev"}}))) return rc;
+    if (batch * n_triangles > 0 && (rc = check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}}))) return rc;
     TSAMD_HIP(tsamd::launch_rasterize(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, workspace_dev, rast_out_dev,
                                       pair_masks_out_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -61,9 +54,9 @@ int tsamd_interpolate(const float *attr_dev, int64_t attr_batch, int64_t n_verti
     if (rc) return rc;
     if (n_vertices < 0 || n_triangles < 0 || n_channels < 1 || (attr_batch != 1 && attr_batch != batch))
         return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "attr_batch must be 1 or batch, n_channels >= 1, sizes >= 0");
-    const int64_t pixels = batch * int64_t(height) * width;
-    if (pixels > 0 && (!rast_dev || !out_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "rast_dev / out_dev is null");
-    if (pixels > 0 && n_triangles > 0 && (!attr_dev || !tri_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "attr_dev / tri_dev is null");
+    const int64_t pixels = pixel_count(batch, height, width);
+    if (pixels > 0 && (rc = check_not_null({{rast_dev, "rast_dev"}, {out_dev, "out_dev"}}))) return rc;
+    if (pixels > 0 && n_triangles > 0 && (rc = check_not_null({{attr_dev, "attr_dev"}, {tri_dev, "tri_dev"}}))) return rc;
     TSAMD_HIP(tsamd::launch_interpolate(attr_dev, attr_batch, n_vertices, n_channels, rast_dev, tri_dev, n_triangles, batch, height, width, out_dev,
                                         static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -77,10 +70,10 @@ int tsamd_interpolate_backward(const float *attr_dev, int64_t attr_batch, int64_
     if (rc) return rc;
     if (n_vertices < 0 || n_triangles < 0 || n_channels < 1 || (attr_batch != 1 && attr_batch != batch))
         return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "attr_batch must be 1 or batch, n_channels >= 1, sizes >= 0");
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     if (attr_batch * n_vertices > 0 && !grad_attr_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_attr_dev is null");
-    if (pixels > 0 && (!rast_dev || !grad_out_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "rast_dev / grad_out_dev is null");
-    if (pixels > 0 && n_triangles > 0 && (!attr_dev || !tri_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "attr_dev / tri_dev is null");
+    if (pixels > 0 && (rc = check_not_null({{rast_dev, "rast_dev"}, {grad_out_dev, "grad_out_dev"}}))) return rc;
+    if (pixels > 0 && n_triangles > 0 && (rc = check_not_null({{attr_dev, "attr_dev"}, {tri_dev, "tri_dev"}}))) return rc;
     TSAMD_HIP(tsamd::launch_interpolate_backward(attr_dev, attr_batch, n_vertices, n_channels, rast_dev, tri_dev, n_triangles, batch, height, width,
                                                  grad_out_dev, grad_attr_dev, grad_rast_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -92,10 +85,10 @@ int tsamd_rasterize_backward(const float *pos_clip_dev, int64_t batch, int64_t n
     int rc = check_image(batch, height, width);
     if (rc) return rc;
     if (n_vertices < 0 || n_triangles < 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "negative size");
-    const int64_t pixels = batch * int64_t(height) * width;
     if (batch * n_vertices > 0 && !grad_pos_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_pos_dev is null");
-    if (pixels > 0 && n_triangles > 0 && (!pos_clip_dev || !tri_dev || !rast_dev || !grad_rast_dev))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "null device pointer");
+    if (pixel_count(batch, height, width) > 0 && n_triangles > 0 &&
+        (rc = check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {rast_dev, "rast_dev"}, {grad_rast_dev, "grad_rast_dev"}})))
+        return rc;
     TSAMD_HIP(tsamd::launch_rasterize_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, rast_dev, grad_rast_dev,
                                                grad_pos_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -110,7 +103,10 @@ int64_t tsamd_antialias_topology_workspace_bytes(int64_t n_triangles)
 int tsamd_antialias_topology(const int32_t *tri_dev, int64_t n_triangles, void *workspace_dev, int32_t *edge_partner_dev, void *stream)
 {
     if (n_triangles < 0 || n_triangles >= (int64_t(1) << 30)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "n_triangles out of range (0 .. 2^30 - 1)");
-    if (n_triangles > 0 && (!tri_dev || !workspace_dev || !edge_partner_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "null device pointer");
+    if (n_triangles > 0) {
+        const int rc = check_not_null({{tri_dev, "tri_dev"}, {workspace_dev, "workspace_dev"}, {edge_partner_dev, "edge_partner_dev"}});
+        if (rc) return rc;
+    }
     TSAMD_HIP(tsamd::launch_antialias_topology(tri_dev, n_triangles, workspace_dev, edge_partner_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
 }
@@ -137,11 +133,11 @@ int tsamd_antialias_prepare(const float *rast_dev, const float *pos_clip_dev, co
 {
     int rc = check_antialias(batch, n_vertices, n_triangles, height, width, 1);
     if (rc) return rc;
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     if ((pixels > 0 || batch * n_vertices > 0) && !prepared_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "prepared_dev is null");
-    if ((pixels > 0 && !rast_dev && !pair_masks_dev) || (batch * n_vertices > 0 && !pos_clip_dev))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "rast_dev (without pair_masks_dev) / pos_clip_dev is null");
-    if (batch * n_triangles > 0 && (!tri_dev || !edge_partner_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "tri_dev / edge_partner_dev is null");
+    if (pixels > 0 && !rast_dev && !pair_masks_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "without pair_masks_dev, rast_dev is null");
+    if (batch * n_vertices > 0 && !pos_clip_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "pos_clip_dev is null");
+    if (batch * n_triangles > 0 && (rc = check_not_null({{tri_dev, "tri_dev"}, {edge_partner_dev, "edge_partner_dev"}}))) return rc;
     TSAMD_HIP(tsamd::launch_antialias_prepare(rast_dev, pos_clip_dev, tri_dev, edge_partner_dev, pair_masks_dev, batch, n_vertices, n_triangles, height, width,
                                               prepared_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -153,10 +149,9 @@ int tsamd_antialias(const float *color_dev, const float *rast_dev, const float *
 {
     int rc = check_antialias(batch, n_vertices, n_triangles, height, width, n_channels);
     if (rc) return rc;
-    const int64_t pixels = batch * int64_t(height) * width;
-    if (pixels > 0 && (!color_dev || !rast_dev || !out_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "color_dev / rast_dev / out_dev is null");
-    if (pixels > 0 && n_triangles > 0 && (!pos_clip_dev || !tri_dev || !edge_partner_dev))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "pos_clip_dev / tri_dev / edge_partner_dev is null");
+    const int64_t pixels = pixel_count(batch, height, width);
+    if (pixels > 0 && (rc = check_not_null({{color_dev, "color_dev"}, {rast_dev, "rast_dev"}, {out_dev, "out_dev"}}))) return rc;
+    if (pixels > 0 && n_triangles > 0 && (rc = check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {edge_partner_dev, "edge_partner_dev"}}))) return rc;
     TSAMD_HIP(tsamd::launch_antialias(color_dev, rast_dev, pos_clip_dev, prepared_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width,
                                       n_channels, out_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -169,11 +164,10 @@ int tsamd_antialias_backward(const float *color_dev, const float *rast_dev, cons
 {
     int rc = check_antialias(batch, n_vertices, n_triangles, height, width, n_channels);
     if (rc) return rc;
-    const int64_t pixels = batch * int64_t(height) * width;
+    const int64_t pixels = pixel_count(batch, height, width);
     if (!grad_color_dev && !grad_pos_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_color_dev and grad_pos_dev are both null");
-    if (pixels > 0 && (!color_dev || !rast_dev || !grad_out_dev)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "color_dev / rast_dev / grad_out_dev is null");
-    if (pixels > 0 && n_triangles > 0 && (!pos_clip_dev || !tri_dev || !edge_partner_dev))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "pos_clip_dev / tri_dev / edge_partner_dev is null");
+    if (pixels > 0 && (rc = check_not_null({{color_dev, "color_dev"}, {rast_dev, "rast_dev"}, {grad_out_dev, "grad_out_dev"}}))) return rc;
+    if (pixels > 0 && n_triangles > 0 && (rc = check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {edge_partner_dev, "edge_partner_dev"}}))) return rc;
     TSAMD_HIP(tsamd::launch_antialias_backward(color_dev, rast_dev, pos_clip_dev, prepared_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height,
                                                width, n_channels, grad_out_dev, pos_gradient_boost, grad_color_dev, grad_pos_dev,
                                                static_cast<hipStream_t>(stream)));
@@ -181,39 +175,15 @@ int tsamd_antialias_backward(const float *color_dev, const float *rast_dev, cons
 }
 
 namespace {
-// the first null pointer of a list of (pointer, name) pairs, named on its own
-struct NamedPtr {
-    const void *ptr;
-    const char *name;
-};
-int check_not_null(std::initializer_list<NamedPtr> args)
-{
-    for (const NamedPtr &a : args)
-        if (!a.ptr) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(a.name) + " is null");
-    return TSAMD_OK;
-}
-
-// the arguments tsamd_silhouette and its two backward calls share, with the limits and the words of tsamd_rasterize
-int check_silhouette(int64_t batch, int64_t n_vertices, int64_t n_triangles, int32_t height, int32_t width)
-{
-    int rc = check_image(batch, height, width);
-    if (rc) return rc;
-    if (n_vertices < 0 || n_triangles < 0 || n_triangles > (int64_t(1) << 24) - 1)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "negative size or more than 2^24 - 1 triangles (the id + 1 is returned as a float32, exact up to 2^24)");
-    if ((batch + 7) / 8 * 8 * ((n_triangles + 255) / 256) > int64_t(INT32_MAX))
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch x triangles / 256 exceeds the grid limit (2^31 - 1 workgroups)");
-    return TSAMD_OK;
-}
-
+// the arguments the two backward calls of tsamd_silhouette share
 int check_silhouette_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles,
                               const int32_t *edge_partner_dev, int32_t height, int32_t width, const int32_t *ids_dev, const void *cover_masks_dev,
                               const float *grad_pos_dev)
 {
-    int rc = check_silhouette(batch, n_vertices, n_triangles, height, width);
+    int rc = check_render(batch, n_vertices, n_triangles, height, width);
     if (rc) return rc;
-    const int64_t pixels = batch * int64_t(height) * width;
     if (batch * n_vertices > 0 && !grad_pos_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_pos_dev is null");
-    if (pixels <= 0 || batch * n_triangles <= 0) return TSAMD_OK;
+    if (pixel_count(batch, height, width) <= 0 || batch * n_triangles <= 0) return TSAMD_OK;
     return check_not_null({{ids_dev, "ids_dev"}, {cover_masks_dev, "cover_masks_dev"}, {pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"},
                            {edge_partner_dev, "edge_partner_dev"}});
 }
@@ -223,10 +193,9 @@ int tsamd_silhouette(const float *pos_clip_dev, int64_t batch, int64_t n_vertice
                      const int32_t *edge_partner_dev, int32_t height, int32_t width, void *workspace_dev, int32_t *ids_out_dev, void *cover_masks_out_dev,
                      float *alpha_out_dev, void *stream)
 {
-    int rc = check_silhouette(batch, n_vertices, n_triangles, height, width);
+    int rc = check_render(batch, n_vertices, n_triangles, height, width);
     if (rc) return rc;
-    const int64_t pixels = batch * int64_t(height) * width;
-    if (pixels > 0 && (rc = check_not_null({{workspace_dev, "workspace_dev"}, {ids_out_dev, "ids_out_dev"}, {cover_masks_out_dev, "cover_masks_out_dev"},
+    if (pixel_count(batch, height, width) > 0 && (rc = check_not_null({{workspace_dev, "workspace_dev"}, {ids_out_dev, "ids_out_dev"}, {cover_masks_out_dev, "cover_masks_out_dev"},
                                             {alpha_out_dev, "alpha_out_dev"}})))
         return rc;
     if (batch * n_triangles > 0 && (rc = check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {edge_partner_dev, "edge_partner_dev"}}))) return rc;
@@ -244,7 +213,7 @@ int tsamd_silhouette_backward(const float *pos_clip_dev, int64_t batch, int64_t 
     int rc = check_silhouette_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, edge_partner_dev, height, width, ids_dev, cover_masks_dev,
                                        grad_pos_dev);
     if (rc) return rc;
-    if (batch * int64_t(height) * width > 0 && batch * n_triangles > 0 && !grad_alpha_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_alpha_dev is null");
+    if (pixel_count(batch, height, width) > 0 && batch * n_triangles > 0 && !grad_alpha_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_alpha_dev is null");
     TSAMD_HIP(tsamd::launch_silhouette_backward(pos_clip_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width, ids_dev, cover_masks_dev,
                                                 grad_alpha_dev, nullptr, nullptr, nullptr, pos_gradient_boost, grad_pos_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -276,7 +245,7 @@ int tsamd_silhouette_mse_backward(const float *pos_clip_dev, int64_t batch, int6
     int rc = check_silhouette_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, edge_partner_dev, height, width, ids_dev, cover_masks_dev,
                                        grad_pos_dev);
     if (rc) return rc;
-    if (batch * int64_t(height) * width > 0 && batch * n_triangles > 0 &&
+    if (pixel_count(batch, height, width) > 0 && batch * n_triangles > 0 &&
         (rc = check_not_null({{alpha_dev, "alpha_dev"}, {target_dev, "target_dev"}, {grad_loss_dev, "grad_loss_dev"}})))
         return rc;
     TSAMD_HIP(tsamd::launch_silhouette_backward(pos_clip_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width, ids_dev, cover_masks_dev,

@@ -1,47 +1,27 @@
 // C ABI of the texture stage's image side (include/tssplat_amd.h, tsamd_shade*): stateless entry points over a caller-owned blend
 // plan.  Every argument is checked before the first device call.
-#include <initializer_list>
-#include <string>
-
 #include "capi_common.h"
 #include "raster.h"
 #include "shade.h"
 
 using tsamd::capi_fail;
+using tsamd::check_not_null;
+using tsamd::kMaxPixels;
+using tsamd::pixel_count;
 
 namespace {
 
-struct NamedPtr {
-    const void *ptr;
-    const char *name;
-};
-int check_not_null(std::initializer_list<NamedPtr> args)
-{
-    for (const NamedPtr &a : args)
-        if (!a.ptr) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(a.name) + " is null");
-    return TSAMD_OK;
-}
+constexpr int64_t kMaxBlends = (int64_t(1) << 31) - 1;   // record offsets and indices are 32-bit, as pixel indices are (kMaxPixels)
 
-constexpr int64_t kMaxPixels = int64_t(1) << 30;   // pixel and pair-slot (2 per pixel) indices are 32-bit
-constexpr int64_t kMaxBlends = (int64_t(1) << 31) - 1;   // record offsets and indices are 32-bit too
-
-int check_image(int64_t batch, int32_t height, int32_t width)
-{
-    if (batch < 0 || height < 0 || width < 0 || height > 8192 || width > 8192)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch / height / width out of range (0 .. 8192 pixels per side)");
-    if (batch > kMaxPixels || batch * int64_t(height) * width >= kMaxPixels)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "batch x height x width must stay below 2^30 pixels (32-bit pixel and pair indices)");
-    return TSAMD_OK;
-}
+int check_image(int64_t batch, int32_t height, int32_t width) { return tsamd::check_image(batch, height, width, true); }
+int64_t pixels_of(const tsamd_blend_plan *plan) { return pixel_count(plan->batch, plan->height, plan->width); }
 
 int check_plan_extract(const float *rast_dev, const float *pos_clip_dev, const void *prepared_dev, const int32_t *tri_dev, const int32_t *edge_partner_dev, int64_t batch,
                        int64_t n_vertices, int64_t n_triangles, int32_t height, int32_t width)
 {
     int rc = check_image(batch, height, width);
-    if (rc) return rc;
-    if (n_vertices < 0 || n_triangles < 0 || n_triangles > (int64_t(1) << 24) - 1)
-        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "negative size or more than 2^24 - 1 triangles (the id + 1 is returned as a float32, exact up to 2^24)");
-    if (batch * int64_t(height) * width <= 0 || n_triangles == 0 || n_vertices == 0) return TSAMD_OK;
+    if (rc || (rc = tsamd::check_mesh_sizes(n_vertices, n_triangles, batch, false))) return rc;
+    if (pixel_count(batch, height, width) <= 0 || n_triangles == 0 || n_vertices == 0) return TSAMD_OK;
     return check_not_null({{rast_dev, "rast_dev"}, {pos_clip_dev, "pos_clip_dev"}, {prepared_dev, "prepared_dev"}, {tri_dev, "tri_dev"}, {edge_partner_dev, "edge_partner_dev"}});
 }
 
@@ -52,7 +32,7 @@ int check_plan(const tsamd_blend_plan *plan)
     if (plan->struct_size != int32_t(sizeof(tsamd_blend_plan))) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "plan->struct_size is not sizeof(tsamd_blend_plan)");
     int rc = check_image(plan->batch, plan->height, plan->width);
     if (rc) return rc;
-    const int64_t pixels = plan->batch * int64_t(plan->height) * plan->width;
+    const int64_t pixels = pixels_of(plan);
     if (plan->n_points < 0 || plan->n_points > pixels) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "plan->n_points out of range (0 .. batch x height x width)");
     if (plan->n_blends < 0 || plan->n_blends > 6 * pixels || plan->n_blends > kMaxBlends)
         return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "plan->n_blends out of range (0 .. 6 per pixel, at most 2^31 - 1)");
@@ -79,7 +59,7 @@ int tsamd_shade_plan_count(const float *rast_dev, const float *pos_clip_dev, con
 {
     int rc = check_plan_extract(rast_dev, pos_clip_dev, prepared_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width);
     if (rc) return rc;
-    if (batch * int64_t(height) * width <= 0) return TSAMD_OK;
+    if (pixel_count(batch, height, width) <= 0) return TSAMD_OK;
     if (!counts_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "counts_out_dev is null");
     TSAMD_HIP(tsamd::launch_blend_plan(rast_dev, pos_clip_dev, prepared_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width, counts_out_dev,
                                        nullptr, 0, nullptr, nullptr, nullptr, static_cast<hipStream_t>(stream)));
@@ -92,8 +72,7 @@ int tsamd_shade_plan_fill(const float *rast_dev, const float *pos_clip_dev, cons
 {
     int rc = check_plan_extract(rast_dev, pos_clip_dev, prepared_dev, tri_dev, edge_partner_dev, batch, n_vertices, n_triangles, height, width);
     if (rc) return rc;
-    const int64_t pixels = batch * int64_t(height) * width;
-    if (n_blends < 0 || n_blends > 6 * pixels || n_blends > kMaxBlends)
+    if (n_blends < 0 || n_blends > 6 * pixel_count(batch, height, width) || n_blends > kMaxBlends)
         return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "n_blends out of range (0 .. 6 per pixel, at most 2^31 - 1)");
     if (n_blends == 0) return TSAMD_OK;
     if ((rc = check_not_null({{offsets_dev, "offsets_dev"}, {dst_out_dev, "dst_out_dev"}, {src_out_dev, "src_out_dev"}, {weight_out_dev, "weight_out_dev"}}))) return rc;
@@ -107,7 +86,7 @@ int tsamd_shade(const tsamd_blend_plan *plan, const float *color_dev, const floa
     int rc = check_plan(plan);
     if (rc) return rc;
     if (plan->n_points > 0 && !color_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "color_dev is null");
-    if (plan->batch * int64_t(plan->height) * plan->width > 0 && (rc = check_not_null({{background_dev, "background_dev"}, {out_dev, "out_dev"}}))) return rc;
+    if (pixels_of(plan) > 0 && (rc = check_not_null({{background_dev, "background_dev"}, {out_dev, "out_dev"}}))) return rc;
     TSAMD_HIP(tsamd::launch_shade(*plan, color_dev, background_dev, out_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
 }
@@ -135,7 +114,7 @@ int tsamd_shade_l1(const tsamd_blend_plan *plan, const float *color_dev, const f
     if (target_channels != 3 && target_channels != 4) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "target_channels must be 3 or 4");
     if (!loss_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "loss_out_dev is null");
     if (plan->n_points > 0 && !color_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "color_dev is null");
-    if (plan->batch * int64_t(plan->height) * plan->width > 0 &&
+    if (pixels_of(plan) > 0 &&
         (rc = check_not_null({{background_dev, "background_dev"}, {target_dev, "target_dev"}, {workspace_dev, "workspace_dev"}})))
         return rc;
     const bool want_signs = point_sign_out_dev || dst_sign_out_dev;

@@ -11,15 +11,14 @@
 //              partials added in a fixed order by a second kernel, float(sum / n)
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
+#include "det_mean.h"
 #include "shade.h"
 
 namespace tsamd {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kMaxBlocks = 2048;   // 8 workgroups per CU: the loss kernel's fixed grid
+constexpr int kBlock = kMeanBlock;   // (the loss kernel sums its lanes with det_mean.h's tree)
+constexpr int kMaxBlocks = 2048;     // 8 workgroups per CU: the loss kernel's fixed grid, one pixel per lane and pass
 
 struct Rgb {
     float x, y, z;
@@ -124,15 +123,6 @@ __global__ __launch_bounds__(kBlock) void shade_l1_backward_kernel(tsamd_blend_p
     store3(grad_color, k, acc);
 }
 
-__device__ __forceinline__ double block_sum(double v, double *lds)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + (lds[2] + lds[3]));
-}
-
 __global__ __launch_bounds__(kBlock) void shade_l1_kernel(tsamd_blend_plan P, const float *color, const float *background, const float *target, int target_channels,
                                                           int64_t pixels, double *partials, float *image_out, float *point_sign, float *dst_sign)
 {
@@ -156,17 +146,8 @@ __global__ __launch_bounds__(kBlock) void shade_l1_kernel(tsamd_blend_plan P, co
     if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
-__global__ __launch_bounds__(kBlock) void shade_l1_final_kernel(const double *partials, int n_partials, int64_t n, float *loss)
-{
-    __shared__ double lds[kBlock / 64];
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < n_partials; k += kBlock) acc += partials[k];
-    const double sum = block_sum(acc, lds);
-    if (threadIdx.x == 0) *loss = float(sum / double(n));
-}
-
 unsigned blocks_for(int64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
-int l1_blocks(int64_t pixels) { return int(std::min<int64_t>(kMaxBlocks, std::max<int64_t>(1, (pixels + kBlock - 1) / kBlock))); }
+int l1_blocks(int64_t pixels) { return mean_blocks(pixels, kBlock, kMaxBlocks); }
 int64_t pixels_of(const tsamd_blend_plan &plan) { return plan.batch * int64_t(plan.height) * plan.width; }
 
 }  // namespace
@@ -186,7 +167,7 @@ hipError_t launch_shade_backward(const tsamd_blend_plan &plan, const float *grad
     return hipGetLastError();
 }
 
-int64_t shade_l1_workspace_bytes(int64_t pixels) { return (int64_t(l1_blocks(pixels)) * 8 + 255) / 256 * 256; }
+int64_t shade_l1_workspace_bytes(int64_t pixels) { return mean_workspace_bytes(l1_blocks(pixels)); }
 
 hipError_t launch_shade_l1(const tsamd_blend_plan &plan, const float *color, const float *background, const float *target, int target_channels, void *workspace,
                            float *loss, float *image_out, float *point_sign_out, float *dst_sign_out, hipStream_t stream)
@@ -196,10 +177,8 @@ hipError_t launch_shade_l1(const tsamd_blend_plan &plan, const float *color, con
     const int blocks = l1_blocks(pixels);
     hipLaunchKernelGGL(shade_l1_kernel, dim3(blocks), dim3(kBlock), 0, stream, plan, color, background, target, target_channels, pixels, static_cast<double *>(workspace),
                        image_out, point_sign_out, dst_sign_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(shade_l1_final_kernel, dim3(1), dim3(kBlock), 0, stream, static_cast<const double *>(workspace), blocks, 3 * pixels, loss);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, 3 * pixels, loss, stream);
 }
 
 hipError_t launch_shade_l1_backward(const tsamd_blend_plan &plan, const float *point_sign, const float *dst_sign, const float *grad_loss, float *grad_color,

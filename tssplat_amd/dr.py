@@ -78,6 +78,11 @@ def _check_cuda_f32(name: str, t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def _ptr(t):
+    """The address of ``t`` for the C ABI; ``None`` (a null pointer) for ``None`` or an empty tensor."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
 # TSSPLAT_AMD_DR_CHECK=1: count, on every rasterize call, the triangles this slice DROPS -- a vertex that is not finite or
 # outside the +-16384-pixel guard band (a finite vertex at w <= 0 is clipped against the near plane, not dropped) -- and warn.
 # A device read per call: a debugging aid, off by default (objects inside the frustum, the reference's case, lose nothing).
@@ -107,6 +112,26 @@ def _warn_dropped(pos, tri, height, width) -> None:
                       f"guard band and are DROPPED whole", RuntimeWarning, stacklevel=3)
 
 
+def _check_pos(name: str, pos: torch.Tensor, batch=None) -> torch.Tensor:
+    pos = _check_cuda_f32("pos", pos)
+    if pos.dim() != 3 or pos.shape[2] != 4 or (batch is not None and pos.shape[0] != batch):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: pos must be [B, V, 4] clip-space positions (instanced mode)")
+    return pos
+
+
+def _check_resolution(name: str, resolution, n_triangles: int):
+    """``(height, width)`` within the limits of this slice (include/tssplat_amd.h): the triangle id + 1 travels as a float32 (exact
+    up to 2^24), and window coordinates are snapped within +-16384 pixels -- a triangle with a vertex beyond that guard band is
+    dropped whole (one with vertices at w <= 0 is clipped against the near plane): harmless for objects inside the frustum, which
+    the reference renders."""
+    height, width = int(resolution[0]), int(resolution[1])
+    if n_triangles > (1 << 24) - 1:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: more than 2^24 - 1 triangles")
+    if not (0 <= height <= 8192 and 0 <= width <= 8192):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: resolution out of range (0 .. 8192 pixels per side)")
+    return height, width
+
+
 def _check_tri(tri: torch.Tensor, device) -> torch.Tensor:
     if not isinstance(tri, torch.Tensor) or tri.dim() != 2 or tri.shape[1] != 3:
         raise RuntimeError("tssplat_amd.dr: tri must be an [T, 3] tensor")
@@ -127,7 +152,7 @@ class _RasterizeFunc(torch.autograd.Function):
         ws = glctx.workspace(B, V, height, width, pos.device)
         with _device_ctx(pos.device):
             _capi.check(_lib.tsamd_rasterize(pos.data_ptr(), B, V, tri.data_ptr(), int(tri.shape[0]), height, width, ws.data_ptr(),
-                                             rast.data_ptr(), None if pair_masks is None else pair_masks.data_ptr(), _stream_ptr(pos.device)))
+                                             rast.data_ptr(), _ptr(pair_masks), _stream_ptr(pos.device)))
         ctx.save_for_backward(pos, tri, rast)
         return rast
 
@@ -173,18 +198,9 @@ def rasterize(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor,
         raise NotImplementedError("tssplat_amd.dr.rasterize: range mode is not supported")
     if grad_db:
         raise NotImplementedError("tssplat_amd.dr.rasterize: grad_db=True is not supported (the reference passes grad_db=False)")
-    pos = _check_cuda_f32("pos", pos)
-    if pos.dim() != 3 or pos.shape[2] != 4:
-        raise RuntimeError("tssplat_amd.dr.rasterize: pos must be [B, V, 4] clip-space positions (instanced mode)")
+    pos = _check_pos("rasterize", pos)
     tri = _check_tri(tri, pos.device)
-    height, width = int(resolution[0]), int(resolution[1])
-    # limits of this slice (include/tssplat_amd.h): the triangle id + 1 travels as a float32 (exact up to 2^24), and window
-    # coordinates are snapped within +-16384 pixels -- a triangle with a vertex beyond that guard band is dropped whole (one with
-    # vertices at w <= 0 is clipped against the near plane): harmless for objects inside the frustum, which the reference renders
-    if int(tri.shape[0]) > (1 << 24) - 1:
-        raise RuntimeError("tssplat_amd.dr.rasterize: more than 2^24 - 1 triangles")
-    if not (0 <= height <= 8192 and 0 <= width <= 8192):
-        raise RuntimeError("tssplat_amd.dr.rasterize: resolution out of range (0 .. 8192 pixels per side)")
+    height, width = _check_resolution("rasterize", resolution, int(tri.shape[0]))
     if _CHECK_DROPPED and tri.shape[0] > 0:
         _warn_dropped(pos, tri, height, width)
     masks = None
@@ -220,8 +236,7 @@ class _InterpolateFunc(torch.autograd.Function):
         grad_rast = torch.empty_like(rast) if ctx.needs_input_grad[1] else None
         with _device_ctx(rast.device):
             _capi.check(_lib.tsamd_interpolate_backward(attr.data_ptr(), A, V, Cn, rast.data_ptr(), tri.data_ptr(), int(tri.shape[0]), B, H, W, g.data_ptr(),
-                                                        grad_attr.data_ptr(), None if grad_rast is None else grad_rast.data_ptr(),
-                                                        _stream_ptr(rast.device)))
+                                                        grad_attr.data_ptr(), _ptr(grad_rast), _stream_ptr(rast.device)))
         return grad_attr, grad_rast, None
 
 
@@ -283,6 +298,18 @@ def _topology_for(tri: torch.Tensor) -> TopologyHash:
     return topo
 
 
+def _mesh_args(name: str, pos, tri, topology_hash, device=None):
+    """``(pos, tri, topo)`` of an operator that analyses silhouette edges: ``pos[B, V, 4]``, ``tri[T, 3]`` on ``device`` (default:
+    where ``pos`` lives) and the edge partner table -- ``topology_hash``, or the kept one of this triangle list."""
+    pos = _check_pos(name, pos)
+    device = pos.device if device is None else device
+    tri = _check_tri(tri, device)
+    topo = _topology_for(tri) if topology_hash is None else topology_hash
+    if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != device:
+        raise RuntimeError(f"tssplat_amd.dr.{name}: topology_hash does not belong to this triangle list")
+    return pos, tri, topo
+
+
 # None: decide per call (see _AntialiasFunc.forward); True / False force the prepared / the per-pair form of the antialias analysis
 PREPARE_ANTIALIAS = None
 
@@ -302,8 +329,8 @@ class _AntialiasFunc(torch.autograd.Function):
         with _device_ctx(color.device):
             stream = _stream_ptr(color.device)
             if prepare:
-                _capi.check(_lib.tsamd_antialias_prepare(rast.data_ptr(), pos.data_ptr(), tri.data_ptr(), opp.data_ptr(),
-                                                         None if pair_masks is None else pair_masks.data_ptr(), B, V, T, H, W, win.data_ptr(), stream))
+                _capi.check(_lib.tsamd_antialias_prepare(rast.data_ptr(), pos.data_ptr(), tri.data_ptr(), opp.data_ptr(), _ptr(pair_masks), B, V, T, H, W,
+                                                         win.data_ptr(), stream))
             _capi.check(_lib.tsamd_antialias(color.data_ptr(), rast.data_ptr(), pos.data_ptr(), win.data_ptr() if prepare else None, tri.data_ptr(),
                                              opp.data_ptr(), B, V, T, H, W, Cn, out.data_ptr(), stream))
         ctx.save_for_backward(color, rast, pos, tri, opp, win)
@@ -321,10 +348,8 @@ class _AntialiasFunc(torch.autograd.Function):
         if grad_color is None and grad_pos is None:
             return None, None, None, None, None, None, None
         with _device_ctx(color.device):
-            _capi.check(_lib.tsamd_antialias_backward(color.data_ptr(), rast.data_ptr(), pos.data_ptr(), win.data_ptr() if win.numel() else None,
-                                                      tri.data_ptr(), opp.data_ptr(),
-                                                      B, V, T, H, W, Cn, g.data_ptr(), ctx.boost, None if grad_color is None else grad_color.data_ptr(),
-                                                      None if grad_pos is None else grad_pos.data_ptr(), _stream_ptr(color.device)))
+            _capi.check(_lib.tsamd_antialias_backward(color.data_ptr(), rast.data_ptr(), pos.data_ptr(), _ptr(win), tri.data_ptr(), opp.data_ptr(),
+                                                      B, V, T, H, W, Cn, g.data_ptr(), ctx.boost, _ptr(grad_color), _ptr(grad_pos), _stream_ptr(color.device)))
         return grad_color, None, grad_pos, None, None, None, None
 
 
@@ -337,32 +362,19 @@ def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: t
     pos = _check_cuda_f32("pos", pos)
     if color.dim() != 4 or rast.dim() != 4 or rast.shape[3] != 4 or tuple(color.shape[:3]) != tuple(rast.shape[:3]):
         raise RuntimeError("tssplat_amd.dr.antialias: color must be [B, H, W, C] and rast [B, H, W, 4] of the same image size")
-    if pos.dim() != 3 or pos.shape[2] != 4 or pos.shape[0] != rast.shape[0]:
-        raise RuntimeError("tssplat_amd.dr.antialias: pos must be [B, V, 4] clip-space positions (instanced mode)")
+    pos = _check_pos("antialias", pos, rast.shape[0])
     if color.device != rast.device or pos.device != rast.device:
         raise RuntimeError("tssplat_amd.dr.antialias: color, rast and pos must live on the same device")
-    tri = _check_tri(tri, rast.device)
-    topo = _topology_for(tri) if topology_hash is None else topology_hash
-    if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != rast.device:
-        raise RuntimeError("tssplat_amd.dr.antialias: topology_hash does not belong to this triangle list")
+    pos, tri, topo = _mesh_args("antialias", pos, tri, topology_hash, rast.device)
     return _AntialiasFunc.apply(color, rast, pos, tri, topo.opp, float(pos_gradient_boost), pair_masks)
 
 
 # ---- the alpha stage without a rast image ----
 
 def _silhouette_args(name: str, pos, tri, resolution, topology_hash):
-    pos = _check_cuda_f32("pos", pos)
-    if pos.dim() != 3 or pos.shape[2] != 4:
-        raise RuntimeError(f"tssplat_amd.dr.{name}: pos must be [B, V, 4] clip-space positions (instanced mode)")
-    tri = _check_tri(tri, pos.device)
-    height, width = int(resolution[0]), int(resolution[1])
-    if int(tri.shape[0]) > (1 << 24) - 1:
-        raise RuntimeError(f"tssplat_amd.dr.{name}: more than 2^24 - 1 triangles")
-    if not (0 <= height <= 8192 and 0 <= width <= 8192):
-        raise RuntimeError(f"tssplat_amd.dr.{name}: resolution out of range (0 .. 8192 pixels per side)")
-    topo = _topology_for(tri) if topology_hash is None else topology_hash
-    if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != pos.device:
-        raise RuntimeError(f"tssplat_amd.dr.{name}: topology_hash does not belong to this triangle list")
+    pos = _check_pos(name, pos)
+    height, width = _check_resolution(name, resolution, int(_check_tri(tri, pos.device).shape[0]))   # (the limits before a partner table is built)
+    pos, tri, topo = _mesh_args(name, pos, tri, topology_hash)
     return pos, tri, height, width, topo
 
 
@@ -479,7 +491,7 @@ class BlendPlan:
         st.n_points, st.n_blends, st.n_dst, st.n_src = self.n_points, self.n_blends, self.n_dst, self.n_src
         for name in self._STRUCT_FIELDS:
             t = getattr(self, name)
-            setattr(st, name + "_dev", t.data_ptr() if t.numel() else None)
+            setattr(st, name + "_dev", _ptr(t))
         self._struct = st
 
     def tensors(self) -> dict:
@@ -512,17 +524,12 @@ def plan_blends(rast: torch.Tensor, pos: torch.Tensor, tri: torch.Tensor, topolo
     ``float32(|t - 1/2|)``.  Runs once per plan: the records come from a count / scan / fill pass of the antialias analysis, the
     two groupings from stable sorts; it synchronises with the host (two sizes are read back)."""
     rast = _check_cuda_f32("rast", rast.detach())
-    pos = _check_cuda_f32("pos", pos.detach())
     if rast.dim() != 4 or rast.shape[3] != 4:
         raise RuntimeError("tssplat_amd.dr.plan_blends: rast must be [B, H, W, 4]")
-    if pos.dim() != 3 or pos.shape[2] != 4 or pos.shape[0] != rast.shape[0]:
-        raise RuntimeError("tssplat_amd.dr.plan_blends: pos must be [B, V, 4] clip-space positions (instanced mode)")
+    pos = _check_pos("plan_blends", pos, rast.shape[0]).detach()
     if pos.device != rast.device:
         raise RuntimeError("tssplat_amd.dr.plan_blends: rast and pos must live on the same device")
-    tri = _check_tri(tri, rast.device)
-    topo = _topology_for(tri) if topology_hash is None else topology_hash
-    if not isinstance(topo, TopologyHash) or topo.n_triangles != int(tri.shape[0]) or topo.opp.device != rast.device:
-        raise RuntimeError("tssplat_amd.dr.plan_blends: topology_hash does not belong to this triangle list")
+    pos, tri, topo = _mesh_args("plan_blends", pos, tri, topology_hash, rast.device)
     B, H, W = (int(k) for k in rast.shape[:3])
     V, T, P = int(pos.shape[1]), int(tri.shape[0]), B * H * W
     if P >= 1 << 30:
@@ -624,10 +631,9 @@ class _ShadeL1Func(torch.autograd.Function):
         point_sign = torch.empty((plan.n_points, 3), dtype=torch.float32, device=dev) if need_grad else None
         dst_sign = torch.empty((plan.n_dst, 3), dtype=torch.float32, device=dev) if need_grad else None
         ws = torch.empty((int(_lib.tsamd_shade_l1_workspace_bytes(plan.batch * plan.height * plan.width)),), dtype=torch.uint8, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
         with _device_ctx(dev):
             _capi.check(_lib.tsamd_shade_l1(plan._struct, color.data_ptr(), background.data_ptr(), target.data_ptr(), int(target.shape[3]), ws.data_ptr(),
-                                            loss.data_ptr(), ptr(image), ptr(point_sign), ptr(dst_sign), _stream_ptr(dev)))
+                                            loss.data_ptr(), _ptr(image), _ptr(point_sign), _ptr(dst_sign), _stream_ptr(dev)))
         ctx.plan = plan
         if need_grad:
             ctx.save_for_backward(point_sign, dst_sign)
@@ -641,9 +647,7 @@ class _ShadeL1Func(torch.autograd.Function):
         g = grad_loss.to(torch.float32).contiguous()            # stays on the device: the kernel reads it there
         grad_color = torch.empty((plan.n_points, 3), dtype=torch.float32, device=g.device)
         with _device_ctx(g.device):
-            _capi.check(_lib.tsamd_shade_l1_backward(plan._struct, point_sign.data_ptr() if point_sign.numel() else None,
-                                                     dst_sign.data_ptr() if dst_sign.numel() else None, g.data_ptr(), grad_color.data_ptr(),
-                                                     _stream_ptr(g.device)))
+            _capi.check(_lib.tsamd_shade_l1_backward(plan._struct, _ptr(point_sign), _ptr(dst_sign), g.data_ptr(), grad_color.data_ptr(), _stream_ptr(g.device)))
         return grad_color, None, None, None, None
 
 
@@ -687,8 +691,7 @@ class _TextureFunc(torch.autograd.Function):
         if grad_tex is not None or grad_uv is not None:
             with _device_ctx(uv.device):
                 _capi.check(_lib.tsamd_texture_backward(tex.data_ptr(), TB, TH, TW, Cn, uv.data_ptr(), B, H, W, filter_mode, boundary_mode, g.data_ptr(),
-                                                        None if grad_tex is None else grad_tex.data_ptr(),
-                                                        None if grad_uv is None else grad_uv.data_ptr(), _stream_ptr(uv.device)))
+                                                        _ptr(grad_tex), _ptr(grad_uv), _stream_ptr(uv.device)))
         return grad_tex, grad_uv, None, None
 
 
