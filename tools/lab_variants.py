@@ -300,17 +300,6 @@ struct FinishArgs {"""),
         (K, '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n', '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n' + "    " + '__builtin_amdgcn_s_setprio(2);\n'),
         (K, '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n', '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
     ]),
-    "asmpart": ("the tile's energy terms stored by an untracked (inline asm) store: no vmcnt(0) at the join of the lane-0 branch, the last wave does not start pass 3 behind a store acknowledgement", [
-        (K, """            if (lane == 0) {
-                g_partials[2 * size_t(tile)] = s;
-                g_partials[2 * size_t(tile) + 1] = b;
-            }""", """            {
-                const v2u sw = __builtin_bit_cast(v2u, s), bw = __builtin_bit_cast(v2u, b);
-                const v4u val = {uint32_t(__builtin_amdgcn_readlane(int(sw.x), 0)), uint32_t(__builtin_amdgcn_readlane(int(sw.y), 0)),
-                                 uint32_t(__builtin_amdgcn_readlane(int(bw.x), 0)), uint32_t(__builtin_amdgcn_readlane(int(bw.y), 0))};
-                GLOBAL_AS double *dst = g_partials + 2 * size_t(tile);
-                asm volatile("global_store_dwordx4 %0, %1, off" : : "v"(dst), "v"(val) : "memory");
-            }""")]),
     "identblocks": ("vertex blocks of the per-vertex sums in wave order (no reversal of waves 4-7)", [
         (K, "        if (wave & 4) {   // (a permutation", "        if (false) {   // (a permutation")]),
 }
@@ -402,28 +391,56 @@ VARIANTS["stamps"] = ("product kernel + 100 MHz phase timestamps of wave 0 in si
     (K, "    __syncthreads();\n    // behind the barrier: what pass 2 and the end of the tile need", "    __syncthreads();\n    ts[1] = @T@;\n    // behind the barrier: what pass 2 and the end of the tile need"),
     (K, "    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----", "    ts[2] = @T@;\n    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----"),
     (K, "    __syncthreads();  // every read of F is done; overwrite it with H in place", "    __syncthreads();  // every read of F is done; overwrite it with H in place\n    ts[3] = @T@;"),
-    (K, "        publish_wave_sums();\n        __syncthreads();\n        sum_waves();\n", "        publish_wave_sums();\n        __syncthreads();\n        ts[4] = @T@;\n        sum_waves();\n"),
+    (K, "        publish_wave_sums();\n        __syncthreads();   // (the wave pairs are in red[]; sum_waves() at the end of the tile)\n",
+        "        publish_wave_sums();\n        __syncthreads();   // (the wave pairs are in red[]; sum_waves() at the end of the tile)\n        ts[4] = @T@;\n"),
     (K, "        __syncthreads();   // all waves done with H and with the staged positions", "        __syncthreads();   // all waves done with H and with the staged positions\n        ts[5] = @T@;"),
     (K, "        __syncthreads();\n\n        // ---- per-vertex sums: lane = vertex", "        __syncthreads();\n        ts[6] = @T@;\n\n        // ---- per-vertex sums: lane = vertex"),
-    (K, "    }\n#undef t_own\n}", """        ts[7] = @T@;
+    (K, "    }\n#undef t_own\n", """        ts[7] = @T@;
         if ((tid == 0 || tid == 704) && @BLK@)
             printf("blk %d wave %d (x10 ns): positions %llu pass1 %llu pass2 %llu H-stored %llu pass3 %llu scatter %llu sums+stores %llu | total %llu\\n", int(blockIdx.x), tid >> 6,
                    ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6], ts[7] - ts[0]);
     }
 #undef t_own
-}""")]])
+""")]])
 
 # ... and the inside of the per-vertex sums (wave 0 = the block of the fullest vertices): row loop / wait for the destination ids / stores issued
 VARIANTS["stamps2"] = ("stamps + the per-vertex sums split into row loop, wait for vdst, stores", [(_f, _o, _n.replace("@T@", _T).replace("@BLK@", _BLK)) for _f, _o, _n in [
     (K, "    const TileDesc td = a.tiles[tile];", "    unsigned long long ts[4];\n    int sum_rows = 0;\n    const TileDesc td = a.tiles[tile];"),
     (K, "        __syncthreads();\n\n        // ---- per-vertex sums: lane = vertex", "        __syncthreads();\n        ts[0] = @T@;\n\n        // ---- per-vertex sums: lane = vertex"),
     (K, "            if (v < td.n_verts) {\n                const bool excl = row >= 0;", "            sum_rows = rows;\n            asm volatile(\"\" : \"+v\"(gx), \"+v\"(gy), \"+v\"(gz));\n            ts[1] = @T@;\n            asm volatile(\"\" : \"+v\"(row));\n            asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n            ts[2] = @T@;\n            if (v < td.n_verts) {\n                const bool excl = row >= 0;"),
-    (K, "    }\n#undef t_own\n}", """        ts[3] = @T@;
+    (K, "    }\n#undef t_own\n", """        ts[3] = @T@;
         if ((tid == 0 || tid == 64 || tid == 192) && @BLK@)
             printf("blk %d wave %d (x10 ns): rows %d: row loop %llu, wait for vdst %llu, stores issued %llu\\n", int(blockIdx.x), tid >> 6, sum_rows, ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2]);
     }
 #undef t_own
-}""")]])
+""")]])
+
+# Is the acknowledgement of the energy-partial store on the workgroup's critical path?  Wave 0 and the LAST wave (the one that adds up the wave
+# pairs and stores the tile's (E_s, E_b)) of the same six workgroups, all times from the H-store barrier on: `drained` = an explicit
+# s_waitcnt vmcnt(0) where the compiler's own stands at the head of pass 3 (behind the store in `ack_stamps_early`: the store's acknowledgement),
+# `pass3 done` = the wave arrives at the pre-scatter barrier, `barrier left` = the workgroup's last wave has arrived, then scatter, sums + stores
+# (wave 0: the row walk, whose first trip holds the compiler's other vmcnt(0), for dst_row) and `partials acked` = the reduction at the end of the tile
+# and the acknowledgement of its store.  t0 (the low digits of the 100 MHz clock at the H-store barrier) puts the two waves of a workgroup on one axis.
+_ACK = [(_f, _o, _n.replace("@T@", _T).replace("@BLK@", _BLK)) for _f, _o, _n in [
+    (K, "    const TileDesc td = a.tiles[tile];", "    unsigned long long ts[7];\n    const TileDesc td = a.tiles[tile];"),
+    (K, "        __syncthreads();   // (the wave pairs are in red[]; sum_waves() at the end of the tile)\n",
+        "        __syncthreads();   // (the wave pairs are in red[]; sum_waves() at the end of the tile)\n        ts[0] = @T@;\n        //@EARLY@\n"
+        "        asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n        ts[1] = @T@;\n"),
+    (K, "        __syncthreads();   // all waves done with H and with the staged positions", "        ts[2] = @T@;\n        __syncthreads();   // all waves done with H and with the staged positions\n        ts[3] = @T@;"),
+    (K, "        __syncthreads();\n\n        // ---- per-vertex sums: lane = vertex", "        __syncthreads();\n        ts[4] = @T@;\n\n        // ---- per-vertex sums: lane = vertex"),
+    (K, "        sum_waves();   // the tile's (E_s, E_b): the last wave's last instruction, its acknowledgement behind wave 0's row walk\n    }\n", """        ts[5] = @T@;
+        //@LATE@
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ts[6] = @T@;
+        if ((tid == 0 || (nw > 1 && tid == 64 * (nw - 1))) && @BLK@)
+            printf("blk %d wave %d of %d (x10 ns from the H-store barrier, t0 %llu): drained %llu pass3 done %llu barrier left %llu scatter done %llu sums+stores done %llu partials acked %llu\\n",
+                   int(blockIdx.x), wave, nw, ts[0] % 100000ull, ts[1] - ts[0], ts[2] - ts[0], ts[3] - ts[0], ts[4] - ts[0], ts[5] - ts[0], ts[6] - ts[0]);
+    }
+""")]]
+VARIANTS["ack_stamps"] = ("product kernel + stamps of wave 0 and the last wave around pass 3 and the end of the tile (printf; run a handful of evaluations only)",
+                          [(_f, _o, _n.replace("//@LATE@", "sum_waves();").replace("        //@EARLY@\n", "")) for _f, _o, _n in _ACK])
+VARIANTS["ack_stamps_early"] = ("ack_stamps with the reduction where it stood before: right behind the H-store barrier, its store in front of pass 3",
+                                [(_f, _o, _n.replace("//@EARLY@", "sum_waves();").replace("        //@LATE@\n", "")) for _f, _o, _n in _ACK])
 
 # candidate (round 6, from the stamps): the row loop of the per-vertex sums is one wave's dependent chain -- ~45 instructions per four rows, then a
 # wait for eight LDS reads: 0.17 us per trip, 2.3 us for a.veg's 56-row hubs (wave 0 is the last wave of its workgroup by that much).  Two trips in

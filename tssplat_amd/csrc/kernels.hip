@@ -561,9 +561,10 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
             for (int c = 0; c < 9; ++c) UNDEF(H[p][c]);
     }
     // ---- the two energy terms are complete: deterministic block reduction (fixed order; doubles across waves) ----
-    // Done HERE, around a barrier the tile needs anyway, not at the end of the kernel: there the reduction was a serial
-    // tail (wave sums, a barrier, one lane summing the waves) between this workgroup and its successor on the CU,
-    // and the kernel time follows that tail at better than 1 : 1.
+    // The wave sums are published HERE, in front of a barrier the tile needs anyway, not at the end of the kernel: there the
+    // reduction was a serial tail (wave sums, a barrier, one lane summing the waves) between this workgroup and its successor
+    // on the CU, and the kernel time follows that tail at better than 1 : 1.  (What the gradient kernels do leave for the end
+    // -- kSumLate below -- needs no barrier and sits in a wave that has, as a rule, no vertex block to walk.)
     const int wave = tid / kWave, lane = tid % kWave, nw = (nthr + kWave - 1) / kWave;
     auto publish_wave_sums = [&]() {
         e_s = wave_sum(e_s);
@@ -584,8 +585,14 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
             }
         }
     };
-    // With a gradient the wave sums go out behind the H stores (their DPP chain overlaps the stores' drain) and are added
-    // up after the next barrier, inside pass 3: tile kernel -0.5 % against doing both around the barrier after pass 2.
+    // With a gradient the wave sums go out behind the H stores (their DPP chain overlaps the stores' drain: tile kernel -0.5 %
+    // against doing both around the barrier after pass 2) and the last wave adds them up as the LAST thing it does, behind its
+    // vertex sums: red[] lies below the records and nothing writes it again.  Added up right behind the H-store barrier, the
+    // conditional store of the pair made pass 3 of that wave begin with a full drain (the opaque copy of the neighbour planes
+    // needs their load landed, and behind a branch the compiler can only wait for vmcnt(0)), i.e. with the acknowledgement of
+    // its own 16-byte store, while the workgroup's other waves waited for it at the barrier after pass 3.  At the end the
+    // acknowledgement overlaps wave 0's row walk: no global store precedes the tile's last barrier
+    // (tests/test_tile_store_placement.py).
     constexpr bool kSumLate = WITH_GRAD;
     if (!kSumLate) publish_wave_sums();
     __syncthreads();  // every read of F is done; overwrite it with H in place
@@ -603,8 +610,7 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
             }
         }
         publish_wave_sums();
-        __syncthreads();
-        sum_waves();
+        __syncthreads();   // (the wave pairs are in red[]; sum_waves() at the end of the tile)
 
         // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----
         STAGE_PRIORITY(2);
@@ -745,6 +751,7 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
             for (int vb = vb0 + nw; 64 * vb < td.n_verts; vb += nw)
                 vertex_sums(vb, 64 * vb + lane < td.n_verts ? g_vdst[td.vert_off + 64 * vb + lane] : 0);
         }
+        sum_waves();   // the tile's (E_s, E_b): the last wave's last instruction, its acknowledgement behind wave 0's row walk
     }
 #undef t_own
 #undef INDEX_LOAD
