@@ -14,10 +14,18 @@ absent):
   grad_limit 0.01)`, cosine schedule, order 2 -> 4 at iteration 1 000, smooth_eng_coeff / n_spheres (tetmesh_geometry.py:242).
 
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
+                                 [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
 
 --silhouette: how the loop renders alpha and takes the image loss -- `operators` (the default: rasterize, clamp, antialias, MSELoss),
 `fused` (MeshRasterizer(fused_silhouette=True): dr.silhouette, then MSELoss) or `fused-loss` (MeshRasterizer.silhouette_loss:
 dr.silhouette_mse, no gradient image).  --no-stages: leave out the stand-alone stage timings (`stages_ms`).
+
+--fit-depth: the trainer's depth term (trainer.py:77-79, :106-109: `+ MSE(d * a_ref, d_ref * a_ref) * 100` once `it` has passed
+--fit-depth-start) -- `operators` (forward(fit_depth=True): rasterize, antialias, interpolate, norm, two MSELoss calls) or
+`fused-loss` (MeshRasterizer.silhouette_depth_loss: one rasterisation, no image chain); before the start the loop is --silhouette's.
+The target distances are rendered once, without gradients, from the target mesh by the operator chain.  --depth-bench PATH: both
+modes on the same seed plus the depth stage timings (median of five repeats of 200 iterations, HIP events), written to PATH
+(profiles/depth_bench.json).
 
 One JSON line: silhouette IoU over all views, inverted tets, seconds per iteration and the stand-alone stage times."""
 import argparse
@@ -40,6 +48,17 @@ def render_alpha(glctx, verts, tri, mvp, res):
     rast, _ = dr.rasterize(glctx, pos_clip, tri, resolution=[res, res], grad_db=False)
     alpha = torch.clamp(rast[..., -1:], 0, 1).contiguous()
     return dr.antialias(alpha, rast, pos_clip, tri)
+
+
+def render_depth(glctx, verts, tri, mvp, campos, res):
+    """Distance-to-camera image of a triangle mesh, `[B, H, W, 1]`: the depth branch of MeshRasterizer.forward (mesh_rasterizer.py:150-161)."""
+    import torch
+    import tssplat_amd.dr as dr
+    posw = torch.cat([verts, torch.ones_like(verts[:, :1])], dim=1)
+    pos_clip = torch.matmul(posw, mvp.transpose(1, 2)).contiguous()
+    rast, _ = dr.rasterize(glctx, pos_clip, tri, resolution=[res, res], grad_db=False)
+    world, _ = dr.interpolate(verts[None, ...].contiguous(), rast, tri)
+    return torch.norm(world - campos[:, None, None, :], dim=-1, keepdim=True)
 
 
 def place_spheres(target_alpha, mvp, n_spheres, grid=72, min_radius=0.05, shrink=0.92):
@@ -92,7 +111,8 @@ def build_spheres(centres, radii, k):
     return np.concatenate(rest), np.concatenate(tets).astype(np.int32)
 
 
-def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators"):
+def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
+        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1)):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -101,6 +121,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
 
     if silhouette not in ("operators", "fused", "fused-loss"):
         raise ValueError(f"unknown --silhouette mode {silhouette!r}")
+    if fit_depth not in ("off", "operators", "fused-loss"):
+        raise ValueError(f"unknown --fit-depth mode {fit_depth!r}")
     target_npz = target_npz or os.path.join(ROOT, "tests", "golden", "mario_mesh.npz")
     tgt = np.load(target_npz)
     tv = torch.from_numpy(tgt["vertices"].astype(np.float32)).cuda()
@@ -109,6 +131,10 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     glctx = dr.RasterizeCudaContext()
     with torch.no_grad():
         target = render_alpha(glctx, tv, tf, mvp, res).clone()
+    campos = torch.from_numpy(scenes.dataset_campos(views)).cuda()
+    if fit_depth != "off":
+        with torch.no_grad():
+            target_depth = render_depth(glctx, tv, tf, mvp, campos, res).clone()
     centres, radii, hull_frac, left = place_spheres(target, mvp, n_spheres)
     S = len(radii)
     rest, tets = build_spheres(centres, radii, k)
@@ -130,7 +156,14 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(iters):
-        if silhouette == "fused-loss":
+        if fit_depth == "fused-loss" and fit_depth_start < it:
+            out = ren.silhouette_depth_loss(mvp, target, campos, target_depth, iter_num=it, resolution=res)
+            img_loss = out["img_loss"] * 20 + out["depth_loss"] * 100
+        elif fit_depth == "operators" and fit_depth_start < it:                          # trainer.py:77-79, :106-109
+            out = ren(mvp, only_alpha=True, iter_num=it, resolution=res, fit_depth=True, campos=campos)
+            img_loss = shade_loss(out["shaded"][..., -1], target[..., -1]) * 20
+            img_loss = img_loss + shade_loss(out["d"][..., -1] * target[..., -1], target_depth[..., -1] * target[..., -1]) * 100
+        elif silhouette == "fused-loss":
             out = ren.silhouette_loss(mvp, target, iter_num=it, resolution=res)
             img_loss = out["img_loss"] * 20
         else:
@@ -155,7 +188,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     inverted = int((np.sign(dets(x)) != np.sign(dets(rest.astype(np.float64)))).sum())
     rec = {
         "metric": "s per iteration, geometry-fitting loop on the reference's object (BASELINE config 5)", "value": dt / iters, "unit": "s/iteration",
-        "higher_is_better": False, "silhouette": silhouette, "iterations": iters, "wall_s": dt, "ms_per_iteration": 1e3 * dt / iters,
+        "higher_is_better": False, "silhouette": silhouette, "fit_depth": fit_depth, "fit_depth_start": fit_depth_start, "iterations": iters, "wall_s": dt, "ms_per_iteration": 1e3 * dt / iters,
         "silhouette_iou": iou, "silhouette_iou_at_start": iou0, "inverted_tets": inverted, "tets": int(tets.shape[0]),
         "img_loss_first_last": [log[0][1], log[-1][1]], "reg_first_last": [log[0][2], log[-1][2]],
         "spheres": {"placed": S, "asked": n_spheres, "radii_min_max": [float(radii.min()), float(radii.max())], "visual_hull_fraction_of_cube": hull_frac,
@@ -178,6 +211,15 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             e1.record()
             torch.cuda.synchronize()
             return e0.elapsed_time(e1) / reps
+
+        def timed_alternating(fns, reps, repeats):
+            """ms per call of every function of `fns`: `repeats` windows of `reps` calls each, the functions taking turns window by
+            window (what shares the machine hits both alike) -> {name: sorted list of the windows' means}"""
+            windows = {name: [] for name in fns}
+            for _ in range(repeats):
+                for name, fn in fns.items():
+                    windows[name].append(timed(fn, reps))
+            return {name: sorted(t) for name, t in windows.items()}
         data = geo(iter_num=5)
         pos = ren.transform_pos(mvp, data.v_pos).contiguous().detach()
         tri = data.t_pos_idx
@@ -202,6 +244,51 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         def sil_mse_fb(j):
             pos_g.grad = None
             dr.silhouette_mse(ren.glctx, pos_g, tri, [res, res], target).backward()
+        depth_stages = {}
+        if fit_depth != "off":
+            # the depth term on its own, forward + backward, given the rasterisation each path starts from: `rast` (kept in the
+            # graph: the backward runs interpolate's and rasterize's) against the ids of the alpha stage
+            world_g = data.v_pos.detach().clone().requires_grad_(True)
+            a_ref, d_ref = target[..., -1].contiguous(), target_depth[..., -1].contiguous()
+            rast_g, _ = dr.rasterize(ren.glctx, pos_g, tri, resolution=[res, res], grad_db=False)
+            topo = dr.antialias_construct_topology_hash(tri)
+            _, ids, _ = dr._silhouette_forward(pos, tri, topo.opp, ren.glctx, res, res)
+            lib, check, stream = dr._lib, dr._capi.check, dr._stream_ptr(pos.device)
+            B, V, T = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
+            ws = torch.empty(int(lib.tsamd_depth_mse_workspace_bytes(B * res * res)), dtype=torch.uint8, device=pos.device)
+            loss_f, one = torch.empty((), device=pos.device), torch.ones((), device=pos.device)
+            gw, gp = torch.empty_like(world_g), torch.empty_like(pos)
+
+            def depth_chain_fb(j):
+                pos_g.grad = world_g.grad = None
+                x, _ = dr.interpolate(world_g[None, ...], rast_g, tri)
+                d = torch.norm(x - campos[:, None, None, :], dim=-1, keepdim=True)
+                shade_loss(d[..., -1] * a_ref, d_ref * a_ref).backward(retain_graph=True)
+
+            def depth_fused_fb(j):
+                args = (pos.data_ptr(), B, V, tri.data_ptr(), T, res, res, ids.data_ptr(), world_g.data_ptr(), campos.data_ptr(), d_ref.data_ptr(), a_ref.data_ptr())
+                check(lib.tsamd_depth_mse(*args, ws.data_ptr(), loss_f.data_ptr(), None, stream))
+                check(lib.tsamd_depth_mse_backward(*args, one.data_ptr(), 0, gw.data_ptr(), gp.data_ptr(), stream))
+
+            def terms_chain_fb(j):
+                pos_g.grad = world_g.grad = None
+                r, _ = dr.rasterize(ren.glctx, pos_g, tri, resolution=[res, res], grad_db=False)
+                a = dr.antialias(torch.clamp(r[..., -1:].detach(), 0, 1).contiguous(), r, pos_g, tri)
+                x, _ = dr.interpolate(world_g[None, ...], r, tri)
+                d = torch.norm(x - campos[:, None, None, :], dim=-1, keepdim=True)
+                (shade_loss(a[..., -1], a_ref) * 20 + shade_loss(d[..., -1] * a_ref, d_ref * a_ref) * 100).backward()
+
+            def terms_fused_fb(j):
+                pos_g.grad = world_g.grad = None
+                la, ld = dr.silhouette_depth_mse(ren.glctx, pos_g, tri, [res, res], target, world_g, campos, target_depth, target)
+                (la * 20 + ld * 100).backward()
+            reps, repeats = depth_stage_reps
+            windows = timed_alternating({"depth_operators_forward_backward": depth_chain_fb, "depth_fused_forward_backward": depth_fused_fb,
+                                         "image_terms_operators_forward_backward": terms_chain_fb, "image_terms_fused_forward_backward": terms_fused_fb},
+                                        reps, repeats)
+            depth_stages = {name: t[len(t) // 2] for name, t in windows.items()}
+            rec["depth_stage_windows_ms"] = {"calls_per_window": reps, "windows": windows}
+            del rast_g
         rec["stages_ms"] = {
             "energy_and_surface_forward_backward": timed(geo_fb),
             "rasterize": timed(lambda j: dr.rasterize(ren.glctx, pos, tri, resolution=[res, res], grad_db=False)),
@@ -209,7 +296,36 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             "silhouette_forward_backward": timed(sil_fb),
             "silhouette_mse_forward_backward": timed(sil_mse_fb),
             "optimizer_step": timed(lambda j: opt.step()),
+            **depth_stages,
         }
+    return rec
+
+
+def depth_bench(path, **kw):
+    """Both --fit-depth modes on the same seed and the depth stage timings, as one record written to `path`."""
+    kw = dict(kw, silhouette="fused-loss")
+    ops = run(fit_depth="operators", stages=False, **kw)
+    fused = run(fit_depth="fused-loss", stages=True, depth_stage_reps=(200, 5), **kw)
+    w = fused["depth_stage_windows_ms"]["windows"]
+
+    def pair(chain, own):
+        return {"operators_ms": fused["stages_ms"][chain], "fused_ms": fused["stages_ms"][own], "operators_ms_min_max": [w[chain][0], w[chain][-1]],
+                "fused_ms_min_max": [w[own][0], w[own][-1]], "ratio_operators_over_fused": fused["stages_ms"][chain] / fused["stages_ms"][own],
+                "ranges_overlap": not (w[own][-1] < w[chain][0] or w[chain][-1] < w[own][0])}
+    keep = ("ms_per_iteration", "silhouette_iou", "silhouette_iou_at_start", "inverted_tets", "img_loss_first_last", "fit_depth", "fit_depth_start", "iterations")
+    rec = {"metric": "depth term forward + backward, operator chain over fused pair (medians of five windows of 200 calls, HIP events)",
+           "value": fused["stages_ms"]["depth_operators_forward_backward"] / fused["stages_ms"]["depth_fused_forward_backward"], "unit": "x",
+           "higher_is_better": True, "config": fused["config"],
+           "depth_term": pair("depth_operators_forward_backward", "depth_fused_forward_backward"),
+           "both_image_terms_with_their_rasterisation": pair("image_terms_operators_forward_backward", "image_terms_fused_forward_backward"),
+           "windows_ms": fused["depth_stage_windows_ms"],
+           "training": {"operators": {k: ops[k] for k in keep}, "fused-loss": {k: fused[k] for k in keep},
+                        "ms_per_iteration_operators_over_fused": ops["ms_per_iteration"] / fused["ms_per_iteration"]},
+           "stages_ms": fused["stages_ms"]}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write("\n")
     return rec
 
 
@@ -224,9 +340,17 @@ def main():
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--silhouette", choices=["operators", "fused", "fused-loss"], default="operators")
     ap.add_argument("--no-stages", action="store_true", help="skip the stand-alone stage timings")
+    ap.add_argument("--fit-depth", choices=["off", "operators", "fused-loss"], default="off")
+    ap.add_argument("--fit-depth-start", type=int, default=0, help="the depth term enters once the iteration has passed this one")
+    ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
     args = ap.parse_args()
+    if args.depth_bench:
+        rec = depth_bench(args.depth_bench, target_npz=args.target, n_spheres=args.spheres, k=args.k, views=args.views, res=args.res, iters=args.iters,
+                          verbose=args.verbose, fit_depth_start=args.fit_depth_start)
+        print(json.dumps({k: rec[k] for k in ("metric", "value", "unit", "depth_term", "both_image_terms_with_their_rasterisation", "training")}))
+        return
     print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
-                         stages=not args.no_stages)))
+                         stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start)))
 
 
 if __name__ == "__main__":

@@ -52,6 +52,17 @@ hipError_t launch_silhouette_backward(const float *pos_clip, const int32_t *tri,
 // loss = mean((alpha - target)^2) over n floats, bitwise repeatable; n = 0 stores 0
 int64_t silhouette_mse_workspace_bytes(int64_t n);
 hipError_t launch_silhouette_mse(const float *alpha, const float *target, int64_t n, void *workspace, float *loss, hipStream_t stream);
+// The depth term (raster_kernels.hip): loss = mean over batch * height * width of (d m - t m)^2 with d = || interpolate(world_pos) -
+// campos[view] || from the alpha stage's ids (|| campos || on background), bitwise repeatable; depth_out (optional): d per pixel.
+// No pixel or no triangle: loss 0, nothing else written.  backward: grad_world [n_vertices, 3] is zero-filled by the launch,
+// grad_pos [batch, n_vertices, 4] too unless accumulate_pos != 0 (then it is added to).
+int64_t depth_mse_workspace_bytes(int64_t n);
+hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
+                            const float *world_pos, const float *campos, const float *target, const float *mask, void *workspace, float *loss, float *depth_out,
+                            hipStream_t stream);
+hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                     const int32_t *ids, const float *world_pos, const float *campos, const float *target, const float *mask, const float *grad_loss,
+                                     int accumulate_pos, float *grad_world, float *grad_pos, hipStream_t stream);
 hipError_t launch_interpolate(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels, const float *rast, const int32_t *tri,
                               int64_t n_tri, int64_t batch, int height, int width, float *out, hipStream_t stream);
 // grad_attr is zero-filled by the launch; grad_rast may be null

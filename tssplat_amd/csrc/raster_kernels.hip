@@ -16,6 +16,8 @@
 //                          (which pixels differ from their right / upper neighbour) that the antialias kernels start from
 //   silhouette_cover_kernel  the alpha stage's resolve pass: id, coverage 0 / 1 and the coverage masks per pixel, from the keys alone
 //   interpolate_kernel / interpolate_backward_kernel  one lane per pixel
+//   depth_mse_kernel / depth_mse_backward_kernel  the depth term without an image chain: distance to the camera of the
+//                          interpolated world position, masked MSE (det_mean.h) and both of its scatters from the alpha stage's ids
 //
 // Bound: the depth image -- L2 atomics and the reads in front of them (pricing builds, profiles/r04_raster_experiments.md: walk
 // 0.46 ms, fragment queue + depth reads 0.23, atomics 0.31 of 1.10 ms on the 512-sphere surface); 12 B of indices + 3 x 16 B of
@@ -24,6 +26,7 @@
 
 #include <algorithm>
 
+#include "det_mean.h"
 #include "raster.h"
 
 // Coverage, depth and silhouette decisions repeat the oracle's operations one by one: a multiply and an add must round
@@ -392,6 +395,49 @@ __global__ __launch_bounds__(256) void rasterize_clip_kernel(const float4 *pos, 
     }
 }
 
+// The homogeneous edge functions of a pixel centre against the clip-space triangle (v0, v1, v2): what the barycentrics of the
+// resolve pass are ratios of and what rasterize_backward's quotient rule differentiates.  ONE statement of the expressions for
+// every kernel that needs (u, v): the operations and their order are part of the contract (this file is compiled without
+// contraction), so the kernels agree to the bit.
+struct EdgeFunctions {
+    float fx, fy;                           // the pixel centre in normalised device coordinates
+    float p0x, p0y, p1x, p1y, p2x, p2y;     // v_k.xy - f v_k.w
+    float a0, a1;                           // u = a0 / s, v = a1 / s
+    float s;                                // a0 + a1 + a2, 1 where that sum is 0
+};
+
+__device__ __forceinline__ EdgeFunctions edge_functions(const float4 v0, const float4 v1, const float4 v2, int px, int py, int height, int width)
+{
+    EdgeFunctions e;
+    e.fx = (float(px) + 0.5f) / float(width) * 2.f - 1.f, e.fy = (float(py) + 0.5f) / float(height) * 2.f - 1.f;
+    e.p0x = v0.x - e.fx * v0.w, e.p0y = v0.y - e.fy * v0.w;
+    e.p1x = v1.x - e.fx * v1.w, e.p1y = v1.y - e.fy * v1.w;
+    e.p2x = v2.x - e.fx * v2.w, e.p2y = v2.y - e.fy * v2.w;
+    e.a0 = e.p1x * e.p2y - e.p1y * e.p2x, e.a1 = e.p2x * e.p0y - e.p2y * e.p0x;
+    const float a2 = e.p0x * e.p1y - e.p0y * e.p1x;
+    const float s = e.a0 + e.a1 + a2;
+    e.s = s == 0.f ? 1.f : s;
+    return e;
+}
+
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
+
+// d (u, v) / d clip-space (x, y, w) of the three vertices, times the gradient (gu, gv): the quotient rule of u = a0 / s, v = a1 / s
+// (oracle/raster_oracle.py::rasterize_backward), the clamps of the forward treated as inactive.  d[3 k ..] = (x, y, w) of vertex k.
+__device__ __forceinline__ void edge_functions_backward(const EdgeFunctions &e, float gu, float gv, float d[9])
+{
+    const float is = 1.f / e.s;
+    const float u = e.a0 * is, v = e.a1 * is;
+    const float dot = gu * u + gv * v;
+    const float da0 = (gu - dot) * is, da1 = (gv - dot) * is, da2 = -dot * is;
+    d[0] = da1 * -e.p2y + da2 * e.p1y, d[1] = da1 * e.p2x + da2 * -e.p1x;
+    d[3] = da0 * e.p2y + da2 * -e.p0y, d[4] = da0 * -e.p2x + da2 * e.p0x;
+    d[6] = da0 * -e.p1y + da1 * e.p0y, d[7] = da0 * e.p1x + da1 * -e.p0x;
+    d[2] = -e.fx * d[0] - e.fy * d[1];
+    d[5] = -e.fx * d[3] - e.fy * d[4];
+    d[8] = -e.fx * d[6] - e.fy * d[7];
+}
+
 // A wave holds 64 consecutive pixels of the flattened [view, row, column] image -- what the pair masks are indexed by, and the
 // order in which keys are read and `rast` is written as one stream.  (Four rows x 64 columns per workgroup, the upper neighbour
 // handed over in LDS, was tried: the strided streams alone cost 138 -> 172 us on 120 views x 512^2.)
@@ -474,18 +520,12 @@ __global__ __launch_bounds__(256) void rasterize_resolve_kernel(const float4 *po
         const int64_t t = int64_t(key[k] & 0xFFFFFFFFull);
         const float4 *pv = pos + b[k] * n_vertices;
         const float4 v0 = pv[tri[3 * t]], v1 = pv[tri[3 * t + 1]], v2 = pv[tri[3 * t + 2]];
-        const float fx = (float(px[k]) + 0.5f) / float(width) * 2.f - 1.f, fy = (float(py[k]) + 0.5f) / float(height) * 2.f - 1.f;
-        const float p0x = v0.x - fx * v0.w, p0y = v0.y - fy * v0.w;
-        const float p1x = v1.x - fx * v1.w, p1y = v1.y - fy * v1.w;
-        const float p2x = v2.x - fx * v2.w, p2y = v2.y - fy * v2.w;
-        const float a0 = p1x * p2y - p1y * p2x, a1 = p2x * p0y - p2y * p0x, a2 = p0x * p1y - p0y * p1x;
-        float s = a0 + a1 + a2;
-        s = s == 0.f ? 1.f : s;
-        const float b0f = a0 / s, b1f = a1 / s, b2f = 1.f - b0f - b1f;
+        const EdgeFunctions e = edge_functions(v0, v1, v2, px[k], py[k], height, width);
+        const float b0f = e.a0 / e.s, b1f = e.a1 / e.s, b2f = 1.f - b0f - b1f;
         const float z = b0f * v0.z + b1f * v1.z + b2f * v2.z;
         float w = b0f * v0.w + b1f * v1.w + b2f * v2.w;
         w = w == 0.f ? 1.f : w;
-        rast[gid[k]] = make_float4(fminf(fmaxf(b0f, 0.f), 1.f), fminf(fmaxf(b1f, 0.f), 1.f), fminf(fmaxf(z / w, -1.f), 1.f), float(t + 1));
+        rast[gid[k]] = make_float4(clamp01(b0f), clamp01(b1f), fminf(fmaxf(z / w, -1.f), 1.f), float(t + 1));
     }
 }
 
@@ -616,23 +656,7 @@ __global__ __launch_bounds__(256) void rasterize_backward_kernel(const float4 *p
         const int py = int(pix / width), px = int(pix - int64_t(py) * width);
         const float4 *pv = pos + b * n_vertices;
         const float4 v0 = pv[i0], v1 = pv[i1], v2 = pv[i2];
-        const float fx = (float(px) + 0.5f) / float(width) * 2.f - 1.f, fy = (float(py) + 0.5f) / float(height) * 2.f - 1.f;
-        const float p0x = v0.x - fx * v0.w, p0y = v0.y - fy * v0.w;
-        const float p1x = v1.x - fx * v1.w, p1y = v1.y - fy * v1.w;
-        const float p2x = v2.x - fx * v2.w, p2y = v2.y - fy * v2.w;
-        const float a0 = p1x * p2y - p1y * p2x, a1 = p2x * p0y - p2y * p0x, a2 = p0x * p1y - p0y * p1x;
-        float s = a0 + a1 + a2;
-        s = s == 0.f ? 1.f : s;
-        const float is = 1.f / s;
-        const float u = a0 * is, v = a1 * is;
-        const float dot = g.x * u + g.y * v;
-        const float da0 = (g.x - dot) * is, da1 = (g.y - dot) * is, da2 = -dot * is;
-        d[0] = da1 * -p2y + da2 * p1y, d[1] = da1 * p2x + da2 * -p1x;
-        d[3] = da0 * p2y + da2 * -p0y, d[4] = da0 * -p2x + da2 * p0x;
-        d[6] = da0 * -p1y + da1 * p0y, d[7] = da0 * p1x + da1 * -p0x;
-        d[2] = -fx * d[0] - fy * d[1];
-        d[5] = -fx * d[3] - fy * d[4];
-        d[8] = -fx * d[6] - fy * d[7];
+        edge_functions_backward(edge_functions(v0, v1, v2, px, py, height, width), g.x, g.y, d);
     }
     // lanes of one triangle (and view) in a row: one set of atomics per run
     const Runs runs = find_runs(valid ? b * (int64_t(1) << 32) + t : -1 - int64_t(threadIdx.x));
@@ -726,6 +750,177 @@ __global__ __launch_bounds__(256) void interpolate_backward_kernel(const float *
         }
     }
     if (valid && grad_rast) grad_rast[gid] = make_float4(du, dv, 0.f, 0.f);
+}
+
+// ---- the depth term: MSE of the distance to the camera, without an image chain ----
+// What the reference's trainer.py:104-115 builds from out["d"] = ||interpolate(v_pos, rast) - campos|| (mesh_rasterizer.py:151-161):
+// loss = mean((d m - t m)^2).  Per pixel the chain moves a 16-byte rast pixel, a 12-byte position and their gradients; here a
+// pixel is its triangle id (the alpha stage's by-product), a target and a mask -- 12 bytes -- plus cached vertex gathers.
+// (u, v) are the clamped barycentrics of the resolve pass (edge_functions, the same operations), w = 1 - u - v and the
+// interpolation are interpolate_kernel's; a background pixel has x = 0, so d = ||campos||, as in the chain.
+struct DepthPoint {
+    float u, v, w;          // barycentric weights of (i0, i1, i2)
+    float dx, dy, dz;       // x - campos
+    float d;                // its length
+};
+
+__device__ __forceinline__ void distance_to(float x, float y, float z, const float *c, DepthPoint &p)
+{
+    p.dx = x - c[0], p.dy = y - c[1], p.dz = z - c[2];
+    p.d = sqrtf(p.dx * p.dx + p.dy * p.dy + p.dz * p.dz);
+}
+
+// the covered pixel (px, py) of a view: clip-space vertices pv, world positions `world`, camera c
+__device__ __forceinline__ EdgeFunctions depth_point(const float4 *pv, const float *world, const float *c, int32_t i0, int32_t i1, int32_t i2, int px, int py,
+                                                     int height, int width, DepthPoint &p, float a[9])
+{
+    const EdgeFunctions e = edge_functions(pv[i0], pv[i1], pv[i2], px, py, height, width);
+    p.u = clamp01(e.a0 / e.s), p.v = clamp01(e.a1 / e.s);
+    p.w = 1.f - p.u - p.v;
+    const float *a0 = world + 3 * int64_t(i0), *a1 = world + 3 * int64_t(i1), *a2 = world + 3 * int64_t(i2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a[k] = a0[k], a[3 + k] = a1[k], a[6 + k] = a2[k];
+    distance_to(p.u * a[0] + p.v * a[3] + p.w * a[6], p.u * a[1] + p.v * a[4] + p.w * a[7], p.u * a[2] + p.v * a[5] + p.w * a[8], c, p);
+    return e;
+}
+
+// Triangle named by an id of the alpha stage (triangle + 1, 0 = background) and its vertex indices; false for background, an id
+// outside [1, n_tri] and a vertex index outside [0, n_vertices): nothing is read through those (as triangle_of / triangle_indices)
+__device__ __forceinline__ bool triangle_of_id(int32_t id, const int32_t *tri, int64_t n_tri, int64_t n_vertices, int32_t &i0, int32_t &i1, int32_t &i2)
+{
+    if (id < 1 || int64_t(id) > n_tri) return false;
+    return triangle_indices(tri, int64_t(id) - 1, n_vertices, i0, i1, i2);
+}
+
+// view, row and column of pixel gid; b0 = the view of the wave's first pixel (a wave of `span` pixels crosses at most one view
+// boundary when hw >= span), as in the resolve pass
+__device__ __forceinline__ void locate_pixel(int64_t gid, int64_t hw, int width, bool one_boundary, int64_t b0, int64_t &b, int &px, int &py)
+{
+    uint32_t pix;
+    if (one_boundary) {
+        const int64_t off = gid - b0 * hw;
+        b = off >= hw ? b0 + 1 : b0;
+        pix = uint32_t(off >= hw ? off - hw : off);
+    } else {
+        b = gid / hw;
+        pix = uint32_t(gid - b * hw);
+    }
+    py = int(pix / uint32_t(width));
+    px = int(pix - uint32_t(py) * uint32_t(width));
+}
+
+constexpr int kDepthPixels = 4;                                 // 64-pixel chunks per wave and round, all their loads in flight together
+constexpr int kDepthPerBlock = kMeanBlock * kDepthPixels;       // pixels per workgroup and round
+constexpr int kDepthMaxBlocks = 8192;                           // (the loss's bits depend on these two: det_mean.h)
+
+// One lane per pixel; a workgroup strides over rounds of kDepthPerBlock pixels and stores one double: the sum of (d m - t m)^2,
+// each product rounded on its own, squared and added in float64.  d_out (optional): the distance image, every pixel of it.
+__global__ __launch_bounds__(kMeanBlock) void depth_mse_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
+                                                               int width, const int32_t *ids, const float *world, const float *campos, const float *target,
+                                                               const float *mask, double *partials, float *d_out)
+{
+    constexpr int K = kDepthPixels;
+    __shared__ double lds[kMeanBlock / 64];
+    const int64_t hw = int64_t(height) * width, total = batch * hw;
+    const int lane = int(threadIdx.x) & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+    const bool one_boundary = hw >= 64 * K;
+    double acc = 0.0;
+    for (int64_t first = int64_t(blockIdx.x) * kDepthPerBlock; first < total; first += int64_t(gridDim.x) * kDepthPerBlock) {
+        const int64_t gid0 = first + int64_t(wave) * (64 * K);
+        int32_t id[K];
+        float tg[K], m[K];
+        bool want[K];
+        // all global loads first, together (the latency of one round trip, not of three)
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int64_t gid = gid0 + 64 * k + lane;
+            const bool have = gid < total;
+            id[k] = have ? ids[gid] : 0;
+            tg[k] = have ? target[gid] : 0.f;
+            m[k] = have ? mask[gid] : 0.f;
+            want[k] = have && (m[k] != 0.f || d_out != nullptr);     // a masked-out pixel adds 0: no vertex work unless its d is asked for
+        }
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < K; ++k) any = any || want[k];
+        if (__ballot(any) == 0ull) continue;                          // wave-uniform: nothing in these chunks enters the loss
+        const int64_t b0 = one_boundary ? gid0 / hw : 0;              // (on the scalar unit)
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (!want[k]) continue;
+            const int64_t gid = gid0 + 64 * k + lane;
+            int64_t b;
+            int px, py;
+            locate_pixel(gid, hw, width, one_boundary, b0, b, px, py);
+            const float *c = campos + 3 * b;
+            DepthPoint p;
+            int32_t i0, i1, i2;
+            if (triangle_of_id(id[k], tri, n_tri, n_vertices, i0, i1, i2)) {
+                float a[9];
+                depth_point(pos + b * n_vertices, world, c, i0, i1, i2, px, py, height, width, p, a);
+            } else {
+                distance_to(0.f, 0.f, 0.f, c, p);
+            }
+            if (d_out) d_out[gid] = p.d;
+            const float r = p.d * m[k] - tg[k] * m[k];
+            acc += double(r) * double(r);
+        }
+    }
+    const double sum = block_sum(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+// One lane per pixel, one pass: (u, v, d) recomputed, g_x = grad_loss 2 (d m - t m) m / n * (x - campos) / d (0 where d = 0), then
+// BOTH scatters behind one run detection -- interpolate_backward's (u, v, w) g_x into grad_world[V, 3] and, through
+// (du, dv) = (g_x . (a0 - a2), g_x . (a1 - a2)) and the quotient rule of rasterize_backward, (x, y, w) into grad_pos[B, V, 4].
+// The run key holds the view: grad_pos is per view, and a wave of a small image spans several views that show the same triangle.
+// No gradient image and no grad_rast exist.  EVERY lane reaches find_runs.
+__global__ __launch_bounds__(256) void depth_mse_backward_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
+                                                                 int width, const int32_t *ids, const float *world, const float *campos, const float *target,
+                                                                 const float *mask, const float *grad_loss, float *grad_world, float4 *grad_pos)
+{
+    const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t hw = int64_t(height) * width, total = batch * hw;
+    bool valid = gid < total;
+    int32_t id = 0, i0 = 0, i1 = 0, i2 = 0;
+    float tg = 0.f, m = 0.f;
+    if (valid) id = ids[gid], tg = target[gid], m = mask[gid];
+    valid = valid && m != 0.f && triangle_of_id(id, tri, n_tri, n_vertices, i0, i1, i2);   // (background: x = 0 is a constant)
+    int64_t b = 0;
+    float dw[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, z) of the three world positions
+    float dc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, w) of the three clip-space positions
+    if (valid) {
+        int px, py;
+        locate_pixel(gid, hw, width, false, 0, b, px, py);
+        DepthPoint p;
+        float a[9];
+        const EdgeFunctions e = depth_point(pos + b * n_vertices, world, campos + 3 * b, i0, i1, i2, px, py, height, width, p, a);
+        const float r = p.d * m - tg * m;
+        const float gd = (2.f * r * m) * (grad_loss[0] / float(total));
+        const float gx = p.d == 0.f ? 0.f : gd * (p.dx / p.d), gy = p.d == 0.f ? 0.f : gd * (p.dy / p.d), gz = p.d == 0.f ? 0.f : gd * (p.dz / p.d);
+        dw[0] = p.u * gx, dw[1] = p.u * gy, dw[2] = p.u * gz;
+        dw[3] = p.v * gx, dw[4] = p.v * gy, dw[5] = p.v * gz;
+        dw[6] = p.w * gx, dw[7] = p.w * gy, dw[8] = p.w * gz;
+        const float du = gx * (a[0] - a[6]) + gy * (a[1] - a[7]) + gz * (a[2] - a[8]);
+        const float dv = gx * (a[3] - a[6]) + gy * (a[4] - a[7]) + gz * (a[5] - a[8]);
+        edge_functions_backward(e, du, dv, dc);
+    }
+    const Runs runs = find_runs(valid ? b * (int64_t(1) << 32) + int64_t(id) : -1 - int64_t(threadIdx.x));
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dw[k] = run_sum(runs, dw[k]), dc[k] = run_sum(runs, dc[k]);
+    if (valid && runs.last) {
+        float *gp = reinterpret_cast<float *>(grad_pos + b * n_vertices);
+        const int64_t at[3] = {int64_t(i0), int64_t(i1), int64_t(i2)};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            atomicAdd(grad_world + 3 * at[k] + 0, dw[3 * k]);
+            atomicAdd(grad_world + 3 * at[k] + 1, dw[3 * k + 1]);
+            atomicAdd(grad_world + 3 * at[k] + 2, dw[3 * k + 2]);
+            atomicAdd(gp + 4 * at[k] + 0, dc[3 * k]);
+            atomicAdd(gp + 4 * at[k] + 1, dc[3 * k + 1]);
+            atomicAdd(gp + 4 * at[k] + 3, dc[3 * k + 2]);
+        }
+    }
 }
 
 unsigned blocks_for(int64_t n) { return unsigned((n + 255) / 256); }
@@ -824,6 +1019,37 @@ hipError_t launch_interpolate_backward(const float *attr, int64_t attr_batch, in
     if (batch * hw <= 0) return hipSuccess;
     hipLaunchKernelGGL(interpolate_backward_kernel, dim3(blocks_for(batch * hw)), dim3(256), 0, stream, attr, attr_batch, n_vertices, channels,
                        reinterpret_cast<const float4 *>(rast), tri, n_tri, batch, hw, grad_out, grad_attr, reinterpret_cast<float4 *>(grad_rast));
+    return hipGetLastError();
+}
+
+int64_t depth_mse_workspace_bytes(int64_t n) { return mean_workspace_bytes(mean_blocks(n, kDepthPerBlock, kDepthMaxBlocks)); }
+
+hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
+                            const float *world_pos, const float *campos, const float *target, const float *mask, void *workspace, float *loss, float *depth_out,
+                            hipStream_t stream)
+{
+    const int64_t pixels = pixel_count(batch, height, width);
+    if (pixels <= 0 || n_tri <= 0) return hipMemsetAsync(loss, 0, sizeof(float), stream);
+    const int blocks = mean_blocks(pixels, kDepthPerBlock, kDepthMaxBlocks);
+    hipLaunchKernelGGL(depth_mse_kernel, dim3(blocks), dim3(kMeanBlock), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri, batch, height,
+                       width, ids, world_pos, campos, target, mask, static_cast<double *>(workspace), depth_out);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, pixels, loss, stream);
+}
+
+hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                     const int32_t *ids, const float *world_pos, const float *campos, const float *target, const float *mask, const float *grad_loss,
+                                     int accumulate_pos, float *grad_world, float *grad_pos, hipStream_t stream)
+{
+    hipError_t e;
+    if (n_vertices > 0 && (e = hipMemsetAsync(grad_world, 0, size_t(n_vertices) * 3 * sizeof(float), stream)) != hipSuccess) return e;
+    if (!accumulate_pos && batch * n_vertices > 0 &&
+        (e = hipMemsetAsync(grad_pos, 0, size_t(batch) * size_t(n_vertices) * 4 * sizeof(float), stream)) != hipSuccess)
+        return e;
+    const int64_t pixels = pixel_count(batch, height, width);
+    if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
+    hipLaunchKernelGGL(depth_mse_backward_kernel, dim3(blocks_for(pixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri,
+                       batch, height, width, ids, world_pos, campos, target, mask, grad_loss, grad_world, reinterpret_cast<float4 *>(grad_pos));
     return hipGetLastError();
 }
 

@@ -22,7 +22,9 @@ beyond the +-16384-pixel guard band is dropped; the silhouette of a clipped tria
 
 ``silhouette`` and ``silhouette_mse`` are this package's own: the alpha stage of the reference's trainer (``only_alpha=True``:
 ``MSE(antialias(clamp(rast[..., -1:], 0, 1)))``) without the ``rast`` image, the clamp, the antialias copy and the dense loss
-gradient -- the same blends as the three operators above give on the 0 / 1 coverage image.
+gradient -- the same blends as the three operators above give on the 0 / 1 coverage image.  ``silhouette_depth_mse`` adds the
+trainer's depth term (``fit_depth``: ``MSE(||interpolate(v_pos, rast) - campos|| * mask, target * mask)``) to that one rasterisation,
+from the triangle ids the alpha stage leaves: no ``rast`` image, no interpolated image, no gradient image.
 
 ``plan_blends``, ``shade`` and ``shade_l1`` are this package's own too: the colour stage under frozen geometry and fixed views.
 There the blends of ``antialias`` do not depend on what is being trained, so they are extracted once into a :class:`BlendPlan`,
@@ -41,7 +43,7 @@ from . import _capi
 from .tet_spheres_ext import _device_ctx, _stream_ptr
 
 __all__ = ["RasterizeCudaContext", "rasterize", "interpolate", "antialias", "antialias_construct_topology_hash", "texture", "silhouette",
-           "silhouette_mse", "BlendPlan", "plan_blends", "shade", "shade_l1"]
+           "silhouette_mse", "silhouette_depth_mse", "BlendPlan", "plan_blends", "shade", "shade_l1"]
 
 _lib = _capi.load()
 
@@ -459,6 +461,83 @@ def silhouette_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Te
         raise RuntimeError("tssplat_amd.dr.silhouette_mse: target must be [B, H, W] or [B, H, W, 1] of the image size")
     loss, alpha = _SilhouetteMseFunc.apply(pos, tri, topo.opp, glctx, height, width, target.detach(), float(pos_gradient_boost))
     return (loss, alpha.detach()) if return_alpha else loss
+
+
+class _SilhouetteDepthMseFunc(torch.autograd.Function):
+    """One node for both image terms of the geometry stage: one rasterisation forward, ``tsamd_silhouette_mse_backward`` followed by
+    ``tsamd_depth_mse_backward(accumulate_pos=1)`` backward -- the second lands on what the first wrote."""
+
+    @staticmethod
+    def forward(ctx, pos, world, tri, opp, glctx, height, width, target_alpha, campos, target_depth, depth_mask, boost, want_depth):
+        dev = pos.device
+        B, V, T = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
+        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
+        n = alpha.numel()
+        alpha_loss = torch.empty((), dtype=torch.float32, device=dev)
+        depth_loss = torch.empty((), dtype=torch.float32, device=dev)
+        if not want_depth:
+            depth = torch.empty((0,), dtype=torch.float32, device=dev)
+        elif n * T > 0:
+            depth = torch.empty((B, height, width, 1), dtype=torch.float32, device=dev)
+        else:
+            depth = torch.zeros((B, height, width, 1), dtype=torch.float32, device=dev)      # (the call writes no image without triangles)
+        ws = torch.empty((max(int(_lib.tsamd_silhouette_mse_workspace_bytes(n)), int(_lib.tsamd_depth_mse_workspace_bytes(n))),), dtype=torch.uint8, device=dev)
+        with _device_ctx(dev):
+            stream = _stream_ptr(dev)
+            _capi.check(_lib.tsamd_silhouette_mse(alpha.data_ptr(), target_alpha.data_ptr(), n, ws.data_ptr(), alpha_loss.data_ptr(), stream))
+            _capi.check(_lib.tsamd_depth_mse(_ptr(pos), B, V, _ptr(tri), T, height, width, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
+                                             _ptr(depth_mask), ws.data_ptr(), depth_loss.data_ptr(), _ptr(depth), stream))
+        ctx.save_for_backward(pos, world, tri, opp, ids, masks, alpha, target_alpha, campos, target_depth, depth_mask)
+        ctx.boost = float(boost)
+        ctx.mark_non_differentiable(alpha, depth)
+        return alpha_loss, depth_loss, alpha, depth
+
+    @staticmethod
+    def backward(ctx, grad_alpha_loss, grad_depth_loss, _grad_alpha, _grad_depth):
+        pos, world, tri, opp, ids, masks, alpha, target_alpha, campos, target_depth, depth_mask = ctx.saved_tensors
+        B, V, T, H, W = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0]), int(ids.shape[1]), int(ids.shape[2])
+        g = torch.stack([grad_alpha_loss.reshape(()), grad_depth_loss.reshape(())]).to(torch.float32)      # stays on the device: the kernels read it there
+        grad_pos = torch.empty_like(pos)
+        grad_world = torch.empty_like(world)
+        with _device_ctx(pos.device):
+            stream = _stream_ptr(pos.device)
+            _capi.check(_lib.tsamd_silhouette_mse_backward(pos.data_ptr(), B, V, tri.data_ptr(), T, opp.data_ptr(), H, W, ids.data_ptr(), masks.data_ptr(),
+                                                           alpha.data_ptr(), target_alpha.data_ptr(), g.data_ptr(), ctx.boost, grad_pos.data_ptr(), stream))
+            _capi.check(_lib.tsamd_depth_mse_backward(_ptr(pos), B, V, _ptr(tri), T, H, W, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
+                                                      _ptr(depth_mask), g.data_ptr() + 4, 1, _ptr(grad_world), _ptr(grad_pos), stream))
+        return (grad_pos, grad_world) + (None,) * 11
+
+
+def silhouette_depth_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor, resolution, target_alpha: torch.Tensor, world_pos: torch.Tensor,
+                         campos: torch.Tensor, target_depth: torch.Tensor, depth_mask: torch.Tensor, topology_hash=None, pos_gradient_boost: float = 1.0,
+                         return_images: bool = False):
+    """``(alpha_loss, depth_loss)``, two 0-dim tensors (bitwise repeatable), from ONE rasterisation: ``alpha_loss`` is
+    :func:`silhouette_mse`'s; ``depth_loss = mean((d * depth_mask - target_depth * depth_mask) ** 2)`` over ``B H W`` pixels with
+    ``d = norm(interpolate(world_pos, rast, tri) - campos[:, None, None], dim=-1)`` of ``rasterize(glctx, pos, tri, resolution)`` --
+    ``||campos||`` on background, as that chain gives -- without ``rast``, the interpolated image or a gradient image.  ``world_pos``
+    is ``[V, 3]`` or ``[1, V, 3]``, ``campos`` ``[B, 3]``, the two targets and the mask ``[B, H, W]`` or ``[B, H, W, 1]`` float32;
+    gradients flow to ``pos`` (the silhouette blends, and ``(u, v)`` as through ``rasterize``) and ``world_pos``, nowhere else.
+    Without triangles ``depth_loss`` is 0.  ``return_images=True``: ``(alpha_loss, depth_loss, alpha.detach(), d.detach())``, both
+    ``[B, H, W, 1]``."""
+    name = "silhouette_depth_mse"
+    pos, tri, height, width, topo = _silhouette_args(name, pos, tri, resolution, topology_hash)
+    B, V = int(pos.shape[0]), int(pos.shape[1])
+    shape = (B, height, width)
+    images = []
+    for label, t in (("target_alpha", target_alpha), ("target_depth", target_depth), ("depth_mask", depth_mask)):
+        t = _check_cuda_f32(label, t)
+        if t.device != pos.device or tuple(t.shape) not in (shape, shape + (1,)):
+            raise RuntimeError(f"tssplat_amd.dr.{name}: {label} must be [B, H, W] or [B, H, W, 1] of the image size, on the device of pos")
+        images.append(t.detach())
+    world_pos = _check_cuda_f32("world_pos", world_pos)
+    if world_pos.device != pos.device or tuple(world_pos.shape) not in ((V, 3), (1, V, 3)):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: world_pos must be [V, 3] or [1, V, 3] with V = {V} (the vertices of pos), on the device of pos")
+    campos = _check_cuda_f32("campos", campos)
+    if campos.device != pos.device or tuple(campos.shape) != (B, 3):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: campos must be [B, 3] = [{B}, 3], on the device of pos")
+    alpha_loss, depth_loss, alpha, depth = _SilhouetteDepthMseFunc.apply(pos, world_pos, tri, topo.opp, glctx, height, width, images[0], campos.detach(),
+                                                                         images[1], images[2], float(pos_gradient_boost), bool(return_images))
+    return (alpha_loss, depth_loss, alpha.detach(), depth.detach()) if return_images else (alpha_loss, depth_loss)
 
 
 # ---- the colour stage under a blend plan ----

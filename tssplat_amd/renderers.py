@@ -173,6 +173,22 @@ class MeshRasterizer(torch.nn.Module):
                                          pos_gradient_boost=1.0, return_alpha=True)
         return {"img_loss": loss, "geo_regularization": data.smooth_barrier_energy, "shaded": shaded}
 
+    def silhouette_depth_loss(self, mvp: torch.Tensor, target_alpha: torch.Tensor, campos: torch.Tensor, target_depth: torch.Tensor, iter_num: int,
+                              resolution: int, permute_surface_scheduler=None, depth_mask: Optional[torch.Tensor] = None):
+        """The geometry stage's render and BOTH image losses in one (trainer.py:96-115 with ``fit_depth``):
+        ``{"img_loss", "depth_loss", "geo_regularization", "shaded", "d"}`` with ``img_loss`` as :meth:`silhouette_loss` gives it and
+        ``depth_loss`` the plain mean squared error of ``forward(..., only_alpha=True, fit_depth=True, campos=campos)["d"][..., -1] *
+        depth_mask`` against ``target_depth * depth_mask`` through ``dr.silhouette_depth_mse`` -- one rasterisation, no ``rast`` image,
+        no interpolated image, no gradient image.  ``depth_mask`` defaults to ``target_alpha`` (the trainer's ``color_ref[..., -1]``);
+        the caller applies the trainer's weights; ``shaded`` and ``d`` are detached."""
+        data = self._geometry_forward(iter_num, permute_surface_scheduler)
+        pos_clip = self.transform_pos(mvp, data.v_pos).contiguous()
+        mask = target_alpha if depth_mask is None else depth_mask
+        img_loss, depth_loss, shaded, d = dr.silhouette_depth_mse(self.glctx, pos_clip, data.t_pos_idx, [resolution, resolution], target_alpha, data.v_pos,
+                                                                  campos.to(self.device), target_depth, mask, topology_hash=self.tri_hash,
+                                                                  pos_gradient_boost=1.0, return_images=True)
+        return {"img_loss": img_loss, "depth_loss": depth_loss, "geo_regularization": data.smooth_barrier_energy, "shaded": shaded, "d": d}
+
     def shade_loss(self, view_plan: ViewPlan, background: torch.Tensor, target: torch.Tensor, iter_num: int, permute_surface_scheduler=None):
         """The colour stage's render and image loss in one, under a view plan: ``{"img_loss", "geo_regularization", "shaded"}`` with
         ``img_loss`` the plain ``L1Loss`` of ``forward(..., view_plan=view_plan)["shaded"][..., :3]`` against ``target[..., :3]``

@@ -345,6 +345,15 @@ def orbit_mvps(n_views: int, distance: float = 3.0, fov_deg: float = 40.0, near:
     return np.stack(out).astype(np.float32)
 
 
+def dataset_campos(n_views: int, radius: float = 4.0) -> np.ndarray:
+    """The eyes of :func:`dataset_mvps` (``batch["campos"]`` of the reference's loader), float32 ``[n, 3]``."""
+    golden = (1 + 5 ** 0.5) / 2
+    i = np.arange(n_views)
+    theta = 2 * np.pi * i / golden
+    phi = np.arccos(1 - 2 * i / n_views)
+    return (np.stack([np.cos(theta) * np.sin(phi), np.sin(theta) * np.sin(phi), np.cos(phi)], axis=1) * radius).astype(np.float32)
+
+
 def dataset_mvps(n_views: int, radius: float = 4.0, fov_deg: float = 39.3077, near: float = 0.001, far: float = 10.0) -> np.ndarray:
     """The camera set of the reference's image data (/root/reference/data/render_dataset.py:15-57, :96-148): ``n_views`` eyes on a
     golden-ratio spiral over the sphere of ``radius`` around the origin, looking at the origin (up = z, or y when the view
