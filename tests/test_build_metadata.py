@@ -1,6 +1,6 @@
 """Kernel descriptors of the gfx950 code object the library was built with (no GPU needed).
 
-The tile kernels address LDS by absolute byte address (kernels.hip: lds_at): correct only while they have no static
+The tile kernels address LDS by absolute byte address (tile_kernel.hip: lds_at): correct only while they have no static
 LDS object, which the library re-checks at run time (configure_kernels) and this test checks at build time.  Their
 occupancy (two 768-thread workgroups per CU) needs <= 80 VGPRs without spills."""
 import os
@@ -23,6 +23,11 @@ def test_tile_kernels_have_no_static_lds_and_do_not_spill():
     # 2 slots x 768 threads: built-in, explicit operator, rebuild_dminv; the three fat-wave layouts (3 x 512, 4 x 768, 3 x 1024):
     # built-in only -- each with / without gradient
     assert len(tiles) == 12, sorted(tiles)
+    # ... and the cache-retaining twins of the first three, for plans that share index planes: the same absolute LDS addressing
+    shared = {k: v for k, v in meta.items() if "tile_shared_index_kernel" in k}
+    assert len(shared) == 6, sorted(shared)
+    assert all("Li768ELi6E" in k for k in shared), sorted(shared)              # default lane layout only
+    tiles.update(shared)
     for name, rec in tiles.items():
         assert rec["group_segment_fixed_size"] == 0, (name, rec)      # dynamic LDS array at LDS address 0
         assert rec["vgpr_spill_count"] == 0 and rec["private_segment_fixed_size"] == 0, (name, rec)

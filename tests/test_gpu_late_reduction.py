@@ -1,4 +1,4 @@
-"""The gradient tile kernels add up a tile's energy pair at the END of the tile (kernels.hip: kSumLate, sum_waves): the wave sums
+"""The gradient tile kernels add up a tile's energy pair at the END of the tile (tile_kernel.hip: kSumLate, sum_waves): the wave sums
 are published to the reduction scratch behind the H stores, and the last wave reads them back after its own vertex sums -- three
 passes, a scatter and the per-vertex sums later, with the force array written over the records next to the scratch in between.
 

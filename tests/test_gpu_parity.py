@@ -531,7 +531,7 @@ def test_random_tiling_options_on_gpu(ext):
     assert ran >= min(10, trials)
 
 
-# Every lane layout tile_kernel_for() hands out besides the default (kernels.hip): 3 slots per lane x 512 threads (two workgroups
+# Every lane layout tile_kernel_for() hands out besides the default (tile_kernel.hip): 3 slots per lane x 512 threads (two workgroups
 # per CU), 3 x 1 024 and 4 x 768 (one workgroup per CU, up to 160 KiB).  VERDICT r5 / ADVICE r5: these six instantiations were
 # only covered by the CPU plan replay.  Device-side differences against the default: plane loads of SPT dwords at a 12- / 16-byte lane
 # stride, 1 024-thread blocks (16 waves in the block reduction), the reversed vertex blocks of waves 4-7 at other wave counts,
@@ -588,7 +588,7 @@ def test_lane_layouts_whole_sphere_tiles(ext, kw):
 def test_unfactored_coefficient_branch_gradient(ext, c1, c2, order):
     """Pass 3 works with c2 / c1 and applies c1 once per vertex -- except where the ratio is not a well-behaved fp32 number (c1 == 0:
     only the penalty is left; |c2 / c1| > 2^40; NaN for 0 / 0), where c1 and c2 are applied separately and the vertex sums are written
-    unscaled (kernels.hip: `factored`, q_scale).  VERDICT r5: that branch's GRADIENT was never compared with the oracle.  Multi-tile
+    unscaled (tile_kernel.hip: `factored`, q_scale).  VERDICT r5: that branch's GRADIENT was never compared with the oracle.  Multi-tile
     scene with many inverted tets, both coefficient routes: launch arguments and the device-side coefficient buffer of a graph replay."""
     from tssplat_amd import scenes
     sc = scenes.make_scene("kuhn19", 2)

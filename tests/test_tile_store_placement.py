@@ -4,7 +4,7 @@ A tile's passes are separated by workgroup barriers and every phase is as long a
 front of a barrier costs more than its issue slot: the `vmcnt` counter retires in order, so the next wait of that wave for
 an OLDER load -- the compiler places a full `s_waitcnt vmcnt(0)` at the head of pass 3 -- also waits for the store's
 acknowledgement, and the workgroup's other waves wait for that wave at the next barrier.  The per-tile energy pair used to be
-stored right behind the H-store barrier (kernels.hip: kSumLate); it is now the last wave's last instruction.  The property
+stored right behind the H-store barrier (tile_kernel.hip: kSumLate); it is now the last wave's last instruction.  The property
 asserted here is the general one: in every tile kernel built with the gradient, no `global_store*` instruction stands in front
 of the kernel's last `s_barrier` (the one between the scatter and the per-vertex sums).  The body is straight-line code from
 barrier to barrier, so the order of addresses is the order of execution."""
@@ -34,7 +34,7 @@ def test_no_global_store_in_front_of_the_last_barrier_of_a_gradient_tile_kernel(
     for name, ops in grad.items():
         barriers = [i for i, op in enumerate(ops) if op == "s_barrier"]
         stores = [i for i, op in enumerate(ops) if op.startswith("global_store")]
-        assert len(barriers) >= 6, (name, len(barriers))          # the six barriers of a tile (kernels.hip: tile_body)
+        assert len(barriers) >= 6, (name, len(barriers))          # the six barriers of a tile (tile_kernel.hip: tile_body)
         assert stores, name                                        # the vertex sums and the energy pair
         assert not any(op.startswith(("flat_store", "buffer_store", "scratch_store")) for op in ops), name   # (stores come in one flavour)
         early = [i for i in stores if i < barriers[-1]]

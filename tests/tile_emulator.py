@@ -2,7 +2,7 @@
 
 Walks the host copy of a tiling plan (through the C ABI's introspection calls)
 and performs, tile by tile, exactly the passes of
-tssplat_amd/csrc/kernels.hip::tile_energy_kernel in numpy float64 -- the
+tssplat_amd/csrc/tile_kernel.hip::tile_energy_kernel in numpy float64 -- the
 scatter of every slot's four corner forces into the tile's per-vertex force
 array (row table + vertex + rank) and the row-by-row sums included -- followed
 by the finish kernel's staging sum.  If this matches the oracle, the plan data

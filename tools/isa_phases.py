@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction mix of a tile kernel per barrier-separated phase, from hipcc's -save-temps assembly.
 
-    hipcc -c tssplat_amd/csrc/kernels.hip <DEVICE_FLAGS> -save-temps -o /tmp/k.o   (in a scratch directory)
-    python tools/isa_phases.py /tmp/isa/kernels-hip-amdgcn-amd-amdhsa-gfx950.s [mangled-name-substring]
+    hipcc -c tssplat_amd/csrc/tile_kernel.hip <DEVICE_FLAGS> -save-temps -o /tmp/k.o   (in a scratch directory)
+    python tools/isa_phases.py /tmp/isa/tile_kernel-hip-amdgcn-amd-amdhsa-gfx950.s [mangled-name-substring]
 
 Counts are static (one pass through straight-line code; loops counted once), which is what the tile kernel's
 passes are: fully unrolled over the slots of a lane.  Used for profiles/r03_issue_model.md.

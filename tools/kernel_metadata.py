@@ -3,7 +3,7 @@
 
     python tools/kernel_metadata.py [path/to/lib.so]
 
-Used by tests/test_build_metadata.py: the tile kernels address LDS by absolute byte address (kernels.hip: lds_at), which
+Used by tests/test_build_metadata.py: the tile kernels address LDS by absolute byte address (tile_kernel.hip: lds_at), which
 is only right while they have NO static LDS object (group_segment_fixed_size == 0), and their occupancy depends on the
 register count staying within the launch bounds without spills.  Needs the LLVM tools that ship with ROCm.
 """

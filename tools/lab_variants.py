@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Laboratory builds of the tile kernel WITHOUT touching the product source: every variant is a list of textual patches applied
-to a COPY of tssplat_amd/csrc/kernels.hip (and, optionally, any other file of _build.SOURCES), compiled into tssplat_amd/libtssplat_amd_<name>.so next to
+to a COPY of tssplat_amd/csrc/tile_kernel.hip (and, where a patch names it, any other file of _build.SOURCES: the step kernels, the launch
+layer, capi.cpp), compiled into tssplat_amd/libtssplat_amd_<name>.so next to
 the product library and selected per process with TSSPLAT_AMD_LIB (tools/ab_variants.py does that).  The shipped kernels carry no
 experiment switches; pricing builds ("what does this phase cost?": results WRONG on purpose) and candidate
 changes live here, reproducible from this file.
@@ -17,7 +18,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tssplat_amd import _build  # noqa: E402
 
-K = "kernels.hip"
+K = "tile_kernel.hip"        # the tile kernel and its dispatch table
+S = "step_kernels.hip"       # finish kernel, energy reduction, optimiser kernels
+L = "eval_launch.cpp"        # launch recipe, configure_kernels, graphs
 
 # name -> (description, [(file, old, new), ...])
 VARIANTS = {
@@ -46,173 +49,43 @@ VARIANTS = {
         (K, "reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + td.blob_off);", "reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + a.tiles[tile & 31].blob_off);")]),
     "onewg_nostream32": ("pricing: one workgroup per CU AND the planes from L2 (tile t mod 32) -- the floor of the LDS-DMA loader / consumer design", [
         (K, "reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + td.blob_off);", "reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + a.tiles[tile & 31].blob_off);"),
-        (K, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
-        (K, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
+        (L, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
+        (L, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
     "onewg_exit_p1": ("pricing: one workgroup per CU, leave after pass 1 -- stage A of a LONE workgroup (stream + F); `onewg` minus this = the chain of passes a "
                       "lone 12-wave workgroup needs behind it, i.e. what a loader / consumer workgroup's consumers would still have to do per tile", [
         (K, "    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----",
             "    if (e_b == 12345.678f) g_partials[0] = e_b;\n    if (WITH_GRAD) return;\n    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----"),
-        (K, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
-        (K, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
-    # ---- round 6: a tile FED BY LDS-DMA, built and measured.  One 1 024-thread workgroup per CU (160 KiB) runs TWO
-    #      consecutive tiles: waves 0-11 evaluate tile A as the product does (planes from HBM into registers) while waves 12-15 -- the loaders --
-    #      fetch tile B's vertex ids and positions and pull its eleven non-neighbour planes into an LDS ring behind tile A's map with
-    #      global_load_lds (16 B per lane, no VGPRs); tile B then runs with its planes and positions read from LDS.  Results are the
-    #      product's (same arithmetic).  t(pair) - t(tile A alone, `onewg`) = what a DMA-fed tile costs a lone 12-wave workgroup. ----
-    "dma2": ("built: two tiles per 1 024-thread workgroup, the second one fed by LDS-DMA loader waves (see the comment above)", [
-        (K, """template <bool WITH_GRAD, bool WEIGHTED, bool REBUILD, int SPT>
-__device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, int32_t gv0)
-{""", """constexpr uint32_t kRing = 81920u;                                // LDS ring of the DMA-fed tile: planes 0-1 and 4-12 of the device image ...
-constexpr uint32_t kRingPos = kRing + 11u * 1536u * 4u + 1024u;    // ... and its staged positions (float4 per vertex)
-template <bool WITH_GRAD, bool WEIGHTED, bool REBUILD, int SPT, int FEED = 0>
-__device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, int32_t gv0)
-{"""),
-        (K, "    const int tid = threadIdx.x, nthr = blockDim.x;", "    const int tid = threadIdx.x, nthr = blockDim.x > 768 ? 768 : blockDim.x;   // (the loader waves are not the tile's)"),
-        (K, """    auto pair_u = [&](int q, VU &lo, VU &hi) {
-        if (kPaired) {""", """    auto pair_u = [&](int q, VU &lo, VU &hi) {
-        if (FEED == 1 && q == 0) {   // the vertex planes out of the ring
-            const v4u t = *lds_at<const v4u>(kRing + 16u * uint32_t(lt));
-            lo[0] = t.x, lo[1] = t.y, hi[0] = t.z, hi[1] = t.w;
-        } else if (kPaired) {"""),
-        (K, """    auto pair_f = [&](int q, VF &lo, VF &hi) {
-        if (kPaired) {""", """    auto pair_f = [&](int q, VF &lo, VF &hi) {
-        if (FEED == 1 && q < 12) {   // Dm^-1 out of the ring (planes 4 ... sit behind planes 0-1: two planes further down)
-            const v4f t = *lds_at<const v4f>(kRing + 4u * uint32_t(q - 2) * uint32_t(td.s_pad) + 16u * uint32_t(lt));
-            lo[0] = t.x, lo[1] = t.y, hi[0] = t.z, hi[1] = t.w;
-        } else if (kPaired) {"""),
-        (K, """        const size_t gv = size_t(gv0) * 3;
-        px = g_x[gv], py = g_x[gv + 1], pz = g_x[gv + 2];""", """        if (FEED == 1) {   // staged by the loader waves behind the ring
-            const v4f p4 = *lds_at<const v4f>(kRingPos + 16u * uint32_t(tid < td.n_verts ? tid : 0));
-            px = p4.x, py = p4.y, pz = p4.z;
-        } else {
-            const size_t gv = size_t(gv0) * 3;
-            px = g_x[gv], py = g_x[gv + 1], pz = g_x[gv + 2];
-        }"""),
-        (K, "        dm[8] = plane_f(12);", """        if (FEED == 1) {
-            const v2f t = *lds_at<const v2f>(kRing + 40u * uint32_t(td.s_pad) + 8u * uint32_t(lt));
-            dm[8][0] = t.x, dm[8][1] = t.y;
-        } else {
-            dm[8] = plane_f(12);
-        }"""),
-        (K, """struct FinishArgs {""", """// one wave-instruction of LDS-DMA: 64 lanes x 16 bytes from gsrc (per lane) to LDS bytes [lds_base, lds_base + 1024)
-__device__ __forceinline__ void dma16(const GLOBAL_AS unsigned char *gsrc, uint32_t lds_base)
-{
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void *)gsrc, (LDS_AS void *)(uintptr_t)lds_base, 16, 0, 0);
-}
-
-__global__ __launch_bounds__(1024, 4) void tile_energy_dma2_kernel(const KernelArgs a)
-{
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int tile_end = (xcd + 1) * a.tiles_per_xcd < a.n_tiles ? (xcd + 1) * a.tiles_per_xcd : a.n_tiles;
-    const int tile_a = xcd * a.tiles_per_xcd + 2 * jb, tile_b = tile_a + 1;
-    if (2 * jb >= a.tiles_per_xcd || tile_a >= tile_end) return;
-    const bool have_b = 2 * jb + 1 < a.tiles_per_xcd && tile_b < tile_end;
-    const int tid = threadIdx.x;
-    if (tid < 768) {   // ---- the twelve waves that evaluate: tile A from HBM, tile B from the ring ----
-        const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile_a) * size_t(a.vert_stride) + size_t(tid < a.vert_stride ? tid : 0)]);
-        __builtin_amdgcn_sched_barrier(0);
-        tile_body<true, false, false, 2, 0>(a, tile_a, gv0);
-        __syncthreads();   // tile A is done with its LDS; the loaders arrive here with tile B's planes landed
-        __syncthreads();   // (one barrier MORE between the loaders' wait and the first read of the ring: the guide's rule for two wave groups)
-        if (have_b) tile_body<true, false, false, 2, 1>(a, tile_b, 0);
-    } else {           // ---- the four loader waves ----
-        const int ll = tid - 768, lw = ll >> 6, lane = ll & 63;
-        if (have_b) {
-            const TileDesc tb = a.tiles[tile_b];
-            const auto g_gvid = as_global(a.gvid);
-            const auto g_x = as_global(a.x);
-            // ids -> positions of tile B's vertices (two per lane), staged behind the ring
-            const size_t vb = size_t(tile_b) * size_t(a.vert_stride);
-            const int v0 = ll, v1 = ll + 256;
-            const int32_t g0 = g_gvid[vb + size_t(v0 < a.vert_stride ? v0 : 0)], g1 = g_gvid[vb + size_t(v1 < a.vert_stride ? v1 : 0)];
-            const float p0x = g_x[size_t(g0) * 3], p0y = g_x[size_t(g0) * 3 + 1], p0z = g_x[size_t(g0) * 3 + 2];
-            const float p1x = g_x[size_t(g1) * 3], p1y = g_x[size_t(g1) * 3 + 1], p1z = g_x[size_t(g1) * 3 + 2];
-            if (v0 < tb.n_verts) *lds_at<v4f>(kRingPos + 16u * uint32_t(v0)) = v4f{p0x, p0y, p0z, 0.f};
-            if (v1 < tb.n_verts) *lds_at<v4f>(kRingPos + 16u * uint32_t(v1)) = v4f{p1x, p1y, p1z, 0.f};
-            // ... behind tile A's second barrier: its consumers have their own planes by then, the CU's ingest is free, and the DMA runs
-            // beside tile A's passes 2-3 / scatter / sums (issued at the head of tile A instead, it shares the ingest with tile A's
-            // own stream: 0.5975 ms against 0.5662 for one workgroup per CU without any DMA)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_s_barrier();
-            // the planes: device-image bytes of planes 0-1 and of planes 4-12, 1 KiB per wave-instruction, no VGPRs
-            const GLOBAL_AS unsigned char *src = as_global(a.blob) + tb.blob_off;
-            const uint32_t b01 = 8u * uint32_t(tb.s_pad), b412 = 36u * uint32_t(tb.s_pad);
-            // (s_pad is a multiple of 4, not of 256: the last piece of a range is cut to the range by the lane mask -- a lane that
-            // is off writes nothing)
-            for (uint32_t k = uint32_t(lw); k * 1024u < b01; k += 4u) {
-                const uint32_t piece = uint32_t(__builtin_amdgcn_readfirstlane(int(k)));
-                if (piece * 1024u + uint32_t(lane) * 16u < b01) dma16(src + size_t(piece) * 1024 + size_t(lane) * 16, kRing + piece * 1024u);
-            }
-            for (uint32_t k = uint32_t(lw); k * 1024u < b412; k += 4u) {
-                const uint32_t piece = uint32_t(__builtin_amdgcn_readfirstlane(int(k)));
-                if (piece * 1024u + uint32_t(lane) * 16u < b412)
-                    dma16(src + size_t(16u * uint32_t(tb.s_pad)) + size_t(piece) * 1024 + size_t(lane) * 16, kRing + b01 + piece * 1024u);
-            }
-        }
-        // tile A's six barriers (raw: a pending LDS-DMA must not be drained by them), the DMA landed before the seventh
-        for (int b = have_b ? 2 : 0; b < 6; ++b) __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_s_barrier();
-        if (have_b)
-            for (int b = 0; b < 6; ++b) __builtin_amdgcn_s_barrier();
-    }
-}
-
-struct FinishArgs {"""),
-        (K, "        return grad ? TSAMD_FN(true, 768, 6, false, false, 2) : TSAMD_FN(false, 768, 6, false, false, 2);\n    }\n    if (weighted || rebuild) return nullptr;",
-            "        return grad ? reinterpret_cast<const void *>(&tile_energy_dma2_kernel) : TSAMD_FN(false, 768, 6, false, false, 2);\n    }\n    if (weighted || rebuild) return nullptr;"),
-        (K, """        r.tile_block = dim3(unsigned(e.block_threads));
-        r.tile_grid = dim3(unsigned(8 * k.tiles_per_xcd));
-        r.tile_lds = size_t(e.lds_bytes);""", """        r.tile_block = dim3(unsigned(e.block_threads));
-        r.tile_grid = dim3(unsigned(8 * k.tiles_per_xcd));
-        r.tile_lds = size_t(e.lds_bytes);
-        if (r.tile_fn == reinterpret_cast<const void *>(&tile_energy_dma2_kernel)) {
-            r.tile_block = dim3(1024u);
-            r.tile_grid = dim3(unsigned(8 * ((k.tiles_per_xcd + 1) / 2)));
-            r.tile_lds = size_t(163840);
-        }"""),
-        (K, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 163840;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
+        (L, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
+        (L, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
     "fold_price": ("pricing: NO finish launch; every workgroup ends with a device-scope release fence + one atomic on a counter (in the first dword of the "
                    "energy partials' last pair: results wrong) -- the floor of a finish folded into the tile kernel for small plans (the last tile of a "
                    "sphere to arrive sums its shared vertices, the last of all reduces the energy)", [
         (K, "        if (64 * nw < td.n_verts) {   // more vertices than lanes (rare;", 
             "        __threadfence();\n        __syncthreads();\n        if (tid == 0) atomicAdd(reinterpret_cast<unsigned int *>(a.partials + 2 * size_t(a.n_tiles)), 1u);\n        if (64 * nw < td.n_verts) {   // more vertices than lanes (rare;"),
-        (K, "    if (f.n_finish > 0) {\n        // one vertex per thread", "    if (f.n_finish < 0) {\n        // one vertex per thread"),
-        (K, "    } else if (f.energy) {\n        r.finish_fn = reinterpret_cast<const void *>(&energy_reduce_kernel);", "    } else if (f.energy && !e.grad) {\n        r.finish_fn = reinterpret_cast<const void *>(&energy_reduce_kernel);"),
+        (L, "    if (f.n_finish > 0) {\n        r.finish_fn = step_kernels().finish;", "    if (f.n_finish < 0) {\n        r.finish_fn = step_kernels().finish;"),
+        (L, "    } else if (f.energy) {\n        r.finish_fn = step_kernels().energy_reduce;", "    } else if (f.energy && !e.grad) {\n        r.finish_fn = step_kernels().energy_reduce;"),
         ("capi.cpp", "upload(h->d_partials, nullptr, P.tiles.size() * 2, h->device_bytes)", "upload(h->d_partials, nullptr, P.tiles.size() * 2 + 2, h->device_bytes)")]),
     "ntstore_excl": ("candidate: non-temporal stores for the EXCLUSIVE result rows (grad: not read again by this evaluation); staging rows stay temporal", [
         (K, "                dst[0] = gx * sc;\n                dst[1] = gy * sc;\n                dst[2] = gz * sc;",
             "                if (excl) {\n                    __builtin_nontemporal_store(gx * sc, dst);\n                    __builtin_nontemporal_store(gy * sc, dst + 1);\n                    __builtin_nontemporal_store(gz * sc, dst + 2);\n                } else {\n                    dst[0] = gx * sc;\n                    dst[1] = gy * sc;\n                    dst[2] = gz * sc;\n                }")]),
     "fin_nodep": ("pricing: the finish kernel's staging rows at an address computed from the vertex number (2 or 3 rows from 2.5 k: results wrong) instead of "
                   "from fin_off[k] -- what a class-major staging layout (rows at computable addresses, one dependent level less) could buy at most", [
-        (K, "        const int32_t e0 = FIN_LOAD(&a.fin_off[k]), e1 = FIN_LOAD(&a.fin_off[k + 1]);   // consecutive rows, tile order",
+        (S, "        const int32_t e0 = FIN_LOAD(&a.fin_off[k]), e1 = FIN_LOAD(&a.fin_off[k + 1]);   // consecutive rows, tile order",
             "        const int32_t e0 = int32_t((k * 5) >> 1), e1 = e0 + 2 + int32_t(k & 1);   // (pricing)")]),
-    "ntfinish": ("the finish kernel's loads non-temporal (measured: finish kernel +50 %)", [(K, "#define FIN_LOAD(p) (*(p))", "#define FIN_LOAD(p) __builtin_nontemporal_load(p)")]),
-    "tids": ("vertex ids, destinations and row table through ordinary (temporal) loads, as until round 6", [
-        (K, "    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);",
-            "    const int32_t gv0 = as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)];"),
-        (K, "dst_row = __builtin_nontemporal_load(&g_vdst[td.vert_off + 64 * vb0 + lane]);", "dst_row = g_vdst[td.vert_off + 64 * vb0 + lane];"),
-        (K, "row0 = __builtin_nontemporal_load(&g_rowtab[tid < 65 ? tid : 64]);", "row0 = g_rowtab[tid < 65 ? tid : 64];")]),
+    "ntfinish": ("the finish kernel's loads non-temporal (measured: finish kernel +50 %)", [(S, "#define FIN_LOAD(p) (*(p))", "#define FIN_LOAD(p) __builtin_nontemporal_load(p)")]),
     "onewg": ("pricing: ONE workgroup per CU (100 KiB of dynamic LDS requested per workgroup, same tiles, same kernel)", [
-        (K, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
-        (K, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
+        (L, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
+        (L, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
     "onewg_nostream": ("pricing: one workgroup per CU AND no stream -- the floor of the LDS-DMA loader / consumer design (a CU's LDS holds ONE tile's records "
                        "next to the next tile's ring; 1 024 threads per workgroup cap the consumers at 12 waves + 4 loaders)", [
         (K, "reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + td.blob_off);", "reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + (td.blob_off & 0));"),
-        (K, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
-        (K, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
+        (L, "        r.tile_lds = size_t(e.lds_bytes);", "        r.tile_lds = size_t(100 * 1024);"),
+        (L, "    if (lds_bytes <= configured[dev]) return hipSuccess;", "    lds_bytes = 100 * 1024;\n    if (lds_bytes <= configured[dev]) return hipSuccess;")]),
     "rows8": ("candidate: per-vertex sums walk EIGHT rows per trip instead of four (a.veg's fullest vertices carry up to 56 rows: 7 dependent LDS round trips instead of 14)", [
         (K, "            for (int r = 0; r < rows; r += 4) {\n                const LDS_AS float *f[4];\n#pragma unroll\n                for (int u = 0; u < 4; ++u) {",
             "            for (int r = 0; r < rows; r += 8) {\n                const LDS_AS float *f[8];\n#pragma unroll\n                for (int u = 0; u < 8; ++u) {"),
         (K, "#pragma unroll\n                for (int u = 0; u < 4; ++u) {\n                    gx += f[u][0];",
             "#pragma unroll\n                for (int u = 0; u < 8; ++u) {\n                    gx += f[u][0];")]),
-    "tplanes": ("the planes through ordinary (temporal) loads, as until round 6 (the product loads them non-temporally)", [
-        (K, "return __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS PlaneU *>(pl + q * td.s_pad + SPT * lt)); };", "return *reinterpret_cast<const GLOBAL_AS PlaneU *>(pl + q * td.s_pad + SPT * lt); };"),
-        (K, "return __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS PlaneF *>(pl + q * td.s_pad + SPT * lt)); };", "return *reinterpret_cast<const GLOBAL_AS PlaneF *>(pl + q * td.s_pad + SPT * lt); };"),
-        (K, "            const VU2 t = __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS VU2 *>(pl + q * td.s_pad + 2 * SPT * lt));", "            const VU2 t = *reinterpret_cast<const GLOBAL_AS VU2 *>(pl + q * td.s_pad + 2 * SPT * lt);"),
-        (K, "            const VF2 t = __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS VF2 *>(pl + q * td.s_pad + 2 * SPT * lt));", "            const VF2 t = *reinterpret_cast<const GLOBAL_AS VF2 *>(pl + q * td.s_pad + 2 * SPT * lt);")]),
     # ---- candidates ----
     "stagger": ("the second workgroup of every CU starts half a tile late (first 512 workgroups: 256-511 sleep ~2.7 us)", [
         (K, "    if (jb >= a.tiles_per_xcd || tile >= tile_end) return;\n",
@@ -269,7 +142,7 @@ struct FinishArgs {"""),
         (K, '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n', '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
     ]),
     "prioB": ("head (load issue) = 3, pass 1 = 0, pass 2 = 1, pass 3 = 2, tail = 3", [
-        (K, '    const int32_t gv0 = as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)];\n', '    const int32_t gv0 = as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)];\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
+        (K, '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n', '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
         (K, '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n', '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n' + "    " + '__builtin_amdgcn_s_setprio(0);\n'),
         (K, '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n', '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n' + "    " + '__builtin_amdgcn_s_setprio(1);\n'),
         (K, '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n', '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n' + "    " + '__builtin_amdgcn_s_setprio(2);\n'),
@@ -288,7 +161,7 @@ struct FinishArgs {"""),
         (K, '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n', '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n' + "    " + '__builtin_amdgcn_s_setprio(0);\n'),
     ]),
     "prioE": ("head = 3, pass 1 = 1, pass 2 = 2, pass 3 = 3, tail = 3", [
-        (K, '    const int32_t gv0 = as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)];\n', '    const int32_t gv0 = as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)];\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
+        (K, '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n', '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
         (K, '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n', '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n' + "    " + '__builtin_amdgcn_s_setprio(1);\n'),
         (K, '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n', '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n' + "    " + '__builtin_amdgcn_s_setprio(2);\n'),
         (K, '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n', '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
@@ -305,85 +178,7 @@ struct FinishArgs {"""),
 }
 
 
-# debugging aids of `dma2`: one ingredient of the DMA-fed tile taken from HBM again
-_D = VARIANTS["dma2"][1]
-VARIANTS["dma2_chk"] = ("dma2 debug: tile B takes Dm^-1 from HBM, compares the ring with it and adds 1000 per mismatching lane-load to the barrier energy", _D + [
-    (K, """            const v4f t = *lds_at<const v4f>(kRing + 4u * uint32_t(q - 2) * uint32_t(td.s_pad) + 16u * uint32_t(lt));
-            lo[0] = t.x, lo[1] = t.y, hi[0] = t.z, hi[1] = t.w;""",
-        """            const v4f t = *lds_at<const v4f>(kRing + 4u * uint32_t(q - 2) * uint32_t(td.s_pad) + 16u * uint32_t(lt));
-            const VF2 h = __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS VF2 *>(pl + q * td.s_pad + 2 * SPT * lt));
-            if (active && (t.x != h[0] || t.y != h[1] || t.z != h[2] || t.w != h[3])) dbg_mismatch += 1000.f;
-            lo[0] = h[0], lo[1] = h[1], hi[0] = h[2], hi[1] = h[3];"""),
-    (K, "    auto pair_u = [&](int q, VU &lo, VU &hi) {", "    float dbg_mismatch = 0.f;\n    auto pair_u = [&](int q, VU &lo, VU &hi) {"),
-    (K, "    float e_b = 0.f, e_s = 0.f;", "    float e_b = dbg_mismatch, e_s = 0.f;\n    if (FEED == 1 && tid == 0 && *lds_at<const uint32_t>(kRingPos - 16u) != uint32_t(tile)) e_b += 1.0e6f;"),
-    (K, """        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();""", """        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        if (ll == 0) *lds_at<uint32_t>(kRingPos - 16u) = uint32_t(tile_b);   // (debug: "everything of tile B has landed")
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();""")])
-
-# `dma2` leaves the head of the DMA-fed tile on HBM: the LDS is full (two tile maps' worth: records + ring), so the neighbour planes, the row
-# table and the descriptor of tile B are fetched when tile B starts -- with its planes already in LDS there is nothing left to hide them
-# behind.  `dma2p` has the CONSUMERS fetch them into registers (five VGPRs; the 1 024-thread workgroup has 128) a phase before tile A ends.
-VARIANTS["dma2p"] = ("dma2 + tile B's neighbour planes / row table / descriptor prefetched into the consumers' registers at tile A's scatter", _D + [
-    (K, "constexpr uint32_t kRing = 81920u; ", "struct NextHead {\n    TileDesc td;\n    uint32_t nb[4];\n    uint32_t row0;\n};\nconstexpr uint32_t kRing = 81920u; "),
-    (K, "__device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, int32_t gv0)\n{",
-        "__device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, int32_t gv0, NextHead *nh = nullptr)\n{"),
-    (K, "    const TileDesc td = a.tiles[tile];", "    const TileDesc td = FEED == 1 ? nh->td : a.tiles[tile];"),
-    (K, "    pair_u(2, q_nb01, q_nb23);", """    if (FEED == 1) {
-        q_nb01[0] = nh->nb[0], q_nb01[1] = nh->nb[1], q_nb23[0] = nh->nb[2], q_nb23[1] = nh->nb[3];
-    } else {
-        pair_u(2, q_nb01, q_nb23);
-    }"""),
-    (K, "    if (WITH_GRAD) row0 = __builtin_nontemporal_load(&g_rowtab[tid < 65 ? tid : 64]);",
-        "    if (WITH_GRAD) row0 = FEED == 1 ? nh->row0 : __builtin_nontemporal_load(&g_rowtab[tid < 65 ? tid : 64]);"),
-    (K, "        __syncthreads();   // all waves done with H and with the staged positions", """        if (FEED == 0 && nh) {   // the head of the NEXT tile, a phase ahead (behind dst_row: the in-order wait for that one leaves these in flight)
-            const GLOBAL_AS uint32_t *npl = reinterpret_cast<const GLOBAL_AS uint32_t *>(g_blob + nh->td.blob_off);
-            const int nlt = tid < nh->td.s_pad / SPT ? tid : 0;
-            const v4u t = __builtin_nontemporal_load(reinterpret_cast<const GLOBAL_AS v4u *>(npl + 2 * nh->td.s_pad + 4 * nlt));
-            nh->nb[0] = t.x, nh->nb[1] = t.y, nh->nb[2] = t.z, nh->nb[3] = t.w;
-            const GLOBAL_AS uint16_t *nrt = reinterpret_cast<const GLOBAL_AS uint16_t *>(npl + size_t(kPlanes) * nh->td.s_pad);
-            nh->row0 = __builtin_nontemporal_load(&nrt[tid < 65 ? tid : 64]);
-        }
-        __syncthreads();   // all waves done with H and with the staged positions"""),
-    (K, """        tile_body<true, false, false, 2, 0>(a, tile_a, gv0);""", """        NextHead nh;
-        nh.td = a.tiles[have_b ? tile_b : tile_a];   // (scalar loads: back with tile A's own descriptor)
-        tile_body<true, false, false, 2, 0>(a, tile_a, gv0, &nh);"""),
-    (K, "        if (have_b) tile_body<true, false, false, 2, 1>(a, tile_b, 0);", "        if (have_b) tile_body<true, false, false, 2, 1>(a, tile_b, 0, &nh);")])
-
-# where the time of a pair goes: 100 MHz timestamps (s_memrealtime) of wave 0 and of loader wave 12 of two mid-launch workgroups, printed
-_T = "__builtin_amdgcn_s_memrealtime()"
-VARIANTS["dma2p_t"] = ("dma2p + phase timestamps of two mid-launch workgroups (printf; run a handful of evaluations only)", VARIANTS["dma2p"][1] + [(_f, _o, _n.replace("@T@", _T)) for _f, _o, _n in [
-    (K, "    uint32_t row0;\n};\nconstexpr uint32_t kRing", "    uint32_t row0;\n    unsigned long long ts[3];\n};\nconstexpr uint32_t kRing"),
-    (K, "    __syncthreads();\n    // behind the barrier: what pass 2 and the end of the tile need",
-        "    __syncthreads();\n    if (nh) nh->ts[0] = @T@;\n    // behind the barrier: what pass 2 and the end of the tile need"),
-    (K, "    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----",
-        "    if (nh) nh->ts[1] = @T@;\n    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----"),
-    (K, "        if (FEED == 0 && nh) {   // the head of the NEXT tile", "        if (nh) nh->ts[2] = @T@;\n        if (FEED == 0 && nh) {   // the head of the NEXT tile"),
-    (K, "        NextHead nh;\n", "        NextHead nh;\n        const unsigned long long T0 = @T@;\n"),
-    (K, "        if (have_b) tile_body<true, false, false, 2, 1>(a, tile_b, 0, &nh);", """        const unsigned long long T2 = @T@;
-        NextHead nhb = nh;
-        if (have_b) tile_body<true, false, false, 2, 1>(a, tile_b, 0, &nhb);
-        const unsigned long long T3 = @T@;
-        if (tid == 0 && have_b && (blockIdx.x == 4000 || blockIdx.x == 4003 || blockIdx.x == 7001))
-            printf("cons blk %d (x10 ns)  A: positions %llu pass1 %llu scatter %llu end %llu | join %llu | B: positions %llu pass1 %llu scatter %llu end %llu\\n", int(blockIdx.x),
-                   nh.ts[0] - T0, nh.ts[1] - T0, nh.ts[2] - T0, T1 - T0, T2 - T1, nhb.ts[0] - T2, nhb.ts[1] - T2, nhb.ts[2] - T2, T3 - T2);"""),
-    (K, "        __syncthreads();   // tile A is done with its LDS; the loaders arrive here", "        const unsigned long long T1 = @T@;\n        __syncthreads();   // tile A is done with its LDS; the loaders arrive here"),
-    (K, "        const int ll = tid - 768, lw = ll >> 6, lane = ll & 63;", "        const int ll = tid - 768, lw = ll >> 6, lane = ll & 63;\n        const unsigned long long L0 = @T@;\n        unsigned long long L1 = L0, L2 = L0;"),
-    (K, "            // the planes: device-image bytes of planes 0-1 and of planes 4-12, 1 KiB per wave-instruction, no VGPRs", "            L1 = @T@;\n            // the planes: device-image bytes of planes 0-1 and of planes 4-12, 1 KiB per wave-instruction, no VGPRs"),
-    (K, "        // tile A's six barriers (raw: a pending LDS-DMA must not be drained by them), the DMA landed before the seventh", "        L2 = @T@;\n        // tile A's six barriers (raw: a pending LDS-DMA must not be drained by them), the DMA landed before the seventh"),
-    (K, """        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_s_barrier();
-        if (have_b)""", """        const unsigned long long L3 = @T@;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        const unsigned long long L4 = @T@;
-        if (ll == 0 && have_b && (blockIdx.x == 4000 || blockIdx.x == 4003 || blockIdx.x == 7001))
-            printf("load blk %d (x10 ns)  dma issue starts %llu, issued %llu, tile A's barriers passed %llu, landed %llu\\n", int(blockIdx.x), L1 - L0, L2 - L0, L3 - L0, L4 - L0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_s_barrier();
-        if (have_b)""")]])
-
+_T = "__builtin_amdgcn_s_memrealtime()"   # 100 MHz timestamp
 # the product kernel's phases as seen by wave 0 of a few mid-launch workgroups (two workgroups per CU: each one's phases stretch by what the other takes)
 _BLK = "(blockIdx.x == 4000 || blockIdx.x == 4003 || blockIdx.x == 7001 || blockIdx.x == 9002 || blockIdx.x == 12005 || blockIdx.x == 15000)"
 VARIANTS["stamps"] = ("product kernel + 100 MHz phase timestamps of wave 0 in six mid-launch workgroups (printf; run a handful of evaluations only)", [(_f, _o, _n.replace("@T@", _T).replace("@BLK@", _BLK)) for _f, _o, _n in [
@@ -516,19 +311,27 @@ for _n in FLAG_VARIANTS:
     VARIANTS[_n] = (f"compiler flags: {_n}", [(K, "// gfx950 (MI355X / CDNA4) kernels", "// gfx950 (MI355X / CDNA4) kernels")])
 
 
-def build(name: str) -> str:
-    if name in DEFINE_VARIANTS:
-        return _build.build_variant(name, DEFINE_VARIANTS[name][1])
-    desc, patches = VARIANTS[name]
-    if name in COMBOS:
-        patches = [q for n in COMBOS[name] for q in VARIANTS[n][1]]
+def patched_sources(name: str) -> dict:
+    """file -> patched text of every file the variant touches (a combination: its parts' patches in turn).  Text only, no
+    compiler.  LookupError when an anchor is no longer in its file (tests/test_lab_variants.py asks every variant)."""
+    patches = [q for n in COMBOS[name] for q in VARIANTS[n][1]] if name in COMBOS else VARIANTS[name][1]
     srcs = {}
     for f, old, new in patches:
         if f not in srcs:
             srcs[f] = open(os.path.join(_build.CSRC, f)).read()
         if old not in srcs[f]:
-            raise SystemExit(f"variant {name}: patch anchor not found in {f}: {old[:70]!r}")
+            raise LookupError(f"variant {name}: patch anchor not found in {f}: {old[:70]!r}")
         srcs[f] = srcs[f].replace(old, new)
+    return srcs
+
+
+def build(name: str) -> str:
+    if name in DEFINE_VARIANTS:
+        return _build.build_variant(name, DEFINE_VARIANTS[name][1])
+    try:
+        srcs = patched_sources(name)
+    except LookupError as e:
+        raise SystemExit(str(e))
     hipcc = _build._hipcc()
     _build.build()                                      # the product objects of everything that is not patched
     os.makedirs(_build._OBJ, exist_ok=True)

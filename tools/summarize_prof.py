@@ -99,7 +99,7 @@ def main():
                 "read_bytes": tile["hbm_read_bytes_gfx950_corrected"],
                 "write_bytes": tile["hbm_write_bytes"],
                 "note": "FETCH_SIZE x 1024 x 2 (gfx950 wide-read correction) + WRITE_SIZE x 1024, separate --pmc passes",
-                # fingerprint of kernels.hip + every planner source and header (_build.traffic_digest) at the time of the measurement: bench.py drops the figure when
+                # fingerprint of tile_kernel.hip, launch_args.h and every planner source and header (_build.traffic_digest) at the time of the measurement: bench.py drops the figure when
                 # the sources it runs have moved on (a static traffic.json goes stale silently)
                 "sources": _traffic_digest(),
             }

@@ -20,10 +20,10 @@ LIB = os.path.join(_HERE, "libtssplat_amd.so")
 _OBJ = os.path.join(_HERE, "_obj")
 ARCH = "gfx950"
 
-SOURCES = ["plan.cpp", "plan_mesh.cpp", "plan_tiling.cpp", "plan_layout.cpp", "plan_planes.cpp", "partition.cpp", "conflict_opt.cpp", "capi.cpp", "kernels.hip", "surface.cpp", "surface_capi.cpp", "surface_kernels.hip",
+SOURCES = ["plan.cpp", "plan_mesh.cpp", "plan_tiling.cpp", "plan_layout.cpp", "plan_planes.cpp", "partition.cpp", "conflict_opt.cpp", "capi.cpp", "tile_kernel.hip", "step_kernels.hip", "eval_launch.cpp", "surface.cpp", "surface_capi.cpp", "surface_kernels.hip",
            "raster_capi.cpp", "raster_kernels.hip", "aa_kernels.hip", "grid_capi.cpp", "grid_kernels.hip",
            "mlp_capi.cpp", "mlp_kernels.hip", "texture_capi.cpp", "texture_kernels.hip", "shade_capi.cpp", "shade_kernels.hip"]
-HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "surface.h", "raster.h", "grid.h", "mlp.h", "texture.h", "shade.h", "det_mean.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
+HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "launch_args.h", "surface.h", "raster.h", "grid.h", "mlp.h", "texture.h", "shade.h", "det_mean.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
 
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-pthread"]
 # -fno-slp-vectorize: SLP packs the 3x3 algebra into v_pk_*_f32, which runs at the scalar-fp32 rate on
@@ -59,12 +59,14 @@ def _digest() -> str:
 
 def traffic_digest() -> str:
     """Fingerprint of the sources that decide how many bytes one evaluation moves: the tile kernel and the plan layout, i.e.
-    kernels.hip and EVERY planner source and header of SOURCES / HEADERS (plan*.cpp, partition.cpp, plan.h, planner.h).
+    tile_kernel.hip with its argument blocks (launch_args.h) and EVERY planner source and header of SOURCES / HEADERS (plan*.cpp,
+    partition.cpp, plan.h, planner.h).  Not the step kernels nor the launch layer (step_kernels.hip, eval_launch.cpp): an edit
+    there moves no byte of tile traffic.
     tools/summarize_prof.py stamps profiles/traffic.json with it when it condenses the rocprofv3 PMC passes; bench.py reports
     ``roofline.traffic`` only while the stamp matches the sources it runs."""
     h = hashlib.sha256()
     planner = sorted(n for n in SOURCES + HEADERS if n.startswith("plan") or n.startswith("partition"))   # every planner file
-    for name in ["kernels.hip"] + planner:
+    for name in ["tile_kernel.hip", "launch_args.h"] + planner:
         with open(os.path.join(CSRC, name), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

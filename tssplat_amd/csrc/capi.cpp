@@ -160,7 +160,7 @@ int to_device(tsamd_handle *h, int device)
         const hipError_t ce = tsamd::configure_kernels(P.lds_bytes);
         if (ce == hipErrorInvalidDeviceFunction)
             return fail(TSAMD_ERR_HIP, "a tile kernel of this build has a static LDS object: its dynamic LDS array no longer starts at LDS "
-                                       "address 0, which the kernels' absolute LDS addressing relies on (kernels.hip: lds_at)");
+                                       "address 0, which the kernels' absolute LDS addressing relies on (tile_kernel.hip: lds_at)");
         TSAMD_HIP(ce);
     }
     return TSAMD_OK;

@@ -1,4 +1,5 @@
-// Launch interface between the C ABI (capi.cpp) and the gfx950 kernels (kernels.hip).
+// Launch interface between the C ABI (capi.cpp) and the gfx950 kernels (tile_kernel.hip, step_kernels.hip); eval_launch.cpp
+// and step_kernels.hip implement it.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -22,7 +23,7 @@ struct EvalArgs {
     bool weighted = false;        // the plan carries an explicit element operator (22 planes per slot; 18 when it is symmetric)
     int32_t n_planes = 13;        // dword planes per slot of this plan (where a tile's incidence list starts)
     int32_t spt = kSlotsPerLane;  // slots per lane the plan is laid out for (selects the kernel instantiation)
-    bool index_nt = true;         // the plan shares (almost) no index planes: load them non-temporally (Plan::index_rep, kernels.hip: tile_body)
+    bool index_nt = true;         // the plan shares (almost) no index planes: load them non-temporally (Plan::index_rep, tile_kernel.hip: tile_body)
     // per evaluation
     const float *x;
     const float *grad_out;  // device scalar or nullptr

@@ -22,9 +22,7 @@
 // per forward+backward: :154, :185, :257).
 #include <hip/hip_runtime.h>
 
-#include <vector>
-
-#include "kernels.h"
+#include "launch_args.h"
 
 namespace tsamd {
 namespace {
@@ -259,26 +257,6 @@ __device__ __forceinline__ float wave_sum(float v)
                 r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
     return (r0 + r1) + (r2 + r3);
 }
-
-struct KernelArgs {
-    const TileDesc *tiles;
-    const uint8_t *blob;
-    const int32_t *gvid;
-    const int32_t *vdst;  // per tile vertex: >= 0 row of grad, < 0 staging row ~vdst (plan.h)
-    const float *x;
-    const float *grad_out;
-    float *grad;
-    float *stage;
-    double *partials;
-    float c1, c2;
-    float ratio;        // c2 / c1, divided on the host (set_coefficients): a division costs every wave of every tile a dozen instructions
-    const float *coef;  // optional: (c1, c2) read on the device instead (tsamd_evaluate_dev_coef); the kernel then divides itself
-    int order;
-    int n_tiles;
-    int tiles_per_xcd;
-    int vert_stride;   // gvid / vdst entries per tile: tile t's vertex ids start at t * vert_stride (= its descriptor's vert_off)
-    int n_planes;      // dword planes per slot (explicit-operator plans: 22, or 18 for a symmetric operator -- plan.h)
-};
 
 constexpr uint32_t kXS = kRowTabBytes;   // LDS byte address of the staged positions (plan.h: LDS map of a tile)
 constexpr uint32_t kZeroEntry = 4u * 66u;   // three zero dwords behind the 65 row starts: what a lane without an entry in a row reads
@@ -794,704 +772,41 @@ __global__ __launch_bounds__(BLOCK, WPE) void tile_shared_index_kernel(const Ker
     tile_entry<WITH_GRAD, WEIGHTED, REBUILD, kSlotsPerLane, false>(a);
 }
 
-struct FinishArgs {
-    const int32_t *fin_vid, *fin_off;
-    int64_t n_finish;
-    const float *stage;
-    float *grad;
-    const float *grad_out;
-    const double *partials;
-    int64_t n_tiles;
-    float c1, c2;
-    const float *coef;  // optional device (c1, c2), see KernelArgs
-    float *energy;
-    double *terms;
-    float *energy_copy;   // optional second destination of the energy (a replay's per-launch argument: the ring slot of an energy exchange)
-};
-
-// Per-tile energy partials -> E = c1 E_s + c2 E_b (tet_spheres_cuda.cu:191), one workgroup of T threads, fixed
-// order (bitwise repeatable).  Each thread owns tiles tid, tid + T, ... and issues its loads in batches of eight
-// before summing: a plain dependent loop costs one HBM latency per tile (60 us for 19 k tiles).
-template <int T>
-__device__ __forceinline__ void energy_reduce(const FinishArgs &a, double *red)
-{
-    const int tid = threadIdx.x;
-    const double2 *part = reinterpret_cast<const double2 *>(a.partials);
-    double s = 0.0, b = 0.0;
-    int64_t t = tid;
-    for (; t + 7 * T < a.n_tiles; t += 8 * T) {
-        double2 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = part[t + u * T];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            s += v[u].x;
-            b += v[u].y;
-        }
-    }
-    for (; t < a.n_tiles; t += T) {
-        const double2 v = part[t];
-        s += v.x;
-        b += v.y;
-    }
-    red[tid] = s;
-    red[T + tid] = b;
-    __syncthreads();
-    for (int off = T / 2; off > 0; off >>= 1) {
-        if (tid < off) {
-            red[tid] += red[tid + off];
-            red[T + tid] += red[T + tid + off];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        a.terms[0] = red[0];
-        a.terms[1] = red[T];
-        const float c1 = a.coef ? a.coef[0] : a.c1, c2 = a.coef ? a.coef[1] : a.c2;
-        const float e = float(double(c1) * red[0] + double(c2) * red[T]);
-        a.energy[0] = e;
-        if (a.energy_copy) a.energy_copy[0] = e;
-    }
-}
-
-// Forward-only evaluations: just the energy.
-__global__ __launch_bounds__(1024) void energy_reduce_kernel(const FinishArgs a)
-{
-    __shared__ double red[2 * 1024];
-    energy_reduce<1024>(a, red);
-}
-
-// Workgroup 0 reduces the energy partials (when asked to) while the others sum, for every vertex touched by
-// several tiles, its staged partial gradients in plan order (deterministic): one launch, and the 8 us of the
-// single-workgroup reduction hide behind the vertex work.
-// (Ordinary loads: non-temporal ones for the staging rows and lists -- read for the last time / once per evaluation -- were measured,
-// round 6: finish kernel 0.0269 -> 0.0409 ms on 512 x kuhn19, 0.0297 -> 0.0414 on a.veg x 952.  The rows are still in the memory-side
-// cache from the tile kernel's stores; a non-temporal read gives that up.)
-#define FIN_LOAD(p) (*(p))
-__global__ __launch_bounds__(256) void finish_kernel(const FinishArgs a)
-{
-    __shared__ double red[2 * 256];
-    const int tid = threadIdx.x;
-    if (blockIdx.x == 0) {
-        if (a.energy) energy_reduce<256>(a, red);
-        return;
-    }
-    const float gscale = a.grad_out ? *a.grad_out : 1.f;
-    // one thread per shared vertex (measured faster than one thread per output float: 0.065 vs 0.093 ms)
-    const int64_t stride = int64_t(gridDim.x - 1) * 256;
-    for (int64_t k = int64_t(blockIdx.x - 1) * 256 + tid; k < a.n_finish; k += stride) {
-        float gx = 0.f, gy = 0.f, gz = 0.f;
-        const int32_t e0 = FIN_LOAD(&a.fin_off[k]), e1 = FIN_LOAD(&a.fin_off[k + 1]);   // consecutive rows, tile order
-        // the first four rows go out together (most shared vertices have 2-4 copies): one memory latency instead of one
-        // per row; rows beyond the vertex's own are re-reads of its last row and are not added.  Finish kernel 0.037 ->
-        // 0.031 ms on the 512-sphere scene (2 / 3 / 8 rows: 0.034 / 0.031 / 0.031); same order of additions.
-        constexpr int kRowsAhead = 4;
-        {
-            float3 r[kRowsAhead];
-#pragma unroll
-            for (int j = 0; j < kRowsAhead; ++j) {
-                // (a vertex no tet references is in the list with zero rows: e1 - 1 may be -1 -- read row 0, add nothing)
-                const int32_t e = e0 + j < e1 ? e0 + j : (e1 > 0 ? e1 - 1 : 0);
-                const float *p = a.stage + size_t(e) * 3;
-                r[j] = make_float3(FIN_LOAD(p), FIN_LOAD(p + 1), FIN_LOAD(p + 2));
-            }
-#pragma unroll
-            for (int j = 0; j < kRowsAhead; ++j)
-                if (e0 + j < e1) {
-                    gx += r[j].x;
-                    gy += r[j].y;
-                    gz += r[j].z;
-                }
-        }
-        for (int32_t e = e0 + kRowsAhead; e < e1; ++e) {
-            const float *r = a.stage + size_t(e) * 3;
-            gx += FIN_LOAD(r);
-            gy += FIN_LOAD(r + 1);
-            gz += FIN_LOAD(r + 2);
-        }
-        float *g = a.grad + size_t(FIN_LOAD(&a.fin_vid[k])) * 3;
-        g[0] = gx * gscale;
-        g[1] = gy * gscale;
-        g[2] = gz * gscale;
-    }
-}
-
-__global__ __launch_bounds__(256) void scale_kernel(const float *in, const float *scalar, float *out, int64_t n)
-{
-    const float s = *scalar;
-    if (in == out && s == 1.f) return;  // in-place by exactly 1 (the usual autograd grad_output): nothing to do
-    const int64_t stride = int64_t(gridDim.x) * 256;
-    const int64_t n4 = n >> 2;
-    const float4 *in4 = reinterpret_cast<const float4 *>(in);
-    float4 *out4 = reinterpret_cast<float4 *>(out);
-    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    if (vec) {
-        for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n4; i += stride) {
-            float4 v = in4[i];
-            out4[i] = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
-        }
-        for (int64_t i = 4 * n4 + int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) out[i] = in[i] * s;
-    } else {
-        for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) out[i] = in[i] * s;
-    }
-}
-
-// max |g| over the array, as the bit pattern of a non-negative float (monotone under uint compare)
-__global__ __launch_bounds__(256) void absmax_kernel(const float *g, int64_t n, unsigned int *out)
-{
-    __shared__ float red[256 / kWave];
-    float m = 0.f;
-    const int64_t stride = int64_t(gridDim.x) * 256;
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) m = fmaxf(m, fabsf(g[i]));
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, kWave));
-    if (threadIdx.x % kWave == 0) red[threadIdx.x / kWave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 256 / kWave; ++w) m = fmaxf(m, red[w]);
-        atomicMax(out, __float_as_uint(m));
-    }
-}
-
-__global__ __launch_bounds__(256) void clamp_kernel(float *g, int64_t n, const unsigned int *mx, float thr, float s)
-{
-    const float m = __uint_as_float(*mx);
-    if (!(m > thr)) return;
-    const float f = s / m;
-    const int64_t stride = int64_t(gridDim.x) * 256;
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) g[i] *= f;
-}
-
-// ---- AdamUniform (reference utils/optimizer.py:38-89), two passes, no host sync ----
-// pass 1: moments in place (optimizer.py:61-62) + max g2 and max |g1| (the two global maxima the reference
-//         takes with .max(), :74 and :84, are monotone in the bias-corrected values)
-__global__ __launch_bounds__(256) void adam_moments_kernel(const float *grad, float *g1, float *g2, int64_t n, float b1,
-                                                           float b2, unsigned int *ws)
-{
-    __shared__ float red[2 * (256 / kWave)];
-    float mx2 = 0.f, mx1 = 0.f;
-    const int64_t stride = int64_t(gridDim.x) * 256, gid = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    auto upd = [&](float g, float &a, float &b) {
-        a = a * b1 + g * (1.f - b1);
-        b = b * b2 + (g * g) * (1.f - b2);
-        mx1 = fmaxf(mx1, fabsf(a));
-        mx2 = fmaxf(mx2, b);
-    };
-    // 16 B per lane (torch allocations are 16-B aligned; the tail and odd alignments take the scalar loop)
-    const bool vec = ((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(g1) | reinterpret_cast<uintptr_t>(g2)) & 15) == 0;
-    const int64_t n4 = vec ? n >> 2 : 0;
-    for (int64_t i = gid; i < n4; i += stride) {
-        const float4 g = reinterpret_cast<const float4 *>(grad)[i];
-        float4 a = reinterpret_cast<float4 *>(g1)[i], b = reinterpret_cast<float4 *>(g2)[i];
-        upd(g.x, a.x, b.x);
-        upd(g.y, a.y, b.y);
-        upd(g.z, a.z, b.z);
-        upd(g.w, a.w, b.w);
-        reinterpret_cast<float4 *>(g1)[i] = a;
-        reinterpret_cast<float4 *>(g2)[i] = b;
-    }
-    for (int64_t i = 4 * n4 + gid; i < n; i += stride) {
-        float a = g1[i], b = g2[i];
-        upd(grad[i], a, b);
-        g1[i] = a;
-        g2[i] = b;
-    }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        mx1 = fmaxf(mx1, __shfl_down(mx1, off, kWave));
-        mx2 = fmaxf(mx2, __shfl_down(mx2, off, kWave));
-    }
-    const int wave = threadIdx.x / kWave;
-    if (threadIdx.x % kWave == 0) {
-        red[2 * wave] = mx1;
-        red[2 * wave + 1] = mx2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 256 / kWave; ++w) {
-            mx1 = fmaxf(mx1, red[2 * w]);
-            mx2 = fmaxf(mx2, red[2 * w + 1]);
-        }
-        atomicMax(ws, __float_as_uint(mx1));      // non-negative floats order like their bit patterns
-        atomicMax(ws + 1, __float_as_uint(mx2));
-    }
-}
-
-// pass 2: gr = m1 / (1e-8 + max sqrt(m2)) (:74), optional max-abs clamp to `limit` (:84-86), p -= lr * gr (:88)
-__global__ __launch_bounds__(256) void adam_apply_kernel(float *p, const float *g1, int64_t n, float lr, float bias1,
-                                                         float bias2, float limit, const unsigned int *ws)
-{
-    const float mx1 = __uint_as_float(ws[0]) / bias1;             // max |m1|
-    const float denom = 1e-8f + sqrtf(__uint_as_float(ws[1]) / bias2);
-    float scale = 1.f / denom;
-    const float s = mx1 / denom;                                  // max |gr|
-    if (limit > 0.f && s > limit) scale *= limit / s;
-    const float k = lr * scale / bias1;
-    const int64_t stride = int64_t(gridDim.x) * 256, gid = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g1)) & 15) == 0;
-    const int64_t n4 = vec ? n >> 2 : 0;
-    for (int64_t i = gid; i < n4; i += stride) {
-        float4 v = reinterpret_cast<float4 *>(p)[i];
-        const float4 a = reinterpret_cast<const float4 *>(g1)[i];
-        v.x -= k * a.x;
-        v.y -= k * a.y;
-        v.z -= k * a.z;
-        v.w -= k * a.w;
-        reinterpret_cast<float4 *>(p)[i] = v;
-    }
-    for (int64_t i = 4 * n4 + gid; i < n; i += stride) p[i] -= k * g1[i];
-}
-
-// Grid of the kernels that end in one atomicMax per workgroup (adam_moments_kernel, absmax_kernel): few, long-running workgroups.
-// The atomics of all workgroups hit the same two words and serialise: 4 096 workgroups cost AdamUniform.step 0.127 ms at 12.3 M
-// elements, 512 cost 0.065 (6.0 TB/s algorithmic), 256 0.063, 16 384 0.305; 0.705 against 0.802 ms at 120 M elements.
-constexpr int kReduceGridCap = 512;
-
-int grid_for(int64_t n, int per_block, int cap)
-{
-    int64_t b = (n + per_block - 1) / per_block;
-    return int(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
-
-hipError_t launch_eval_kernels(const EvalArgs &e, hipStream_t stream, hipEvent_t *ev);
-
-namespace {
 
 // The lane layouts tile kernels are built for: (slots per lane, block-size cap, waves per SIMD of the launch bounds).
 //   2 x 768 @ 6 : 80 VGPRs, two workgroups of <= 80 KiB per CU -- the default, every operator variant
 //   3 x 512 @ 4 : 128 VGPRs, two workgroups per CU of fewer, fatter waves (built-in operator)
 //   4 x 768 @ 3 : 168 VGPRs, one workgroup per CU with up to 160 KiB: whole small tet-spheres as ONE tile, no halo, no
 //   3 x 1024 @ 4: 128 VGPRs, the same with more waves                   shared vertices (built-in operator)
-#define TSAMD_FN(...) reinterpret_cast<const void *>(&tile_energy_kernel<__VA_ARGS__>)
-#define TSAMD_FN_SHARED(...) reinterpret_cast<const void *>(&tile_shared_index_kernel<__VA_ARGS__>)
-// index_nt: the plan shares (almost) no index planes (EvalArgs::index_nt); false selects the cache-retaining twin where one is built
-const void *tile_kernel_for(int spt, int block_threads, bool grad, bool weighted, bool rebuild, bool index_nt)
-{
-    if (spt == 2 && block_threads <= 768 && !index_nt) {
-        if (weighted) return grad ? TSAMD_FN_SHARED(true, 768, 6, true, false) : TSAMD_FN_SHARED(false, 768, 6, true, false);
-        if (rebuild) return grad ? TSAMD_FN_SHARED(true, 768, 6, false, true) : TSAMD_FN_SHARED(false, 768, 6, false, true);
-        return grad ? TSAMD_FN_SHARED(true, 768, 6, false, false) : TSAMD_FN_SHARED(false, 768, 6, false, false);
-    }
-    if (spt == 2 && block_threads <= 768) {
-        if (weighted) return grad ? TSAMD_FN(true, 768, 6, true, false, 2) : TSAMD_FN(false, 768, 6, true, false, 2);
-        if (rebuild) return grad ? TSAMD_FN(true, 768, 6, false, true, 2) : TSAMD_FN(false, 768, 6, false, true, 2);
-        return grad ? TSAMD_FN(true, 768, 6, false, false, 2) : TSAMD_FN(false, 768, 6, false, false, 2);
-    }
-    if (weighted || rebuild) return nullptr;
-    if (spt == 3 && block_threads <= 512) return grad ? TSAMD_FN(true, 512, 4, false, false, 3) : TSAMD_FN(false, 512, 4, false, false, 3);
-    if (spt == 4 && block_threads <= 768) return grad ? TSAMD_FN(true, 768, 3, false, false, 4) : TSAMD_FN(false, 768, 3, false, false, 4);
-    if (spt == 3 && block_threads <= 1024) return grad ? TSAMD_FN(true, 1024, 4, false, false, 3) : TSAMD_FN(false, 1024, 4, false, false, 3);
-    return nullptr;
-}
+// Every instantiation there is, in the order tile_kernel_for() tries them: the cache-retaining twins (default layout only) in
+// front of their non-temporal kernels, 3 x 512 in front of 3 x 1024.
+#define TSAMD_FN(...) {reinterpret_cast<const void *>(&tile_energy_kernel<false, __VA_ARGS__>), reinterpret_cast<const void *>(&tile_energy_kernel<true, __VA_ARGS__>)}
+#define TSAMD_FN_SHARED(...) {reinterpret_cast<const void *>(&tile_shared_index_kernel<false, __VA_ARGS__>), reinterpret_cast<const void *>(&tile_shared_index_kernel<true, __VA_ARGS__>)}
+const TileKernelRow kTileKernels[9] = {
+    // spt, cap, weighted, rebuild, index_nt
+    {2, 768, true, false, false, TSAMD_FN_SHARED(768, 6, true, false)},
+    {2, 768, false, true, false, TSAMD_FN_SHARED(768, 6, false, true)},
+    {2, 768, false, false, false, TSAMD_FN_SHARED(768, 6, false, false)},
+    {2, 768, true, false, true, TSAMD_FN(768, 6, true, false, 2)},
+    {2, 768, false, true, true, TSAMD_FN(768, 6, false, true, 2)},
+    {2, 768, false, false, true, TSAMD_FN(768, 6, false, false, 2)},
+    {3, 512, false, false, true, TSAMD_FN(512, 4, false, false, 3)},
+    {4, 768, false, false, true, TSAMD_FN(768, 3, false, false, 4)},
+    {3, 1024, false, false, true, TSAMD_FN(1024, 4, false, false, 3)},
+};
 #undef TSAMD_FN
 #undef TSAMD_FN_SHARED
 
-}  // namespace
-
-bool lane_layout_supported(int spt, int max_threads) { return tile_kernel_for(spt, max_threads, true, false, false, true) != nullptr; }
-
-hipError_t configure_kernels(int lds_bytes)
+const void *tile_kernel_for(int spt, int block_threads, bool grad, bool weighted, bool rebuild, bool index_nt)
 {
-    // hipFuncAttributeMaxDynamicSharedMemorySize is per function, i.e. per process and device -- not per handle: only
-    // ever raise it, or a handle with small tiles would lower the limit under an earlier handle with large ones
-    static int configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds_bytes <= configured[dev]) return hipSuccess;
-    // every tile kernel a plan can reach
-    static const int layouts[][2] = {{2, 768}, {3, 512}, {4, 768}, {3, 1024}};
-    for (const auto &lay : layouts)
-        for (int variant = 0; variant < 12; ++variant) {
-            const int op = (variant % 6) / 2;
-            if (variant >= 6 && lay[0] != kSlotsPerLane) continue;   // (the cache-retaining twins exist for the default layout only)
-            const void *fn = tile_kernel_for(lay[0], lay[1], (variant & 1) != 0, op == 1, op == 2, variant < 6);
-            if (!fn) continue;
-            // lds_at() addresses the dynamic LDS array by absolute byte address: that is only right while the array starts
-            // at LDS address 0, i.e. while the kernel has no static LDS object in front of it (a static __shared__ variable,
-            // an LDS-using helper that was not inlined, a compiler-generated module-LDS block)
-            hipFuncAttributes attr;
-            hipError_t e = hipFuncGetAttributes(&attr, fn);
-            if (e != hipSuccess) return e;
-            if (attr.sharedSizeBytes != 0) return hipErrorInvalidDeviceFunction;
-            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-            if (e != hipSuccess) return e;
-        }
-    configured[dev] = lds_bytes;
-    return hipSuccess;
-}
-
-hipError_t launch_eval(const EvalArgs &e, hipStream_t stream, hipEvent_t *ev)
-{
-    if (ev) {
-        hipError_t err = hipEventRecord(ev[0], stream);
-        if (err != hipSuccess) return err;
-    }
-    hipError_t rc = launch_eval_kernels(e, stream, ev);
-    if (rc == hipSuccess && ev) rc = hipEventRecord(ev[2], stream);
-    return rc;
-}
-
-namespace {
-
-// What one evaluation launches: the tile kernel (if the plan has tiles) and then either the finish kernel (shared-vertex
-// sums + the energy reduction in its workgroup 0) or, without a gradient, the energy reduction alone.  One description
-// serves the stream launches below and the nodes of an EvalGraph.
-struct LaunchRecipe {
-    KernelArgs k;
-    FinishArgs f;
-    const void *tile_fn = nullptr, *finish_fn = nullptr;   // nullptr = not launched
-    dim3 tile_grid, tile_block, finish_grid, finish_block;
-    size_t tile_lds = 0;
-};
-
-void set_coefficients(KernelArgs &k, float c1, float c2)
-{
-    k.c1 = c1;
-    k.c2 = c2;
-    k.ratio = c2 / c1;   // (IEEE single-precision division, like the kernel's own: inf / NaN for c1 == 0 are handled there)
-}
-
-hipError_t make_recipe(const EvalArgs &e, LaunchRecipe &r)
-{
-    if (e.n_tiles > 0) {
-        KernelArgs &k = r.k;
-        k.tiles = e.tiles;
-        k.blob = e.blob;
-        k.gvid = e.gvid;
-        k.vdst = e.vdst;
-        k.x = e.x;
-        k.grad_out = e.grad_out;
-        k.grad = e.grad;
-        k.stage = e.stage;
-        k.partials = e.partials;
-        set_coefficients(k, e.c1, e.c2);
-        k.coef = e.coef;
-        k.order = e.order;
-        k.n_tiles = int(e.n_tiles);
-        k.tiles_per_xcd = int((e.n_tiles + 7) / 8);
-        k.vert_stride = e.vert_stride;
-        k.n_planes = e.n_planes;
-        r.tile_fn = tile_kernel_for(e.spt, e.block_threads, e.grad != nullptr, e.weighted, e.rebuild, e.index_nt);
-        if (!r.tile_fn) return hipErrorInvalidConfiguration;
-        r.tile_block = dim3(unsigned(e.block_threads));
-        r.tile_grid = dim3(unsigned(8 * k.tiles_per_xcd));
-        r.tile_lds = size_t(e.lds_bytes);
-    }
-    FinishArgs &f = r.f;
-    f.fin_vid = e.fin_vid;
-    f.fin_off = e.fin_off;
-    f.n_finish = e.grad ? e.n_finish : 0;
-    f.stage = e.stage;
-    f.grad = e.grad;
-    f.grad_out = e.grad_out;
-    f.partials = e.partials;
-    f.n_tiles = e.n_tiles;
-    f.c1 = e.c1;
-    f.c2 = e.c2;
-    f.coef = e.coef;
-    f.energy = e.energy;
-    f.terms = e.terms;
-    f.energy_copy = nullptr;
-    if (f.n_finish > 0) {
-        // one vertex per thread: the per-vertex chain off[k] -> rows -> store is pure latency, so expose all of it
-        r.finish_fn = reinterpret_cast<const void *>(&finish_kernel);
-        r.finish_grid = dim3(1u + unsigned(grid_for(f.n_finish, 256, 1 << 20)));
-        r.finish_block = dim3(256);
-    } else if (f.energy) {
-        r.finish_fn = reinterpret_cast<const void *>(&energy_reduce_kernel);
-        r.finish_grid = dim3(1);
-        r.finish_block = dim3(1024);
-    }
-    return hipSuccess;
-}
-
-}  // namespace
-
-hipError_t launch_eval_kernels(const EvalArgs &e, hipStream_t stream, hipEvent_t *ev)
-{
-    LaunchRecipe r;
-    hipError_t err = make_recipe(e, r);
-    if (err != hipSuccess) return err;
-    if (r.tile_fn) {
-        void *argv[] = {&r.k};
-        err = hipLaunchKernel(r.tile_fn, r.tile_grid, r.tile_block, argv, r.tile_lds, stream);
-        if (err != hipSuccess) return err;
-    }
-    if (ev) {
-        err = hipEventRecord(ev[1], stream);
-        if (err != hipSuccess) return err;
-    }
-    if (r.finish_fn) {
-        void *argv[] = {&r.f};
-        err = hipLaunchKernel(r.finish_fn, r.finish_grid, r.finish_block, argv, 0, stream);
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
-}
-
-// ---- the evaluation as an explicit HIP graph (tile node -> finish node) ----
-// The coefficients are kernel ARGUMENTS of both nodes: a launch updates them with hipGraphExecKernelNodeSetParams --
-// host-side bookkeeping, nothing on the GPU's timeline -- so a replay follows the reference's coefficient schedule
-// (energies/smooth_barrier.py:47-58) without a device-side coefficient buffer and its per-step 8-byte copy (measured
-// round 3: 64 x kuhn8 24.3 us per replayed step with that copy against 15.6 us with constant coefficients).
-struct EvalGraph {
-    LaunchRecipe r;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipGraphNode_t tile_node = nullptr, finish_node = nullptr;
-    hipKernelNodeParams tile_p, finish_p;
-    void *tile_argv[1], *finish_argv[1];
-    float *own_grad = nullptr;   // the gradient buffer the graph was created with (a launch may name another one)
-};
-
-hipError_t eval_graph_create(const EvalArgs &e, EvalGraph **out)
-{
-    *out = nullptr;
-    EvalGraph *g = new EvalGraph();
-    hipError_t err = make_recipe(e, g->r);
-    g->own_grad = e.grad;
-    auto fail = [&](hipError_t code) {
-        eval_graph_destroy(g);
-        return code;
-    };
-    if (err != hipSuccess) return fail(err);
-    if ((err = hipGraphCreate(&g->graph, 0)) != hipSuccess) return fail(err);
-    if (g->r.tile_fn) {
-        g->tile_argv[0] = &g->r.k;
-        hipKernelNodeParams &p = g->tile_p;
-        p = hipKernelNodeParams{};
-        p.func = const_cast<void *>(g->r.tile_fn);
-        p.gridDim = g->r.tile_grid;
-        p.blockDim = g->r.tile_block;
-        p.sharedMemBytes = unsigned(g->r.tile_lds);
-        p.kernelParams = g->tile_argv;
-        p.extra = nullptr;
-        if ((err = hipGraphAddKernelNode(&g->tile_node, g->graph, nullptr, 0, &p)) != hipSuccess) return fail(err);
-    }
-    if (g->r.finish_fn) {
-        g->finish_argv[0] = &g->r.f;
-        hipKernelNodeParams &p = g->finish_p;
-        p = hipKernelNodeParams{};
-        p.func = const_cast<void *>(g->r.finish_fn);
-        p.gridDim = g->r.finish_grid;
-        p.blockDim = g->r.finish_block;
-        p.sharedMemBytes = 0;
-        p.kernelParams = g->finish_argv;
-        p.extra = nullptr;
-        if ((err = hipGraphAddKernelNode(&g->finish_node, g->graph, g->tile_node ? &g->tile_node : nullptr, g->tile_node ? 1 : 0, &p)) !=
-            hipSuccess)
-            return fail(err);
-    }
-    if ((err = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0)) != hipSuccess) return fail(err);
-    *out = g;
-    return hipSuccess;
-}
-
-hipError_t eval_graph_launch(EvalGraph *g, float c1, float c2, hipStream_t stream, float *energy_copy, float *grad)
-{
-    hipError_t err;
-    const bool coef = g->r.k.c1 != c1 || g->r.k.c2 != c2 || g->r.f.c1 != c1 || g->r.f.c2 != c2;
-    // (the gradient's address is an argument of both nodes, the energy copy's of the finish node -- per-launch, like the coefficients)
-    if (!grad) grad = g->own_grad;
-    if (grad != g->r.f.grad && !g->own_grad) return hipErrorInvalidValue;   // (a graph created without a gradient has no backward kernels)
-    const bool moved = grad != g->r.f.grad;
-    if (coef || moved) {
-        set_coefficients(g->r.k, c1, c2);
-        g->r.f.c1 = c1;
-        g->r.f.c2 = c2;
-        g->r.k.grad = grad;
-        if (g->tile_node && (err = hipGraphExecKernelNodeSetParams(g->exec, g->tile_node, &g->tile_p)) != hipSuccess) return err;
-    }
-    if (coef || moved || g->r.f.energy_copy != energy_copy) {
-        if (energy_copy && (!g->finish_node || !g->r.f.energy)) return hipErrorInvalidValue;   // (no node reduces the energy in this graph)
-        g->r.f.energy_copy = energy_copy;
-        g->r.f.grad = grad;
-        if (g->finish_node && (err = hipGraphExecKernelNodeSetParams(g->exec, g->finish_node, &g->finish_p)) != hipSuccess) return err;
-    }
-    return hipGraphLaunch(g->exec, stream);
-}
-
-void eval_graph_destroy(EvalGraph *g)
-{
-    if (!g) return;
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    delete g;
-}
-
-// ---- n optimisation steps as one graph (trainer.py:128-133 folded: energy + backward, optimizer.step) ----
-// Every step is four kernel nodes in a chain -- tile, finish, adam_moments, adam_apply -- and the steps are chained to each
-// other through the parameter (apply of step k writes what tile of step k + 1 reads).  Nothing per step on the host: one launch
-// per n steps, the schedule (coefficients, order, bias corrections, step limit) goes in as node arguments beforehand.
-struct TrainLoopGraph {
-    struct Adam {
-        const float *grad;
-        float *g1, *g2, *p;
-        int64_t n;
-        float b1, b2, lr, bias1, bias2, limit;
-        unsigned int *ws;
-    };
-    int n = 0;
-    std::vector<LaunchRecipe> r;
-    std::vector<Adam> adam;
-    std::vector<hipGraphNode_t> tile, finish, moments, apply;
-    std::vector<hipKernelNodeParams> tile_p, finish_p, moments_p, apply_p;
-    std::vector<void *> argv;     // [n][1 + 1 + 7 + 8]
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int adam_grid = 0;
-};
-
-hipError_t train_loop_create(const EvalArgs &e, float *param, float *g1, float *g2, int64_t n_param, void *ws, int n_iters, TrainLoopGraph **out)
-{
-    *out = nullptr;
-    if (n_iters < 1 || n_iters > 4096 || n_param < 1 || !e.grad || !e.energy) return hipErrorInvalidValue;
-    TrainLoopGraph *g = new TrainLoopGraph();
-    auto fail = [&](hipError_t code) {
-        train_loop_destroy(g);
-        return code;
-    };
-    g->n = n_iters;
-    g->r.resize(n_iters);
-    g->adam.resize(n_iters);
-    g->tile.assign(n_iters, nullptr);
-    g->finish.assign(n_iters, nullptr);
-    g->moments.assign(n_iters, nullptr);
-    g->apply.assign(n_iters, nullptr);
-    g->tile_p.resize(n_iters);
-    g->finish_p.resize(n_iters);
-    g->moments_p.resize(n_iters);
-    g->apply_p.resize(n_iters);
-    g->argv.resize(size_t(n_iters) * 17);
-    g->adam_grid = grid_for(n_param, 1024, kReduceGridCap);
-    hipError_t err;
-    if ((err = hipGraphCreate(&g->graph, 0)) != hipSuccess) return fail(err);
-    // the optimiser's two-dword scratch of every step, zeroed once per launch
-    hipGraphNode_t prev = nullptr;
-    {
-        hipMemsetParams m = {};
-        m.dst = ws;
-        m.elementSize = 4;
-        m.width = size_t(2 * n_iters);
-        m.height = 1;
-        m.value = 0;
-        if ((err = hipGraphAddMemsetNode(&prev, g->graph, nullptr, 0, &m)) != hipSuccess) return fail(err);
-    }
-    for (int k = 0; k < n_iters; ++k) {
-        EvalArgs ek = e;
-        ek.x = param;
-        ek.energy = e.energy + k;
-        if ((err = make_recipe(ek, g->r[k])) != hipSuccess) return fail(err);
-        LaunchRecipe &r = g->r[k];
-        void **av = g->argv.data() + size_t(k) * 17;
-        auto add = [&](hipGraphNode_t *node, hipKernelNodeParams &p, const void *fn, dim3 grid, dim3 block, size_t lds, void **args) {
-            p = hipKernelNodeParams{};
-            p.func = const_cast<void *>(fn);
-            p.gridDim = grid;
-            p.blockDim = block;
-            p.sharedMemBytes = unsigned(lds);
-            p.kernelParams = args;
-            p.extra = nullptr;
-            const hipError_t rc = hipGraphAddKernelNode(node, g->graph, prev ? &prev : nullptr, prev ? 1 : 0, &p);
-            if (rc == hipSuccess) prev = *node;
-            return rc;
-        };
-        if (r.tile_fn) {
-            av[0] = &r.k;
-            if ((err = add(&g->tile[k], g->tile_p[k], r.tile_fn, r.tile_grid, r.tile_block, r.tile_lds, av)) != hipSuccess) return fail(err);
-        }
-        if (r.finish_fn) {
-            av[1] = &r.f;
-            if ((err = add(&g->finish[k], g->finish_p[k], r.finish_fn, r.finish_grid, r.finish_block, 0, av + 1)) != hipSuccess) return fail(err);
-        }
-        TrainLoopGraph::Adam &a = g->adam[k];
-        a = TrainLoopGraph::Adam{e.grad, g1, g2, param, n_param, 0.9f, 0.999f, 0.f, 1.f, 1.f, -1.f, static_cast<unsigned int *>(ws) + 2 * k};
-        void **am = av + 2, **aa = av + 9;
-        am[0] = &a.grad, am[1] = &a.g1, am[2] = &a.g2, am[3] = &a.n, am[4] = &a.b1, am[5] = &a.b2, am[6] = &a.ws;
-        aa[0] = &a.p, aa[1] = &a.g1, aa[2] = &a.n, aa[3] = &a.lr, aa[4] = &a.bias1, aa[5] = &a.bias2, aa[6] = &a.limit, aa[7] = &a.ws;
-        if ((err = add(&g->moments[k], g->moments_p[k], reinterpret_cast<const void *>(&adam_moments_kernel), dim3(unsigned(g->adam_grid)), dim3(256), 0,
-                       am)) != hipSuccess)
-            return fail(err);
-        if ((err = add(&g->apply[k], g->apply_p[k], reinterpret_cast<const void *>(&adam_apply_kernel), dim3(unsigned(g->adam_grid)), dim3(256), 0, aa)) !=
-            hipSuccess)
-            return fail(err);
-    }
-    if ((err = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0)) != hipSuccess) return fail(err);
-    *out = g;
-    return hipSuccess;
-}
-
-hipError_t train_loop_launch(TrainLoopGraph *g, const TrainLoopStep *steps, float lr, float b1, float b2, hipStream_t stream)
-{
-    hipError_t err;
-    for (int k = 0; k < g->n; ++k) {
-        LaunchRecipe &r = g->r[k];
-        const TrainLoopStep &s = steps[k];
-        if (r.k.c1 != s.c1 || r.k.c2 != s.c2 || r.k.order != s.order || r.f.c1 != s.c1 || r.f.c2 != s.c2) {
-            set_coefficients(r.k, s.c1, s.c2);
-            r.f.c1 = s.c1;
-            r.f.c2 = s.c2;
-            r.k.order = s.order;
-            if (g->tile[k] && (err = hipGraphExecKernelNodeSetParams(g->exec, g->tile[k], &g->tile_p[k])) != hipSuccess) return err;
-            if (g->finish[k] && (err = hipGraphExecKernelNodeSetParams(g->exec, g->finish[k], &g->finish_p[k])) != hipSuccess) return err;
-        }
-        TrainLoopGraph::Adam &a = g->adam[k];
-        if (a.b1 != b1 || a.b2 != b2) {
-            a.b1 = b1;
-            a.b2 = b2;
-            if ((err = hipGraphExecKernelNodeSetParams(g->exec, g->moments[k], &g->moments_p[k])) != hipSuccess) return err;
-        }
-        if (a.lr != lr || a.bias1 != s.bias1 || a.bias2 != s.bias2 || a.limit != s.limit) {
-            a.lr = lr;
-            a.bias1 = s.bias1;
-            a.bias2 = s.bias2;
-            a.limit = s.limit;
-            if ((err = hipGraphExecKernelNodeSetParams(g->exec, g->apply[k], &g->apply_p[k])) != hipSuccess) return err;
-        }
-    }
-    return hipGraphLaunch(g->exec, stream);
-}
-
-void train_loop_destroy(TrainLoopGraph *g)
-{
-    if (!g) return;
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    delete g;
-}
-
-hipError_t launch_scale(const float *in, const float *scalar, float *out, int64_t n, hipStream_t stream)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(scale_kernel, dim3(unsigned(grid_for(n, 1024, 2048))), dim3(256), 0, stream, in, scalar, out, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_adam_uniform(float *p, const float *grad, float *g1, float *g2, int64_t n, float lr, float b1, float b2,
-                               float bias1, float bias2, float limit, void *workspace, hipStream_t stream)
-{
-    if (n <= 0) return hipSuccess;
-    unsigned int *ws = static_cast<unsigned int *>(workspace);
-    hipError_t e = hipMemsetAsync(ws, 0, 2 * sizeof(unsigned int), stream);
-    if (e != hipSuccess) return e;
-    const int g = grid_for(n, 1024, kReduceGridCap);
-    hipLaunchKernelGGL(adam_moments_kernel, dim3(unsigned(g)), dim3(256), 0, stream, grad, g1, g2, n, b1, b2, ws);
-    hipLaunchKernelGGL(adam_apply_kernel, dim3(unsigned(g)), dim3(256), 0, stream, p, g1, n, lr, bias1, bias2, limit, ws);
-    return hipGetLastError();
-}
-
-hipError_t launch_grad_limit(float *grad, int64_t n, float thr, float s, void *workspace, hipStream_t stream)
-{
-    if (n <= 0) return hipSuccess;
-    unsigned int *mx = static_cast<unsigned int *>(workspace);
-    hipError_t e = hipMemsetAsync(mx, 0, sizeof(unsigned int), stream);
-    if (e != hipSuccess) return e;
-    const int g = grid_for(n, 1024, kReduceGridCap);
-    hipLaunchKernelGGL(absmax_kernel, dim3(unsigned(g)), dim3(256), 0, stream, grad, n, mx);
-    hipLaunchKernelGGL(clamp_kernel, dim3(unsigned(g)), dim3(256), 0, stream, grad, n, mx, thr, s);
-    return hipGetLastError();
+    // first match; a plan that shares index planes falls back to the non-temporal kernel where no twin is built
+    // (no plan is both weighted and rebuild -- EvalArgs derives them from one plane count --; asked for both, weighted wins)
+    rebuild = rebuild && !weighted;
+    for (const TileKernelRow &row : kTileKernels)
+        if (row.spt == spt && block_threads <= row.cap && row.weighted == weighted && row.rebuild == rebuild && (row.index_nt || !index_nt))
+            return row.fn[grad];
+    return nullptr;
 }
 
 }  // namespace tsamd
