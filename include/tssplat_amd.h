@@ -682,6 +682,40 @@ int tsamd_texture_backward(const float *tex_dev, int64_t tex_batch, int32_t tex_
                            const float *uv_dev, int64_t batch, int32_t height, int32_t width, int32_t filter_mode,
                            int32_t boundary_mode, const float *grad_out_dev, float *grad_tex_dev, float *grad_uv_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Sphere initialisation: silhouettes -> visual hull -> exact squared distance transform -> greedy ball cover, the job of the
+ * reference's data/generate_init_spheres.py (whose skeleton + MILP selection is NOT rebuilt: DESIGN.md).  Semantics are fixed by
+ * tests/spheres_init_oracle.py and are stated in integers, separately rounded float32 operations and single double products, so
+ * the results are bitwise repeatable.  Stateless; the caller owns all buffers, workspaces included; the current HIP device is
+ * used and nothing synchronises the host.
+ *
+ * The grid: G = grid voxels per axis, 1 .. 512, over the cube [lo, hi]^3; h = (hi - lo) / G; voxel (i, j, k) has the flat
+ * index (i G + j) G + k and the centre float32(lo + (index + 0.5) h) per axis (double arithmetic, rounded once).
+ *
+ * tsamd_hull_carve: alpha_dev [batch, height, width, channels] f32, mvp_dev [batch, 4, 4] f32 row-major (clip = mvp (x, y, z, 1)),
+ * height, width 1 .. 8192 (0 only with batch 0).  bits_workspace_dev: batch x height x ceil(width / 32) u32; the call first packs
+ * alpha[..., channel] > threshold into it, one bit per pixel (bit x % 32 of word x / 32 of its row).  hull_out_dev [G, G, G] u8 is
+ * 1 where, for every view, with clip_r = ((m[r][0] x + m[r][1] y) + m[r][2] z) + m[r][3] in float32: clip_3 > 0, nx = clip_0 /
+ * clip_3 and ny = clip_1 / clip_3 have |nx| < 1 and |ny| < 1, and the pixel (min(width - 1, floor(((nx + 1) 0.5) width)), the
+ * same in y with height; row 0 is ny = -1) has its bit set.  A comparison with a NaN is false.  No read leaves the image whatever
+ * mvp holds.  batch 0: every voxel is inside.
+ *
+ * tsamd_edt_squared: mask_dev [G, G, G] u8 (non-zero = true).  d2_out_dev [G, G, G] i32 = the squared distance in voxel units from
+ * each voxel to the nearest false voxel (0 where the mask is false; nothing outside the array counts as background).
+ * workspace_dev: G^3 i32.  status_out_dev: one i32, 1 when the mask has a false voxel, else 0 -- d2_out_dev is then undefined.
+ *
+ * tsamd_greedy_cover: at most n_spheres (0 .. 2^20) times: take q = max d2 over the uncovered voxels (initially hull_dev), the
+ * lowest flat index k among equals; stop when nothing is uncovered, q == 0 or double(q) hs2 < m2; record (k, q) and clear every
+ * voxel v with double(D2(v, k)) <= double(q) s2, D2 the squared index distance.  The caller passes s2 = shrink^2, hs2 = (h
+ * shrink)^2 and m2 = min_radius^2.  One launch per record and one more; count_out_dev (one i32) and the first count entries of
+ * flat_out_dev / q_out_dev [n_spheres] i32 hold the records, uncovered_out_dev [G, G, G] u8 (may be hull_dev itself) what is left.
+ * workspace_dev: 8 (n_spheres + 1) bytes, 8-byte aligned. */
+int tsamd_hull_carve(const float *alpha_dev, int64_t batch, int32_t height, int32_t width, int32_t channels, int32_t channel, float threshold,
+                     const float *mvp_dev, int32_t grid, double lo, double hi, uint32_t *bits_workspace_dev, uint8_t *hull_out_dev, void *stream);
+int tsamd_edt_squared(const uint8_t *mask_dev, int32_t grid, int32_t *workspace_dev, int32_t *d2_out_dev, int32_t *status_out_dev, void *stream);
+int tsamd_greedy_cover(const uint8_t *hull_dev, const int32_t *d2_dev, int32_t grid, int32_t n_spheres, double s2, double hs2, double m2,
+                       void *workspace_dev, uint8_t *uncovered_out_dev, int32_t *flat_out_dev, int32_t *q_out_dev, int32_t *count_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

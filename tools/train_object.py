@@ -15,6 +15,11 @@ absent):
 
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
+                                 [--placement host|device --grid N]
+
+--placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
+so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
+the same algorithm as HIP kernels, stated in integers).  --grid: voxels per axis of the placement grid (72).
 
 --silhouette: how the loop renders alpha and takes the image loss -- `operators` (the default: rasterize, clamp, antialias, MSELoss),
 `fused` (MeshRasterizer(fused_silhouette=True): dr.silhouette, then MSELoss) or `fused-loss` (MeshRasterizer.silhouette_loss:
@@ -112,7 +117,7 @@ def build_spheres(centres, radii, k):
 
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
-        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1)):
+        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), placement="host", grid=72):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -123,6 +128,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         raise ValueError(f"unknown --silhouette mode {silhouette!r}")
     if fit_depth not in ("off", "operators", "fused-loss"):
         raise ValueError(f"unknown --fit-depth mode {fit_depth!r}")
+    if placement not in ("host", "device"):
+        raise ValueError(f"unknown --placement {placement!r}")
     target_npz = target_npz or os.path.join(ROOT, "tests", "golden", "mario_mesh.npz")
     tgt = np.load(target_npz)
     tv = torch.from_numpy(tgt["vertices"].astype(np.float32)).cuda()
@@ -135,11 +142,19 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     if fit_depth != "off":
         with torch.no_grad():
             target_depth = render_depth(glctx, tv, tf, mvp, campos, res).clone()
-    centres, radii, hull_frac, left = place_spheres(target, mvp, n_spheres)
-    S = len(radii)
-    rest, tets = build_spheres(centres, radii, k)
-    flags = types.SimpleNamespace(smooth_eng_coeff=2e-4 / S, barrier_coeff=2e-4, increase_order_iter=1000)   # gso.yaml:8-11, tetmesh_geometry.py:242-243
-    geo = geometry.TetMeshGeometry(rest, tets, smooth_barrier_param=flags)
+    if placement == "device":
+        from tssplat_amd import spheres_init
+        kp = spheres_init.init_spheres(target, mvp, n_spheres, grid=grid)
+        radii, hull_frac, left, S = kp.r, kp.hull_fraction, kp.uncovered_fraction, len(kp)
+        flags = types.SimpleNamespace(smooth_eng_coeff=2e-4, barrier_coeff=2e-4, increase_order_iter=1000)   # gso.yaml:8-11; the class divides by S
+        geo = geometry.TetMeshMultiSphereGeometry(kp, k=k, smooth_barrier_param=flags)
+        rest, tets = geo.tet_v.detach().cpu().numpy(), geo.tet_elem.cpu().numpy()
+    else:
+        centres, radii, hull_frac, left = place_spheres(target, mvp, n_spheres, grid=grid)
+        S = len(radii)
+        rest, tets = build_spheres(centres, radii, k)
+        flags = types.SimpleNamespace(smooth_eng_coeff=2e-4 / S, barrier_coeff=2e-4, increase_order_iter=1000)   # gso.yaml:8-11, tetmesh_geometry.py:242-243
+        geo = geometry.TetMeshGeometry(rest, tets, smooth_barrier_param=flags)
     ren = renderers.MeshRasterizer(geo, fused_silhouette=silhouette != "operators")
     opt = AdamUniform(ren.parameters(), lr=0.2, grad_limit=True, grad_limit_values=[0.01, 0.01], grad_limit_iters=[1500])   # gso.yaml:37-41
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, iters, eta_min=1e-4)                                           # trainer.py:57-58
@@ -192,7 +207,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         "silhouette_iou": iou, "silhouette_iou_at_start": iou0, "inverted_tets": inverted, "tets": int(tets.shape[0]),
         "img_loss_first_last": [log[0][1], log[-1][1]], "reg_first_last": [log[0][2], log[-1][2]],
         "spheres": {"placed": S, "asked": n_spheres, "radii_min_max": [float(radii.min()), float(radii.max())], "visual_hull_fraction_of_cube": hull_frac,
-                    "hull_voxel_centres_left_uncovered": left},
+                    "hull_voxel_centres_left_uncovered": left, "placement": placement, "grid": grid},
         "config": {"workload": f"{S} tet-spheres x kuhn{k}: {int(tets.shape[0])} tets, {int(geo.surface_fid.shape[0])} surface triangles; {views} views x {res}^2 per iteration; "
                                f"target {os.path.basename(target_npz)} ({int(tv.shape[0])} vertices, {int(tf.shape[0])} triangles)",
                    "data": "silhouettes of the reference's mesh_data/mario_example/model.obj rendered with tssplat_amd.dr from data/render_dataset.py's cameras",
@@ -342,15 +357,17 @@ def main():
     ap.add_argument("--no-stages", action="store_true", help="skip the stand-alone stage timings")
     ap.add_argument("--fit-depth", choices=["off", "operators", "fused-loss"], default="off")
     ap.add_argument("--fit-depth-start", type=int, default=0, help="the depth term enters once the iteration has passed this one")
+    ap.add_argument("--placement", choices=["host", "device"], default="host", help="place the tet-spheres with the host helper (default) or with tssplat_amd.spheres_init")
+    ap.add_argument("--grid", type=int, default=72, help="voxels per axis of the placement grid")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
     args = ap.parse_args()
     if args.depth_bench:
         rec = depth_bench(args.depth_bench, target_npz=args.target, n_spheres=args.spheres, k=args.k, views=args.views, res=args.res, iters=args.iters,
-                          verbose=args.verbose, fit_depth_start=args.fit_depth_start)
+                          verbose=args.verbose, fit_depth_start=args.fit_depth_start, placement=args.placement, grid=args.grid)
         print(json.dumps({k: rec[k] for k in ("metric", "value", "unit", "depth_term", "both_image_terms_with_their_rasterisation", "training")}))
         return
     print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
-                         stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start)))
+                         stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, placement=args.placement, grid=args.grid)))
 
 
 if __name__ == "__main__":

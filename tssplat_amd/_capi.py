@@ -216,6 +216,12 @@ SIGNATURES = {
                                 C.c_int32, C.c_void_p, C.c_void_p]),
     "tsamd_texture_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # sphere initialisation: visual hull, squared distance transform, greedy ball cover
+    "tsamd_hull_carve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_double,
+                                   C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_edt_squared": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_greedy_cover": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

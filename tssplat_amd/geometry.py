@@ -269,3 +269,66 @@ class TetMeshGeometry(torch.nn.Module):
             smooth_barrier_energy = self.mesh_smooth_barrier(self.tet_v, iter_num, smooth_coeff, barrier_coeff)
         return TetMeshGeometryForwardData(self.tet_v, self.tet_elem, self.surface_vid, self.surface_fid, smooth_barrier_energy,
                                           surface_ops=self._surface_ops)
+
+
+class TetMeshMultiSphereGeometry(TetMeshGeometry):
+    """Mirror of ``TetMeshMultiSphereGeometry`` (geometry/tetmesh_geometry.py:202-382) from key points: one template tet-sphere,
+    scaled by the radius and moved to the centre of every key point, concatenated with offset tet indices (:310-331).
+
+    ``key_points``: a ``spheres_init.KeyPoints`` or the path of a key-point file in the reference's JSON layout (:235-239).
+    The template is ``template=(verts, tets)``, a unit sphere around the origin, or ``k`` for ``scenes.kuhn_ball(k)`` normalised to
+    unit radius (the reference remeshes a surface sphere and runs TetWild on every copy; neither exists here).  The energy runs
+    with ``smooth_eng_coeff / S`` on a COPY of ``smooth_barrier_param`` (:242-243; the default is config/gso.yaml:8-11).
+    ``all_spheres_vtx_idx`` holds every sphere's vertex ids, ``all_spheres_elem_idx`` its LOCAL element array, as the reference
+    stores them (:323-326)."""
+
+    def __init__(self, key_points, template=None, k=None, use_smooth_barrier: bool = True, smooth_barrier_param=None, **kwargs):
+        from . import scenes
+        from .spheres_init import KeyPoints
+        if not isinstance(key_points, KeyPoints):
+            key_points = KeyPoints.load_json(key_points)
+        S = len(key_points)
+        if S == 0:
+            raise ValueError("TetMeshMultiSphereGeometry: no key points (an empty mesh has no energy and no surface)")
+        if (template is None) == (k is None):
+            raise ValueError("TetMeshMultiSphereGeometry: give either template=(verts, tets) or k (scenes.kuhn_ball(k))")
+        if template is None:
+            tv, tt = scenes.kuhn_ball(int(k))
+            tv = np.asarray(tv, dtype=np.float64)
+            tv = tv / np.linalg.norm(tv, axis=1).max()
+        else:
+            tv, tt = template
+            tv = np.asarray(tv, dtype=np.float64).reshape(-1, 3)
+        tt = np.ascontiguousarray(np.asarray(tt, dtype=np.int32).reshape(-1, 4))
+        n = int(tv.shape[0])
+        if tt.size and (tt.min() < 0 or tt.max() >= n):
+            raise ValueError("TetMeshMultiSphereGeometry: template tets index vertices outside the template")
+        pt, r = key_points.pt.astype(np.float64), key_points.r.astype(np.float64)
+        verts = np.concatenate([(tv * r[s] + pt[s]).astype(np.float32) for s in range(S)], axis=0)
+        elem = np.concatenate([tt + s * n for s in range(S)], axis=0).astype(np.int32)
+        if use_smooth_barrier:
+            if smooth_barrier_param is None:
+                smooth_barrier_param = {"smooth_eng_coeff": 2e-4, "barrier_coeff": 2e-4, "increase_order_iter": 1000}
+            param = dict(smooth_barrier_param) if isinstance(smooth_barrier_param, dict) else dict(vars(smooth_barrier_param))
+            if "smooth_eng_coeff" in param:
+                param["smooth_eng_coeff"] = param["smooth_eng_coeff"] / S
+            smooth_barrier_param = param
+        super().__init__(verts, elem, use_smooth_barrier=use_smooth_barrier, smooth_barrier_param=smooth_barrier_param, **kwargs)
+        self.key_points = key_points
+        self.all_spheres_vtx_idx = [list(range(s * n, (s + 1) * n)) for s in range(S)]
+        self.all_spheres_elem_idx = [tt.copy() for _ in range(S)]
+
+    def export(self, path: str, filename: str) -> None:
+        """``filename.veg`` plus what the reference's export writes with ``save_npy`` (tetrahedron_mesh.py:89-91) and per sphere
+        (tetmesh_geometry.py:373-382): ``filename_vtx.npy``, ``filename_elem.npy``, ``filename_sp{i}_vtx.npy``, ``filename_sp{i}_elem.npy``."""
+        import os
+        from . import scenes
+        os.makedirs(path, exist_ok=True)
+        tet_v = self.tet_v.detach().cpu().numpy().reshape(-1, 3)
+        elem = self.tet_elem.cpu().numpy()
+        scenes.write_veg(os.path.join(path, filename + ".veg"), tet_v, elem)
+        np.save(os.path.join(path, filename + "_vtx.npy"), tet_v)
+        np.save(os.path.join(path, filename + "_elem.npy"), elem)
+        for i, (vid, sphere_elem) in enumerate(zip(self.all_spheres_vtx_idx, self.all_spheres_elem_idx)):
+            np.save(os.path.join(path, filename + f"_sp{i}_vtx.npy"), tet_v[vid, :])
+            np.save(os.path.join(path, filename + f"_sp{i}_elem.npy"), sphere_elem)
