@@ -716,6 +716,49 @@ int tsamd_edt_squared(const uint8_t *mask_dev, int32_t grid, int32_t *workspace_
 int tsamd_greedy_cover(const uint8_t *hull_dev, const int32_t *d2_dev, int32_t grid, int32_t n_spheres, double s2, double hs2, double m2,
                        void *workspace_dev, uint8_t *uncovered_out_dev, int32_t *flat_out_dev, int32_t *q_out_dev, int32_t *count_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Merging tet-spheres into one closed surface (the job the reference gives to TetWild, not a rebuild of it): the union field of
+ * all tets on the grid above, then marching tetrahedra on its level set.  Semantics are fixed by tests/union_oracle.py: float64
+ * arithmetic on float32 inputs, every multiply, add, subtract, divide and square root rounded on its own in the order written
+ * there, the maximum over tets taken on integers, so the results are bitwise repeatable.  Stateless; the caller owns all buffers;
+ * the current HIP device is used and nothing synchronises the host.
+ *
+ * The grid: as above with G = grid in 2 .. 512; a node is a voxel centre, lo + (index + 0.5) h per axis in float64 (NOT rounded
+ * to float32), flat index (i G + j) G + k.
+ *
+ * tsamd_union_field: tet_v_dev [n_vertices, 3] f32, elem_dev [n_tets, 4] i32 (n_tets <= 2^30).  A tet (a, b, c, d) contributes
+ * only if its four indices lie in [0, n_vertices), its twelve coordinates are finite and its signed volume (b - a) . ((c - a) x
+ * (d - a)) is > 0 (the orientation of scenes.kuhn_ball); other tets contribute nothing and nothing is read through a bad index.
+ * For each face of a contributing tet, with q, r, s its corners ordered (b, d, c), (a, c, d), (a, d, b), (a, b, c): n = (r - q) x
+ * (s - q) / |.|, which points at the opposite corner, and dist(p) = (n_x (p_x - q_x) + n_y (p_y - q_y)) + n_z (p_z - q_z);
+ * m_t(p) = the least of the four (taken by d < m: a NaN never replaces a number).  The tet covers the node index box, per axis,
+ * [ceil((min - lo) / h - 0.5) - 1, floor((max - lo) / h - 0.5) + 1] clipped to [0, G - 1]: its bounding box dilated by one
+ * node.  field_out_dev [G, G, G] f32 = the greatest m_t(p) over the contributing tets whose box holds p, rounded once to
+ * float32, -0.0 stored as +0.0, -inf where no tet covers the node.  Near the union's boundary this is the signed distance to the
+ * nearest face plane, positive inside.  The call fills the buffer itself (it serves as the integer image of the maximum until
+ * a last pass decodes it in place).
+ *
+ * tsamd_surface_count / tsamd_surface_emit: field_dev [G, G, G] f32.  A node is inside iff field > level (a NaN is outside;
+ * level must not be NaN).  Each cube of 2^3 neighbouring nodes is cut into the six Kuhn tets, one per axis permutation in
+ * lexicographic order (axis 0 = i), with corners o, o + e_p1, o + e_p1 + e_p2, o + (1, 1, 1).  A node owns the seven edges
+ * towards node + (di, dj, dk), mask m = 4 di + 2 dj + dk in 1 .. 7.  One vertex exists per owned edge whose ends both lie in the
+ * grid and differ in sign, numbered in (node flat index, m) order; with a the inside end, t = (f_a - level) / (f_a - f_b) in
+ * float64 (t = 0 when that is not a number in [0, 1], which takes a non-finite value at an end) and the position is p_a + t (p_b -
+ * p_a) per axis, rounded once to float32.  Each tet emits 0, 1 or 2 triangles in (cube's node flat index, permutation,
+ * triangle) order, wound from the permutation's parity so that normals point from inside to outside; no geometric test.
+ * tsamd_surface_count writes, per node, vmask_out_dev [G^3] u8 (bit m - 1: owned edge m carries a vertex), vcount_out_dev [G^3]
+ * u8 (its bit count) and tcount_out_dev [G^3] u8 (triangles of the cube at this node, 0 on the upper borders), and
+ * open_out_dev (one i32): 1 when a node on the grid's border is inside, else 0 -- the surface is closed iff it is 0.
+ * tsamd_surface_emit takes the EXCLUSIVE prefix sums voffset_dev / toffset_dev [G^3] i32 of the two counts and their totals
+ * n_vertices / n_triangles, and writes v_out_dev [n_vertices, 3] f32 and faces_out_dev [n_triangles, 3] i32.  Nothing is read or
+ * written out of bounds whatever the masks and offsets hold; both totals 0: nothing is launched. */
+int tsamd_union_field(const float *tet_v_dev, int64_t n_vertices, const int32_t *elem_dev, int64_t n_tets, int32_t grid, double lo, double hi,
+                      float *field_out_dev, void *stream);
+int tsamd_surface_count(const float *field_dev, int32_t grid, float level, uint8_t *vmask_out_dev, uint8_t *vcount_out_dev, uint8_t *tcount_out_dev,
+                        int32_t *open_out_dev, void *stream);
+int tsamd_surface_emit(const float *field_dev, int32_t grid, double lo, double hi, float level, const uint8_t *vmask_dev, const int32_t *voffset_dev,
+                       const int32_t *toffset_dev, int64_t n_vertices, int64_t n_triangles, float *v_out_dev, int32_t *faces_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ absent):
 
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
-                                 [--placement host|device --grid N]
+                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
 so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
@@ -31,6 +31,10 @@ dr.silhouette_mse, no gradient image).  --no-stages: leave out the stand-alone s
 The target distances are rendered once, without gradients, from the target mesh by the operator chain.  --depth-bench PATH: both
 modes on the same seed plus the depth stage timings (median of five repeats of 200 iterations, HIP events), written to PATH
 (profiles/depth_bench.json).
+
+--merge-grid N: after the fit, `tssplat_amd.merge` (`union_field`, `extract_surface`: what `merge_tets` runs) turns all spheres into ONE closed surface at N nodes per axis
+(`merged_surface.obj` under --merge-out) and the record gains `merged`: `closed`, the counts and `volume_iou_vs_hull`, the merged
+solid's occupancy against `spheres_init.visual_hull` of the target silhouettes at the same grid and bounds.
 
 One JSON line: silhouette IoU over all views, inverted tets, seconds per iteration and the stand-alone stage times."""
 import argparse
@@ -117,7 +121,7 @@ def build_spheres(centres, radii, k):
 
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
-        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), placement="host", grid=72):
+        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -214,6 +218,21 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
                    "schedule": "config/gso.yaml: lr 0.2 cosine, grad_limit 0.01, order 2 -> 4 at 1000, coeff_scheduler, smooth_eng_coeff / n_spheres"},
         "log": log,
     }
+    if merge_grid:  # the fitted spheres as ONE closed surface, and a 3-D figure: its occupancy against the targets' visual hull
+        from tssplat_amd import merge, spheres_init
+        tet_v = geo.tet_v.detach()
+        bounds = merge.default_bounds(tet_v, merge_grid)
+        level = merge.default_level(merge_grid, bounds)
+        field = merge.union_field(tet_v, geo.tet_elem, merge_grid, bounds)
+        mv, mf, closed = merge.extract_surface(field, bounds, level)
+        occ = merge.occupancy(field, level)
+        merge_out = merge_out or os.path.join(ROOT, "bench_outputs", "train_object")
+        os.makedirs(merge_out, exist_ok=True)
+        merge.write_obj(os.path.join(merge_out, "merged_surface.obj"), mv, mf)
+        hull = spheres_init.visual_hull(target, mvp, grid=merge_grid, bounds=bounds)
+        rec["merged"] = {"file": "merged_surface.obj", "grid": merge_grid, "bounds": list(bounds), "level": level,
+                         "vertices": int(mv.shape[0]), "triangles": int(mf.shape[0]), "closed": closed,
+                         "inside_fraction": int(occ.sum()) / float(merge_grid ** 3), "volume_iou_vs_hull": merge.volume_iou(occ, hull)}
     if stages:      # the stages on their own (HIP events; they overlap nothing, so their sum is close to one iteration)
         def timed(fn, reps=20):
             for j in range(3):
@@ -359,6 +378,8 @@ def main():
     ap.add_argument("--fit-depth-start", type=int, default=0, help="the depth term enters once the iteration has passed this one")
     ap.add_argument("--placement", choices=["host", "device"], default="host", help="place the tet-spheres with the host helper (default) or with tssplat_amd.spheres_init")
     ap.add_argument("--grid", type=int, default=72, help="voxels per axis of the placement grid")
+    ap.add_argument("--merge-grid", type=int, default=0, metavar="N", help="merge the fitted spheres into one closed surface at N nodes per axis (0: off)")
+    ap.add_argument("--merge-out", default=None, metavar="DIR", help="where merged_surface.obj goes (bench_outputs/train_object)")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
     args = ap.parse_args()
     if args.depth_bench:
@@ -367,7 +388,8 @@ def main():
         print(json.dumps({k: rec[k] for k in ("metric", "value", "unit", "depth_term", "both_image_terms_with_their_rasterisation", "training")}))
         return
     print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
-                         stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, placement=args.placement, grid=args.grid)))
+                         stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, placement=args.placement, grid=args.grid,
+                         merge_grid=args.merge_grid, merge_out=args.merge_out)))
 
 
 if __name__ == "__main__":

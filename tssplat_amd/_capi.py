@@ -222,6 +222,11 @@ SIGNATURES = {
     "tsamd_edt_squared": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsamd_greedy_cover": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # merging tet-spheres: union field on the voxel grid, marching tetrahedra in a count and an emit phase
+    "tsamd_union_field": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "tsamd_surface_count": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_surface_emit": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

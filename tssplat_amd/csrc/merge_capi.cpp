@@ -1,0 +1,75 @@
+// C ABI of the tet-sphere merge (include/tssplat_amd.h, tsamd_union_field / tsamd_surface_count / tsamd_surface_emit): stateless
+// entry points over caller-owned buffers.  Every argument is checked before the first device call.
+#include <cmath>
+
+#include "capi_common.h"
+#include "merge.h"
+
+using tsamd::capi_fail;
+using tsamd::check_not_null;
+
+namespace {
+
+int check_grid(int32_t grid)
+{
+    if (grid < tsamd::kMergeMinGrid || grid > tsamd::kMergeMaxGrid) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grid out of range (2 .. 512)");
+    return TSAMD_OK;
+}
+
+int check_cube(double lo, double hi)
+{
+    if (!(lo < hi) || !std::isfinite(hi - lo) || !std::isfinite(lo)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "lo must be below hi, both finite");
+    return TSAMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsamd_union_field(const float *tet_v_dev, int64_t n_vertices, const int32_t *elem_dev, int64_t n_tets, int32_t grid, double lo, double hi,
+                      float *field_out_dev, void *stream)
+{
+    int rc = check_grid(grid);
+    if (rc) return rc;
+    if (n_vertices < 0 || n_vertices > INT32_MAX) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "n_vertices out of range (0 .. 2^31 - 1: elem holds 32-bit indices)");
+    if (n_tets < 0 || n_tets > tsamd::kMergeMaxTets) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "n_tets out of range (0 .. 2^30)");
+    if ((rc = check_cube(lo, hi))) return rc;
+    if (n_tets > 0 && (rc = check_not_null({{elem_dev, "elem_dev"}}))) return rc;
+    if (n_tets > 0 && n_vertices > 0 && (rc = check_not_null({{tet_v_dev, "tet_v_dev"}}))) return rc;
+    if (!field_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "field_out_dev is null");
+    TSAMD_HIP(tsamd::launch_union_field(tet_v_dev, n_vertices, elem_dev, n_tets, grid, lo, (hi - lo) / grid, field_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_surface_count(const float *field_dev, int32_t grid, float level, uint8_t *vmask_out_dev, uint8_t *vcount_out_dev, uint8_t *tcount_out_dev,
+                        int32_t *open_out_dev, void *stream)
+{
+    int rc = check_grid(grid);
+    if (rc) return rc;
+    if (std::isnan(level)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "level is NaN");
+    if ((rc = check_not_null({{field_dev, "field_dev"}, {vmask_out_dev, "vmask_out_dev"}, {vcount_out_dev, "vcount_out_dev"}, {tcount_out_dev, "tcount_out_dev"},
+                              {open_out_dev, "open_out_dev"}})))
+        return rc;
+    TSAMD_HIP(tsamd::launch_surface_count(field_dev, grid, level, vmask_out_dev, vcount_out_dev, tcount_out_dev, open_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_surface_emit(const float *field_dev, int32_t grid, double lo, double hi, float level, const uint8_t *vmask_dev, const int32_t *voffset_dev,
+                       const int32_t *toffset_dev, int64_t n_vertices, int64_t n_triangles, float *v_out_dev, int32_t *faces_out_dev, void *stream)
+{
+    int rc = check_grid(grid);
+    if (rc || (rc = check_cube(lo, hi))) return rc;
+    if (std::isnan(level)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "level is NaN");
+    const int64_t nodes = int64_t(grid) * grid * grid;
+    if (n_vertices < 0 || n_vertices > 7 * nodes) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "n_vertices out of range (0 .. 7 grid^3)");
+    if (n_triangles < 0 || n_triangles > 12 * nodes) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "n_triangles out of range (0 .. 12 grid^3)");
+    if ((rc = check_not_null({{field_dev, "field_dev"}, {vmask_dev, "vmask_dev"}, {voffset_dev, "voffset_dev"}, {toffset_dev, "toffset_dev"}}))) return rc;
+    if (n_vertices > 0 && !v_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "v_out_dev is null");
+    if (n_triangles > 0 && !faces_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "faces_out_dev is null");
+    if (n_vertices == 0 && n_triangles == 0) return TSAMD_OK;             // nothing to write
+    TSAMD_HIP(tsamd::launch_surface_emit(field_dev, grid, lo, (hi - lo) / grid, level, vmask_dev, voffset_dev, toffset_dev, n_vertices, n_triangles, v_out_dev,
+                                         faces_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+}  // extern "C"

@@ -199,7 +199,7 @@ class TetMeshGeometry(torch.nn.Module):
     package's own reader) and the reference's ``Config`` fields as keyword arguments.  ``uv`` / ``uv_idx`` (the reference's
     names, tetmesh_geometry.py:150-153, there filled by xatlas) are the per-wedge UVs of this package's closed-form atlas
     (tssplat_amd/atlas.py) at ``uv_resolution`` texels, built on first access.  Remeshing / geometry export are not mirrored
-    (offline tools)."""
+    (offline tools); ``export_merged`` is this package's own."""
 
     uv_resolution = 1024
 
@@ -257,6 +257,17 @@ class TetMeshGeometry(torch.nn.Module):
         from . import scenes
         v, t = scenes.read_veg(path)
         return cls(v, t, **kwargs)
+
+    def export_merged(self, path: str, filename: str, grid: int = 128, bounds=None):
+        """Writes ``filename_merged.obj`` under ``path``: the union of all tets as ONE closed, consistently oriented triangle mesh
+        (:func:`tssplat_amd.merge.merge_tets` at ``grid`` nodes per axis; plain ``v`` / ``f`` lines) and returns the
+        ``MergedSurface``.  For a multi-sphere geometry this is the merge of the spheres into one shape."""
+        import os
+        from . import merge
+        os.makedirs(path, exist_ok=True)
+        merged = merge.merge_tets(self.tet_v.detach(), self.tet_elem, grid=grid, bounds=bounds)
+        merge.write_obj(os.path.join(path, filename + "_merged.obj"), merged.v, merged.faces)
+        return merged
 
     def forward(self, iter_num, **kwargs):
         if "permute_surface_v" in kwargs:                               # tetmesh_geometry.py:176-182
