@@ -291,6 +291,10 @@ int tsamd_grad_limit(float *grad_dev, int64_t n, float s_threshold, float s, voi
  *   if grad_limit > 0 and max|gr| > grad_limit: gr *= grad_limit / max|gr|;   optimizer.py:84-86
  *   param -= lr * gr                                                   optimizer.py:88
  * `step` is the 1-based count AFTER the increment of optimizer.py:55.  workspace_dev: >= 16 bytes.
+ * Non-finite gradients: a +inf entry makes both maxima inf, so every finite entry of param stays as it is, bit for bit,
+ * and the entry itself becomes NaN (g1, g2 inf there) -- what the reference's torch chain gives too.
+ * A NaN entry DEPARTS from the reference: the maxima here drop NaN (fmaxf), so every other entry is stepped as if that entry
+ * were absent and only its own param, g1 and g2 become NaN, where torch's .max() propagates NaN into every entry.
  */
 int tsamd_adam_uniform_step(float *param_dev, const float *grad_dev, float *g1_dev, float *g2_dev, int64_t n,
                             float lr, float beta1, float beta2, int64_t step, float grad_limit,

@@ -250,6 +250,49 @@ def test_forward_only_equals_fused_and_is_deterministic(ext):
     assert abs(e_fwd[0] - e_fused[0]) <= 1e-6 * abs(e_fused[0])
 
 
+def test_energy_reduction_batched_loads_in_finish_kernel(ext):
+    """64 x kuhn8 cut into 64-thread tiles: more than 7 * 256 tiles and shared vertices, so workgroup 0 of the finish kernel
+    (energy_reduce<256>) issues a batch of eight loads per lane and then two or three single ones."""
+    from tssplat_amd import scenes
+    sc = scenes.make_scene("kuhn8", 64)
+    ts = ext.TetSpheres(sc.rest.reshape(-1), sc.tets.reshape(-1), max_threads=64)
+    info = ts.plan_info()
+    assert info["n_tiles"] > 7 * 256 and info["finish_vertices"] > 0, info
+    x = scenes.deform(sc, 0.3)
+    _assert_parity(ext, ts, sc.rest, sc.tets, x, 2e-4 / 64, 2e-4, 2, go=0.37, label="kuhn8x64 64-thread tiles s=0.3 p=2")
+
+
+def test_energy_reduction_batched_loads_forward_only(ext):
+    """256 x kuhn8 cut into 64-thread tiles: more than 7 * 1024 tiles, so the forward-only reduction (energy_reduce<1024>)
+    takes its batched loads as well.  The fused evaluation is guarded by the C oracle; the forward-only one sums the same
+    per-tile partials in another fixed order, and every partial is non-negative (tile_kernel.hip: e_s adds 0.5 * squares,
+    e_b adds Jm^2 or Jm^4), so each term agrees with the fused one to n_tiles * 2^-52 relative."""
+    from tssplat_amd import scenes
+    sc = scenes.make_scene("kuhn8", 256)
+    ts = ext.TetSpheres(sc.rest.reshape(-1), sc.tets.reshape(-1), max_threads=64)
+    n_tiles = ts.plan_info()["n_tiles"]
+    assert n_tiles > 7 * 1024, n_tiles
+    x_np = scenes.deform(sc, 0.3)
+    c1, c2 = 2e-4 / 256, 2e-4
+    e, g = _eval_gpu(ext, ts, x_np, c1, c2, 2)
+    fused = ts.energy_terms()
+    _assert_guards_c("kuhn8x256 64-thread tiles s=0.3 p=2", sc.rest, sc.tets, x_np, c1, c2, 2, e, g, terms=fused)
+    x = torch.from_numpy(x_np).cuda()
+
+    def forward_only(t):
+        e32 = float(ext.forward(t, ts, c1, c2, 2, fuse=False))
+        return e32, ts.energy_terms()
+
+    runs = [forward_only(x.clone().requires_grad_(True)), forward_only(x.clone().requires_grad_(True))]
+    with torch.no_grad():
+        runs.append(forward_only(x))
+    for e32, terms in runs:
+        for got, want in zip(terms, fused):
+            assert want > 0 and abs(got - want) <= n_tiles * 2.0 ** -52 * want, (terms, fused)
+        assert e32 == float(np.float32(float(np.float32(c1)) * terms[0] + float(np.float32(c2)) * terms[1])), (e32, terms)
+    assert runs[0] == runs[1] == runs[2], runs       # fixed-order reduction: bitwise repeatable
+
+
 def test_function_surface_and_cache(ext):
     """SmoothnessBarrierFunc contract (energies/smooth_barrier.py:9-31) and the fused-pass cache."""
     from tssplat_amd import scenes
