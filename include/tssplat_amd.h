@@ -71,7 +71,9 @@ typedef struct tsamd_options {
     int32_t host_only;         /* 1 = build the tiling plan only, never touch HIP (CPU tests)       */
     int32_t num_threads;       /* host threads used to build the plan; 0 = hardware concurrency     */
     int32_t debug_flags;       /* bit1 = no LDS-conflict-aware ordering at all (measurements); bit2 = no shared index planes: every
-                                * tile is its own index representative (tsamd_get_index_reps; same results, bit for bit); other bits ignored */
+                                * tile is its own index representative (tsamd_get_index_reps; same results, bit for bit); bit3 = no regular-batch addressing: every tile
+                                * and finish vertex reads its own ids, destinations and lists (tsamd_get_regular_batch reports period 0;
+                                * same results, bit for bit); other bits ignored */
     int32_t slots_per_thread;  /* tets per lane: 0 = 2.  Lane layouts with a kernel: 2 (max_threads <= 768, two 80 KiB workgroups per
                                 * CU: the default, every operator variant); 3 (max_threads <= 512, or <= 1024 for one workgroup per
                                 * CU) and 4 (max_threads <= 768): fewer, fatter waves, built-in operator only -- with lds_budget_bytes
@@ -189,6 +191,16 @@ int tsamd_get_finish_lists(const tsamd_handle *h, int64_t *n_finish, const int32
  * of the plan that carries the same bytes (the same tile of an earlier copy of one template), t itself if there is none.  Tile t's
  * own bytes (tsamd_get_tile) are byte-equal to its representative's. */
 int tsamd_get_index_reps(const tsamd_handle *h, const int32_t **rep);
+/* Regular batch: out7 = {period, copies, V, S, K, div_mul, div_shift}.  period > 0: the plan is `copies` >= 2 repetitions of its
+ * first `period` tiles -- tile t is copy c = t / period of template tile r = t % period, and with V vertices, S staging rows and K
+ * finish vertices per copy
+ *   gvid[t][v] = gvid[r][v] + c V;   vdst[t][v] = vdst[r][v] + c V where that is >= 0, ~vdst[t][v] = ~vdst[r][v] + c S where it is < 0;
+ *   vid[k] = vid[k % K] + (k / K) V;   off[k] = off[k % K] + (k / K) S   (k = n_finish included),
+ * every entry compared at create time.  The kernels then read the template's entries (bytes every copy shares) and add the copy's
+ * constants; c = (t * div_mul) >> div_shift in 64 bits, exact for every tile of the plan.  period = 0 (and zeros throughout): anything
+ * else -- a single copy, mixed templates, one odd sphere -- or debug_flags bit3; the kernels read every tile's own entries.  Same
+ * results either way, bit for bit. */
+int tsamd_get_regular_batch(const tsamd_handle *h, int64_t *out7);
 /* face adjacency computed at create time: 4 ints per tet, -1 = boundary face */
 int tsamd_get_adjacency(const tsamd_handle *h, const int32_t **nbr);
 

@@ -142,7 +142,7 @@ VARIANTS = {
         (K, '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n', '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
     ]),
     "prioB": ("head (load issue) = 3, pass 1 = 0, pass 2 = 1, pass 3 = 2, tail = 3", [
-        (K, '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n', '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
+        (K, '    const int32_t gv0 = INDEX_NT ? __builtin_nontemporal_load(gv_ptr) : *gv_ptr;\n', '    const int32_t gv0 = INDEX_NT ? __builtin_nontemporal_load(gv_ptr) : *gv_ptr;\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
         (K, '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n', '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n' + "    " + '__builtin_amdgcn_s_setprio(0);\n'),
         (K, '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n', '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n' + "    " + '__builtin_amdgcn_s_setprio(1);\n'),
         (K, '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n', '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n' + "    " + '__builtin_amdgcn_s_setprio(2);\n'),
@@ -161,7 +161,7 @@ VARIANTS = {
         (K, '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n', '        // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----\n' + "    " + '__builtin_amdgcn_s_setprio(0);\n'),
     ]),
     "prioE": ("head = 3, pass 1 = 1, pass 2 = 2, pass 3 = 3, tail = 3", [
-        (K, '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n', '    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
+        (K, '    const int32_t gv0 = INDEX_NT ? __builtin_nontemporal_load(gv_ptr) : *gv_ptr;\n', '    const int32_t gv0 = INDEX_NT ? __builtin_nontemporal_load(gv_ptr) : *gv_ptr;\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),
         (K, '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n', '    // ---- pass 1: F = Ds Dm^-1, inversion penalty ----\n' + "    " + '__builtin_amdgcn_s_setprio(1);\n'),
         (K, '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n', '    // ---- pass 2: H = L F on owned slots (0 on halo slots), E_s = 1/2 |H|^2 ----\n' + "    " + '__builtin_amdgcn_s_setprio(2);\n'),
         (K, '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n', '        // ---- pass 3: P = L^T H + (c2 / c1) dpen cof(F);  d = P Dm^-T (per-tet vertex forces, c1 applied at the end) ----\n' + "    " + '__builtin_amdgcn_s_setprio(3);\n'),

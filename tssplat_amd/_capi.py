@@ -102,6 +102,7 @@ SIGNATURES = {
     "tsamd_get_finish_lists": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int32)),
                                          C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]),
     "tsamd_get_index_reps": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32))]),
+    "tsamd_get_regular_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "tsamd_get_adjacency": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32))]),
     "tsamd_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "tsamd_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p,

@@ -23,6 +23,7 @@
 #include "capi_common.h"
 #include "kernels.h"
 #include "plan.h"
+#include "regular_batch.h"
 
 namespace {
 
@@ -44,6 +45,7 @@ using tsamd::DeviceGuard;
 
 struct tsamd_handle {
     tsamd::Plan plan;
+    tsamd::RegularBatch regular;   // period 0 unless the plan is copies of one template (regular_batch.h)
     bool host_only = true;
     int device = -1;
     int64_t device_bytes = 0;
@@ -261,6 +263,8 @@ int create_common(const float *rest, int64_t n, const int32_t *tets, int64_t m, 
         }
         if (rc3 == 0 && alt.tiles.size() <= 2048 && double(alt.total_slots) <= 1.002 * double(h->plan.total_slots)) h->plan = std::move(alt);
     }
+    // bit 3 of the debug word: every tile and finish vertex reads its own ids, destinations and lists (A/B of the regular addressing)
+    if (!(opt.debug_flags & 8)) h->regular = tsamd::detect_regular_batch(h->plan);
     if (!opt.host_only) {
         rc = to_device(h, opt.device);
         if (rc) {
@@ -303,6 +307,7 @@ tsamd::EvalArgs eval_args(tsamd_handle *h, const float *x, const float *grad_out
     a.spt = h->plan.spt;
     // cache-retaining index loads where most tiles read another tile's index planes, non-temporal ones where (almost) none does
     a.index_nt = 2 * h->plan.n_index_shared < int64_t(h->plan.tiles.size());
+    a.regular = h->regular;
     a.x = x;
     a.grad_out = grad_out;
     a.c1 = c1;
@@ -448,6 +453,15 @@ int tsamd_get_index_reps(const tsamd_handle *h, const int32_t **rep)
 {
     if (!h || !rep) return fail(TSAMD_ERR_INVALID_ARGUMENT, "null argument");
     *rep = h->plan.index_rep.data();
+    return TSAMD_OK;
+}
+
+int tsamd_get_regular_batch(const tsamd_handle *h, int64_t *out7)
+{
+    if (!h || !out7) return fail(TSAMD_ERR_INVALID_ARGUMENT, "null argument");
+    const tsamd::RegularBatch &r = h->regular;
+    const int64_t v[7] = {r.period, r.copies, r.V, r.S, r.K, int64_t(r.div_mul), int64_t(r.div_shift)};
+    std::copy(v, v + 7, out7);
     return TSAMD_OK;
 }
 

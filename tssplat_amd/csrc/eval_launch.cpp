@@ -75,6 +75,11 @@ hipError_t make_recipe(const EvalArgs &e, LaunchRecipe &r)
         k.tiles_per_xcd = int((e.n_tiles + 7) / 8);
         k.vert_stride = e.vert_stride;
         k.n_planes = e.n_planes;
+        k.reg_period = uint32_t(e.regular.period);   // (all five are 0 for a plan that is not regular)
+        k.reg_mul = e.regular.div_mul;
+        k.reg_shift = e.regular.div_shift;
+        k.reg_v = e.regular.V;
+        k.reg_s = e.regular.S;
         r.tile_fn = tile_kernel_for(e.spt, e.block_threads, e.grad != nullptr, e.weighted, e.rebuild, e.index_nt);
         if (!r.tile_fn) return hipErrorInvalidConfiguration;
         r.tile_block = dim3(unsigned(e.block_threads));
@@ -96,9 +101,15 @@ hipError_t make_recipe(const EvalArgs &e, LaunchRecipe &r)
     f.energy = e.energy;
     f.terms = e.terms;
     f.energy_copy = nullptr;
+    // (the x grid is capped: a copy with more entries than it covers -- no plan in sight -- takes the list loop)
+    const bool regular = e.regular.period > 0 && e.regular.K > 0 && int64_t(finish_grid(e.regular.K) - 1) * 256 >= e.regular.K;
+    f.reg_k = regular ? e.regular.K : 0;
+    f.reg_copies = regular ? e.regular.copies : 0;
+    f.reg_v = regular ? e.regular.V : 0;
+    f.reg_s = regular ? e.regular.S : 0;
     if (f.n_finish > 0) {
         r.finish_fn = step_kernels().finish;
-        r.finish_grid = dim3(finish_grid(f.n_finish));
+        r.finish_grid = regular ? finish_grid_regular(f.reg_k, f.reg_copies) : dim3(finish_grid(f.n_finish));
         r.finish_block = dim3(256);
     } else if (f.energy) {
         r.finish_fn = step_kernels().energy_reduce;

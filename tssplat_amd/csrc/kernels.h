@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "plan.h"
+#include "regular_batch.h"
 
 namespace tsamd {
 
@@ -24,6 +25,7 @@ struct EvalArgs {
     int32_t n_planes = 13;        // dword planes per slot of this plan (where a tile's incidence list starts)
     int32_t spt = kSlotsPerLane;  // slots per lane the plan is laid out for (selects the kernel instantiation)
     bool index_nt = true;         // the plan shares (almost) no index planes: load them non-temporally (Plan::index_rep, tile_kernel.hip: tile_body)
+    RegularBatch regular;         // period > 0: tiles and finish vertices address their template's ids, destinations and lists
     // per evaluation
     const float *x;
     const float *grad_out;  // device scalar or nullptr

@@ -28,6 +28,11 @@ struct KernelArgs {
     int tiles_per_xcd;
     int vert_stride;   // gvid / vdst entries per tile: tile t's vertex ids start at t * vert_stride (= its descriptor's vert_off)
     int n_planes;      // dword planes per slot (explicit-operator plans: 22, or 18 for a symmetric operator -- plan.h)
+    // Regular batch (regular_batch.h): tile t is copy c = (t * reg_mul) >> reg_shift (64-bit product; = t / reg_period, checked on
+    // the host for every tile) of template tile r = t - c * reg_period.  The first-round ids and destinations are read at r's
+    // entries and corrected by c * reg_v vertices / c * reg_s staging rows.  All zero for any other plan: c = 0, r = t.
+    uint32_t reg_period, reg_mul, reg_shift;
+    int reg_v, reg_s;
 };
 
 struct FinishArgs {
@@ -43,6 +48,11 @@ struct FinishArgs {
     float *energy;
     double *terms;
     float *energy_copy;   // optional second destination of the energy (a replay's per-launch argument: the ring slot of an energy exchange)
+    // Regular batch: reg_k > 0 finish entries per copy, n_finish = reg_copies * reg_k.  A thread owns template entry kk < reg_k and
+    // walks copies c = blockIdx.y, blockIdx.y + gridDim.y, ...: entry c * reg_k + kk sums the template's rows moved by c * reg_s
+    // into the template's vertex moved by c * reg_v.  reg_k == 0: every thread reads its own entries of the lists.
+    int64_t reg_k;
+    int reg_copies, reg_v, reg_s;
 };
 
 // ---- tile_kernel.hip ----
@@ -64,6 +74,7 @@ struct StepKernels {
 };
 StepKernels step_kernels();
 unsigned finish_grid(int64_t n_finish);
+dim3 finish_grid_regular(int64_t per_copy, int copies);   // FinishArgs::reg_k > 0
 unsigned adam_grid(int64_t n);
 
 }  // namespace tsamd

@@ -70,51 +70,67 @@ __global__ __launch_bounds__(1024) void energy_reduce_kernel(const FinishArgs a)
 // round 6: finish kernel 0.0269 -> 0.0409 ms on 512 x kuhn19, 0.0297 -> 0.0414 on a.veg x 952.  The rows are still in the memory-side
 // cache from the tile kernel's stores; a non-temporal read gives that up.)
 #define FIN_LOAD(p) (*(p))
+// One finish vertex: grad[vid] = gscale * (sum of staging rows [e0, e1), in order).
+__device__ __forceinline__ void finish_vertex(const FinishArgs &a, int32_t e0, int32_t e1, int32_t vid, float gscale)
+{
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    // the first four rows go out together (most shared vertices have 2-4 copies): one memory latency instead of one
+    // per row; rows beyond the vertex's own are re-reads of its last row and are not added.  Finish kernel 0.037 ->
+    // 0.031 ms on the 512-sphere scene (2 / 3 / 8 rows: 0.034 / 0.031 / 0.031); same order of additions.
+    constexpr int kRowsAhead = 4;
+    {
+        float3 r[kRowsAhead];
+#pragma unroll
+        for (int j = 0; j < kRowsAhead; ++j) {
+            // (a vertex no tet references is in the list with zero rows: e1 - 1 may be -1 -- read row 0, add nothing)
+            const int32_t e = e0 + j < e1 ? e0 + j : (e1 > 0 ? e1 - 1 : 0);
+            const float *p = a.stage + size_t(e) * 3;
+            r[j] = make_float3(FIN_LOAD(p), FIN_LOAD(p + 1), FIN_LOAD(p + 2));
+        }
+#pragma unroll
+        for (int j = 0; j < kRowsAhead; ++j)
+            if (e0 + j < e1) {
+                gx += r[j].x;
+                gy += r[j].y;
+                gz += r[j].z;
+            }
+    }
+    for (int32_t e = e0 + kRowsAhead; e < e1; ++e) {
+        const float *r = a.stage + size_t(e) * 3;
+        gx += FIN_LOAD(r);
+        gy += FIN_LOAD(r + 1);
+        gz += FIN_LOAD(r + 2);
+    }
+    float *g = a.grad + size_t(vid) * 3;
+    g[0] = gx * gscale;
+    g[1] = gy * gscale;
+    g[2] = gz * gscale;
+}
+
 __global__ __launch_bounds__(256) void finish_kernel(const FinishArgs a)
 {
     __shared__ double red[2 * 256];
     const int tid = threadIdx.x;
     if (blockIdx.x == 0) {
-        if (a.energy) energy_reduce<256>(a, red);
+        if (a.energy && blockIdx.y == 0) energy_reduce<256>(a, red);
         return;
     }
     const float gscale = a.grad_out ? *a.grad_out : 1.f;
+    if (a.reg_k > 0) {
+        // Regular batch (launch_args.h): the grid is (1 + template entries / 256) x (copies, at most 65 535).  The template's three
+        // list entries are bytes every copy reads -- cache hits, not one HBM round trip per vertex in front of its rows -- and are
+        // read once per thread; each copy's rows and vertex follow by adding its constants.
+        const int64_t kk = int64_t(blockIdx.x - 1) * 256 + tid;
+        if (kk >= a.reg_k) return;
+        const int32_t e0 = FIN_LOAD(&a.fin_off[kk]), e1 = FIN_LOAD(&a.fin_off[kk + 1]), vid = FIN_LOAD(&a.fin_vid[kk]);
+        for (int c = int(blockIdx.y); c < a.reg_copies; c += int(gridDim.y)) finish_vertex(a, e0 + c * a.reg_s, e1 + c * a.reg_s, vid + c * a.reg_v, gscale);
+        return;
+    }
     // one thread per shared vertex (measured faster than one thread per output float: 0.065 vs 0.093 ms)
     const int64_t stride = int64_t(gridDim.x - 1) * 256;
     for (int64_t k = int64_t(blockIdx.x - 1) * 256 + tid; k < a.n_finish; k += stride) {
-        float gx = 0.f, gy = 0.f, gz = 0.f;
         const int32_t e0 = FIN_LOAD(&a.fin_off[k]), e1 = FIN_LOAD(&a.fin_off[k + 1]);   // consecutive rows, tile order
-        // the first four rows go out together (most shared vertices have 2-4 copies): one memory latency instead of one
-        // per row; rows beyond the vertex's own are re-reads of its last row and are not added.  Finish kernel 0.037 ->
-        // 0.031 ms on the 512-sphere scene (2 / 3 / 8 rows: 0.034 / 0.031 / 0.031); same order of additions.
-        constexpr int kRowsAhead = 4;
-        {
-            float3 r[kRowsAhead];
-#pragma unroll
-            for (int j = 0; j < kRowsAhead; ++j) {
-                // (a vertex no tet references is in the list with zero rows: e1 - 1 may be -1 -- read row 0, add nothing)
-                const int32_t e = e0 + j < e1 ? e0 + j : (e1 > 0 ? e1 - 1 : 0);
-                const float *p = a.stage + size_t(e) * 3;
-                r[j] = make_float3(FIN_LOAD(p), FIN_LOAD(p + 1), FIN_LOAD(p + 2));
-            }
-#pragma unroll
-            for (int j = 0; j < kRowsAhead; ++j)
-                if (e0 + j < e1) {
-                    gx += r[j].x;
-                    gy += r[j].y;
-                    gz += r[j].z;
-                }
-        }
-        for (int32_t e = e0 + kRowsAhead; e < e1; ++e) {
-            const float *r = a.stage + size_t(e) * 3;
-            gx += FIN_LOAD(r);
-            gy += FIN_LOAD(r + 1);
-            gz += FIN_LOAD(r + 2);
-        }
-        float *g = a.grad + size_t(FIN_LOAD(&a.fin_vid[k])) * 3;
-        g[0] = gx * gscale;
-        g[1] = gy * gscale;
-        g[2] = gz * gscale;
+        finish_vertex(a, e0, e1, FIN_LOAD(&a.fin_vid[k]), gscale);
     }
 }
 
@@ -265,6 +281,8 @@ StepKernels step_kernels()
 
 // workgroup 0 for the energy + one vertex per thread: the per-vertex chain off[k] -> rows -> store is pure latency, so expose all of it
 unsigned finish_grid(int64_t n_finish) { return 1u + unsigned(grid_for(n_finish, 256, 1 << 20)); }
+// regular batch: x as above over the entries of ONE copy, y over the copies (a thread walks copies y, y + grid.y, ...)
+dim3 finish_grid_regular(int64_t per_copy, int copies) { return dim3(finish_grid(per_copy), unsigned(copies < 65535 ? copies : 65535)); }
 
 unsigned adam_grid(int64_t n) { return unsigned(grid_for(n, 1024, kReduceGridCap)); }
 

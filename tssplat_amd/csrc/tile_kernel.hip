@@ -275,7 +275,7 @@ __device__ __forceinline__ uint32_t pos_hi(uint32_t w) { return ((w >> 16) & kVe
 // SPT slots per lane (the plan is laid out for it); the default, two, with launch bounds <768 threads, 6 waves per SIMD> gives
 // the 80-VGPR budget at which two workgroups share a CU.
 template <bool WITH_GRAD, bool WEIGHTED, bool REBUILD, int SPT, bool INDEX_NT>
-__device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, int32_t gv0)
+__device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, int32_t gv0, const uint32_t reg_vert_off, const int reg_cv, const int reg_cs)
 {
     // named here, not passed in: a pointer parameter would be a generic pointer and every LDS access of the
     // out-of-line copy would turn into a flat_* instruction
@@ -359,12 +359,26 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
     // ---- stream the tile ----
     // A CU pulls cold data at ~11 bytes per cycle whatever the rest of the chip does (tools/ubench_ingest.hip), in the order the
     // loads were issued, wave after wave.  The order below is built around that FIFO:
-    //   1. (kernel entry) the vertex ids;  2. the two vertex planes -- 12 KB per workgroup, about what the id's latency covers;
-    //   3. the positions, as soon as the ids are back: they reach the LDS behind 12 KB instead of behind the whole stream, so the
-    //      barrier that publishes them falls EARLY in the stream, not at its end;
+    //   1. (kernel entry) the vertex ids;
+    //   2. the positions, as soon as the ids are back: the gather is the head of the FIFO, so the barrier that publishes the
+    //      positions falls at the very start of the stream.  (Until the ids of a regular batch came from L2 the two vertex planes
+    //      went out in front of the gather, 12 KB to cover the id's trip to HBM.  With the gather first the tile kernel of 512 x
+    //      kuhn19 takes 296.3 us against 299.4 -- and 296.1 against 300.1 with every tile reading its own ids, debug bit 3: the id
+    //      and the tile descriptor, which the planes' addresses need, come back together anyway;
+    //      profiles/regular_batch.md.)
+    //   3. the two vertex planes;
     //   4. the nine Dm^-1 planes: every wave computes its F as soon as ITS planes have landed;
     //   5. the neighbour planes (and an explicit operator's weights) and the row table, which nobody needs before pass 2, go
     //      out after the barrier.
+    // the positions: unconditional loads (lanes beyond the tile's vertices hold vertex 0 and do not store), so that the
+    // stream stays straight-line code whose waits the compiler can count
+    asm volatile("" : "+v"(gv0));  // (the wait for the id lands here: vmcnt(0), nothing else is in flight yet)
+    float px, py, pz;
+    {
+        const size_t gv = size_t(gv0 + reg_cv) * 3;   // (the template's id moved to this copy: regular batches, tile_entry)
+        px = g_x[gv], py = g_x[gv + 1], pz = g_x[gv + 2];
+    }
+    __builtin_amdgcn_sched_barrier(0);
     VU q_lv01, q_lv23, q_nb01, q_nb23;
     pair_u(0, q_lv01, q_lv23);
     VF dm[9];
@@ -375,15 +389,6 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
     const GLOBAL_AS v4f *g_rest = reinterpret_cast<const GLOBAL_AS v4f *>(reinterpret_cast<const GLOBAL_AS uint16_t *>(pl + size_t(kBasePlanes) * td.s_pad) + kRowTabEntries);
     v4f rest0 = v4f{0.f, 0.f, 0.f, 0.f};
     if (REBUILD) rest0 = g_rest[tid < td.n_verts ? tid : 0];
-    // the positions: unconditional loads (lanes beyond the tile's vertices hold vertex 0 and do not store), so that the
-    // stream stays straight-line code whose waits the compiler can count
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" : "+v"(gv0));  // (the wait for the id lands here: vmcnt(2), the two vertex planes stay in flight)
-    float px, py, pz;
-    {
-        const size_t gv = size_t(gv0) * 3;
-        px = g_x[gv], py = g_x[gv + 1], pz = g_x[gv + 2];
-    }
     __builtin_amdgcn_sched_barrier(0);
     if (!REBUILD) {
 #pragma unroll
@@ -392,7 +397,7 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
     }
     __builtin_amdgcn_sched_barrier(0);
     if (tid < td.n_verts) {
-        *lds_at<v4f>(kXS + 16u * uint32_t(tid)) = v4f{px, py, pz, 0.f};   // (waits for the positions only: vmcnt(9))
+        *lds_at<v4f>(kXS + 16u * uint32_t(tid)) = v4f{px, py, pz, 0.f};   // (waits for the positions only: the planes behind them stay in flight)
         if (REBUILD) *lds_at<v4f>(RS + 16u * uint32_t(tid)) = rest0;
     }
     for (int v = tid + nthr; v < td.n_verts; v += nthr) {  // tiles with more vertices than lanes (rare)
@@ -662,7 +667,9 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
             vb0 = g4 + (top - wave);
         }
         int32_t dst_row = 0;  // where this lane's first vertex goes: fetched here, a whole phase ahead of its use
-        if (64 * vb0 + lane < td.n_verts) dst_row = __builtin_nontemporal_load(&g_vdst[td.vert_off + 64 * vb0 + lane]);
+        // (regular batches: the template tile's entry, bytes every copy reads -- the flavour of the index planes; moved to this copy
+        // where it is used)
+        if (64 * vb0 + lane < td.n_verts) dst_row = INDEX_LOAD(&g_vdst[reg_vert_off + uint32_t(64 * vb0 + lane)]);
         __syncthreads();   // all waves done with H and with the staged positions
         // ---- scatter the vertex forces: (f0, f1, f2, f3), f0 = -(f1 + f2 + f3), 12 bytes each ----
         STAGE_PRIORITY(3);
@@ -689,7 +696,9 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
         const float gscale = grad_out_scale * out_scale;
         const uint32_t tab = *lds_at<const uint32_t>(4u * uint32_t(lane));
         const uint32_t wid = *lds_at<const uint32_t>(4u * uint32_t(lane) + 4u) - tab;   // 12 * (vertices in row `lane`)
-        auto vertex_sums = [&](int vb, int32_t row) {
+        // row: the destination as the plan's list names it, for the tile at whose entries it was read -- the template's with the copy's
+        // constants (cv vertices, cs staging rows) still to be added, or the tile's own with 0, 0
+        auto vertex_sums = [&](int vb, int32_t row, int cv, int cs) {
             const int v = 64 * vb + lane;
             const uint32_t v12 = 12u * uint32_t(v);
             const int rows = __builtin_popcountll(__builtin_amdgcn_ballot_w64(wid > 768u * uint32_t(vb)));
@@ -715,7 +724,7 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
             }
             if (v < td.n_verts) {
                 const bool excl = row >= 0;
-                GLOBAL_AS float *dst = (excl ? g_grad : g_stage) + size_t(excl ? row : ~row) * 3;
+                GLOBAL_AS float *dst = (excl ? g_grad : g_stage) + size_t(excl ? row + cv : ~row + cs) * 3;
                 const float sc = excl ? gscale : out_scale;
                 // (non-temporal stores here were measured: tile kernel +28 %; the wave's end waits for their acknowledgement)
                 dst[0] = gx * sc;
@@ -723,11 +732,11 @@ __device__ __forceinline__ void tile_body(const KernelArgs &a, const int tile, i
                 dst[2] = gz * sc;
             }
         };
-        if (64 * vb0 < td.n_verts) vertex_sums(vb0, dst_row);
+        if (64 * vb0 < td.n_verts) vertex_sums(vb0, dst_row, reg_cv, reg_cs);
         if (64 * nw < td.n_verts) {   // more vertices than lanes (rare; a wave-uniform branch: the loads of the extra rounds and the
                                       // waits the compiler puts around a loop with loads stay out of the common path)
             for (int vb = vb0 + nw; 64 * vb < td.n_verts; vb += nw)
-                vertex_sums(vb, 64 * vb + lane < td.n_verts ? g_vdst[td.vert_off + 64 * vb + lane] : 0);
+                vertex_sums(vb, 64 * vb + lane < td.n_verts ? g_vdst[td.vert_off + 64 * vb + lane] : 0, 0, 0);   // (the tile's own entries)
         }
         sum_waves();   // the tile's (E_s, E_b): the last wave's last instruction, its acknowledgement behind wave 0's row walk
     }
@@ -752,9 +761,17 @@ __device__ __forceinline__ void tile_entry(const KernelArgs &a)
     // Entries beyond n_verts name vertex 0 and are never used.
     // (non-temporal, like every read-once array of a tile -- planes, ids, destinations, row table: what they would evict is what IS
     // re-read, the positions shared with neighbouring tiles and the staging rows; round 6: a.veg x 952 tile kernel -6 %, finish -8 %)
-    const int32_t gv0 = __builtin_nontemporal_load(&as_global(a.gvid)[size_t(tile) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)]);
+    // Regular batches (launch_args.h: reg_*): the tile is copy c of template tile r, and its ids are r's plus c * V -- so the load
+    // names r's entries, which every copy reads (in L2 after the first: the flavour of the index planes, never non-temporal for a
+    // plan that shares), and the constant is added when the id is used.  c and r are scalar arithmetic on the workgroup number
+    // and kernel arguments: nothing is loaded in front of the id.  Any other plan: c = 0, r = the tile, today's address.
+    const uint32_t reg_c = uint32_t((uint64_t(uint32_t(tile)) * a.reg_mul) >> a.reg_shift);
+    const uint32_t reg_r = uint32_t(tile) - reg_c * a.reg_period;
+    const uint32_t reg_vert_off = reg_r * uint32_t(a.vert_stride);   // (= r's descriptor's vert_off, for the destinations)
+    const GLOBAL_AS int32_t *gv_ptr = &as_global(a.gvid)[size_t(reg_r) * size_t(a.vert_stride) + size_t(int(threadIdx.x) < a.vert_stride ? threadIdx.x : 0)];
+    const int32_t gv0 = INDEX_NT ? __builtin_nontemporal_load(gv_ptr) : *gv_ptr;
     __builtin_amdgcn_sched_barrier(0);
-    tile_body<WITH_GRAD, WEIGHTED, REBUILD, SPT, INDEX_NT>(a, tile, gv0);
+    tile_body<WITH_GRAD, WEIGHTED, REBUILD, SPT, INDEX_NT>(a, tile, gv0, reg_vert_off, int(reg_c) * a.reg_v, int(reg_c) * a.reg_s);
 }
 
 template <bool WITH_GRAD, int BLOCK, int WPE, bool WEIGHTED = false, bool REBUILD = false, int SPT = kSlotsPerLane>

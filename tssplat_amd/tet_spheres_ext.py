@@ -198,6 +198,14 @@ class TetSpheres:
         _capi.check(_lib.tsamd_get_index_reps(self._handle(), C.byref(p)))
         return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.int32)
 
+    def regular_batch(self) -> dict:
+        """How the plan repeats (tsamd_get_regular_batch): ``period`` tiles per copy -- 0 unless the batch is copies of one
+        template --, ``copies``, ``V`` vertices, ``S`` staging rows and ``K`` finish vertices per copy, and the multiply-shift pair
+        ``div_mul``, ``div_shift`` with which the kernels divide a tile number by the period."""
+        out = (C.c_int64 * 7)()
+        _capi.check(_lib.tsamd_get_regular_batch(self._handle(), out))
+        return dict(zip(("period", "copies", "V", "S", "K", "div_mul", "div_shift"), (int(v) for v in out)))
+
     def set_timing(self, enable: bool) -> None:
         """Record HIP events around the kernels of every evaluation (bench.py roofline leg)."""
         _capi.check(_lib.tsamd_set_timing(self._handle(), int(enable)))
