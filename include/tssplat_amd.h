@@ -465,6 +465,29 @@ int tsamd_depth_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t n
                              int32_t width, const int32_t *ids_dev, const float *world_pos_dev, const float *campos_dev, const float *target_dev,
                              const float *mask_dev, const float *grad_loss_dev, int32_t accumulate_pos, float *grad_world_dev, float *grad_pos_dev, void *stream);
 
+/* The normal term of the geometry stage (the reference's mesh_rasterizer.py:137-149, out["n"] = interpolate(vertex normals * [1, 1, -1],
+ * rast), under a masked MSE), from the ids tsamd_silhouette leaves: no rast image, no interpolated image, no gradient image.  attr_dev
+ * [n_vertices, 3] is any 3-channel vertex attribute.  Per pixel of view b with triangle id t: (u, v) = the clamped barycentrics
+ * tsamd_rasterize writes (the same float32 operations), w = (1 - u) - v, n_c = u a0_c + v a1_c + w a2_c; background -- id 0, an id
+ * outside [1, n_triangles], a vertex index outside [0, n_vertices); nothing is read through those -- has n = 0.  loss_out_dev[0] = mean
+ * over batch * height * width * 3 of (n_c m - t_c m)^2 for target_dev [batch, height, width, 3] and mask_dev [batch, height, width],
+ * broadcast over the channels (each product rounded to float32, squares and sums in float64 on a fixed grid: bitwise repeatable); 0
+ * without pixels or without triangles, and then nothing else is written.  normal_out_dev (optional, [batch, height, width, 3]): n.
+ * workspace_dev: tsamd_normal_mse_workspace_bytes(batch * height * width).
+ * tsamd_normal_mse_backward: with g_c = grad_loss_dev[0] 2 (n_c m - t_c m) m / (3 batch height width), grad_attr_dev [n_vertices, 3]
+ * (zero-filled first) receives the (u, v, w) g scatter of tsamd_interpolate_backward and grad_pos_dev [batch, n_vertices, 4] the gradient
+ * of (u, v) through the quotient rule of tsamd_rasterize_backward (x, y, w; the clamps treated as inactive); grad_pos_dev is zero-filled
+ * first, or added to when accumulate_pos != 0 (on top of tsamd_silhouette_mse_backward's and tsamd_depth_mse_backward's, say).
+ * Background and masked-out pixels contribute nothing.  fp32 atomics: the last bits of the gradients vary from run to run.  Limits and
+ * messages are tsamd_rasterize's. */
+int64_t tsamd_normal_mse_workspace_bytes(int64_t n);
+int tsamd_normal_mse(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
+                     const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev, void *workspace_dev, float *loss_out_dev,
+                     float *normal_out_dev, void *stream);
+int tsamd_normal_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height,
+                              int32_t width, const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev,
+                              const float *grad_loss_dev, int32_t accumulate_pos, float *grad_attr_dev, float *grad_pos_dev, void *stream);
+
 /* The texture stage's image side under frozen geometry and fixed views (the reference's trainer.py with optimize_geo = False:
  * loss = L1(antialias(lerp(background, scatter(color), mask))[..., :3], target[..., :3])).  Which triangle wins a pixel pair, which
  * silhouette edge crosses between the two centres and the weight |t - 1/2| depend on rast / pos_clip only, so antialiasing is a

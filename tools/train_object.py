@@ -15,6 +15,7 @@ absent):
 
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
+                                 [--fit-normal off|operators|fused-loss --fit-normal-start N --normal-weight W] [--normal-bench PATH]
                                  [--placement host|device --grid N] [--merge-grid N --merge-out DIR]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
@@ -31,6 +32,15 @@ dr.silhouette_mse, no gradient image).  --no-stages: leave out the stand-alone s
 The target distances are rendered once, without gradients, from the target mesh by the operator chain.  --depth-bench PATH: both
 modes on the same seed plus the depth stage timings (median of five repeats of 200 iterations, HIP events), written to PATH
 (profiles/depth_bench.json).
+
+--fit-normal: a normal term, `+ MSE(n * a_ref, n_ref * a_ref) * --normal-weight` once `it` has passed --fit-normal-start, with
+`n = out["n"]` of mesh_rasterizer.py:137-149 (the interpolated vertex normals times [1, 1, -1]).  The reference's renderer returns
+that image and its dataset loads normal maps, but its trainer has no normal line: the default weight 100 mirrors the depth term's
+`* 100`.  `operators`: forward(fit_normal=True) and a masked MSELoss; `fused-loss`: MeshRasterizer.silhouette_normal_loss.  With
+--fit-depth in the same mode the three terms come from one forward -- under `fused-loss` from one rasterisation; the two options must
+name the same mode when both are on.  The target normals are rendered once, without gradients, from the target mesh by the operator
+chain with the same [1, 1, -1] convention.  --normal-bench PATH: --fit-normal alone and with --fit-depth, each in both modes on the same
+seed, plus the normal stage timings (median of five windows of 200 calls, HIP events), written to PATH (profiles/normal_bench.json).
 
 --merge-grid N: after the fit, `tssplat_amd.merge` (`union_field`, `extract_surface`: what `merge_tets` runs) turns all spheres into ONE closed surface at N nodes per axis
 (`merged_surface.obj` under --merge-out) and the record gains `merged`: `closed`, the counts and `volume_iou_vs_hull`, the merged
@@ -68,6 +78,31 @@ def render_depth(glctx, verts, tri, mvp, campos, res):
     rast, _ = dr.rasterize(glctx, pos_clip, tri, resolution=[res, res], grad_db=False)
     world, _ = dr.interpolate(verts[None, ...].contiguous(), rast, tri)
     return torch.norm(world - campos[:, None, None, :], dim=-1, keepdim=True)
+
+
+def vertex_normals(verts, tri):
+    """Unit vertex normals of a triangle mesh in plain torch (this runs once, for the target): every triangle adds its area-weighted
+    normal to its three corners; a vertex whose sum vanishes gets +z."""
+    import torch
+    t = tri.long()
+    corners = verts[t]                                                                   # [T, 3 corners, 3]
+    face = torch.linalg.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0])
+    total = torch.zeros_like(verts).index_add_(0, t.reshape(-1), face.repeat_interleave(3, dim=0))
+    flat = (total * total).sum(dim=1, keepdim=True) <= 1e-20
+    total = torch.where(flat, total.new_tensor([0.0, 0.0, 1.0]), total)
+    return total / total.norm(dim=1, keepdim=True)
+
+
+def render_normal(glctx, verts, tri, mvp, res):
+    """Normal image of a triangle mesh, `[B, H, W, 3]`: the normal branch of MeshRasterizer.forward (mesh_rasterizer.py:137-149), the
+    vertex normals times [1, 1, -1] interpolated, 0 on background."""
+    import torch
+    import tssplat_amd.dr as dr
+    posw = torch.cat([verts, torch.ones_like(verts[:, :1])], dim=1)
+    pos_clip = torch.matmul(posw, mvp.transpose(1, 2)).contiguous()
+    rast, _ = dr.rasterize(glctx, pos_clip, tri, resolution=[res, res], grad_db=False)
+    attr = vertex_normals(verts, tri) * verts.new_tensor([1.0, 1.0, -1.0])
+    return dr.interpolate(attr[None, ...].contiguous(), rast, tri)[0]
 
 
 def place_spheres(target_alpha, mvp, n_spheres, grid=72, min_radius=0.05, shrink=0.92):
@@ -121,7 +156,7 @@ def build_spheres(centres, radii, k):
 
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
-        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None):
+        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -132,6 +167,10 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         raise ValueError(f"unknown --silhouette mode {silhouette!r}")
     if fit_depth not in ("off", "operators", "fused-loss"):
         raise ValueError(f"unknown --fit-depth mode {fit_depth!r}")
+    if fit_normal not in ("off", "operators", "fused-loss"):
+        raise ValueError(f"unknown --fit-normal mode {fit_normal!r}")
+    if "off" not in (fit_normal, fit_depth) and fit_normal != fit_depth:
+        raise ValueError(f"--fit-normal {fit_normal} with --fit-depth {fit_depth}: the two terms share one forward, so they must name the same mode")
     if placement not in ("host", "device"):
         raise ValueError(f"unknown --placement {placement!r}")
     target_npz = target_npz or os.path.join(ROOT, "tests", "golden", "mario_mesh.npz")
@@ -146,6 +185,9 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     if fit_depth != "off":
         with torch.no_grad():
             target_depth = render_depth(glctx, tv, tf, mvp, campos, res).clone()
+    if fit_normal != "off":
+        with torch.no_grad():
+            target_normal = render_normal(glctx, tv, tf, mvp, res).clone()
     if placement == "device":
         from tssplat_amd import spheres_init
         kp = spheres_init.init_spheres(target, mvp, n_spheres, grid=grid)
@@ -175,7 +217,20 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(iters):
-        if fit_depth == "fused-loss" and fit_depth_start < it:
+        depth_on = fit_depth != "off" and fit_depth_start < it
+        if fit_normal == "fused-loss" and fit_normal_start < it:
+            depth_args = {"campos": campos, "target_depth": target_depth} if depth_on else {}
+            out = ren.silhouette_normal_loss(mvp, target, target_normal, iter_num=it, resolution=res, **depth_args)
+            img_loss = out["img_loss"] * 20 + out["normal_loss"] * normal_weight
+            if depth_on:
+                img_loss = img_loss + out["depth_loss"] * 100
+        elif fit_normal == "operators" and fit_normal_start < it:
+            out = ren(mvp, only_alpha=True, iter_num=it, resolution=res, fit_normal=True, fit_depth=depth_on, campos=campos)
+            img_loss = shade_loss(out["shaded"][..., -1], target[..., -1]) * 20
+            img_loss = img_loss + shade_loss(out["n"] * target, target_normal * target) * normal_weight
+            if depth_on:
+                img_loss = img_loss + shade_loss(out["d"][..., -1] * target[..., -1], target_depth[..., -1] * target[..., -1]) * 100
+        elif fit_depth == "fused-loss" and fit_depth_start < it:
             out = ren.silhouette_depth_loss(mvp, target, campos, target_depth, iter_num=it, resolution=res)
             img_loss = out["img_loss"] * 20 + out["depth_loss"] * 100
         elif fit_depth == "operators" and fit_depth_start < it:                          # trainer.py:77-79, :106-109
@@ -207,7 +262,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     inverted = int((np.sign(dets(x)) != np.sign(dets(rest.astype(np.float64)))).sum())
     rec = {
         "metric": "s per iteration, geometry-fitting loop on the reference's object (BASELINE config 5)", "value": dt / iters, "unit": "s/iteration",
-        "higher_is_better": False, "silhouette": silhouette, "fit_depth": fit_depth, "fit_depth_start": fit_depth_start, "iterations": iters, "wall_s": dt, "ms_per_iteration": 1e3 * dt / iters,
+        "higher_is_better": False, "silhouette": silhouette, "fit_depth": fit_depth, "fit_depth_start": fit_depth_start,
+        "fit_normal": fit_normal, "fit_normal_start": fit_normal_start, "normal_weight": normal_weight, "iterations": iters, "wall_s": dt, "ms_per_iteration": 1e3 * dt / iters,
         "silhouette_iou": iou, "silhouette_iou_at_start": iou0, "inverted_tets": inverted, "tets": int(tets.shape[0]),
         "img_loss_first_last": [log[0][1], log[-1][1]], "reg_first_last": [log[0][2], log[-1][2]],
         "spheres": {"placed": S, "asked": n_spheres, "radii_min_max": [float(radii.min()), float(radii.max())], "visual_hull_fraction_of_cube": hull_frac,
@@ -279,7 +335,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             pos_g.grad = None
             dr.silhouette_mse(ren.glctx, pos_g, tri, [res, res], target).backward()
         depth_stages = {}
-        if fit_depth != "off":
+        if fit_depth != "off" and fit_normal == "off":             # (with the normal term on, the stage timings below are that term's)
             # the depth term on its own, forward + backward, given the rasterisation each path starts from: `rast` (kept in the
             # graph: the backward runs interpolate's and rasterize's) against the ids of the alpha stage
             world_g = data.v_pos.detach().clone().requires_grad_(True)
@@ -323,6 +379,57 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             depth_stages = {name: t[len(t) // 2] for name, t in windows.items()}
             rec["depth_stage_windows_ms"] = {"calls_per_window": reps, "windows": windows}
             del rast_g
+        normal_stages = {}
+        if fit_normal != "off":
+            # the normal term on its own, forward + backward, given the rasterisation each path starts from (as for the depth term),
+            # and all image terms of this run with their rasterisation
+            with_depth = fit_depth != "off"
+            attr_g = (data._compute_vertex_normal() * torch.tensor([1, 1, -1], dtype=torch.float32, device=pos.device)[None, :]).detach().contiguous().requires_grad_(True)
+            world_g = data.v_pos.detach().clone().requires_grad_(True)
+            a_ref, a_ref3, n_ref = target[..., -1].contiguous(), target.contiguous(), target_normal.contiguous()
+            rast_g, _ = dr.rasterize(ren.glctx, pos_g, tri, resolution=[res, res], grad_db=False)
+            topo = dr.antialias_construct_topology_hash(tri)
+            _, ids, _ = dr._silhouette_forward(pos, tri, topo.opp, ren.glctx, res, res)
+            lib, check, stream = dr._lib, dr._capi.check, dr._stream_ptr(pos.device)
+            B, V, T = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
+            ws = torch.empty(int(lib.tsamd_normal_mse_workspace_bytes(B * res * res)), dtype=torch.uint8, device=pos.device)
+            loss_f, one = torch.empty((), device=pos.device), torch.ones((), device=pos.device)
+            gn, gp = torch.empty_like(attr_g), torch.empty_like(pos)
+
+            def normal_chain_fb(j):
+                pos_g.grad = attr_g.grad = None
+                n, _ = dr.interpolate(attr_g[None, ...], rast_g, tri)
+                shade_loss(n * a_ref3, n_ref * a_ref3).backward(retain_graph=True)
+
+            def normal_fused_fb(j):
+                args = (pos.data_ptr(), B, V, tri.data_ptr(), T, res, res, ids.data_ptr(), attr_g.data_ptr(), n_ref.data_ptr(), a_ref.data_ptr())
+                check(lib.tsamd_normal_mse(*args, ws.data_ptr(), loss_f.data_ptr(), None, stream))
+                check(lib.tsamd_normal_mse_backward(*args, one.data_ptr(), 0, gn.data_ptr(), gp.data_ptr(), stream))
+
+            def all_terms_chain_fb(j):
+                pos_g.grad = attr_g.grad = world_g.grad = None
+                r, _ = dr.rasterize(ren.glctx, pos_g, tri, resolution=[res, res], grad_db=False)
+                a = dr.antialias(torch.clamp(r[..., -1:].detach(), 0, 1).contiguous(), r, pos_g, tri)
+                n, _ = dr.interpolate(attr_g[None, ...], r, tri)
+                total = shade_loss(a[..., -1], a_ref) * 20 + shade_loss(n * a_ref3, n_ref * a_ref3) * normal_weight
+                if with_depth:
+                    x, _ = dr.interpolate(world_g[None, ...], r, tri)
+                    d = torch.norm(x - campos[:, None, None, :], dim=-1, keepdim=True)
+                    total = total + shade_loss(d[..., -1] * a_ref, target_depth[..., -1] * a_ref) * 100
+                total.backward()
+
+            def all_terms_fused_fb(j):
+                pos_g.grad = attr_g.grad = world_g.grad = None
+                got = dr.silhouette_normal_mse(ren.glctx, pos_g, tri, [res, res], target, attr_g, target_normal, target,
+                                               depth=(world_g, campos, target_depth, target) if with_depth else None)
+                (got[0] * 20 + got[-1] * normal_weight + (got[1] * 100 if with_depth else 0)).backward()
+            reps, repeats = normal_stage_reps
+            windows = timed_alternating({"normal_operators_forward_backward": normal_chain_fb, "normal_fused_forward_backward": normal_fused_fb,
+                                         "image_terms_operators_forward_backward": all_terms_chain_fb, "image_terms_fused_forward_backward": all_terms_fused_fb},
+                                        reps, repeats)
+            normal_stages = {name: t[len(t) // 2] for name, t in windows.items()}
+            rec["normal_stage_windows_ms"] = {"calls_per_window": reps, "image_terms": "alpha, depth, normal" if with_depth else "alpha, normal", "windows": windows}
+            del rast_g
         rec["stages_ms"] = {
             "energy_and_surface_forward_backward": timed(geo_fb),
             "rasterize": timed(lambda j: dr.rasterize(ren.glctx, pos, tri, resolution=[res, res], grad_db=False)),
@@ -331,6 +438,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             "silhouette_mse_forward_backward": timed(sil_mse_fb),
             "optimizer_step": timed(lambda j: opt.step()),
             **depth_stages,
+            **normal_stages,
         }
     return rec
 
@@ -363,6 +471,43 @@ def depth_bench(path, **kw):
     return rec
 
 
+def normal_bench(path, **kw):
+    """--fit-normal alone and together with --fit-depth, each in both modes on the same seed, and the normal stage timings, as one
+    record written to `path`."""
+    kw = dict(kw, silhouette="fused-loss")
+    runs = {"normal": {"operators": run(fit_normal="operators", stages=False, **kw),
+                       "fused-loss": run(fit_normal="fused-loss", stages=True, normal_stage_reps=(200, 5), **kw)},
+            "depth_and_normal": {"operators": run(fit_normal="operators", fit_depth="operators", stages=False, **kw),
+                                 "fused-loss": run(fit_normal="fused-loss", fit_depth="fused-loss", stages=True, normal_stage_reps=(200, 5), **kw)}}
+
+    def pair(fused, chain, own):
+        w = fused["normal_stage_windows_ms"]["windows"]
+        return {"operators_ms": fused["stages_ms"][chain], "fused_ms": fused["stages_ms"][own], "operators_ms_min_max": [w[chain][0], w[chain][-1]],
+                "fused_ms_min_max": [w[own][0], w[own][-1]], "ratio_operators_over_fused": fused["stages_ms"][chain] / fused["stages_ms"][own],
+                "ranges_overlap": not (w[own][-1] < w[chain][0] or w[chain][-1] < w[own][0])}
+    keep = ("ms_per_iteration", "silhouette_iou", "silhouette_iou_at_start", "inverted_tets", "img_loss_first_last", "fit_depth", "fit_depth_start", "fit_normal",
+            "fit_normal_start", "normal_weight", "iterations")
+
+    def training(modes):
+        return {**{mode: {k: r[k] for k in keep} for mode, r in modes.items()},
+                "ms_per_iteration_operators_over_fused": modes["operators"]["ms_per_iteration"] / modes["fused-loss"]["ms_per_iteration"]}
+    alone, both = runs["normal"]["fused-loss"], runs["depth_and_normal"]["fused-loss"]
+    term = pair(alone, "normal_operators_forward_backward", "normal_fused_forward_backward")
+    rec = {"metric": "normal term forward + backward, operator chain over fused pair (medians of five windows of 200 calls, HIP events)",
+           "value": term["ratio_operators_over_fused"], "unit": "x", "higher_is_better": True, "config": alone["config"],
+           "normal_term": term,
+           "alpha_and_normal_with_their_rasterisation": pair(alone, "image_terms_operators_forward_backward", "image_terms_fused_forward_backward"),
+           "alpha_depth_and_normal_with_their_rasterisation": pair(both, "image_terms_operators_forward_backward", "image_terms_fused_forward_backward"),
+           "windows_ms": {"normal": alone["normal_stage_windows_ms"], "depth_and_normal": both["normal_stage_windows_ms"]},
+           "training": {"normal": training(runs["normal"]), "depth_and_normal": training(runs["depth_and_normal"])},
+           "stages_ms": {"normal": alone["stages_ms"], "depth_and_normal": both["stages_ms"]}}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write("\n")
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--target", default=None)
@@ -381,14 +526,28 @@ def main():
     ap.add_argument("--merge-grid", type=int, default=0, metavar="N", help="merge the fitted spheres into one closed surface at N nodes per axis (0: off)")
     ap.add_argument("--merge-out", default=None, metavar="DIR", help="where merged_surface.obj goes (bench_outputs/train_object)")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
+    ap.add_argument("--fit-normal", choices=["off", "operators", "fused-loss"], default="off")
+    ap.add_argument("--fit-normal-start", type=int, default=0, help="the normal term enters once the iteration has passed this one")
+    ap.add_argument("--normal-weight", type=float, default=100.0,
+                    help="weight of the normal term (the reference's trainer has no normal line: the default mirrors its depth term's * 100)")
+    ap.add_argument("--normal-bench", default=None, metavar="PATH",
+                    help="run --fit-normal alone and with --fit-depth, each in both modes, and the normal stage timings; write the record to PATH")
     args = ap.parse_args()
+    if args.normal_bench:
+        rec = normal_bench(args.normal_bench, target_npz=args.target, n_spheres=args.spheres, k=args.k, views=args.views, res=args.res, iters=args.iters,
+                           verbose=args.verbose, fit_depth_start=args.fit_depth_start, fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight,
+                           placement=args.placement, grid=args.grid)
+        print(json.dumps({k: rec[k] for k in ("metric", "value", "unit", "normal_term", "alpha_and_normal_with_their_rasterisation",
+                                              "alpha_depth_and_normal_with_their_rasterisation", "training")}))
+        return
     if args.depth_bench:
         rec = depth_bench(args.depth_bench, target_npz=args.target, n_spheres=args.spheres, k=args.k, views=args.views, res=args.res, iters=args.iters,
                           verbose=args.verbose, fit_depth_start=args.fit_depth_start, placement=args.placement, grid=args.grid)
         print(json.dumps({k: rec[k] for k in ("metric", "value", "unit", "depth_term", "both_image_terms_with_their_rasterisation", "training")}))
         return
     print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
-                         stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, placement=args.placement, grid=args.grid,
+                         stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
+                         fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
                          merge_grid=args.merge_grid, merge_out=args.merge_out)))
 
 

@@ -63,6 +63,17 @@ hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vert
 hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
                                      const int32_t *ids, const float *world_pos, const float *campos, const float *target, const float *mask, const float *grad_loss,
                                      int accumulate_pos, float *grad_world, float *grad_pos, hipStream_t stream);
+// The normal term (raster_kernels.hip): loss = mean over batch * height * width * 3 of (n_c m - t_c m)^2 with n = interpolate(attr)
+// for attr [n_vertices, 3] from the alpha stage's ids (0 on background), target [batch, height, width, 3], mask [batch, height, width];
+// bitwise repeatable; normal_out (optional): n per pixel.  No pixel or no triangle: loss 0, nothing else written.  backward: grad_attr
+// [n_vertices, 3] is zero-filled by the launch, grad_pos [batch, n_vertices, 4] too unless accumulate_pos != 0 (then it is added to).
+// n of the workspace size is the pixel count batch * height * width.
+int64_t normal_mse_workspace_bytes(int64_t n);
+hipError_t launch_normal_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
+                             const float *attr, const float *target, const float *mask, void *workspace, float *loss, float *normal_out, hipStream_t stream);
+hipError_t launch_normal_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                      const int32_t *ids, const float *attr, const float *target, const float *mask, const float *grad_loss, int accumulate_pos,
+                                      float *grad_attr, float *grad_pos, hipStream_t stream);
 hipError_t launch_interpolate(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels, const float *rast, const int32_t *tri,
                               int64_t n_tri, int64_t batch, int height, int width, float *out, hipStream_t stream);
 // grad_attr is zero-filled by the launch; grad_rast may be null

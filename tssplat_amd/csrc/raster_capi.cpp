@@ -299,4 +299,50 @@ int tsamd_depth_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t n
     return TSAMD_OK;
 }
 
+namespace {
+// the arguments tsamd_normal_mse and tsamd_normal_mse_backward share
+int check_normal(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
+                 const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev)
+{
+    const int rc = check_render(batch, n_vertices, n_triangles, height, width);
+    if (rc) return rc;
+    if (pixel_count(batch, height, width) <= 0 || n_triangles <= 0) return TSAMD_OK;
+    return check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {ids_dev, "ids_dev"}, {attr_dev, "attr_dev"}, {target_dev, "target_dev"},
+                           {mask_dev, "mask_dev"}});
+}
+}  // namespace
+
+int64_t tsamd_normal_mse_workspace_bytes(int64_t n)
+{
+    if (n < 0) return -1;
+    return tsamd::normal_mse_workspace_bytes(n);
+}
+
+int tsamd_normal_mse(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
+                     const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev, void *workspace_dev, float *loss_out_dev,
+                     float *normal_out_dev, void *stream)
+{
+    int rc = check_normal(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev);
+    if (rc) return rc;
+    if (!loss_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "loss_out_dev is null");
+    if (pixel_count(batch, height, width) > 0 && n_triangles > 0 && !workspace_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "workspace_dev is null");
+    TSAMD_HIP(tsamd::launch_normal_mse(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev, workspace_dev,
+                                       loss_out_dev, normal_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_normal_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height,
+                              int32_t width, const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev,
+                              const float *grad_loss_dev, int32_t accumulate_pos, float *grad_attr_dev, float *grad_pos_dev, void *stream)
+{
+    int rc = check_normal(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev);
+    if (rc) return rc;
+    if (n_vertices > 0 && !grad_attr_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_attr_dev is null");
+    if (batch * n_vertices > 0 && !grad_pos_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_pos_dev is null");
+    if (pixel_count(batch, height, width) > 0 && n_triangles > 0 && !grad_loss_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_loss_dev is null");
+    TSAMD_HIP(tsamd::launch_normal_mse_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev,
+                                                grad_loss_dev, accumulate_pos, grad_attr_dev, grad_pos_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
 }  // extern "C"

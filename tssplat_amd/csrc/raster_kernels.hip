@@ -18,6 +18,8 @@
 //   interpolate_kernel / interpolate_backward_kernel  one lane per pixel
 //   depth_mse_kernel / depth_mse_backward_kernel  the depth term without an image chain: distance to the camera of the
 //                          interpolated world position, masked MSE (det_mean.h) and both of its scatters from the alpha stage's ids
+//   normal_mse_kernel / normal_mse_backward_kernel  the normal term without an image chain: masked MSE of an interpolated
+//                          3-channel vertex attribute and both of its scatters, the structure of the depth pair
 //
 // Bound: the depth image -- L2 atomics and the reads in front of them (pricing builds, profiles/r04_raster_experiments.md: walk
 // 0.46 ms, fragment queue + depth reads 0.23, atomics 0.31 of 1.10 ms on the 512-sphere surface); 12 B of indices + 3 x 16 B of
@@ -770,16 +772,26 @@ __device__ __forceinline__ void distance_to(float x, float y, float z, const flo
     p.d = sqrtf(p.dx * p.dx + p.dy * p.dy + p.dz * p.dz);
 }
 
+// What every id-driven term starts from at a covered pixel (px, py) of a view with clip-space vertices pv: the clamped barycentrics
+// of the resolve pass, w = (1 - u) - v as interpolate_kernel forms it, and the three rows of a 3-channel vertex attribute,
+// a[3 k + c] = channel c of vertex i_k.  (Shared by the depth and the normal pair: ONE statement of these operations.)
+__device__ __forceinline__ EdgeFunctions weights_and_gather(const float4 *pv, const float *attr, int32_t i0, int32_t i1, int32_t i2, int px, int py, int height,
+                                                            int width, float &u, float &v, float &w, float a[9])
+{
+    const EdgeFunctions e = edge_functions(pv[i0], pv[i1], pv[i2], px, py, height, width);
+    u = clamp01(e.a0 / e.s), v = clamp01(e.a1 / e.s);
+    w = 1.f - u - v;
+    const float *a0 = attr + 3 * int64_t(i0), *a1 = attr + 3 * int64_t(i1), *a2 = attr + 3 * int64_t(i2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a[k] = a0[k], a[3 + k] = a1[k], a[6 + k] = a2[k];
+    return e;
+}
+
 // the covered pixel (px, py) of a view: clip-space vertices pv, world positions `world`, camera c
 __device__ __forceinline__ EdgeFunctions depth_point(const float4 *pv, const float *world, const float *c, int32_t i0, int32_t i1, int32_t i2, int px, int py,
                                                      int height, int width, DepthPoint &p, float a[9])
 {
-    const EdgeFunctions e = edge_functions(pv[i0], pv[i1], pv[i2], px, py, height, width);
-    p.u = clamp01(e.a0 / e.s), p.v = clamp01(e.a1 / e.s);
-    p.w = 1.f - p.u - p.v;
-    const float *a0 = world + 3 * int64_t(i0), *a1 = world + 3 * int64_t(i1), *a2 = world + 3 * int64_t(i2);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] = a0[k], a[3 + k] = a1[k], a[6 + k] = a2[k];
+    const EdgeFunctions e = weights_and_gather(pv, world, i0, i1, i2, px, py, height, width, p.u, p.v, p.w, a);
     distance_to(p.u * a[0] + p.v * a[3] + p.w * a[6], p.u * a[1] + p.v * a[4] + p.w * a[7], p.u * a[2] + p.v * a[5] + p.w * a[8], c, p);
     return e;
 }
@@ -923,6 +935,131 @@ __global__ __launch_bounds__(256) void depth_mse_backward_kernel(const float4 *p
     }
 }
 
+// ---- the normal term: masked MSE of an interpolated 3-channel vertex attribute, without an image chain ----
+// What MeshRasterizer.forward(fit_normal=True) and a masked MSELoss build from out["n"] = interpolate(attr, rast) (the reference's
+// mesh_rasterizer.py:137-149): loss = mean over pixels and channels of (n_c m - t_c m)^2, the mask broadcast over the channels.  The
+// chain moves a 16-byte rast pixel, a 12-byte interpolated pixel, the masked products and their gradients; here a pixel is its id,
+// three target floats and a mask -- 20 bytes -- plus cached vertex gathers.  (u, v, w) and the gather are weights_and_gather's, the
+// interpolation is interpolate_kernel's; a background pixel has n = 0.  `attr` is any [V, 3] attribute: the normal is the use.
+constexpr int kNormalPixels = kDepthPixels;                     // 64-pixel chunks per wave and round
+constexpr int kNormalPerBlock = kMeanBlock * kNormalPixels;     // pixels per workgroup and round
+constexpr int kNormalMaxBlocks = 8192;                          // (the loss's bits depend on these two: det_mean.h)
+
+// One lane per pixel; a workgroup strides over rounds of kNormalPerBlock pixels and stores one double: the sum over its pixels and
+// the three channels of (n_c m - t_c m)^2, each product rounded on its own, squared and added in float64 (channel 0, 1, 2 in turn).
+// n_out (optional): the interpolated image [B, H, W, 3], every pixel of it.
+__global__ __launch_bounds__(kMeanBlock) void normal_mse_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
+                                                                int width, const int32_t *ids, const float *attr, const float *target, const float *mask,
+                                                                double *partials, float *n_out)
+{
+    constexpr int K = kNormalPixels;
+    __shared__ double lds[kMeanBlock / 64];
+    const int64_t hw = int64_t(height) * width, total = batch * hw;
+    const int lane = int(threadIdx.x) & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+    const bool one_boundary = hw >= 64 * K;
+    double acc = 0.0;
+    for (int64_t first = int64_t(blockIdx.x) * kNormalPerBlock; first < total; first += int64_t(gridDim.x) * kNormalPerBlock) {
+        const int64_t gid0 = first + int64_t(wave) * (64 * K);
+        int32_t id[K];
+        float tg[K][3], m[K];
+        bool want[K];
+        // all global loads first, together (the latency of one round trip, not of three)
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int64_t gid = gid0 + 64 * k + lane;
+            const bool have = gid < total;
+            id[k] = have ? ids[gid] : 0;
+            m[k] = have ? mask[gid] : 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) tg[k][c] = have ? target[3 * gid + c] : 0.f;
+            want[k] = have && (m[k] != 0.f || n_out != nullptr);     // a masked-out pixel adds 0: no vertex work unless its n is asked for
+        }
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < K; ++k) any = any || want[k];
+        if (__ballot(any) == 0ull) continue;                          // wave-uniform: nothing in these chunks enters the loss
+        const int64_t b0 = one_boundary ? gid0 / hw : 0;              // (on the scalar unit)
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (!want[k]) continue;
+            const int64_t gid = gid0 + 64 * k + lane;
+            float n[3] = {0.f, 0.f, 0.f};
+            int32_t i0, i1, i2;
+            if (triangle_of_id(id[k], tri, n_tri, n_vertices, i0, i1, i2)) {
+                int64_t b;
+                int px, py;
+                locate_pixel(gid, hw, width, one_boundary, b0, b, px, py);
+                float u, v, w, a[9];
+                weights_and_gather(pos + b * n_vertices, attr, i0, i1, i2, px, py, height, width, u, v, w, a);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) n[c] = u * a[c] + v * a[3 + c] + w * a[6 + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (n_out) n_out[3 * gid + c] = n[c];
+                const float r = n[c] * m[k] - tg[k][c] * m[k];
+                acc += double(r) * double(r);
+            }
+        }
+    }
+    const double sum = block_sum(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+// One lane per pixel, one pass: (u, v, n) recomputed, g_c = grad_loss 2 (n_c m - t_c m) m / (3 pixels), then BOTH scatters behind one
+// run detection, as in depth_mse_backward_kernel -- interpolate_backward's (u, v, w) g into grad_attr[V, 3] and, through
+// (du, dv) = (g . (a0 - a2), g . (a1 - a2)) and the quotient rule of rasterize_backward, (x, y, w) into grad_pos[B, V, 4].  The run key
+// holds the view (a wave of a small image spans views that show the same id).  Background and masked-out pixels add nothing.
+// EVERY lane reaches find_runs.
+__global__ __launch_bounds__(256) void normal_mse_backward_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
+                                                                  int width, const int32_t *ids, const float *attr, const float *target, const float *mask,
+                                                                  const float *grad_loss, float *grad_attr, float4 *grad_pos)
+{
+    const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t hw = int64_t(height) * width, total = batch * hw;
+    bool valid = gid < total;
+    int32_t id = 0, i0 = 0, i1 = 0, i2 = 0;
+    float tg[3] = {0.f, 0.f, 0.f}, m = 0.f;
+    if (valid) id = ids[gid], m = mask[gid], tg[0] = target[3 * gid], tg[1] = target[3 * gid + 1], tg[2] = target[3 * gid + 2];
+    valid = valid && m != 0.f && triangle_of_id(id, tri, n_tri, n_vertices, i0, i1, i2);   // (background: n = 0 is a constant)
+    int64_t b = 0;
+    float da[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // the three channels of the three attribute rows
+    float dc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, w) of the three clip-space positions
+    if (valid) {
+        int px, py;
+        locate_pixel(gid, hw, width, false, 0, b, px, py);
+        float u, v, w, a[9], g[3];
+        const EdgeFunctions e = weights_and_gather(pos + b * n_vertices, attr, i0, i1, i2, px, py, height, width, u, v, w, a);
+        const float scale = grad_loss[0] / float(3 * total);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float n = u * a[c] + v * a[3 + c] + w * a[6 + c];
+            const float r = n * m - tg[c] * m;
+            g[c] = (2.f * r * m) * scale;
+            da[c] = u * g[c], da[3 + c] = v * g[c], da[6 + c] = w * g[c];
+        }
+        const float du = g[0] * (a[0] - a[6]) + g[1] * (a[1] - a[7]) + g[2] * (a[2] - a[8]);
+        const float dv = g[0] * (a[3] - a[6]) + g[1] * (a[4] - a[7]) + g[2] * (a[5] - a[8]);
+        edge_functions_backward(e, du, dv, dc);
+    }
+    const Runs runs = find_runs(valid ? b * (int64_t(1) << 32) + int64_t(id) : -1 - int64_t(threadIdx.x));
+#pragma unroll
+    for (int k = 0; k < 9; ++k) da[k] = run_sum(runs, da[k]), dc[k] = run_sum(runs, dc[k]);
+    if (valid && runs.last) {
+        float *gp = reinterpret_cast<float *>(grad_pos + b * n_vertices);
+        const int64_t at[3] = {int64_t(i0), int64_t(i1), int64_t(i2)};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            atomicAdd(grad_attr + 3 * at[k] + 0, da[3 * k]);
+            atomicAdd(grad_attr + 3 * at[k] + 1, da[3 * k + 1]);
+            atomicAdd(grad_attr + 3 * at[k] + 2, da[3 * k + 2]);
+            atomicAdd(gp + 4 * at[k] + 0, dc[3 * k]);
+            atomicAdd(gp + 4 * at[k] + 1, dc[3 * k + 1]);
+            atomicAdd(gp + 4 * at[k] + 3, dc[3 * k + 2]);
+        }
+    }
+}
+
 unsigned blocks_for(int64_t n) { return unsigned((n + 255) / 256); }
 
 // The stages every rasterisation starts with -- depth keys cleared, vertices snapped, triangles binned, the rare ones clipped: after
@@ -1050,6 +1187,36 @@ hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64
     if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
     hipLaunchKernelGGL(depth_mse_backward_kernel, dim3(blocks_for(pixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri,
                        batch, height, width, ids, world_pos, campos, target, mask, grad_loss, grad_world, reinterpret_cast<float4 *>(grad_pos));
+    return hipGetLastError();
+}
+
+int64_t normal_mse_workspace_bytes(int64_t n) { return mean_workspace_bytes(mean_blocks(n, kNormalPerBlock, kNormalMaxBlocks)); }
+
+hipError_t launch_normal_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
+                             const float *attr, const float *target, const float *mask, void *workspace, float *loss, float *normal_out, hipStream_t stream)
+{
+    const int64_t pixels = pixel_count(batch, height, width);
+    if (pixels <= 0 || n_tri <= 0) return hipMemsetAsync(loss, 0, sizeof(float), stream);
+    const int blocks = mean_blocks(pixels, kNormalPerBlock, kNormalMaxBlocks);
+    hipLaunchKernelGGL(normal_mse_kernel, dim3(blocks), dim3(kMeanBlock), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri, batch, height,
+                       width, ids, attr, target, mask, static_cast<double *>(workspace), normal_out);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, 3 * pixels, loss, stream);
+}
+
+hipError_t launch_normal_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                      const int32_t *ids, const float *attr, const float *target, const float *mask, const float *grad_loss, int accumulate_pos,
+                                      float *grad_attr, float *grad_pos, hipStream_t stream)
+{
+    hipError_t e;
+    if (n_vertices > 0 && (e = hipMemsetAsync(grad_attr, 0, size_t(n_vertices) * 3 * sizeof(float), stream)) != hipSuccess) return e;
+    if (!accumulate_pos && batch * n_vertices > 0 &&
+        (e = hipMemsetAsync(grad_pos, 0, size_t(batch) * size_t(n_vertices) * 4 * sizeof(float), stream)) != hipSuccess)
+        return e;
+    const int64_t pixels = pixel_count(batch, height, width);
+    if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
+    hipLaunchKernelGGL(normal_mse_backward_kernel, dim3(blocks_for(pixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri,
+                       batch, height, width, ids, attr, target, mask, grad_loss, grad_attr, reinterpret_cast<float4 *>(grad_pos));
     return hipGetLastError();
 }
 

@@ -24,7 +24,9 @@ beyond the +-16384-pixel guard band is dropped; the silhouette of a clipped tria
 ``MSE(antialias(clamp(rast[..., -1:], 0, 1)))``) without the ``rast`` image, the clamp, the antialias copy and the dense loss
 gradient -- the same blends as the three operators above give on the 0 / 1 coverage image.  ``silhouette_depth_mse`` adds the
 trainer's depth term (``fit_depth``: ``MSE(||interpolate(v_pos, rast) - campos|| * mask, target * mask)``) to that one rasterisation,
-from the triangle ids the alpha stage leaves: no ``rast`` image, no interpolated image, no gradient image.
+from the triangle ids the alpha stage leaves: no ``rast`` image, no interpolated image, no gradient image.  ``silhouette_normal_mse``
+adds the normal term (``fit_normal``: a masked ``MSE`` of ``interpolate(vertex normals, rast)``) in the same way, with the depth term
+beside it when asked: alpha, depth and normal from one rasterisation and one autograd node.
 
 ``plan_blends``, ``shade`` and ``shade_l1`` are this package's own too: the colour stage under frozen geometry and fixed views.
 There the blends of ``antialias`` do not depend on what is being trained, so they are extracted once into a :class:`BlendPlan`,
@@ -43,7 +45,7 @@ from . import _capi
 from .tet_spheres_ext import _device_ctx, _stream_ptr
 
 __all__ = ["RasterizeCudaContext", "rasterize", "interpolate", "antialias", "antialias_construct_topology_hash", "texture", "silhouette",
-           "silhouette_mse", "silhouette_depth_mse", "BlendPlan", "plan_blends", "shade", "shade_l1"]
+           "silhouette_mse", "silhouette_depth_mse", "silhouette_normal_mse", "BlendPlan", "plan_blends", "shade", "shade_l1"]
 
 _lib = _capi.load()
 
@@ -463,6 +465,31 @@ def silhouette_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Te
     return (loss, alpha.detach()) if return_alpha else loss
 
 
+# the argument checks the id-driven terms (depth, normal) share; every result is detached unless it carries a gradient
+
+def _scalar_image(name: str, label: str, t, pos, shape):
+    t = _check_cuda_f32(label, t)
+    if t.device != pos.device or tuple(t.shape) not in (shape, shape + (1,)):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: {label} must be [B, H, W] or [B, H, W, 1] of the image size, on the device of pos")
+    return t.detach()
+
+
+def _vertex_attribute(name: str, label: str, t, pos):
+    V = int(pos.shape[1])
+    t = _check_cuda_f32(label, t)
+    if t.device != pos.device or tuple(t.shape) not in ((V, 3), (1, V, 3)):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: {label} must be [V, 3] or [1, V, 3] with V = {V} (the vertices of pos), on the device of pos")
+    return t
+
+
+def _camera_positions(name: str, campos, pos):
+    B = int(pos.shape[0])
+    campos = _check_cuda_f32("campos", campos)
+    if campos.device != pos.device or tuple(campos.shape) != (B, 3):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: campos must be [B, 3] = [{B}, 3], on the device of pos")
+    return campos.detach()
+
+
 class _SilhouetteDepthMseFunc(torch.autograd.Function):
     """One node for both image terms of the geometry stage: one rasterisation forward, ``tsamd_silhouette_mse_backward`` followed by
     ``tsamd_depth_mse_backward(accumulate_pos=1)`` backward -- the second lands on what the first wrote."""
@@ -521,23 +548,111 @@ def silhouette_depth_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: to
     ``[B, H, W, 1]``."""
     name = "silhouette_depth_mse"
     pos, tri, height, width, topo = _silhouette_args(name, pos, tri, resolution, topology_hash)
-    B, V = int(pos.shape[0]), int(pos.shape[1])
-    shape = (B, height, width)
-    images = []
-    for label, t in (("target_alpha", target_alpha), ("target_depth", target_depth), ("depth_mask", depth_mask)):
-        t = _check_cuda_f32(label, t)
-        if t.device != pos.device or tuple(t.shape) not in (shape, shape + (1,)):
-            raise RuntimeError(f"tssplat_amd.dr.{name}: {label} must be [B, H, W] or [B, H, W, 1] of the image size, on the device of pos")
-        images.append(t.detach())
-    world_pos = _check_cuda_f32("world_pos", world_pos)
-    if world_pos.device != pos.device or tuple(world_pos.shape) not in ((V, 3), (1, V, 3)):
-        raise RuntimeError(f"tssplat_amd.dr.{name}: world_pos must be [V, 3] or [1, V, 3] with V = {V} (the vertices of pos), on the device of pos")
-    campos = _check_cuda_f32("campos", campos)
-    if campos.device != pos.device or tuple(campos.shape) != (B, 3):
-        raise RuntimeError(f"tssplat_amd.dr.{name}: campos must be [B, 3] = [{B}, 3], on the device of pos")
-    alpha_loss, depth_loss, alpha, depth = _SilhouetteDepthMseFunc.apply(pos, world_pos, tri, topo.opp, glctx, height, width, images[0], campos.detach(),
+    shape = (int(pos.shape[0]), height, width)
+    images = [_scalar_image(name, label, t, pos, shape) for label, t in (("target_alpha", target_alpha), ("target_depth", target_depth), ("depth_mask", depth_mask))]
+    world_pos = _vertex_attribute(name, "world_pos", world_pos, pos)
+    campos = _camera_positions(name, campos, pos)
+    alpha_loss, depth_loss, alpha, depth = _SilhouetteDepthMseFunc.apply(pos, world_pos, tri, topo.opp, glctx, height, width, images[0], campos,
                                                                          images[1], images[2], float(pos_gradient_boost), bool(return_images))
     return (alpha_loss, depth_loss, alpha.detach(), depth.detach()) if return_images else (alpha_loss, depth_loss)
+
+
+class _SilhouetteNormalMseFunc(torch.autograd.Function):
+    """One node for the image terms of the geometry stage with the normal term among them: one rasterisation forward;
+    ``tsamd_silhouette_mse_backward``, then ``tsamd_depth_mse_backward(accumulate_pos=1)`` when the depth term is there (``world`` is not
+    ``None``), then ``tsamd_normal_mse_backward(accumulate_pos=1)`` backward -- each lands on what the one before wrote."""
+
+    @staticmethod
+    def forward(ctx, pos, normals, world, tri, opp, glctx, height, width, target_alpha, target_normal, normal_mask, campos, target_depth, depth_mask, boost,
+                want_images):
+        dev = pos.device
+        B, V, T = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
+        has_depth = world is not None
+        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
+        n = alpha.numel()
+
+        def image(channels, wanted):
+            if not wanted:
+                return torch.empty((0,), dtype=torch.float32, device=dev)
+            make = torch.empty if n * T > 0 else torch.zeros         # (the calls write no image without triangles)
+            return make((B, height, width, channels), dtype=torch.float32, device=dev)
+        alpha_loss, depth_loss, normal_loss = (torch.empty((), dtype=torch.float32, device=dev) for _ in range(3))
+        depth, normal = image(1, want_images and has_depth), image(3, want_images)
+        ws = torch.empty((max(int(_lib.tsamd_silhouette_mse_workspace_bytes(n)), int(_lib.tsamd_depth_mse_workspace_bytes(n)),
+                              int(_lib.tsamd_normal_mse_workspace_bytes(n))),), dtype=torch.uint8, device=dev)
+        with _device_ctx(dev):
+            stream = _stream_ptr(dev)
+            _capi.check(_lib.tsamd_silhouette_mse(alpha.data_ptr(), target_alpha.data_ptr(), n, ws.data_ptr(), alpha_loss.data_ptr(), stream))
+            if has_depth:
+                _capi.check(_lib.tsamd_depth_mse(_ptr(pos), B, V, _ptr(tri), T, height, width, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
+                                                 _ptr(depth_mask), ws.data_ptr(), depth_loss.data_ptr(), _ptr(depth), stream))
+            _capi.check(_lib.tsamd_normal_mse(_ptr(pos), B, V, _ptr(tri), T, height, width, _ptr(ids), _ptr(normals), _ptr(target_normal), _ptr(normal_mask),
+                                              ws.data_ptr(), normal_loss.data_ptr(), _ptr(normal), stream))
+        saved = [pos, normals, tri, opp, ids, masks, alpha, target_alpha, target_normal, normal_mask]
+        ctx.save_for_backward(*saved, *((world, campos, target_depth, depth_mask) if has_depth else ()))
+        ctx.boost, ctx.has_depth = float(boost), has_depth
+        ctx.mark_non_differentiable(alpha, depth, normal)
+        if has_depth:
+            return alpha_loss, depth_loss, normal_loss, alpha, depth, normal
+        return alpha_loss, normal_loss, alpha, normal
+
+    @staticmethod
+    def backward(ctx, *grads):
+        pos, normals, tri, opp, ids, masks, alpha, target_alpha, target_normal, normal_mask = ctx.saved_tensors[:10]
+        B, V, T, H, W = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0]), int(ids.shape[1]), int(ids.shape[2])
+        n_losses = 3 if ctx.has_depth else 2
+        g = torch.stack([k.reshape(()) for k in grads[:n_losses]]).to(torch.float32)      # stays on the device: the kernels read it there
+        grad_pos = torch.empty_like(pos)
+        grad_normals = torch.empty_like(normals)
+        grad_world = None
+        with _device_ctx(pos.device):
+            stream = _stream_ptr(pos.device)
+            _capi.check(_lib.tsamd_silhouette_mse_backward(pos.data_ptr(), B, V, tri.data_ptr(), T, opp.data_ptr(), H, W, ids.data_ptr(), masks.data_ptr(),
+                                                           alpha.data_ptr(), target_alpha.data_ptr(), g.data_ptr(), ctx.boost, grad_pos.data_ptr(), stream))
+            if ctx.has_depth:
+                world, campos, target_depth, depth_mask = ctx.saved_tensors[10:]
+                grad_world = torch.empty_like(world)
+                _capi.check(_lib.tsamd_depth_mse_backward(_ptr(pos), B, V, _ptr(tri), T, H, W, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
+                                                          _ptr(depth_mask), g.data_ptr() + 4, 1, _ptr(grad_world), _ptr(grad_pos), stream))
+            _capi.check(_lib.tsamd_normal_mse_backward(_ptr(pos), B, V, _ptr(tri), T, H, W, _ptr(ids), _ptr(normals), _ptr(target_normal), _ptr(normal_mask),
+                                                       g.data_ptr() + 4 * (n_losses - 1), 1, _ptr(grad_normals), _ptr(grad_pos), stream))
+        return (grad_pos, grad_normals, grad_world) + (None,) * 13
+
+
+def silhouette_normal_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor, resolution, target_alpha: torch.Tensor, normals: torch.Tensor,
+                          target_normal: torch.Tensor, normal_mask: torch.Tensor, *, depth=None, topology_hash=None, pos_gradient_boost: float = 1.0,
+                          return_images: bool = False):
+    """``(alpha_loss, normal_loss)``, or ``(alpha_loss, depth_loss, normal_loss)`` with ``depth=(world_pos, campos, target_depth,
+    depth_mask)`` -- 0-dim tensors (bitwise repeatable) from ONE rasterisation and one autograd node.  ``alpha_loss`` is
+    :func:`silhouette_mse`'s, ``depth_loss`` :func:`silhouette_depth_mse`'s (the shapes and checks of its arguments too);
+    ``normal_loss = mean((n * normal_mask[..., None] - target_normal * normal_mask[..., None]) ** 2)`` over ``B H W 3`` values with
+    ``n = interpolate(normals, rast, tri)`` of ``rasterize(glctx, pos, tri, resolution)`` -- 0 on background -- without ``rast``, the
+    interpolated image or a gradient image.  ``normals`` is ``[V, 3]`` or ``[1, V, 3]`` (any 3-channel vertex attribute),
+    ``target_normal`` ``[B, H, W, 3]``, ``normal_mask`` ``[B, H, W]`` or ``[B, H, W, 1]``, float32.  Gradients flow to ``pos`` (the
+    silhouette blends, and ``(u, v)`` as through ``rasterize``), ``normals`` and ``world_pos``, nowhere else.  Without triangles
+    ``normal_loss`` is 0.  ``return_images=True``: the detached images are appended in the same order -- ``alpha [B, H, W, 1]``,
+    ``d [B, H, W, 1]`` with ``depth``, ``n [B, H, W, 3]``."""
+    name = "silhouette_normal_mse"
+    pos, tri, height, width, topo = _silhouette_args(name, pos, tri, resolution, topology_hash)
+    shape = (int(pos.shape[0]), height, width)
+    target_alpha = _scalar_image(name, "target_alpha", target_alpha, pos, shape)
+    normal_mask = _scalar_image(name, "normal_mask", normal_mask, pos, shape)
+    target_normal = _check_cuda_f32("target_normal", target_normal)
+    if target_normal.device != pos.device or tuple(target_normal.shape) != shape + (3,):
+        raise RuntimeError(f"tssplat_amd.dr.{name}: target_normal must be [B, H, W, 3] of the image size, on the device of pos")
+    normals = _vertex_attribute(name, "normals", normals, pos)
+    world_pos = campos = target_depth = depth_mask = None
+    if depth is not None:
+        if not isinstance(depth, (tuple, list)) or len(depth) != 4:
+            raise RuntimeError(f"tssplat_amd.dr.{name}: depth must be None or (world_pos, campos, target_depth, depth_mask)")
+        world_pos = _vertex_attribute(name, "world_pos", depth[0], pos)
+        campos = _camera_positions(name, depth[1], pos)
+        target_depth = _scalar_image(name, "target_depth", depth[2], pos, shape)
+        depth_mask = _scalar_image(name, "depth_mask", depth[3], pos, shape)
+    out = _SilhouetteNormalMseFunc.apply(pos, normals, world_pos, tri, topo.opp, glctx, height, width, target_alpha, target_normal.detach(), normal_mask, campos,
+                                         target_depth, depth_mask, float(pos_gradient_boost), bool(return_images))
+    n_losses = 2 if depth is None else 3
+    return out[:n_losses] + tuple(image.detach() for image in out[n_losses:]) if return_images else out[:n_losses]
 
 
 # ---- the colour stage under a blend plan ----

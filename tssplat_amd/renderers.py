@@ -189,6 +189,33 @@ class MeshRasterizer(torch.nn.Module):
                                                                   pos_gradient_boost=1.0, return_images=True)
         return {"img_loss": img_loss, "depth_loss": depth_loss, "geo_regularization": data.smooth_barrier_energy, "shaded": shaded, "d": d}
 
+    def silhouette_normal_loss(self, mvp: torch.Tensor, target_alpha: torch.Tensor, target_normal: torch.Tensor, iter_num: int, resolution: int,
+                               permute_surface_scheduler=None, normal_mask: Optional[torch.Tensor] = None, campos: Optional[torch.Tensor] = None,
+                               target_depth: Optional[torch.Tensor] = None, depth_mask: Optional[torch.Tensor] = None):
+        """The geometry stage's render and its image losses with the normal term, in one:
+        ``{"img_loss", "normal_loss", "geo_regularization", "shaded", "n"}`` with ``img_loss`` as :meth:`silhouette_loss` gives it and
+        ``normal_loss`` the plain mean squared error of ``forward(..., only_alpha=True, fit_normal=True)["n"] * normal_mask[..., None]``
+        against ``target_normal * normal_mask[..., None]`` (``target_normal`` ``[B, H, W, 3]``) through ``dr.silhouette_normal_mse`` -- one
+        rasterisation, no ``rast`` image, no interpolated image, no gradient image.  The vertex attribute is ``forward``'s
+        (mesh_rasterizer.py:138-148): ``data._compute_vertex_normal() * [1, 1, -1]``, so autograd carries its gradient through the
+        vertex-normal operator into ``tet_v``.  With ``campos`` and ``target_depth`` the depth term of :meth:`silhouette_depth_loss`
+        comes from the same rasterisation: ``"depth_loss"`` and ``"d"`` are added.  Both masks default to ``target_alpha``; the caller
+        applies the trainer's weights; ``shaded``, ``n`` and ``d`` are detached."""
+        if (campos is None) != (target_depth is None):
+            raise RuntimeError("MeshRasterizer.silhouette_normal_loss: the depth term needs both campos and target_depth")
+        data = self._geometry_forward(iter_num, permute_surface_scheduler)
+        pos_clip = self.transform_pos(mvp, data.v_pos).contiguous()
+        scale = torch.tensor([1, 1, -1], dtype=torch.float32, device=self.device)[None, :]
+        v_s = (data._compute_vertex_normal() * scale).contiguous()
+        depth = None
+        if campos is not None:
+            depth = (data.v_pos, campos.to(self.device), target_depth, target_alpha if depth_mask is None else depth_mask)
+        got = dr.silhouette_normal_mse(self.glctx, pos_clip, data.t_pos_idx, [resolution, resolution], target_alpha, v_s, target_normal,
+                                       target_alpha if normal_mask is None else normal_mask, depth=depth, topology_hash=self.tri_hash,
+                                       pos_gradient_boost=1.0, return_images=True)
+        names = ("img_loss", "normal_loss", "shaded", "n") if depth is None else ("img_loss", "depth_loss", "normal_loss", "shaded", "d", "n")
+        return {**dict(zip(names, got)), "geo_regularization": data.smooth_barrier_energy}
+
     def shade_loss(self, view_plan: ViewPlan, background: torch.Tensor, target: torch.Tensor, iter_num: int, permute_surface_scheduler=None):
         """The colour stage's render and image loss in one, under a view plan: ``{"img_loss", "geo_regularization", "shaded"}`` with
         ``img_loss`` the plain ``L1Loss`` of ``forward(..., view_plan=view_plan)["shaded"][..., :3]`` against ``target[..., :3]``
