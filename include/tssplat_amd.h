@@ -798,6 +798,38 @@ int tsamd_surface_count(const float *field_dev, int32_t grid, float level, uint8
 int tsamd_surface_emit(const float *field_dev, int32_t grid, double lo, double hi, float level, const uint8_t *vmask_dev, const int32_t *voffset_dev,
                        const int32_t *toffset_dev, int64_t n_vertices, int64_t n_triangles, float *v_out_dev, int32_t *faces_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Flood fill of the field above: connected components of its nodes, the fill of enclosed cavities and the removal of islands.
+ * Semantics are fixed by tests/fill_oracle.py; everything is integer work and bitwise repeatable.  Stateless, caller-owned
+ * buffers, nothing synchronises the host.
+ *
+ * Connectivity is the extraction's own: two nodes are adjacent iff they differ by +-[di, dj, dk] with [di, dj, dk] in {0, 1}^3 and
+ * not all zero -- the seven owned Kuhn edges of a node and their reverses, 14 neighbours ([1, -1, 0] and its kin are not edges).
+ * A node is inside iff field > level (a NaN is outside; level must not be NaN).  A component is a maximal set of nodes with
+ * equal inside bit connected through these edges: inside and outside nodes are labelled in one pass.
+ *
+ * tsamd_grid_components: label_out_dev [G, G, G] i32 = the smallest flat index in the node's component, so label <= index and
+ * label[label[n]] == label[n], whatever the execution order.  status_out_dev: one i32, zero-filled by the call itself; non-zero
+ * afterwards means that a bounded device loop ran out of its bound (1: a find walk, 2: a union) and the labels are not to be
+ * used -- every find walk and every union retry is bounded by a multiple of G^3 that a correct run cannot reach, so a logic
+ * error reports here instead of hanging the device.
+ *
+ * tsamd_field_fill: the exterior is every outside component holding a node of the grid's border.  mode TSAMD_FILL_CAVITIES:
+ * solid = every node that is not exterior (enclosed outside components become inside, islands floating in them included).
+ * mode TSAMD_FILL_OUTER: of that solid, only the component with the most nodes stays (ties: the smaller label).
+ * field_out_dev [G, G, G] f32, which must not be field_dev (the input is never modified): a node whose inside bit is
+ * unchanged keeps its value bit for bit, an outside node that became inside reads +inf, an inside node that became outside reads
+ * -inf.  A changed node has no neighbour of opposite final sign, so these values are never interpolated and the extraction of
+ * the new field is a sub-mesh of the extraction of the old one.  workspace_dev: [2 G^3 + 2] i32, 8-byte aligned, contents
+ * undefined before and after.  stats_out_dev: five i32, zero-filled by the call itself: the status word as above, cavities
+ * (outside components not touching the border), cavity_nodes, islands (solid components dropped) and island_nodes (the last
+ * two are 0 in mode TSAMD_FILL_CAVITIES). */
+#define TSAMD_FILL_CAVITIES 1
+#define TSAMD_FILL_OUTER 2
+int tsamd_grid_components(const float *field_dev, int32_t grid, float level, int32_t *label_out_dev, int32_t *status_out_dev, void *stream);
+int tsamd_field_fill(const float *field_dev, int32_t grid, float level, int32_t mode, void *workspace_dev, float *field_out_dev, int32_t *stats_out_dev,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

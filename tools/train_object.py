@@ -16,7 +16,7 @@ absent):
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
                                  [--fit-normal off|operators|fused-loss --fit-normal-start N --normal-weight W] [--normal-bench PATH]
-                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR]
+                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
 so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
@@ -45,6 +45,8 @@ seed, plus the normal stage timings (median of five windows of 200 calls, HIP ev
 --merge-grid N: after the fit, `tssplat_amd.merge` (`union_field`, `extract_surface`: what `merge_tets` runs) turns all spheres into ONE closed surface at N nodes per axis
 (`merged_surface.obj` under --merge-out) and the record gains `merged`: `closed`, the counts and `volume_iou_vs_hull`, the merged
 solid's occupancy against `spheres_init.visual_hull` of the target silhouettes at the same grid and bounds.
+--merge-fill none|cavities|outer: `merge.fill_field` between the field and the extraction; `merged` then also holds `cavities`,
+`cavity_nodes`, `islands`, `island_nodes`, the Euler characteristic V - F / 2 and the triangle count before (`unfilled`) and after.
 
 One JSON line: silhouette IoU over all views, inverted tets, seconds per iteration and the stand-alone stage times."""
 import argparse
@@ -155,8 +157,24 @@ def build_spheres(centres, radii, k):
     return np.concatenate(rest), np.concatenate(tets).astype(np.int32)
 
 
+def surface_topology(field, level, n_vertices, n_triangles):
+    """What the extraction of a closed `field` consists of, from `merge.components`: the inside and outside components of its nodes,
+    the closed surfaces between them (inside + outside - 1: their adjacency is a tree), the Euler characteristic V - F / 2 and the
+    handles it leaves, surfaces - chi / 2 (a closed surface of genus g has chi = 2 - 2 g)."""
+    import torch
+    from tssplat_amd import merge
+    label = merge.components(field, level).reshape(-1)
+    root = label == torch.arange(label.numel(), dtype=torch.int32, device=label.device)
+    inside = merge.occupancy(field, level).reshape(-1)
+    n_in, n_out = (int(x) for x in torch.stack([(root & inside).sum(), (root & ~inside).sum()]).cpu().numpy())
+    chi = int(n_vertices) - int(n_triangles) // 2
+    surfaces = n_in + n_out - 1
+    return {"inside_components": n_in, "outside_components": n_out, "surfaces": surfaces, "euler_characteristic": chi, "handles": surfaces - chi // 2}
+
+
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
-        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None):
+        fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None,
+        merge_fill="none"):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -281,6 +299,15 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         level = merge.default_level(merge_grid, bounds)
         field = merge.union_field(tet_v, geo.tet_elem, merge_grid, bounds)
         mv, mf, closed = merge.extract_surface(field, bounds, level)
+        fill_rec = {"fill": merge_fill}
+        if merge_fill != "none":   # the flood fill: what it removed, in components, nodes, triangles and Euler characteristic (V - F / 2 on a closed mesh)
+            filled = merge.fill_field(field, level, merge_fill)
+            before = {"vertices": int(mv.shape[0]), "triangles": int(mf.shape[0]), **surface_topology(field, level, mv.shape[0], mf.shape[0])}
+            field = filled.field
+            mv, mf, closed = merge.extract_surface(field, bounds, level)
+            fill_rec.update(cavities=filled.cavities, cavity_nodes=filled.cavity_nodes, islands=filled.islands, island_nodes=filled.island_nodes,
+                            unfilled=before, triangles_before=before["triangles"], triangles_after=int(mf.shape[0]))
+        fill_rec.update(surface_topology(field, level, mv.shape[0], mf.shape[0]))
         occ = merge.occupancy(field, level)
         merge_out = merge_out or os.path.join(ROOT, "bench_outputs", "train_object")
         os.makedirs(merge_out, exist_ok=True)
@@ -288,7 +315,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         hull = spheres_init.visual_hull(target, mvp, grid=merge_grid, bounds=bounds)
         rec["merged"] = {"file": "merged_surface.obj", "grid": merge_grid, "bounds": list(bounds), "level": level,
                          "vertices": int(mv.shape[0]), "triangles": int(mf.shape[0]), "closed": closed,
-                         "inside_fraction": int(occ.sum()) / float(merge_grid ** 3), "volume_iou_vs_hull": merge.volume_iou(occ, hull)}
+                         "inside_fraction": int(occ.sum()) / float(merge_grid ** 3), "volume_iou_vs_hull": merge.volume_iou(occ, hull), **fill_rec}
     if stages:      # the stages on their own (HIP events; they overlap nothing, so their sum is close to one iteration)
         def timed(fn, reps=20):
             for j in range(3):
@@ -525,6 +552,8 @@ def main():
     ap.add_argument("--grid", type=int, default=72, help="voxels per axis of the placement grid")
     ap.add_argument("--merge-grid", type=int, default=0, metavar="N", help="merge the fitted spheres into one closed surface at N nodes per axis (0: off)")
     ap.add_argument("--merge-out", default=None, metavar="DIR", help="where merged_surface.obj goes (bench_outputs/train_object)")
+    ap.add_argument("--merge-fill", choices=["none", "cavities", "outer"], default="none",
+                    help="flood fill before the extraction: fill enclosed cavities, or also keep only the largest solid component")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
     ap.add_argument("--fit-normal", choices=["off", "operators", "fused-loss"], default="off")
     ap.add_argument("--fit-normal-start", type=int, default=0, help="the normal term enters once the iteration has passed this one")
@@ -548,7 +577,7 @@ def main():
     print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
                          stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
                          fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
-                         merge_grid=args.merge_grid, merge_out=args.merge_out)))
+                         merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill)))
 
 
 if __name__ == "__main__":

@@ -23,7 +23,7 @@ ARCH = "gfx950"
 SOURCES = ["plan.cpp", "plan_mesh.cpp", "plan_tiling.cpp", "plan_layout.cpp", "plan_planes.cpp", "partition.cpp", "conflict_opt.cpp", "regular_batch.cpp", "capi.cpp", "tile_kernel.hip", "step_kernels.hip", "eval_launch.cpp", "surface.cpp", "surface_capi.cpp", "surface_kernels.hip",
            "raster_capi.cpp", "raster_kernels.hip", "aa_kernels.hip", "grid_capi.cpp", "grid_kernels.hip",
            "mlp_capi.cpp", "mlp_kernels.hip", "texture_capi.cpp", "texture_kernels.hip", "shade_capi.cpp", "shade_kernels.hip",
-           "init_capi.cpp", "init_kernels.hip", "merge_capi.cpp", "merge_kernels.hip"]
+           "init_capi.cpp", "init_kernels.hip", "merge_capi.cpp", "merge_kernels.hip", "fill_kernels.hip"]
 HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "launch_args.h", "regular_batch.h", "surface.h", "raster.h", "grid.h", "mlp.h", "texture.h", "shade.h", "init.h", "merge.h", "det_mean.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
 
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-pthread"]

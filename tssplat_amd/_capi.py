@@ -234,6 +234,9 @@ SIGNATURES = {
     "tsamd_surface_count": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsamd_surface_emit": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the merge's flood fill: connected components of the field's nodes, cavities filled, islands dropped
+    "tsamd_grid_components": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_field_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

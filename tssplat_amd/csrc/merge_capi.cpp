@@ -1,4 +1,5 @@
-// C ABI of the tet-sphere merge (include/tssplat_amd.h, tsamd_union_field / tsamd_surface_count / tsamd_surface_emit): stateless
+// C ABI of the tet-sphere merge (include/tssplat_amd.h, tsamd_union_field / tsamd_surface_count / tsamd_surface_emit and the flood
+// fill's tsamd_grid_components / tsamd_field_fill): stateless
 // entry points over caller-owned buffers.  Every argument is checked before the first device call.
 #include <cmath>
 
@@ -69,6 +70,33 @@ int tsamd_surface_emit(const float *field_dev, int32_t grid, double lo, double h
     if (n_vertices == 0 && n_triangles == 0) return TSAMD_OK;             // nothing to write
     TSAMD_HIP(tsamd::launch_surface_emit(field_dev, grid, lo, (hi - lo) / grid, level, vmask_dev, voffset_dev, toffset_dev, n_vertices, n_triangles, v_out_dev,
                                          faces_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_grid_components(const float *field_dev, int32_t grid, float level, int32_t *label_out_dev, int32_t *status_out_dev, void *stream)
+{
+    int rc = check_grid(grid);
+    if (rc) return rc;
+    if (std::isnan(level)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "level is NaN");
+    if ((rc = check_not_null({{field_dev, "field_dev"}, {label_out_dev, "label_out_dev"}, {status_out_dev, "status_out_dev"}}))) return rc;
+    TSAMD_HIP(tsamd::launch_grid_components(field_dev, grid, level, label_out_dev, status_out_dev, static_cast<hipStream_t>(stream)));
+    return TSAMD_OK;
+}
+
+int tsamd_field_fill(const float *field_dev, int32_t grid, float level, int32_t mode, void *workspace_dev, float *field_out_dev, int32_t *stats_out_dev,
+                     void *stream)
+{
+    int rc = check_grid(grid);
+    if (rc) return rc;
+    if (std::isnan(level)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "level is NaN");
+    if (mode != tsamd::kFillCavities && mode != tsamd::kFillOuter)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "mode must be TSAMD_FILL_CAVITIES (1) or TSAMD_FILL_OUTER (2)");
+    if ((rc = check_not_null({{field_dev, "field_dev"}, {workspace_dev, "workspace_dev"}, {field_out_dev, "field_out_dev"}, {stats_out_dev, "stats_out_dev"}})))
+        return rc;
+    if (field_out_dev == field_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "field_out_dev must not be field_dev (the input is never modified)");
+    if (reinterpret_cast<uintptr_t>(workspace_dev) % 8 != 0) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "workspace_dev must be 8-byte aligned");
+    TSAMD_HIP(tsamd::launch_field_fill(field_dev, grid, level, mode, static_cast<int32_t *>(workspace_dev), field_out_dev, stats_out_dev,
+                                       static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
 }
 

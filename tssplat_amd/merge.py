@@ -6,10 +6,17 @@ kernels behind ``tsamd_union_field``, ``tsamd_surface_count`` and ``tsamd_surfac
 separately rounded float64 operations and integer maxima so that it is bitwise repeatable; tests/union_oracle.py is the same
 statement in numpy.  There is no CPU fallback.
 
+Flood fill (``tsamd_grid_components``, ``tsamd_field_fill``; tests/fill_oracle.py): the extraction gives one closed surface per
+boundary between an inside and an outside component of the grid's nodes, under the connectivity of the extraction itself (a node
+and node +- (di, dj, dk), (di, dj, dk) in {0, 1}^3 without 0: 14 neighbours).  :func:`components` labels both kinds of component
+with their smallest flat index; :func:`fill_field` makes enclosed outside components inside (``"cavities"``) and then keeps only
+the largest solid component (``"outer"``); ``merge_tets(fill=...)`` extracts the filled field, whose surface is a sub-mesh of the
+unfilled one: the same vertex bits in the same order, without the removed components.
+
 Grid: the one of :mod:`tssplat_amd.spheres_init` -- ``G = grid`` nodes per axis (2 .. 512) over the cube ``[lo, hi]^3``,
 ``h = (hi - lo) / G``, node ``(i, j, k)`` at ``lo + (index + 0.5) h`` per axis (float64), flat index ``(i G + j) G + k``.
 
-Out of scope: filling enclosed cavities or keeping only the outer component, simplifying, smoothing, re-tetrahedralising.
+Out of scope: simplifying, smoothing, re-tetrahedralising.
 """
 from __future__ import annotations
 
@@ -21,18 +28,20 @@ import torch
 
 from . import _capi
 
-__all__ = ["MergedSurface", "union_field", "extract_surface", "merge_tets", "occupancy", "volume_iou", "default_bounds", "default_level",
-           "write_obj", "MIN_GRID", "MAX_GRID"]
+__all__ = ["MergedSurface", "FilledField", "union_field", "extract_surface", "merge_tets", "components", "fill_field", "occupancy", "volume_iou",
+           "default_bounds", "default_level", "write_obj", "MIN_GRID", "MAX_GRID", "FILL_MODES"]
 
 MIN_GRID = 2
 MAX_GRID = 512           # flat node indices < 2^27; 7 vertices and 12 triangles per node stay below 2^31
 _MAX_TETS = 1 << 30      # include/tssplat_amd.h: tsamd_union_field
+FILL_MODES = {"cavities": 1, "outer": 2}      # include/tssplat_amd.h: TSAMD_FILL_CAVITIES, TSAMD_FILL_OUTER
 
 
 @dataclasses.dataclass
 class MergedSurface:
     """One indexed triangle mesh around the union of all tets.  ``closed``: no grid-border node is inside, so every edge lies in
-    exactly two triangles of opposite direction.  ``inside_fraction``: inside nodes over all nodes."""
+    exactly two triangles of opposite direction.  ``inside_fraction``: inside nodes over all nodes, of the field that was extracted.
+    ``fill``: ``"none"``, ``"cavities"`` or ``"outer"``, and what it changed (:class:`FilledField`)."""
     v: torch.Tensor                # float32 [Nv, 3]
     faces: torch.Tensor            # int32 [Nt, 3], normals point from inside to outside
     closed: bool
@@ -40,6 +49,22 @@ class MergedSurface:
     grid: int
     bounds: tuple
     level: float
+    fill: str = "none"
+    cavities: int = 0
+    cavity_nodes: int = 0
+    islands: int = 0
+    island_nodes: int = 0
+
+
+@dataclasses.dataclass
+class FilledField:
+    """``field``: float32 ``[G, G, G]``, a new tensor.  ``cavities``: outside components not touching the grid's border, with
+    ``cavity_nodes`` nodes, all of which became inside; ``islands``: solid components dropped by ``"outer"``, with ``island_nodes``."""
+    field: torch.Tensor
+    cavities: int
+    cavity_nodes: int
+    islands: int
+    island_nodes: int
 
 
 def _fail(name: str, what: str):
@@ -100,6 +125,19 @@ def _check_field(name: str, field) -> torch.Tensor:
     if field.dim() != 3 or not (field.shape[0] == field.shape[1] == field.shape[2]) or not MIN_GRID <= field.shape[0] <= MAX_GRID:
         _fail(name, f"field must be [G, G, G] with G in {MIN_GRID} .. {MAX_GRID}, got {tuple(field.shape)}")
     return field
+
+
+def _check_fill(name: str, mode, allow_none: bool) -> str:
+    allowed = (("none",) if allow_none else ()) + tuple(FILL_MODES)
+    if not isinstance(mode, str) or mode not in allowed:
+        _fail(name, f"{'fill' if allow_none else 'mode'} must be one of {', '.join(repr(m) for m in allowed)}, got {mode!r}")
+    return mode
+
+
+def _check_status(name: str, status: int) -> None:
+    if status:
+        _fail(name, f"the labelling's {'find walk' if status == 1 else 'union'} ran out of its bound (status {status}): a logic error in "
+                    "csrc/fill_kernels.hip, not a property of the field")
 
 
 def _lib_and_stream(device):
@@ -213,6 +251,52 @@ def occupancy(field: torch.Tensor, level: float) -> torch.Tensor:
     return field > _check_level("occupancy", level)
 
 
+def components(field: torch.Tensor, level: float) -> torch.Tensor:
+    """int32 ``[G, G, G]``: per node the smallest flat index ``(i G + j) G + k`` in its component -- a maximal set of nodes with
+    equal inside bit (``field > level``; a NaN is outside) connected through the extraction's edges, node +- (di, dj, dk) with
+    (di, dj, dk) in {0, 1}^3 without 0.  Inside and outside nodes are labelled in one pass; ``label <= index`` and
+    ``label[label] == label``.  One readback: the status word of the bounded device loops."""
+    name = "components"
+    field = _check_field(name, field)
+    level = _check_level(name, level)
+    G = int(field.shape[0])
+    lib, ctx, stream = _lib_and_stream(field.device)
+    label = torch.empty((G, G, G), dtype=torch.int32, device=field.device)
+    status = torch.empty(1, dtype=torch.int32, device=field.device)
+    with ctx:
+        _capi.check(lib.tsamd_grid_components(field.data_ptr(), G, level, label.data_ptr(), status.data_ptr(), stream))
+    _check_status(name, int(status.cpu()[0]))
+    return label
+
+
+def _fill(name, field, level, mode) -> FilledField:
+    """The fill, enqueued, and its one readback: the status word and the four counts together."""
+    G = int(field.shape[0])
+    dev = field.device
+    lib, ctx, stream = _lib_and_stream(dev)
+    out = torch.empty_like(field)
+    workspace = torch.empty(2 * G ** 3 + 2, dtype=torch.int32, device=dev)
+    stats = torch.empty(5, dtype=torch.int32, device=dev)
+    with ctx:
+        _capi.check(lib.tsamd_field_fill(field.data_ptr(), G, level, FILL_MODES[mode], workspace.data_ptr(), out.data_ptr(), stats.data_ptr(), stream))
+    status, cavities, cavity_nodes, islands, island_nodes = (int(x) for x in stats.cpu().numpy())
+    _check_status(name, status)
+    return FilledField(out, cavities, cavity_nodes, islands, island_nodes)
+
+
+def fill_field(field: torch.Tensor, level: float, mode: str) -> FilledField:
+    """The exterior is every outside component that holds a node of the grid's border.  ``mode="cavities"``: every node that is not
+    exterior is solid -- enclosed outside components become inside, and an island floating in one merges into the solid.
+    ``mode="outer"``: of that solid only the component with the most nodes stays (ties: the smaller label).  In the new field a
+    node whose inside bit is unchanged keeps its value bit for bit, an outside node that became inside reads ``+inf`` and an inside
+    node that became outside ``-inf``; neither is ever interpolated, because a changed node has no neighbour of opposite final
+    sign.  The input is not modified.  One readback."""
+    name = "fill_field"
+    field = _check_field(name, field)
+    level = _check_level(name, level)
+    return _fill(name, field, level, _check_fill(name, mode, allow_none=False))
+
+
 def volume_iou(a: torch.Tensor, b: torch.Tensor) -> float:
     """Intersection over union of two boolean grids of one shape, from two integer counts: exact.  1.0 when both are empty."""
     for arg, t in (("a", a), ("b", b)):
@@ -224,18 +308,25 @@ def volume_iou(a: torch.Tensor, b: torch.Tensor) -> float:
     return inter / union if union else 1.0
 
 
-def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=None, level=None) -> MergedSurface:
+def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=None, level=None, fill: str = "none") -> MergedSurface:
     """The union of all contributing tets as one closed, consistently oriented triangle mesh: ``union_field`` then
-    ``extract_surface``.  ``bounds=None``: :func:`default_bounds`; ``level=None``: :func:`default_level`."""
+    ``extract_surface``.  ``bounds=None``: :func:`default_bounds`; ``level=None``: :func:`default_level`.  ``fill``: ``"none"`` extracts
+    the union field as it is (one closed surface per boundary between components); ``"cavities"`` and ``"outer"`` extract
+    :func:`fill_field` of it, at the price of one more readback."""
     name = "merge_tets"
+    fill = _check_fill(name, fill, allow_none=True)
     tet_v, elem = _check_mesh(name, tet_v, elem)
     grid = _check_grid(name, grid)
     lo, hi = default_bounds(tet_v, grid) if bounds is None else _check_bounds(name, bounds)
     level = default_level(grid, (lo, hi)) if level is None else _check_level(name, level)
     field = _union_field(name, tet_v, elem, grid, lo, hi)
+    counts = ()
+    if fill != "none":
+        filled = _fill(name, field, level, fill)
+        field, counts = filled.field, (fill, filled.cavities, filled.cavity_nodes, filled.islands, filled.island_nodes)
     v, faces, closed = _extract(field, lo, hi, level)
     n_inside = int((field > level).sum())
-    return MergedSurface(v, faces, closed, n_inside / float(grid ** 3), grid, (lo, hi), level)
+    return MergedSurface(v, faces, closed, n_inside / float(grid ** 3), grid, (lo, hi), level, *counts)
 
 
 def write_obj(path: str, v, faces) -> None:
