@@ -52,10 +52,12 @@ hipError_t launch_silhouette_backward(const float *pos_clip, const int32_t *tri,
 // loss = mean((alpha - target)^2) over n floats, bitwise repeatable; n = 0 stores 0
 int64_t silhouette_mse_workspace_bytes(int64_t n);
 hipError_t launch_silhouette_mse(const float *alpha, const float *target, int64_t n, void *workspace, float *loss, hipStream_t stream);
-// The depth term (raster_kernels.hip): loss = mean over batch * height * width of (d m - t m)^2 with d = || interpolate(world_pos) -
-// campos[view] || from the alpha stage's ids (|| campos || on background), bitwise repeatable; depth_out (optional): d per pixel.
-// No pixel or no triangle: loss 0, nothing else written.  backward: grad_world [n_vertices, 3] is zero-filled by the launch,
-// grad_pos [batch, n_vertices, 4] too unless accumulate_pos != 0 (then it is added to).
+// The id-driven image terms (raster_kernels.hip): loss = mean over batch * height * width pixels and the term's channels of
+// (x_c m - t_c m)^2, x a value of y = interpolate(attr) for attr [n_vertices, 3] from the alpha stage's ids (y = 0 on background), target
+// [batch, height, width, channels], mask [batch, height, width]; bitwise repeatable; the output image (optional): x per pixel.  No pixel
+// or no triangle: loss 0, nothing else written.  backward: the attribute's gradient [n_vertices, 3] is zero-filled by the launch, grad_pos
+// [batch, n_vertices, 4] too unless accumulate_pos != 0 (then it is added to).  n of the workspace sizes is the pixel count.
+// The depth term, one channel: x = d = || y - campos[view] || with attr = world_pos (|| campos || on background).
 int64_t depth_mse_workspace_bytes(int64_t n);
 hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
                             const float *world_pos, const float *campos, const float *target, const float *mask, void *workspace, float *loss, float *depth_out,
@@ -63,11 +65,7 @@ hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vert
 hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
                                      const int32_t *ids, const float *world_pos, const float *campos, const float *target, const float *mask, const float *grad_loss,
                                      int accumulate_pos, float *grad_world, float *grad_pos, hipStream_t stream);
-// The normal term (raster_kernels.hip): loss = mean over batch * height * width * 3 of (n_c m - t_c m)^2 with n = interpolate(attr)
-// for attr [n_vertices, 3] from the alpha stage's ids (0 on background), target [batch, height, width, 3], mask [batch, height, width];
-// bitwise repeatable; normal_out (optional): n per pixel.  No pixel or no triangle: loss 0, nothing else written.  backward: grad_attr
-// [n_vertices, 3] is zero-filled by the launch, grad_pos [batch, n_vertices, 4] too unless accumulate_pos != 0 (then it is added to).
-// n of the workspace size is the pixel count batch * height * width.
+// The normal term, three channels: x = n = y itself.
 int64_t normal_mse_workspace_bytes(int64_t n);
 hipError_t launch_normal_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
                              const float *attr, const float *target, const float *mask, void *workspace, float *loss, float *normal_out, hipStream_t stream);

@@ -254,15 +254,29 @@ int tsamd_silhouette_mse_backward(const float *pos_clip_dev, int64_t batch, int6
 }
 
 namespace {
-// the arguments tsamd_depth_mse and tsamd_depth_mse_backward share
-int check_depth(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
-                const int32_t *ids_dev, const float *world_pos_dev, const float *campos_dev, const float *target_dev, const float *mask_dev)
+struct Output {
+    const void *ptr;
+    const char *name;
+    int64_t elements;
+};
+
+// The argument checks of the entry points of the id-driven terms (depth, normal), in the order all four make them: the sizes; with a
+// pixel and a triangle (else no kernel runs) the shared pointers, the term's own (`term`, which the entry points take between ids_dev
+// and target_dev), target and mask; every output whose array has elements; with a pixel and a triangle again, `last` (the workspace
+// of a forward call, the upstream gradient of a backward one).
+int check_term(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
+               const int32_t *ids_dev, std::initializer_list<tsamd::NamedPtr> term, const float *target_dev, const float *mask_dev,
+               std::initializer_list<Output> outputs, tsamd::NamedPtr last)
 {
-    const int rc = check_render(batch, n_vertices, n_triangles, height, width);
+    int rc = check_render(batch, n_vertices, n_triangles, height, width);
     if (rc) return rc;
-    if (pixel_count(batch, height, width) <= 0 || n_triangles <= 0) return TSAMD_OK;
-    return check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {ids_dev, "ids_dev"}, {world_pos_dev, "world_pos_dev"}, {campos_dev, "campos_dev"},
-                           {target_dev, "target_dev"}, {mask_dev, "mask_dev"}});
+    const bool runs = pixel_count(batch, height, width) > 0 && n_triangles > 0;
+    if (runs && ((rc = check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {ids_dev, "ids_dev"}})) || (rc = check_not_null(term)) ||
+                 (rc = check_not_null({{target_dev, "target_dev"}, {mask_dev, "mask_dev"}}))))
+        return rc;
+    for (const Output &o : outputs)
+        if (o.elements > 0 && (rc = check_not_null({{o.ptr, o.name}}))) return rc;
+    return runs ? check_not_null({last}) : TSAMD_OK;
 }
 }  // namespace
 
@@ -272,14 +286,19 @@ int64_t tsamd_depth_mse_workspace_bytes(int64_t n)
     return tsamd::depth_mse_workspace_bytes(n);
 }
 
+int64_t tsamd_normal_mse_workspace_bytes(int64_t n)
+{
+    if (n < 0) return -1;
+    return tsamd::normal_mse_workspace_bytes(n);
+}
+
 int tsamd_depth_mse(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
                     const int32_t *ids_dev, const float *world_pos_dev, const float *campos_dev, const float *target_dev, const float *mask_dev,
                     void *workspace_dev, float *loss_out_dev, float *depth_out_dev, void *stream)
 {
-    int rc = check_depth(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, world_pos_dev, campos_dev, target_dev, mask_dev);
+    const int rc = check_term(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, {{world_pos_dev, "world_pos_dev"}, {campos_dev, "campos_dev"}},
+                              target_dev, mask_dev, {{loss_out_dev, "loss_out_dev", 1}}, {workspace_dev, "workspace_dev"});   // (the loss is stored even of nothing)
     if (rc) return rc;
-    if (!loss_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "loss_out_dev is null");
-    if (pixel_count(batch, height, width) > 0 && n_triangles > 0 && !workspace_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "workspace_dev is null");
     TSAMD_HIP(tsamd::launch_depth_mse(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, world_pos_dev, campos_dev, target_dev, mask_dev,
                                       workspace_dev, loss_out_dev, depth_out_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -289,43 +308,22 @@ int tsamd_depth_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t n
                              int32_t width, const int32_t *ids_dev, const float *world_pos_dev, const float *campos_dev, const float *target_dev,
                              const float *mask_dev, const float *grad_loss_dev, int32_t accumulate_pos, float *grad_world_dev, float *grad_pos_dev, void *stream)
 {
-    int rc = check_depth(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, world_pos_dev, campos_dev, target_dev, mask_dev);
+    const int rc = check_term(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, {{world_pos_dev, "world_pos_dev"}, {campos_dev, "campos_dev"}},
+                              target_dev, mask_dev, {{grad_world_dev, "grad_world_dev", n_vertices}, {grad_pos_dev, "grad_pos_dev", batch * n_vertices}},
+                              {grad_loss_dev, "grad_loss_dev"});
     if (rc) return rc;
-    if (n_vertices > 0 && !grad_world_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_world_dev is null");
-    if (batch * n_vertices > 0 && !grad_pos_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_pos_dev is null");
-    if (pixel_count(batch, height, width) > 0 && n_triangles > 0 && !grad_loss_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_loss_dev is null");
     TSAMD_HIP(tsamd::launch_depth_mse_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, world_pos_dev, campos_dev, target_dev,
                                                mask_dev, grad_loss_dev, accumulate_pos, grad_world_dev, grad_pos_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
-}
-
-namespace {
-// the arguments tsamd_normal_mse and tsamd_normal_mse_backward share
-int check_normal(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
-                 const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev)
-{
-    const int rc = check_render(batch, n_vertices, n_triangles, height, width);
-    if (rc) return rc;
-    if (pixel_count(batch, height, width) <= 0 || n_triangles <= 0) return TSAMD_OK;
-    return check_not_null({{pos_clip_dev, "pos_clip_dev"}, {tri_dev, "tri_dev"}, {ids_dev, "ids_dev"}, {attr_dev, "attr_dev"}, {target_dev, "target_dev"},
-                           {mask_dev, "mask_dev"}});
-}
-}  // namespace
-
-int64_t tsamd_normal_mse_workspace_bytes(int64_t n)
-{
-    if (n < 0) return -1;
-    return tsamd::normal_mse_workspace_bytes(n);
 }
 
 int tsamd_normal_mse(const float *pos_clip_dev, int64_t batch, int64_t n_vertices, const int32_t *tri_dev, int64_t n_triangles, int32_t height, int32_t width,
                      const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev, void *workspace_dev, float *loss_out_dev,
                      float *normal_out_dev, void *stream)
 {
-    int rc = check_normal(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev);
+    const int rc = check_term(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, {{attr_dev, "attr_dev"}}, target_dev, mask_dev,
+                              {{loss_out_dev, "loss_out_dev", 1}}, {workspace_dev, "workspace_dev"});
     if (rc) return rc;
-    if (!loss_out_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "loss_out_dev is null");
-    if (pixel_count(batch, height, width) > 0 && n_triangles > 0 && !workspace_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "workspace_dev is null");
     TSAMD_HIP(tsamd::launch_normal_mse(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev, workspace_dev,
                                        loss_out_dev, normal_out_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;
@@ -335,11 +333,9 @@ int tsamd_normal_mse_backward(const float *pos_clip_dev, int64_t batch, int64_t 
                               int32_t width, const int32_t *ids_dev, const float *attr_dev, const float *target_dev, const float *mask_dev,
                               const float *grad_loss_dev, int32_t accumulate_pos, float *grad_attr_dev, float *grad_pos_dev, void *stream)
 {
-    int rc = check_normal(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev);
+    const int rc = check_term(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, {{attr_dev, "attr_dev"}}, target_dev, mask_dev,
+                              {{grad_attr_dev, "grad_attr_dev", n_vertices}, {grad_pos_dev, "grad_pos_dev", batch * n_vertices}}, {grad_loss_dev, "grad_loss_dev"});
     if (rc) return rc;
-    if (n_vertices > 0 && !grad_attr_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_attr_dev is null");
-    if (batch * n_vertices > 0 && !grad_pos_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_pos_dev is null");
-    if (pixel_count(batch, height, width) > 0 && n_triangles > 0 && !grad_loss_dev) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "grad_loss_dev is null");
     TSAMD_HIP(tsamd::launch_normal_mse_backward(pos_clip_dev, batch, n_vertices, tri_dev, n_triangles, height, width, ids_dev, attr_dev, target_dev, mask_dev,
                                                 grad_loss_dev, accumulate_pos, grad_attr_dev, grad_pos_dev, static_cast<hipStream_t>(stream)));
     return TSAMD_OK;

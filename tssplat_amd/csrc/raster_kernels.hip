@@ -16,10 +16,9 @@
 //                          (which pixels differ from their right / upper neighbour) that the antialias kernels start from
 //   silhouette_cover_kernel  the alpha stage's resolve pass: id, coverage 0 / 1 and the coverage masks per pixel, from the keys alone
 //   interpolate_kernel / interpolate_backward_kernel  one lane per pixel
-//   depth_mse_kernel / depth_mse_backward_kernel  the depth term without an image chain: distance to the camera of the
-//                          interpolated world position, masked MSE (det_mean.h) and both of its scatters from the alpha stage's ids
-//   normal_mse_kernel / normal_mse_backward_kernel  the normal term without an image chain: masked MSE of an interpolated
-//                          3-channel vertex attribute and both of its scatters, the structure of the depth pair
+//   term_mse_kernel<Term> / term_mse_backward_kernel<Term>  an image term without an image chain: masked MSE (det_mean.h) of a value
+//                          of the interpolated 3-channel vertex attribute and both of its scatters, from the alpha stage's ids.
+//                          DepthTerm: the distance of the interpolated world position to the camera; NormalTerm: the attribute itself
 //
 // Bound: the depth image -- L2 atomics and the reads in front of them (pricing builds, profiles/r04_raster_experiments.md: walk
 // 0.46 ms, fragment queue + depth reads 0.23, atomics 0.31 of 1.10 ms on the 512-sphere surface); 12 B of indices + 3 x 16 B of
@@ -754,27 +753,20 @@ __global__ __launch_bounds__(256) void interpolate_backward_kernel(const float *
     if (valid && grad_rast) grad_rast[gid] = make_float4(du, dv, 0.f, 0.f);
 }
 
-// ---- the depth term: MSE of the distance to the camera, without an image chain ----
-// What the reference's trainer.py:104-115 builds from out["d"] = ||interpolate(v_pos, rast) - campos|| (mesh_rasterizer.py:151-161):
-// loss = mean((d m - t m)^2).  Per pixel the chain moves a 16-byte rast pixel, a 12-byte position and their gradients; here a
-// pixel is its triangle id (the alpha stage's by-product), a target and a mask -- 12 bytes -- plus cached vertex gathers.
-// (u, v) are the clamped barycentrics of the resolve pass (edge_functions, the same operations), w = 1 - u - v and the
-// interpolation are interpolate_kernel's; a background pixel has x = 0, so d = ||campos||, as in the chain.
-struct DepthPoint {
-    float u, v, w;          // barycentric weights of (i0, i1, i2)
-    float dx, dy, dz;       // x - campos
-    float d;                // its length
-};
-
-__device__ __forceinline__ void distance_to(float x, float y, float z, const float *c, DepthPoint &p)
-{
-    p.dx = x - c[0], p.dy = y - c[1], p.dz = z - c[2];
-    p.d = sqrtf(p.dx * p.dx + p.dy * p.dy + p.dz * p.dz);
-}
+// ---- the id-driven image terms: masked MSE of a value of the interpolated vertex attribute, without an image chain ----
+// A term takes a value x[kChannels] of the point y = interpolate(attr, rast) of a [V, 3] vertex attribute; its loss is the mean over
+// pixels and channels of (x_c m - t_c m)^2, the mask broadcast over the channels.  The depth term is what the reference's
+// trainer.py:104-115 builds from out["d"] = ||interpolate(v_pos, rast) - campos|| (mesh_rasterizer.py:151-161); the normal term what
+// MeshRasterizer.forward(fit_normal=True) and a masked MSELoss build from out["n"] = interpolate(attr, rast) (mesh_rasterizer.py:137-149;
+// `attr` is any [V, 3] attribute: the normal is the use).  Per pixel those chains move a 16-byte rast pixel, a 12-byte interpolated
+// pixel, the masked products and their gradients; here a pixel is its triangle id (the alpha stage's by-product), kChannels target floats
+// and a mask -- 12 or 20 bytes -- plus cached vertex gathers.  (u, v) are the clamped barycentrics of the resolve pass (edge_functions,
+// the same operations), w = 1 - u - v and the interpolation are interpolate_kernel's; a background pixel has y = 0, so d = ||campos||
+// and n = 0, as in the chains.
 
 // What every id-driven term starts from at a covered pixel (px, py) of a view with clip-space vertices pv: the clamped barycentrics
 // of the resolve pass, w = (1 - u) - v as interpolate_kernel forms it, and the three rows of a 3-channel vertex attribute,
-// a[3 k + c] = channel c of vertex i_k.  (Shared by the depth and the normal pair: ONE statement of these operations.)
+// a[3 k + c] = channel c of vertex i_k.  (ONE statement of these operations for every term and both directions.)
 __device__ __forceinline__ EdgeFunctions weights_and_gather(const float4 *pv, const float *attr, int32_t i0, int32_t i1, int32_t i2, int px, int py, int height,
                                                             int width, float &u, float &v, float &w, float a[9])
 {
@@ -784,15 +776,6 @@ __device__ __forceinline__ EdgeFunctions weights_and_gather(const float4 *pv, co
     const float *a0 = attr + 3 * int64_t(i0), *a1 = attr + 3 * int64_t(i1), *a2 = attr + 3 * int64_t(i2);
 #pragma unroll
     for (int k = 0; k < 3; ++k) a[k] = a0[k], a[3 + k] = a1[k], a[6 + k] = a2[k];
-    return e;
-}
-
-// the covered pixel (px, py) of a view: clip-space vertices pv, world positions `world`, camera c
-__device__ __forceinline__ EdgeFunctions depth_point(const float4 *pv, const float *world, const float *c, int32_t i0, int32_t i1, int32_t i2, int px, int py,
-                                                     int height, int width, DepthPoint &p, float a[9])
-{
-    const EdgeFunctions e = weights_and_gather(pv, world, i0, i1, i2, px, py, height, width, p.u, p.v, p.w, a);
-    distance_to(p.u * a[0] + p.v * a[3] + p.w * a[6], p.u * a[1] + p.v * a[4] + p.w * a[7], p.u * a[2] + p.v * a[5] + p.w * a[8], c, p);
     return e;
 }
 
@@ -821,26 +804,57 @@ __device__ __forceinline__ void locate_pixel(int64_t gid, int64_t hw, int width,
     px = int(pix - uint32_t(py) * uint32_t(width));
 }
 
-constexpr int kDepthPixels = 4;                                 // 64-pixel chunks per wave and round, all their loads in flight together
-constexpr int kDepthPerBlock = kMeanBlock * kDepthPixels;       // pixels per workgroup and round
-constexpr int kDepthMaxBlocks = 8192;                           // (the loss's bits depend on these two: det_mean.h)
+// A term is the only place that knows "distance to a camera" from "the attribute itself": its channel count, its per-view constants,
+// its value x at the interpolated point y of a view, and the pull-back of dL/dx to g = dL/dy.  The operations and their order are the
+// result's bits (this file is compiled without contraction).
+struct DepthTerm {
+    static constexpr int kChannels = 1;
+    const float *campos;   // [batch, 3]
 
-// One lane per pixel; a workgroup strides over rounds of kDepthPerBlock pixels and stores one double: the sum of (d m - t m)^2,
-// each product rounded on its own, squared and added in float64.  d_out (optional): the distance image, every pixel of it.
-__global__ __launch_bounds__(kMeanBlock) void depth_mse_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
-                                                               int width, const int32_t *ids, const float *world, const float *campos, const float *target,
-                                                               const float *mask, double *partials, float *d_out)
+    __device__ __forceinline__ void value(int64_t view, const float y[3], float x[1]) const
+    {
+        const float *c = campos + 3 * view;
+        const float dx = y[0] - c[0], dy = y[1] - c[1], dz = y[2] - c[2];
+        x[0] = sqrtf(dx * dx + dy * dy + dz * dz);
+    }
+    // d = ||y - c||: g = g_d (y - c) / d, 0 where d = 0
+    __device__ __forceinline__ void pull(int64_t view, const float y[3], const float x[1], const float gx[1], float g[3]) const
+    {
+        const float *c = campos + 3 * view;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[k] = x[0] == 0.f ? 0.f : gx[0] * ((y[k] - c[k]) / x[0]);
+    }
+};
+
+struct NormalTerm {
+    static constexpr int kChannels = 3;
+
+    __device__ __forceinline__ void value(int64_t, const float y[3], float x[3]) const { x[0] = y[0], x[1] = y[1], x[2] = y[2]; }
+    __device__ __forceinline__ void pull(int64_t, const float *, const float *, const float gx[3], float g[3]) const { g[0] = gx[0], g[1] = gx[1], g[2] = gx[2]; }
+};
+
+constexpr int kTermPixels = 4;                                  // 64-pixel chunks per wave and round, all their loads in flight together
+constexpr int kTermPerBlock = kMeanBlock * kTermPixels;         // pixels per workgroup and round
+constexpr int kTermMaxBlocks = 8192;                            // (the loss's bits depend on these two: det_mean.h)
+
+// One lane per pixel; a workgroup strides over rounds of kTermPerBlock pixels and stores one double: the sum over its pixels and the
+// term's channels of (x_c m - t_c m)^2, each product rounded on its own, squared and added in float64 (channel 0, 1, .. in turn).
+// x_out (optional): the term's image [B, H, W, kChannels], every pixel of it.
+template <class Term>
+__global__ __launch_bounds__(kMeanBlock) void term_mse_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
+                                                              int width, const int32_t *ids, const float *attr, Term term, const float *target, const float *mask,
+                                                              double *partials, float *x_out)
 {
-    constexpr int K = kDepthPixels;
+    constexpr int K = kTermPixels, C = Term::kChannels;
     __shared__ double lds[kMeanBlock / 64];
     const int64_t hw = int64_t(height) * width, total = batch * hw;
     const int lane = int(threadIdx.x) & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
     const bool one_boundary = hw >= 64 * K;
     double acc = 0.0;
-    for (int64_t first = int64_t(blockIdx.x) * kDepthPerBlock; first < total; first += int64_t(gridDim.x) * kDepthPerBlock) {
+    for (int64_t first = int64_t(blockIdx.x) * kTermPerBlock; first < total; first += int64_t(gridDim.x) * kTermPerBlock) {
         const int64_t gid0 = first + int64_t(wave) * (64 * K);
         int32_t id[K];
-        float tg[K], m[K];
+        float tg[K][C], m[K];
         bool want[K];
         // all global loads first, together (the latency of one round trip, not of three)
 #pragma unroll
@@ -848,9 +862,10 @@ __global__ __launch_bounds__(kMeanBlock) void depth_mse_kernel(const float4 *pos
             const int64_t gid = gid0 + 64 * k + lane;
             const bool have = gid < total;
             id[k] = have ? ids[gid] : 0;
-            tg[k] = have ? target[gid] : 0.f;
             m[k] = have ? mask[gid] : 0.f;
-            want[k] = have && (m[k] != 0.f || d_out != nullptr);     // a masked-out pixel adds 0: no vertex work unless its d is asked for
+#pragma unroll
+            for (int c = 0; c < C; ++c) tg[k][c] = have ? target[C * gid + c] : 0.f;
+            want[k] = have && (m[k] != 0.f || x_out != nullptr);     // a masked-out pixel adds 0: no vertex work unless its x is asked for
         }
         bool any = false;
 #pragma unroll
@@ -864,140 +879,19 @@ __global__ __launch_bounds__(kMeanBlock) void depth_mse_kernel(const float4 *pos
             int64_t b;
             int px, py;
             locate_pixel(gid, hw, width, one_boundary, b0, b, px, py);
-            const float *c = campos + 3 * b;
-            DepthPoint p;
+            float y[3] = {0.f, 0.f, 0.f}, x[C];
             int32_t i0, i1, i2;
             if (triangle_of_id(id[k], tri, n_tri, n_vertices, i0, i1, i2)) {
-                float a[9];
-                depth_point(pos + b * n_vertices, world, c, i0, i1, i2, px, py, height, width, p, a);
-            } else {
-                distance_to(0.f, 0.f, 0.f, c, p);
-            }
-            if (d_out) d_out[gid] = p.d;
-            const float r = p.d * m[k] - tg[k] * m[k];
-            acc += double(r) * double(r);
-        }
-    }
-    const double sum = block_sum(acc, lds);
-    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
-}
-
-// One lane per pixel, one pass: (u, v, d) recomputed, g_x = grad_loss 2 (d m - t m) m / n * (x - campos) / d (0 where d = 0), then
-// BOTH scatters behind one run detection -- interpolate_backward's (u, v, w) g_x into grad_world[V, 3] and, through
-// (du, dv) = (g_x . (a0 - a2), g_x . (a1 - a2)) and the quotient rule of rasterize_backward, (x, y, w) into grad_pos[B, V, 4].
-// The run key holds the view: grad_pos is per view, and a wave of a small image spans several views that show the same triangle.
-// No gradient image and no grad_rast exist.  EVERY lane reaches find_runs.
-__global__ __launch_bounds__(256) void depth_mse_backward_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
-                                                                 int width, const int32_t *ids, const float *world, const float *campos, const float *target,
-                                                                 const float *mask, const float *grad_loss, float *grad_world, float4 *grad_pos)
-{
-    const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int64_t hw = int64_t(height) * width, total = batch * hw;
-    bool valid = gid < total;
-    int32_t id = 0, i0 = 0, i1 = 0, i2 = 0;
-    float tg = 0.f, m = 0.f;
-    if (valid) id = ids[gid], tg = target[gid], m = mask[gid];
-    valid = valid && m != 0.f && triangle_of_id(id, tri, n_tri, n_vertices, i0, i1, i2);   // (background: x = 0 is a constant)
-    int64_t b = 0;
-    float dw[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, z) of the three world positions
-    float dc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, w) of the three clip-space positions
-    if (valid) {
-        int px, py;
-        locate_pixel(gid, hw, width, false, 0, b, px, py);
-        DepthPoint p;
-        float a[9];
-        const EdgeFunctions e = depth_point(pos + b * n_vertices, world, campos + 3 * b, i0, i1, i2, px, py, height, width, p, a);
-        const float r = p.d * m - tg * m;
-        const float gd = (2.f * r * m) * (grad_loss[0] / float(total));
-        const float gx = p.d == 0.f ? 0.f : gd * (p.dx / p.d), gy = p.d == 0.f ? 0.f : gd * (p.dy / p.d), gz = p.d == 0.f ? 0.f : gd * (p.dz / p.d);
-        dw[0] = p.u * gx, dw[1] = p.u * gy, dw[2] = p.u * gz;
-        dw[3] = p.v * gx, dw[4] = p.v * gy, dw[5] = p.v * gz;
-        dw[6] = p.w * gx, dw[7] = p.w * gy, dw[8] = p.w * gz;
-        const float du = gx * (a[0] - a[6]) + gy * (a[1] - a[7]) + gz * (a[2] - a[8]);
-        const float dv = gx * (a[3] - a[6]) + gy * (a[4] - a[7]) + gz * (a[5] - a[8]);
-        edge_functions_backward(e, du, dv, dc);
-    }
-    const Runs runs = find_runs(valid ? b * (int64_t(1) << 32) + int64_t(id) : -1 - int64_t(threadIdx.x));
-#pragma unroll
-    for (int k = 0; k < 9; ++k) dw[k] = run_sum(runs, dw[k]), dc[k] = run_sum(runs, dc[k]);
-    if (valid && runs.last) {
-        float *gp = reinterpret_cast<float *>(grad_pos + b * n_vertices);
-        const int64_t at[3] = {int64_t(i0), int64_t(i1), int64_t(i2)};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            atomicAdd(grad_world + 3 * at[k] + 0, dw[3 * k]);
-            atomicAdd(grad_world + 3 * at[k] + 1, dw[3 * k + 1]);
-            atomicAdd(grad_world + 3 * at[k] + 2, dw[3 * k + 2]);
-            atomicAdd(gp + 4 * at[k] + 0, dc[3 * k]);
-            atomicAdd(gp + 4 * at[k] + 1, dc[3 * k + 1]);
-            atomicAdd(gp + 4 * at[k] + 3, dc[3 * k + 2]);
-        }
-    }
-}
-
-// ---- the normal term: masked MSE of an interpolated 3-channel vertex attribute, without an image chain ----
-// What MeshRasterizer.forward(fit_normal=True) and a masked MSELoss build from out["n"] = interpolate(attr, rast) (the reference's
-// mesh_rasterizer.py:137-149): loss = mean over pixels and channels of (n_c m - t_c m)^2, the mask broadcast over the channels.  The
-// chain moves a 16-byte rast pixel, a 12-byte interpolated pixel, the masked products and their gradients; here a pixel is its id,
-// three target floats and a mask -- 20 bytes -- plus cached vertex gathers.  (u, v, w) and the gather are weights_and_gather's, the
-// interpolation is interpolate_kernel's; a background pixel has n = 0.  `attr` is any [V, 3] attribute: the normal is the use.
-constexpr int kNormalPixels = kDepthPixels;                     // 64-pixel chunks per wave and round
-constexpr int kNormalPerBlock = kMeanBlock * kNormalPixels;     // pixels per workgroup and round
-constexpr int kNormalMaxBlocks = 8192;                          // (the loss's bits depend on these two: det_mean.h)
-
-// One lane per pixel; a workgroup strides over rounds of kNormalPerBlock pixels and stores one double: the sum over its pixels and
-// the three channels of (n_c m - t_c m)^2, each product rounded on its own, squared and added in float64 (channel 0, 1, 2 in turn).
-// n_out (optional): the interpolated image [B, H, W, 3], every pixel of it.
-__global__ __launch_bounds__(kMeanBlock) void normal_mse_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
-                                                                int width, const int32_t *ids, const float *attr, const float *target, const float *mask,
-                                                                double *partials, float *n_out)
-{
-    constexpr int K = kNormalPixels;
-    __shared__ double lds[kMeanBlock / 64];
-    const int64_t hw = int64_t(height) * width, total = batch * hw;
-    const int lane = int(threadIdx.x) & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
-    const bool one_boundary = hw >= 64 * K;
-    double acc = 0.0;
-    for (int64_t first = int64_t(blockIdx.x) * kNormalPerBlock; first < total; first += int64_t(gridDim.x) * kNormalPerBlock) {
-        const int64_t gid0 = first + int64_t(wave) * (64 * K);
-        int32_t id[K];
-        float tg[K][3], m[K];
-        bool want[K];
-        // all global loads first, together (the latency of one round trip, not of three)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int64_t gid = gid0 + 64 * k + lane;
-            const bool have = gid < total;
-            id[k] = have ? ids[gid] : 0;
-            m[k] = have ? mask[gid] : 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) tg[k][c] = have ? target[3 * gid + c] : 0.f;
-            want[k] = have && (m[k] != 0.f || n_out != nullptr);     // a masked-out pixel adds 0: no vertex work unless its n is asked for
-        }
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < K; ++k) any = any || want[k];
-        if (__ballot(any) == 0ull) continue;                          // wave-uniform: nothing in these chunks enters the loss
-        const int64_t b0 = one_boundary ? gid0 / hw : 0;              // (on the scalar unit)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            if (!want[k]) continue;
-            const int64_t gid = gid0 + 64 * k + lane;
-            float n[3] = {0.f, 0.f, 0.f};
-            int32_t i0, i1, i2;
-            if (triangle_of_id(id[k], tri, n_tri, n_vertices, i0, i1, i2)) {
-                int64_t b;
-                int px, py;
-                locate_pixel(gid, hw, width, one_boundary, b0, b, px, py);
                 float u, v, w, a[9];
                 weights_and_gather(pos + b * n_vertices, attr, i0, i1, i2, px, py, height, width, u, v, w, a);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) n[c] = u * a[c] + v * a[3 + c] + w * a[6 + c];
+                for (int c = 0; c < 3; ++c) y[c] = u * a[c] + v * a[3 + c] + w * a[6 + c];
             }
+            term.value(b, y, x);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (n_out) n_out[3 * gid + c] = n[c];
-                const float r = n[c] * m[k] - tg[k][c] * m[k];
+            for (int c = 0; c < C; ++c) {
+                if (x_out) x_out[C * gid + c] = x[c];
+                const float r = x[c] * m[k] - tg[k][c] * m[k];
                 acc += double(r) * double(r);
             }
         }
@@ -1006,38 +900,48 @@ __global__ __launch_bounds__(kMeanBlock) void normal_mse_kernel(const float4 *po
     if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
-// One lane per pixel, one pass: (u, v, n) recomputed, g_c = grad_loss 2 (n_c m - t_c m) m / (3 pixels), then BOTH scatters behind one
-// run detection, as in depth_mse_backward_kernel -- interpolate_backward's (u, v, w) g into grad_attr[V, 3] and, through
-// (du, dv) = (g . (a0 - a2), g . (a1 - a2)) and the quotient rule of rasterize_backward, (x, y, w) into grad_pos[B, V, 4].  The run key
-// holds the view (a wave of a small image spans views that show the same id).  Background and masked-out pixels add nothing.
-// EVERY lane reaches find_runs.
-__global__ __launch_bounds__(256) void normal_mse_backward_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
-                                                                  int width, const int32_t *ids, const float *attr, const float *target, const float *mask,
-                                                                  const float *grad_loss, float *grad_attr, float4 *grad_pos)
+// One lane per pixel, one pass: (u, v, y, x) recomputed, g_c = grad_loss 2 (x_c m - t_c m) m / (kChannels pixels) pulled back to g = dL/dy,
+// then BOTH scatters behind one run detection -- interpolate_backward's (u, v, w) g into grad_attr[V, 3] and, through
+// (du, dv) = (g . (a0 - a2), g . (a1 - a2)) and the quotient rule of rasterize_backward, (x, y, w) into grad_pos[B, V, 4].
+// The run key holds the view: grad_pos is per view, and a wave of a small image spans several views that show the same triangle.
+// No gradient image and no grad_rast exist; background and masked-out pixels add nothing.  EVERY lane reaches find_runs.
+template <class Term>
+__global__ __launch_bounds__(256) void term_mse_backward_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
+                                                                int width, const int32_t *ids, const float *attr, Term term, const float *target,
+                                                                const float *mask, const float *grad_loss, float *grad_attr, float4 *grad_pos)
 {
+    constexpr int C = Term::kChannels;
     const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     const int64_t hw = int64_t(height) * width, total = batch * hw;
     bool valid = gid < total;
     int32_t id = 0, i0 = 0, i1 = 0, i2 = 0;
-    float tg[3] = {0.f, 0.f, 0.f}, m = 0.f;
-    if (valid) id = ids[gid], m = mask[gid], tg[0] = target[3 * gid], tg[1] = target[3 * gid + 1], tg[2] = target[3 * gid + 2];
-    valid = valid && m != 0.f && triangle_of_id(id, tri, n_tri, n_vertices, i0, i1, i2);   // (background: n = 0 is a constant)
+    float tg[C] = {}, m = 0.f;
+    if (valid) {
+        id = ids[gid], m = mask[gid];
+#pragma unroll
+        for (int c = 0; c < C; ++c) tg[c] = target[C * gid + c];
+    }
+    valid = valid && m != 0.f && triangle_of_id(id, tri, n_tri, n_vertices, i0, i1, i2);   // (background: y = 0 is a constant)
     int64_t b = 0;
     float da[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // the three channels of the three attribute rows
     float dc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, w) of the three clip-space positions
     if (valid) {
         int px, py;
         locate_pixel(gid, hw, width, false, 0, b, px, py);
-        float u, v, w, a[9], g[3];
+        float u, v, w, a[9], y[3], x[C], gx[C], g[3];
         const EdgeFunctions e = weights_and_gather(pos + b * n_vertices, attr, i0, i1, i2, px, py, height, width, u, v, w, a);
-        const float scale = grad_loss[0] / float(3 * total);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float n = u * a[c] + v * a[3 + c] + w * a[6 + c];
-            const float r = n * m - tg[c] * m;
-            g[c] = (2.f * r * m) * scale;
-            da[c] = u * g[c], da[3 + c] = v * g[c], da[6 + c] = w * g[c];
+        for (int c = 0; c < 3; ++c) y[c] = u * a[c] + v * a[3 + c] + w * a[6 + c];
+        term.value(b, y, x);
+        const float scale = grad_loss[0] / float(C * total);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float r = x[c] * m - tg[c] * m;
+            gx[c] = (2.f * r * m) * scale;
         }
+        term.pull(b, y, x, gx, g);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) da[c] = u * g[c], da[3 + c] = v * g[c], da[6 + c] = w * g[c];
         const float du = g[0] * (a[0] - a[6]) + g[1] * (a[1] - a[7]) + g[2] * (a[2] - a[8]);
         const float dv = g[0] * (a[3] - a[6]) + g[1] * (a[4] - a[7]) + g[2] * (a[5] - a[8]);
         edge_functions_backward(e, du, dv, dc);
@@ -1159,54 +1063,25 @@ hipError_t launch_interpolate_backward(const float *attr, int64_t attr_batch, in
     return hipGetLastError();
 }
 
-int64_t depth_mse_workspace_bytes(int64_t n) { return mean_workspace_bytes(mean_blocks(n, kDepthPerBlock, kDepthMaxBlocks)); }
+namespace {
 
-hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
-                            const float *world_pos, const float *campos, const float *target, const float *mask, void *workspace, float *loss, float *depth_out,
-                            hipStream_t stream)
+template <class Term>
+hipError_t launch_term_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
+                           const float *attr, Term term, const float *target, const float *mask, void *workspace, float *loss, float *x_out, hipStream_t stream)
 {
     const int64_t pixels = pixel_count(batch, height, width);
     if (pixels <= 0 || n_tri <= 0) return hipMemsetAsync(loss, 0, sizeof(float), stream);
-    const int blocks = mean_blocks(pixels, kDepthPerBlock, kDepthMaxBlocks);
-    hipLaunchKernelGGL(depth_mse_kernel, dim3(blocks), dim3(kMeanBlock), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri, batch, height,
-                       width, ids, world_pos, campos, target, mask, static_cast<double *>(workspace), depth_out);
+    const int blocks = mean_blocks(pixels, kTermPerBlock, kTermMaxBlocks);
+    hipLaunchKernelGGL(term_mse_kernel<Term>, dim3(blocks), dim3(kMeanBlock), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri, batch,
+                       height, width, ids, attr, term, target, mask, static_cast<double *>(workspace), x_out);
     const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, pixels, loss, stream);
+    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, Term::kChannels * pixels, loss, stream);
 }
 
-hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
-                                     const int32_t *ids, const float *world_pos, const float *campos, const float *target, const float *mask, const float *grad_loss,
-                                     int accumulate_pos, float *grad_world, float *grad_pos, hipStream_t stream)
-{
-    hipError_t e;
-    if (n_vertices > 0 && (e = hipMemsetAsync(grad_world, 0, size_t(n_vertices) * 3 * sizeof(float), stream)) != hipSuccess) return e;
-    if (!accumulate_pos && batch * n_vertices > 0 &&
-        (e = hipMemsetAsync(grad_pos, 0, size_t(batch) * size_t(n_vertices) * 4 * sizeof(float), stream)) != hipSuccess)
-        return e;
-    const int64_t pixels = pixel_count(batch, height, width);
-    if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
-    hipLaunchKernelGGL(depth_mse_backward_kernel, dim3(blocks_for(pixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri,
-                       batch, height, width, ids, world_pos, campos, target, mask, grad_loss, grad_world, reinterpret_cast<float4 *>(grad_pos));
-    return hipGetLastError();
-}
-
-int64_t normal_mse_workspace_bytes(int64_t n) { return mean_workspace_bytes(mean_blocks(n, kNormalPerBlock, kNormalMaxBlocks)); }
-
-hipError_t launch_normal_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
-                             const float *attr, const float *target, const float *mask, void *workspace, float *loss, float *normal_out, hipStream_t stream)
-{
-    const int64_t pixels = pixel_count(batch, height, width);
-    if (pixels <= 0 || n_tri <= 0) return hipMemsetAsync(loss, 0, sizeof(float), stream);
-    const int blocks = mean_blocks(pixels, kNormalPerBlock, kNormalMaxBlocks);
-    hipLaunchKernelGGL(normal_mse_kernel, dim3(blocks), dim3(kMeanBlock), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri, batch, height,
-                       width, ids, attr, target, mask, static_cast<double *>(workspace), normal_out);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, 3 * pixels, loss, stream);
-}
-
-hipError_t launch_normal_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
-                                      const int32_t *ids, const float *attr, const float *target, const float *mask, const float *grad_loss, int accumulate_pos,
-                                      float *grad_attr, float *grad_pos, hipStream_t stream)
+template <class Term>
+hipError_t launch_term_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                    const int32_t *ids, const float *attr, Term term, const float *target, const float *mask, const float *grad_loss,
+                                    int accumulate_pos, float *grad_attr, float *grad_pos, hipStream_t stream)
 {
     hipError_t e;
     if (n_vertices > 0 && (e = hipMemsetAsync(grad_attr, 0, size_t(n_vertices) * 3 * sizeof(float), stream)) != hipSuccess) return e;
@@ -1215,9 +1090,43 @@ hipError_t launch_normal_mse_backward(const float *pos_clip, int64_t batch, int6
         return e;
     const int64_t pixels = pixel_count(batch, height, width);
     if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
-    hipLaunchKernelGGL(normal_mse_backward_kernel, dim3(blocks_for(pixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri,
-                       batch, height, width, ids, attr, target, mask, grad_loss, grad_attr, reinterpret_cast<float4 *>(grad_pos));
+    hipLaunchKernelGGL(term_mse_backward_kernel<Term>, dim3(blocks_for(pixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices,
+                       n_tri, batch, height, width, ids, attr, term, target, mask, grad_loss, grad_attr, reinterpret_cast<float4 *>(grad_pos));
     return hipGetLastError();
+}
+
+}  // namespace
+
+int64_t depth_mse_workspace_bytes(int64_t n) { return mean_workspace_bytes(mean_blocks(n, kTermPerBlock, kTermMaxBlocks)); }
+int64_t normal_mse_workspace_bytes(int64_t n) { return depth_mse_workspace_bytes(n); }
+
+hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
+                            const float *world_pos, const float *campos, const float *target, const float *mask, void *workspace, float *loss, float *depth_out,
+                            hipStream_t stream)
+{
+    return launch_term_mse(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, world_pos, DepthTerm{campos}, target, mask, workspace, loss, depth_out, stream);
+}
+
+hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                     const int32_t *ids, const float *world_pos, const float *campos, const float *target, const float *mask, const float *grad_loss,
+                                     int accumulate_pos, float *grad_world, float *grad_pos, hipStream_t stream)
+{
+    return launch_term_mse_backward(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, world_pos, DepthTerm{campos}, target, mask, grad_loss, accumulate_pos,
+                                    grad_world, grad_pos, stream);
+}
+
+hipError_t launch_normal_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
+                             const float *attr, const float *target, const float *mask, void *workspace, float *loss, float *normal_out, hipStream_t stream)
+{
+    return launch_term_mse(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, attr, NormalTerm{}, target, mask, workspace, loss, normal_out, stream);
+}
+
+hipError_t launch_normal_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
+                                      const int32_t *ids, const float *attr, const float *target, const float *mask, const float *grad_loss, int accumulate_pos,
+                                      float *grad_attr, float *grad_pos, hipStream_t stream)
+{
+    return launch_term_mse_backward(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, attr, NormalTerm{}, target, mask, grad_loss, accumulate_pos, grad_attr,
+                                    grad_pos, stream);
 }
 
 }  // namespace tsamd

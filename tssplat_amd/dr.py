@@ -35,6 +35,7 @@ no image-sized temporary in either direction (``shade_l1`` writes an image only 
 """
 from __future__ import annotations
 
+import collections
 import weakref
 
 import os
@@ -422,31 +423,70 @@ def silhouette(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor
     return _SilhouetteFunc.apply(pos, tri, topo.opp, glctx, height, width, float(pos_gradient_boost))
 
 
-class _SilhouetteMseFunc(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pos, tri, opp, glctx, height, width, target, boost):
-        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
-        n = alpha.numel()
-        loss = torch.empty((), dtype=torch.float32, device=pos.device)
-        ws = torch.empty((int(_lib.tsamd_silhouette_mse_workspace_bytes(n)),), dtype=torch.uint8, device=pos.device)
-        with _device_ctx(pos.device):
-            _capi.check(_lib.tsamd_silhouette_mse(alpha.data_ptr(), target.data_ptr(), n, ws.data_ptr(), loss.data_ptr(), _stream_ptr(pos.device)))
-        ctx.save_for_backward(pos, tri, opp, ids, masks, alpha, target)
-        ctx.boost = float(boost)
-        ctx.mark_non_differentiable(alpha)
-        return loss, alpha
+# An id-driven image term of the alpha stage's node, described once: the C entry point of its loss (``<entry>_backward`` and
+# ``<entry>_workspace_bytes`` go with it), the channels of its image, and how many tensors it passes between ``ids_dev`` and the workspace
+# -- its vertex attribute (the differentiable input) first, then its constants, in the entry points' order.
+_ImageTerm = collections.namedtuple("_ImageTerm", "entry channels n_tensors")
+_DEPTH_TERM = _ImageTerm("tsamd_depth_mse", 1, 4)        # world_pos; campos, target_depth, depth_mask
+_NORMAL_TERM = _ImageTerm("tsamd_normal_mse", 3, 3)      # normals; target_normal, normal_mask
+
+
+class _SilhouetteLossFunc(torch.autograd.Function):
+    """One node for the image terms of the geometry stage: one rasterisation forward, the silhouette MSE and the losses of the ``terms``
+    present from its ids; ``tsamd_silhouette_mse_backward`` followed by each term's backward with ``accumulate_pos=1`` backward -- each
+    lands on what the one before wrote.  ``tensors``: the terms' tensors one after the other (:class:`_ImageTerm`)."""
 
     @staticmethod
-    def backward(ctx, grad_loss, _grad_alpha):
-        pos, tri, opp, ids, masks, alpha, target = ctx.saved_tensors
-        B, V, H, W = int(pos.shape[0]), int(pos.shape[1]), int(ids.shape[1]), int(ids.shape[2])
-        g = grad_loss.to(torch.float32).contiguous()           # stays on the device: the kernel reads it there
+    def forward(ctx, pos, tri, opp, glctx, height, width, target_alpha, boost, want_images, terms, *tensors):
+        dev = pos.device
+        B, V, T = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
+        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
+        n = alpha.numel()
+        losses = [torch.empty((), dtype=torch.float32, device=dev) for _ in range(1 + len(terms))]
+        make = torch.empty if n * T > 0 else torch.zeros         # (the calls write no image without triangles)
+        images = [make((B, height, width, term.channels) if want_images else (0,), dtype=torch.float32, device=dev) for term in terms]
+        sizes = [_lib.tsamd_silhouette_mse_workspace_bytes] + [getattr(_lib, term.entry + "_workspace_bytes") for term in terms]
+        ws = torch.empty((max(int(size(n)) for size in sizes),), dtype=torch.uint8, device=dev)
+        with _device_ctx(dev):
+            stream = _stream_ptr(dev)
+            _capi.check(_lib.tsamd_silhouette_mse(alpha.data_ptr(), target_alpha.data_ptr(), n, ws.data_ptr(), losses[0].data_ptr(), stream))
+            at = 0
+            for term, loss, image in zip(terms, losses[1:], images):
+                own = tensors[at:at + term.n_tensors]
+                _capi.check(getattr(_lib, term.entry)(_ptr(pos), B, V, _ptr(tri), T, height, width, _ptr(ids), *(_ptr(t) for t in own), ws.data_ptr(),
+                                                      loss.data_ptr(), _ptr(image), stream))
+                at += term.n_tensors
+        ctx.save_for_backward(pos, tri, opp, ids, masks, alpha, target_alpha, *tensors)
+        ctx.boost, ctx.terms = float(boost), terms
+        ctx.mark_non_differentiable(alpha, *images)
+        return (*losses, alpha, *images)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        pos, tri, opp, ids, masks, alpha, target_alpha, *tensors = ctx.saved_tensors
+        B, V, T, H, W = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0]), int(ids.shape[1]), int(ids.shape[2])
+        g = [k.to(torch.float32).contiguous() for k in grads[:1 + len(ctx.terms)]]      # stay on the device: the kernels read them there
         grad_pos = torch.empty_like(pos)
+        grad_tensors = [None] * len(tensors)
         with _device_ctx(pos.device):
-            _capi.check(_lib.tsamd_silhouette_mse_backward(pos.data_ptr(), B, V, tri.data_ptr(), int(tri.shape[0]), opp.data_ptr(), H, W, ids.data_ptr(),
-                                                           masks.data_ptr(), alpha.data_ptr(), target.data_ptr(), g.data_ptr(), ctx.boost,
-                                                           grad_pos.data_ptr(), _stream_ptr(pos.device)))
-        return grad_pos, None, None, None, None, None, None, None
+            stream = _stream_ptr(pos.device)
+            _capi.check(_lib.tsamd_silhouette_mse_backward(pos.data_ptr(), B, V, tri.data_ptr(), T, opp.data_ptr(), H, W, ids.data_ptr(), masks.data_ptr(),
+                                                           alpha.data_ptr(), target_alpha.data_ptr(), g[0].data_ptr(), ctx.boost, grad_pos.data_ptr(), stream))
+            at = 0
+            for term, g_term in zip(ctx.terms, g[1:]):
+                own = tensors[at:at + term.n_tensors]
+                grad_tensors[at] = torch.empty_like(own[0])
+                _capi.check(getattr(_lib, term.entry + "_backward")(_ptr(pos), B, V, _ptr(tri), T, H, W, _ptr(ids), *(_ptr(t) for t in own), g_term.data_ptr(),
+                                                                    1, _ptr(grad_tensors[at]), _ptr(grad_pos), stream))
+                at += term.n_tensors
+        return (grad_pos,) + (None,) * 9 + tuple(grad_tensors)
+
+
+def _silhouette_losses(glctx, pos, tri, topo, height, width, target_alpha, boost, return_images, terms, *tensors):
+    """The losses of :class:`_SilhouetteLossFunc` -- the silhouette's, then one per term -- and, asked for, its detached images behind them."""
+    out = _SilhouetteLossFunc.apply(pos, tri, topo.opp, glctx, height, width, target_alpha, float(boost), bool(return_images), terms, *tensors)
+    n_losses = 1 + len(terms)
+    return out[:n_losses] + tuple(image.detach() for image in out[n_losses:]) if return_images else out[:n_losses]
 
 
 def silhouette_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor, resolution, target: torch.Tensor, topology_hash=None,
@@ -461,8 +501,8 @@ def silhouette_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Te
     shape = (int(pos.shape[0]), height, width)
     if tuple(target.shape) not in (shape, shape + (1,)):
         raise RuntimeError("tssplat_amd.dr.silhouette_mse: target must be [B, H, W] or [B, H, W, 1] of the image size")
-    loss, alpha = _SilhouetteMseFunc.apply(pos, tri, topo.opp, glctx, height, width, target.detach(), float(pos_gradient_boost))
-    return (loss, alpha.detach()) if return_alpha else loss
+    out = _silhouette_losses(glctx, pos, tri, topo, height, width, target.detach(), pos_gradient_boost, return_alpha, ())
+    return out if return_alpha else out[0]
 
 
 # the argument checks the id-driven terms (depth, normal) share; every result is detached unless it carries a gradient
@@ -490,51 +530,6 @@ def _camera_positions(name: str, campos, pos):
     return campos.detach()
 
 
-class _SilhouetteDepthMseFunc(torch.autograd.Function):
-    """One node for both image terms of the geometry stage: one rasterisation forward, ``tsamd_silhouette_mse_backward`` followed by
-    ``tsamd_depth_mse_backward(accumulate_pos=1)`` backward -- the second lands on what the first wrote."""
-
-    @staticmethod
-    def forward(ctx, pos, world, tri, opp, glctx, height, width, target_alpha, campos, target_depth, depth_mask, boost, want_depth):
-        dev = pos.device
-        B, V, T = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
-        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
-        n = alpha.numel()
-        alpha_loss = torch.empty((), dtype=torch.float32, device=dev)
-        depth_loss = torch.empty((), dtype=torch.float32, device=dev)
-        if not want_depth:
-            depth = torch.empty((0,), dtype=torch.float32, device=dev)
-        elif n * T > 0:
-            depth = torch.empty((B, height, width, 1), dtype=torch.float32, device=dev)
-        else:
-            depth = torch.zeros((B, height, width, 1), dtype=torch.float32, device=dev)      # (the call writes no image without triangles)
-        ws = torch.empty((max(int(_lib.tsamd_silhouette_mse_workspace_bytes(n)), int(_lib.tsamd_depth_mse_workspace_bytes(n))),), dtype=torch.uint8, device=dev)
-        with _device_ctx(dev):
-            stream = _stream_ptr(dev)
-            _capi.check(_lib.tsamd_silhouette_mse(alpha.data_ptr(), target_alpha.data_ptr(), n, ws.data_ptr(), alpha_loss.data_ptr(), stream))
-            _capi.check(_lib.tsamd_depth_mse(_ptr(pos), B, V, _ptr(tri), T, height, width, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
-                                             _ptr(depth_mask), ws.data_ptr(), depth_loss.data_ptr(), _ptr(depth), stream))
-        ctx.save_for_backward(pos, world, tri, opp, ids, masks, alpha, target_alpha, campos, target_depth, depth_mask)
-        ctx.boost = float(boost)
-        ctx.mark_non_differentiable(alpha, depth)
-        return alpha_loss, depth_loss, alpha, depth
-
-    @staticmethod
-    def backward(ctx, grad_alpha_loss, grad_depth_loss, _grad_alpha, _grad_depth):
-        pos, world, tri, opp, ids, masks, alpha, target_alpha, campos, target_depth, depth_mask = ctx.saved_tensors
-        B, V, T, H, W = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0]), int(ids.shape[1]), int(ids.shape[2])
-        g = torch.stack([grad_alpha_loss.reshape(()), grad_depth_loss.reshape(())]).to(torch.float32)      # stays on the device: the kernels read it there
-        grad_pos = torch.empty_like(pos)
-        grad_world = torch.empty_like(world)
-        with _device_ctx(pos.device):
-            stream = _stream_ptr(pos.device)
-            _capi.check(_lib.tsamd_silhouette_mse_backward(pos.data_ptr(), B, V, tri.data_ptr(), T, opp.data_ptr(), H, W, ids.data_ptr(), masks.data_ptr(),
-                                                           alpha.data_ptr(), target_alpha.data_ptr(), g.data_ptr(), ctx.boost, grad_pos.data_ptr(), stream))
-            _capi.check(_lib.tsamd_depth_mse_backward(_ptr(pos), B, V, _ptr(tri), T, H, W, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
-                                                      _ptr(depth_mask), g.data_ptr() + 4, 1, _ptr(grad_world), _ptr(grad_pos), stream))
-        return (grad_pos, grad_world) + (None,) * 11
-
-
 def silhouette_depth_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor, resolution, target_alpha: torch.Tensor, world_pos: torch.Tensor,
                          campos: torch.Tensor, target_depth: torch.Tensor, depth_mask: torch.Tensor, topology_hash=None, pos_gradient_boost: float = 1.0,
                          return_images: bool = False):
@@ -552,71 +547,8 @@ def silhouette_depth_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: to
     images = [_scalar_image(name, label, t, pos, shape) for label, t in (("target_alpha", target_alpha), ("target_depth", target_depth), ("depth_mask", depth_mask))]
     world_pos = _vertex_attribute(name, "world_pos", world_pos, pos)
     campos = _camera_positions(name, campos, pos)
-    alpha_loss, depth_loss, alpha, depth = _SilhouetteDepthMseFunc.apply(pos, world_pos, tri, topo.opp, glctx, height, width, images[0], campos,
-                                                                         images[1], images[2], float(pos_gradient_boost), bool(return_images))
-    return (alpha_loss, depth_loss, alpha.detach(), depth.detach()) if return_images else (alpha_loss, depth_loss)
-
-
-class _SilhouetteNormalMseFunc(torch.autograd.Function):
-    """One node for the image terms of the geometry stage with the normal term among them: one rasterisation forward;
-    ``tsamd_silhouette_mse_backward``, then ``tsamd_depth_mse_backward(accumulate_pos=1)`` when the depth term is there (``world`` is not
-    ``None``), then ``tsamd_normal_mse_backward(accumulate_pos=1)`` backward -- each lands on what the one before wrote."""
-
-    @staticmethod
-    def forward(ctx, pos, normals, world, tri, opp, glctx, height, width, target_alpha, target_normal, normal_mask, campos, target_depth, depth_mask, boost,
-                want_images):
-        dev = pos.device
-        B, V, T = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
-        has_depth = world is not None
-        alpha, ids, masks = _silhouette_forward(pos, tri, opp, glctx, height, width)
-        n = alpha.numel()
-
-        def image(channels, wanted):
-            if not wanted:
-                return torch.empty((0,), dtype=torch.float32, device=dev)
-            make = torch.empty if n * T > 0 else torch.zeros         # (the calls write no image without triangles)
-            return make((B, height, width, channels), dtype=torch.float32, device=dev)
-        alpha_loss, depth_loss, normal_loss = (torch.empty((), dtype=torch.float32, device=dev) for _ in range(3))
-        depth, normal = image(1, want_images and has_depth), image(3, want_images)
-        ws = torch.empty((max(int(_lib.tsamd_silhouette_mse_workspace_bytes(n)), int(_lib.tsamd_depth_mse_workspace_bytes(n)),
-                              int(_lib.tsamd_normal_mse_workspace_bytes(n))),), dtype=torch.uint8, device=dev)
-        with _device_ctx(dev):
-            stream = _stream_ptr(dev)
-            _capi.check(_lib.tsamd_silhouette_mse(alpha.data_ptr(), target_alpha.data_ptr(), n, ws.data_ptr(), alpha_loss.data_ptr(), stream))
-            if has_depth:
-                _capi.check(_lib.tsamd_depth_mse(_ptr(pos), B, V, _ptr(tri), T, height, width, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
-                                                 _ptr(depth_mask), ws.data_ptr(), depth_loss.data_ptr(), _ptr(depth), stream))
-            _capi.check(_lib.tsamd_normal_mse(_ptr(pos), B, V, _ptr(tri), T, height, width, _ptr(ids), _ptr(normals), _ptr(target_normal), _ptr(normal_mask),
-                                              ws.data_ptr(), normal_loss.data_ptr(), _ptr(normal), stream))
-        saved = [pos, normals, tri, opp, ids, masks, alpha, target_alpha, target_normal, normal_mask]
-        ctx.save_for_backward(*saved, *((world, campos, target_depth, depth_mask) if has_depth else ()))
-        ctx.boost, ctx.has_depth = float(boost), has_depth
-        ctx.mark_non_differentiable(alpha, depth, normal)
-        if has_depth:
-            return alpha_loss, depth_loss, normal_loss, alpha, depth, normal
-        return alpha_loss, normal_loss, alpha, normal
-
-    @staticmethod
-    def backward(ctx, *grads):
-        pos, normals, tri, opp, ids, masks, alpha, target_alpha, target_normal, normal_mask = ctx.saved_tensors[:10]
-        B, V, T, H, W = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0]), int(ids.shape[1]), int(ids.shape[2])
-        n_losses = 3 if ctx.has_depth else 2
-        g = torch.stack([k.reshape(()) for k in grads[:n_losses]]).to(torch.float32)      # stays on the device: the kernels read it there
-        grad_pos = torch.empty_like(pos)
-        grad_normals = torch.empty_like(normals)
-        grad_world = None
-        with _device_ctx(pos.device):
-            stream = _stream_ptr(pos.device)
-            _capi.check(_lib.tsamd_silhouette_mse_backward(pos.data_ptr(), B, V, tri.data_ptr(), T, opp.data_ptr(), H, W, ids.data_ptr(), masks.data_ptr(),
-                                                           alpha.data_ptr(), target_alpha.data_ptr(), g.data_ptr(), ctx.boost, grad_pos.data_ptr(), stream))
-            if ctx.has_depth:
-                world, campos, target_depth, depth_mask = ctx.saved_tensors[10:]
-                grad_world = torch.empty_like(world)
-                _capi.check(_lib.tsamd_depth_mse_backward(_ptr(pos), B, V, _ptr(tri), T, H, W, _ptr(ids), _ptr(world), _ptr(campos), _ptr(target_depth),
-                                                          _ptr(depth_mask), g.data_ptr() + 4, 1, _ptr(grad_world), _ptr(grad_pos), stream))
-            _capi.check(_lib.tsamd_normal_mse_backward(_ptr(pos), B, V, _ptr(tri), T, H, W, _ptr(ids), _ptr(normals), _ptr(target_normal), _ptr(normal_mask),
-                                                       g.data_ptr() + 4 * (n_losses - 1), 1, _ptr(grad_normals), _ptr(grad_pos), stream))
-        return (grad_pos, grad_normals, grad_world) + (None,) * 13
+    return _silhouette_losses(glctx, pos, tri, topo, height, width, images[0], pos_gradient_boost, return_images, (_DEPTH_TERM,), world_pos, campos, images[1],
+                              images[2])
 
 
 def silhouette_normal_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: torch.Tensor, resolution, target_alpha: torch.Tensor, normals: torch.Tensor,
@@ -640,19 +572,14 @@ def silhouette_normal_mse(glctx: RasterizeCudaContext, pos: torch.Tensor, tri: t
     target_normal = _check_cuda_f32("target_normal", target_normal)
     if target_normal.device != pos.device or tuple(target_normal.shape) != shape + (3,):
         raise RuntimeError(f"tssplat_amd.dr.{name}: target_normal must be [B, H, W, 3] of the image size, on the device of pos")
-    normals = _vertex_attribute(name, "normals", normals, pos)
-    world_pos = campos = target_depth = depth_mask = None
+    terms, tensors = (_NORMAL_TERM,), (_vertex_attribute(name, "normals", normals, pos), target_normal.detach(), normal_mask)
     if depth is not None:
         if not isinstance(depth, (tuple, list)) or len(depth) != 4:
             raise RuntimeError(f"tssplat_amd.dr.{name}: depth must be None or (world_pos, campos, target_depth, depth_mask)")
-        world_pos = _vertex_attribute(name, "world_pos", depth[0], pos)
-        campos = _camera_positions(name, depth[1], pos)
-        target_depth = _scalar_image(name, "target_depth", depth[2], pos, shape)
-        depth_mask = _scalar_image(name, "depth_mask", depth[3], pos, shape)
-    out = _SilhouetteNormalMseFunc.apply(pos, normals, world_pos, tri, topo.opp, glctx, height, width, target_alpha, target_normal.detach(), normal_mask, campos,
-                                         target_depth, depth_mask, float(pos_gradient_boost), bool(return_images))
-    n_losses = 2 if depth is None else 3
-    return out[:n_losses] + tuple(image.detach() for image in out[n_losses:]) if return_images else out[:n_losses]
+        terms = (_DEPTH_TERM,) + terms
+        tensors = (_vertex_attribute(name, "world_pos", depth[0], pos), _camera_positions(name, depth[1], pos),
+                   _scalar_image(name, "target_depth", depth[2], pos, shape), _scalar_image(name, "depth_mask", depth[3], pos, shape)) + tensors
+    return _silhouette_losses(glctx, pos, tri, topo, height, width, target_alpha, pos_gradient_boost, return_images, terms, *tensors)
 
 
 # ---- the colour stage under a blend plan ----
