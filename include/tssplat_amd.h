@@ -830,6 +830,46 @@ int tsamd_grid_components(const float *field_dev, int32_t grid, float level, int
 int tsamd_field_fill(const float *field_dev, int32_t grid, float level, int32_t mode, void *workspace_dev, float *field_out_dev, int32_t *stats_out_dev,
                      void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Surface metrics: area-uniform surface samples and the nearest-point search that Chamfer distance, F-score and normal
+ * consistency rest on (tssplat_amd/metrics.py).  Semantics are fixed by tests/metrics_oracle.py, in separately rounded
+ * operations and integer minima and maxima: bitwise repeatable and equal to the oracle.  Stateless, caller-owned buffers,
+ * nothing synchronises the host.
+ *
+ * tsamd_sample_surface, phase TSAMD_SAMPLE_WEIGHTS: v_dev [n_vertices, 3] f32, faces_dev [n_triangles, 3] i32.  Per triangle,
+ * in float64 on the float32 corners a, b, c: n = [b - a] x [c - a], each component two rounded products and a difference,
+ * w = sqrt[[nx nx + ny ny] + nz nz].  A triangle with an index outside the vertices, a coordinate that is not finite or w = 0
+ * has the integer weight 0; every other one q = floor[[w / w_max] 2^32] with w_max the largest w, so 1 <= q_max = 2^32.
+ * prefix_dev [n_triangles] i64 receives q (the caller turns it into its inclusive prefix sum); workspace_dev: 8 bytes, 8-byte
+ * aligned.  n_samples, seed and the three outputs are not used.
+ * Phase TSAMD_SAMPLE_DRAW: prefix_dev holds the inclusive prefix sum C of q with Q = C[n_triangles - 1] > 0, which is the
+ * caller's to check.  With mix64[seed, c] the splitmix64 finaliser of seed + [c + 1] 0x9E3779B97F4A7C15, sample i takes
+ * p = the high 64 bits of mix64[seed, 3 i] Q and the first triangle t with C[t] > p; the 24-bit integers
+ * ia = mix64[seed, 3 i + 1] >> 40 and ib = mix64[seed, 3 i + 2] >> 40, both replaced by 2^24 minus themselves when
+ * ia + ib > 2^24; a = ia 2^-24, b = ib 2^-24 and the point [A + a [B - A]] + b [C - A] in float32, every operation rounded
+ * on its own.  points_out_dev [n_samples, 3] f32; normals_out_dev [n_samples, 3] f32 = n / w of the triangle, rounded once;
+ * tri_out_dev [n_samples] i32 = t.  workspace_dev is not used.  Nothing is read out of bounds whatever prefix_dev holds (a
+ * triangle that cannot be drawn gives NaN).  n_samples = 0: nothing is launched.
+ *
+ * tsamd_nearest_points: query_dev [n, 3] f32, ref_dev [m, 3] f32, m >= 1.  Per query the minimum over all ref points of
+ * d2 = [[qx - rx]^2 + [qy - ry]^2] + [qz - rz]^2 in float32, in exactly that order, every operation rounded on its own; the lower
+ * index wins a tie; a pair whose d2 is NaN is skipped; +inf is an ordinary value.  d2_out_dev [n] f32, idx_out_dev [n] i32;
+ * a query with no pair left gives +inf and -1.  ref_chunks: into how many parts the ref points are split over the grid's second
+ * dimension (1 .. min[m, 65535]; 0: the automatic rule that tsamd_nearest_points_info reports); the result does not depend
+ * on it, bit for bit.  workspace_dev: tsamd_nearest_points_workspace_bytes[n] bytes (8 per query; -1 for an n out of range),
+ * 8-byte aligned, filled by the call itself, contents undefined afterwards.  n = 0: nothing is launched.
+ * tsamd_nearest_points_info: the compiled lanes per workgroup, queries per lane and ref points per LDS tile, and the chunk
+ * count the automatic rule picks for n queries and m ref points; it touches no device. */
+#define TSAMD_SAMPLE_WEIGHTS 0
+#define TSAMD_SAMPLE_DRAW 1
+int tsamd_sample_surface(int32_t phase, const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles, int64_t *prefix_dev,
+                         void *workspace_dev, int64_t n_samples, uint64_t seed, float *points_out_dev, float *normals_out_dev, int32_t *tri_out_dev,
+                         void *stream);
+int64_t tsamd_nearest_points_workspace_bytes(int64_t n);
+int tsamd_nearest_points_info(int64_t n, int64_t m, int32_t *block_out, int32_t *queries_per_lane_out, int32_t *ref_tile_out, int32_t *auto_chunks_out);
+int tsamd_nearest_points(const float *query_dev, int64_t n, const float *ref_dev, int64_t m, int32_t ref_chunks, void *workspace_dev, float *d2_out_dev,
+                         int32_t *idx_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

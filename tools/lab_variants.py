@@ -291,6 +291,48 @@ VARIANTS["sums_pipe"] = ("candidate: per-vertex sums software-pipelined, two tri
                 }
             }""")])
 
+# ---- the nearest-point search of the surface metrics (tools/bench_metrics.py --variants prices them; all give the product's bits) ----
+M = "metrics_kernels.hip"
+for _q in (2, 8):
+    VARIANTS[f"nearest_q{_q}"] = (f"nearest points: {_q} queries per lane instead of 4 (the automatic chunk rule still counts blocks of 4: pass ref_chunks)",
+                                  [(M, "constexpr int kQ = kNearestQueriesPerLane;", f"constexpr int kQ = {_q};")])
+for _t in (256, 4096):
+    VARIANTS[f"nearest_tile{_t}"] = (f"nearest points: ref tiles of {_t} points instead of 1024", [(M, "constexpr int kTile = kNearestTile;", f"constexpr int kTile = {_t};")])
+VARIANTS["nearest_selects"] = ("nearest points: a compare and two selects per pair (11.3 VALU per pair) instead of the minimum of each group of 8 ref points and "
+                               "the rare scan for its index -- the loop the kernel started with (profiles/metrics_bench.json)", [
+    (M, """float4 r[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) r[u] = tile[j + u];
+#pragma unroll
+            for (int k = 0; k < kQ; ++k) {
+                uint32_t bits[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const float dx = qx[k] - r[u].x, dy = qy[k] - r[u].y, dz = qz[k] - r[u].z;
+                    bits[u] = __float_as_uint((dx * dx + dy * dy) + dz * dz);
+                }
+                const uint32_t m = min(min(min(bits[0], bits[1]), min(bits[2], bits[3])), min(min(bits[4], bits[5]), min(bits[6], bits[7])));
+                if (m < best[k]) {                             // rare once the stream is a few thousand points old
+                    best[k] = m;
+                    int32_t at = 7;
+#pragma unroll
+                    for (int u = 6; u >= 0; --u) at = bits[u] == m ? u : at;
+                    arg[k] = int32_t(base) + j + at;           // the lowest index of the group's minimum
+                }
+            }""", """#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const float4 r = tile[j + u];
+                const int32_t id = int32_t(base) + j + u;
+#pragma unroll
+                for (int k = 0; k < kQ; ++k) {
+                    const float dx = qx[k] - r.x, dy = qy[k] - r.y, dz = qz[k] - r.z;
+                    const uint32_t bits = __float_as_uint((dx * dx + dy * dy) + dz * dz);
+                    const bool less = bits < best[k];
+                    best[k] = less ? bits : best[k];
+                    arg[k] = less ? id : arg[k];
+                }
+            }""")])
+
 COMBOS = {"fs": ["fma4", "sdwa"], "stamps_rows8": ["stamps", "rows8"]}    # ("undef" -- inactive lanes' arrays left undefined -- was adopted by the product kernel)
 
 

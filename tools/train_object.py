@@ -16,7 +16,7 @@ absent):
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
                                  [--fit-normal off|operators|fused-loss --fit-normal-start N --normal-weight W] [--normal-bench PATH]
-                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer]
+                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer] [--eval-samples N]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
 so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
@@ -47,6 +47,10 @@ seed, plus the normal stage timings (median of five windows of 200 calls, HIP ev
 solid's occupancy against `spheres_init.visual_hull` of the target silhouettes at the same grid and bounds.
 --merge-fill none|cavities|outer: `merge.fill_field` between the field and the extraction; `merged` then also holds `cavities`,
 `cavity_nodes`, `islands`, `island_nodes`, the Euler characteristic V - F / 2 and the triangle count before (`unfilled`) and after.
+
+--eval-samples N (0: off, the record is what it was): `eval`, `tssplat_amd.metrics.compare_meshes` on N samples per surface against the TARGET MESH --
+Chamfer distance, accuracy / completeness, F-score, normal consistency, each with its `noise_floor` -- of `raw_union` (the concatenated tet-sphere
+boundaries, interior sheets included), `merged` (with --merge-grid) and `merged_filled` (with --merge-fill).
 
 One JSON line: silhouette IoU over all views, inverted tets, seconds per iteration and the stand-alone stage times."""
 import argparse
@@ -174,7 +178,7 @@ def surface_topology(field, level, n_vertices, n_triangles):
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
         fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None,
-        merge_fill="none"):
+        merge_fill="none", eval_samples=0):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -292,6 +296,13 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
                    "schedule": "config/gso.yaml: lr 0.2 cosine, grad_limit 0.01, order 2 -> 4 at 1000, coeff_scheduler, smooth_eng_coeff / n_spheres"},
         "log": log,
     }
+    evals = {}
+
+    def evaluate(key, v, f):   # 3-D figures against the target mesh itself: Chamfer distance, F-score, normal consistency and their noise floor
+        from tssplat_amd import metrics
+        evals[key] = {"triangles": int(f.shape[0]), **metrics.compare_meshes(v.contiguous(), f.contiguous(), tv, tf, n=eval_samples, seed=0).as_dict()}
+    if eval_samples:           # (a) the raw concatenated tet-sphere boundary surface: interior sheets wherever spheres overlap
+        evaluate("raw_union", geo.tet_v.detach()[geo.surface_vid.long()], geo.surface_fid)
     if merge_grid:  # the fitted spheres as ONE closed surface, and a 3-D figure: its occupancy against the targets' visual hull
         from tssplat_amd import merge, spheres_init
         tet_v = geo.tet_v.detach()
@@ -299,12 +310,16 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         level = merge.default_level(merge_grid, bounds)
         field = merge.union_field(tet_v, geo.tet_elem, merge_grid, bounds)
         mv, mf, closed = merge.extract_surface(field, bounds, level)
+        if eval_samples:       # (b) the merged surface
+            evaluate("merged", mv, mf)
         fill_rec = {"fill": merge_fill}
         if merge_fill != "none":   # the flood fill: what it removed, in components, nodes, triangles and Euler characteristic (V - F / 2 on a closed mesh)
             filled = merge.fill_field(field, level, merge_fill)
             before = {"vertices": int(mv.shape[0]), "triangles": int(mf.shape[0]), **surface_topology(field, level, mv.shape[0], mf.shape[0])}
             field = filled.field
             mv, mf, closed = merge.extract_surface(field, bounds, level)
+            if eval_samples:   # (c) the filled merged surface
+                evaluate("merged_filled", mv, mf)
             fill_rec.update(cavities=filled.cavities, cavity_nodes=filled.cavity_nodes, islands=filled.islands, island_nodes=filled.island_nodes,
                             unfilled=before, triangles_before=before["triangles"], triangles_after=int(mf.shape[0]))
         fill_rec.update(surface_topology(field, level, mv.shape[0], mf.shape[0]))
@@ -316,6 +331,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         rec["merged"] = {"file": "merged_surface.obj", "grid": merge_grid, "bounds": list(bounds), "level": level,
                          "vertices": int(mv.shape[0]), "triangles": int(mf.shape[0]), "closed": closed,
                          "inside_fraction": int(occ.sum()) / float(merge_grid ** 3), "volume_iou_vs_hull": merge.volume_iou(occ, hull), **fill_rec}
+    if eval_samples:
+        rec["eval"] = {"samples": eval_samples, "seed": 0, "reference": os.path.basename(target_npz), "a": "the surface named by the key", "b": "the target mesh", **evals}
     if stages:      # the stages on their own (HIP events; they overlap nothing, so their sum is close to one iteration)
         def timed(fn, reps=20):
             for j in range(3):
@@ -554,6 +571,8 @@ def main():
     ap.add_argument("--merge-out", default=None, metavar="DIR", help="where merged_surface.obj goes (bench_outputs/train_object)")
     ap.add_argument("--merge-fill", choices=["none", "cavities", "outer"], default="none",
                     help="flood fill before the extraction: fill enclosed cavities, or also keep only the largest solid component")
+    ap.add_argument("--eval-samples", type=int, default=0, metavar="N",
+                    help="surface metrics (tssplat_amd.metrics.compare_meshes) of the raw, merged and filled surfaces against the target mesh on N samples each (0: off)")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
     ap.add_argument("--fit-normal", choices=["off", "operators", "fused-loss"], default="off")
     ap.add_argument("--fit-normal-start", type=int, default=0, help="the normal term enters once the iteration has passed this one")
@@ -577,7 +596,7 @@ def main():
     print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
                          stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
                          fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
-                         merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill)))
+                         merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill, eval_samples=args.eval_samples)))
 
 
 if __name__ == "__main__":

@@ -237,6 +237,12 @@ SIGNATURES = {
     # the merge's flood fill: connected components of the field's nodes, cavities filled, islands dropped
     "tsamd_grid_components": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsamd_field_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # surface metrics: area-uniform surface samples (weights; draw) and the all-pairs nearest-point search
+    "tsamd_sample_surface": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_nearest_points_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "tsamd_nearest_points_info": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tsamd_nearest_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

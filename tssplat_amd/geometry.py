@@ -270,6 +270,16 @@ class TetMeshGeometry(torch.nn.Module):
         merge.write_obj(os.path.join(path, filename + "_merged.obj"), merged.v, merged.faces)
         return merged
 
+    def surface_metrics(self, v_ref: torch.Tensor, f_ref: torch.Tensor, n: int = 100_000, seed: int = 0, thresholds=None):
+        """:func:`tssplat_amd.metrics.compare_meshes` of the boundary surface as it is (``tet_v[surface_vid]``, ``surface_fid``: for a
+        multi-sphere geometry the raw union of the spheres' boundaries, interior sheets included) against the reference mesh
+        ``v_ref`` float32 ``[V, 3]``, ``f_ref`` int32 ``[T, 3]``: Chamfer distance, F-score and normal consistency on ``n`` samples per
+        surface, with their ``noise_floor``."""
+        from . import metrics
+        v = self.tet_v.detach()[self.surface_vid.long()].contiguous()
+        return metrics.compare_meshes(v, self.surface_fid.contiguous(), v_ref, f_ref, n=n, seed=seed,
+                                      thresholds=metrics.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
+
     def forward(self, iter_num, **kwargs):
         if "permute_surface_v" in kwargs:                               # tetmesh_geometry.py:176-182
             assert "permute_surface_v_dev" in kwargs

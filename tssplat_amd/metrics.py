@@ -1,0 +1,288 @@
+"""Surface metrics on the device: area-uniform surface samples, nearest points, Chamfer distance, F-score, normal consistency.
+
+What the fit and the merge could not say so far is how good a surface is in 3-D.  This is the standard evaluation trio on
+sampled surfaces: :func:`sample_surface` draws points uniformly in area, :func:`nearest` finds for every point of one set the
+closest point of the other, and :func:`compare` turns the two directions into the figures of :class:`SurfaceMetrics`.  The
+kernels sit behind ``tsamd_sample_surface`` and ``tsamd_nearest_points`` (include/tssplat_amd.h), stated in separately rounded
+operations and integer minima so that they are bitwise repeatable; tests/metrics_oracle.py is the same statement in numpy and
+Python integers.  There is no CPU fallback.
+
+The search is brute force over all pairs, ``d2 = ((qx - rx)^2 + (qy - ry)^2) + (qz - rz)^2`` in float32 -- never the expanded form
+``|q|^2 + |r|^2 - 2 q.r``, which cancels.  Sampled-against-sampled distances do not go to zero for identical surfaces:
+:func:`compare_meshes` therefore returns a ``noise_floor`` with every record, the ``chamfer_l1`` of the reference sampled with two
+different seeds.
+
+Out of scope: exact point-to-triangle distances; a cell grid or tree that prunes the search (the brute-force kernel is the
+specification any such search must equal); volume IoU against a triangle mesh (needs an inside test); mesh-quality figures.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import torch
+
+from . import _capi
+
+__all__ = ["SurfaceSamples", "SurfaceMetrics", "ThresholdMetrics", "NearestInfo", "sample_surface", "nearest", "nearest_info", "compare", "compare_meshes",
+           "MAX_COUNT", "DEFAULT_THRESHOLDS"]
+
+MAX_COUNT = 2 ** 31 - 1                 # triangles, samples, queries, ref points (include/tssplat_amd.h)
+DEFAULT_THRESHOLDS = (0.01, 0.02)
+_SAMPLE_WEIGHTS, _SAMPLE_DRAW = 0, 1    # include/tssplat_amd.h: TSAMD_SAMPLE_WEIGHTS, TSAMD_SAMPLE_DRAW
+
+
+@dataclasses.dataclass
+class SurfaceSamples:
+    """``n`` points drawn uniformly in area, the unit normal of each point's triangle and that triangle's index."""
+    points: torch.Tensor             # float32 [n, 3]
+    normals: torch.Tensor            # float32 [n, 3]
+    tri: torch.Tensor                # int32 [n]
+
+
+@dataclasses.dataclass
+class ThresholdMetrics:
+    """At distance ``tau`` (the mesh's own units): ``precision = precision_count / N``, the share of ``a``'s samples within ``tau`` of
+    ``b``; ``recall = recall_count / M`` the other way round; ``fscore`` their harmonic mean (0 when both are 0)."""
+    tau: float
+    precision: float
+    recall: float
+    fscore: float
+    precision_count: int
+    recall_count: int
+
+
+@dataclasses.dataclass
+class SurfaceMetrics:
+    """``a`` is the surface under test, ``b`` the reference; ``d_ab`` the distance from a sample of ``a`` to the nearest sample of ``b``.
+    ``chamfer_l1 = (mean d_ab + mean d_ba) / 2``; ``chamfer_l2 = mean d_ab^2 + mean d_ba^2``; ``accuracy = mean d_ab`` and
+    ``completeness = mean d_ba`` with their maxima (one-sided Hausdorff estimates); ``normal_consistency`` the mean absolute cosine
+    between a sample's normal and its nearest sample's, averaged over both directions.  Samples without a nearest point (every
+    pair a NaN) are left out of the means and counted in ``dropped_ab`` / ``dropped_ba``.  ``noise_floor``: :func:`compare_meshes`."""
+    n_a: int
+    n_b: int
+    chamfer_l1: float
+    chamfer_l2: float
+    accuracy: float
+    completeness: float
+    accuracy_max: float
+    completeness_max: float
+    normal_consistency: float
+    dropped_ab: int
+    dropped_ba: int
+    thresholds: list
+    noise_floor: float | None = None
+
+    def as_dict(self) -> dict:
+        return dataclasses.asdict(self)
+
+
+@dataclasses.dataclass
+class NearestInfo:
+    """The compiled constants of the search kernel and the chunk count its automatic rule picks for ``n`` queries, ``m`` ref points."""
+    block: int
+    queries_per_lane: int
+    ref_tile: int
+    auto_chunks: int
+
+
+def _fail(name: str, what: str):
+    raise RuntimeError(f"tssplat_amd.metrics.{name}: {what}")
+
+
+def _check_gpu(name: str, arg: str, t, dtype, device=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback)")
+    if t.dtype != dtype:
+        _fail(name, f"{arg} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
+    if device is not None and t.device != device:
+        _fail(name, f"{arg} must live on the same device as the first tensor argument ({device}), got {t.device}")
+    return t.detach()
+
+
+def _check_rows(name: str, arg: str, t, dtype, cols: int, device=None) -> torch.Tensor:
+    """``[rows, cols]`` (``cols = 0``: ``[rows]``), contiguous, at most MAX_COUNT rows."""
+    t = _check_gpu(name, arg, t, dtype, device)
+    shape = "[N]" if cols == 0 else f"[N, {cols}]"
+    if t.dim() != (1 if cols == 0 else 2) or (cols and t.shape[1] != cols) or t.shape[0] > MAX_COUNT:
+        _fail(name, f"{arg} must be {shape} with N <= 2^31 - 1, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        _fail(name, f"{arg} must be contiguous")
+    return t
+
+
+def _check_count(name: str, arg: str, n, least: int = 0) -> int:
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not least <= int(n) <= MAX_COUNT:
+        _fail(name, f"{arg} must be an integer in {least} .. 2^31 - 1, got {n!r}")
+    return int(n)
+
+
+def _check_seed(name: str, seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        _fail(name, f"seed must be an integer, got {seed!r}")
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _check_thresholds(name: str, thresholds) -> tuple:
+    try:
+        taus = tuple(float(t) for t in thresholds)
+    except (TypeError, ValueError):
+        taus = (float("nan"),)
+    if any(not (t >= 0.0 and np.isfinite(np.float32(t))) for t in taus):
+        _fail(name, f"thresholds must be finite distances >= 0, got {thresholds!r}")
+    return taus
+
+
+def _check_samples(name: str, arg: str, s, device=None) -> SurfaceSamples:
+    if not isinstance(s, SurfaceSamples):
+        _fail(name, f"{arg} must be SurfaceSamples")
+    points = _check_rows(name, f"{arg}.points", s.points, torch.float32, 3, device)
+    normals = _check_rows(name, f"{arg}.normals", s.normals, torch.float32, 3, points.device)
+    if normals.shape[0] != points.shape[0]:
+        _fail(name, f"{arg}.normals must have {arg}.points' rows ({points.shape[0]}), got {normals.shape[0]}")
+    if points.shape[0] == 0:
+        _fail(name, f"{arg}.points holds no sample")
+    return SurfaceSamples(points, normals, s.tri)
+
+
+def _lib_and_stream(device):
+    from .tet_spheres_ext import _device_ctx, _stream_ptr
+    return _capi.load(), _device_ctx(device), _stream_ptr(device)
+
+
+def nearest_info(n: int, m: int) -> NearestInfo:
+    """Touches no device."""
+    n, m = _check_count("nearest_info", "n", n), _check_count("nearest_info", "m", m)
+    out = [C.c_int32() for _ in range(4)]
+    _capi.check(_capi.load().tsamd_nearest_points_info(n, m, *(C.byref(x) for x in out)))
+    return NearestInfo(*(int(x.value) for x in out))
+
+
+def sample_surface(v: torch.Tensor, faces: torch.Tensor, n: int, seed: int = 0) -> SurfaceSamples:
+    """``n`` independent samples of the triangle mesh ``v`` float32 ``[V, 3]``, ``faces`` int32 ``[T, 3]``, uniform in area.  A triangle with
+    an index outside ``[0, V)``, a coordinate that is not finite or no area is never drawn.  The draws are counter-based: sample ``i`` of
+    ``seed`` is the same whatever ``n`` is, on every run.  A surface without a triangle of positive area is an error.  One readback (the
+    total weight)."""
+    name = "sample_surface"
+    v = _check_rows(name, "v", v, torch.float32, 3)
+    faces = _check_rows(name, "faces", faces, torch.int32, 3, v.device)
+    n = _check_count(name, "n", n)
+    seed = _check_seed(name, seed)
+    T = int(faces.shape[0])
+    if T == 0:
+        _fail(name, "faces holds no triangle")
+    lib, ctx, stream = _lib_and_stream(v.device)
+    dev = v.device
+    q = torch.empty(T, dtype=torch.int64, device=dev)
+    workspace = torch.empty(1, dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    with ctx:
+        _capi.check(lib.tsamd_sample_surface(_SAMPLE_WEIGHTS, ptr(v), int(v.shape[0]), faces.data_ptr(), T, q.data_ptr(), workspace.data_ptr(), 0, 0, None,
+                                             None, None, stream))
+    prefix = torch.cumsum(q, 0)                                     # integers: any scan order gives the same bits
+    if int(prefix[-1].cpu()) <= 0:                                  # the one readback
+        _fail(name, "faces holds no triangle of positive area with finite vertices: there is nothing to sample")
+    out = SurfaceSamples(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
+                         torch.empty(n, dtype=torch.int32, device=dev))
+    if n:
+        with ctx:
+            _capi.check(lib.tsamd_sample_surface(_SAMPLE_DRAW, ptr(v), int(v.shape[0]), faces.data_ptr(), T, prefix.data_ptr(), None, n, seed,
+                                                 out.points.data_ptr(), out.normals.data_ptr(), out.tri.data_ptr(), stream))
+    return out
+
+
+def _nearest(name, query, ref, ref_chunks):
+    N, M = int(query.shape[0]), int(ref.shape[0])
+    dev = query.device
+    d2 = torch.empty(N, dtype=torch.float32, device=dev)
+    idx = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:
+        return d2, idx
+    lib, ctx, stream = _lib_and_stream(dev)
+    workspace = torch.empty(int(lib.tsamd_nearest_points_workspace_bytes(N)) // 8, dtype=torch.int64, device=dev)
+    with ctx:
+        _capi.check(lib.tsamd_nearest_points(query.data_ptr(), N, ref.data_ptr(), M, ref_chunks, workspace.data_ptr(), d2.data_ptr(), idx.data_ptr(), stream))
+    return d2, idx
+
+
+def nearest(query: torch.Tensor, ref: torch.Tensor, ref_chunks: int = 0):
+    """``(d2 float32 [N], idx int32 [N])``: per row of ``query`` float32 ``[N, 3]`` the smallest ``d2 = ((qx - rx)^2 + (qy - ry)^2) + (qz - rz)^2``
+    (float32, in that order) over the rows of ``ref`` float32 ``[M, 3]`` and the row it belongs to.  The lower row wins a tie; a pair
+    whose ``d2`` is NaN is skipped; ``+inf`` is an ordinary value; a query with no pair left gets ``(+inf, -1)``.  ``ref_chunks``: into how
+    many parts the kernel splits ``ref`` (0: automatic, :func:`nearest_info`); the result does not depend on it.  Nothing synchronises."""
+    name = "nearest"
+    query = _check_rows(name, "query", query, torch.float32, 3)
+    ref = _check_rows(name, "ref", ref, torch.float32, 3, query.device)
+    M = int(ref.shape[0])
+    if M == 0:
+        _fail(name, "ref holds no point")
+    if isinstance(ref_chunks, bool) or not isinstance(ref_chunks, (int, np.integer)) or not 0 <= int(ref_chunks) <= min(M, 65535):
+        _fail(name, f"ref_chunks must be 0 (automatic) or an integer in 1 .. min(M, 65535) = {min(M, 65535)}, got {ref_chunks!r}")
+    return _nearest(name, query, ref, int(ref_chunks))
+
+
+def _side(d2, idx, n_self, n_other, tau2):
+    """float64 [6 + len(tau2)] on the device: dropped, kept, sum d, max d, sum d2, sum |cos|, then the counts d2 <= tau^2."""
+    keep = idx >= 0
+    d = torch.sqrt(d2).double()                                     # float32 roots, float64 from here on
+    zero = torch.zeros((), dtype=torch.float64, device=d2.device)
+    pick = idx.clamp(min=0).long()
+    a, b = n_self.double(), n_other.double()[pick]
+    cos = ((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]).abs()
+    kept = keep.sum()
+    rows = [(~keep).sum().double(), kept.double(), torch.where(keep, d, zero).sum(), torch.where(keep, d, zero - 1).max(),
+            torch.where(keep, d2.double(), zero).sum(), torch.where(keep, cos, zero).sum()]
+    rows += [(keep & (d2 <= t)).sum().double() for t in tau2]
+    return torch.stack(rows)
+
+
+def _compare(name, a: SurfaceSamples, b: SurfaceSamples, taus) -> SurfaceMetrics:
+    d2_ab, idx_ab = _nearest(name, a.points, b.points, 0)
+    d2_ba, idx_ba = _nearest(name, b.points, a.points, 0)
+    tau2 = [float(np.float32(t) * np.float32(t)) for t in taus]     # fl32(tau)^2 in float32, compared with the float32 d2
+    # plain torch reductions in float64 (no atomics: the same tensors give the same bits), one readback for the whole record
+    ab, ba = torch.stack([_side(d2_ab, idx_ab, a.normals, b.normals, tau2), _side(d2_ba, idx_ba, b.normals, a.normals, tau2)]).cpu().numpy()
+    N, M = int(a.points.shape[0]), int(b.points.shape[0])
+    nan = float("nan")
+
+    def mean(row, k):
+        return float(row[k] / row[1]) if row[1] > 0 else nan
+    th = []
+    for k, t in enumerate(taus):
+        pc, rc = int(ab[6 + k]), int(ba[6 + k])
+        P, R = pc / N, rc / M
+        th.append(ThresholdMetrics(float(t), P, R, 2 * P * R / (P + R) if P + R > 0 else 0.0, pc, rc))
+    return SurfaceMetrics(n_a=N, n_b=M, chamfer_l1=0.5 * (mean(ab, 2) + mean(ba, 2)), chamfer_l2=mean(ab, 4) + mean(ba, 4), accuracy=mean(ab, 2),
+                          completeness=mean(ba, 2), accuracy_max=float(ab[3]) if ab[1] > 0 else nan, completeness_max=float(ba[3]) if ba[1] > 0 else nan,
+                          normal_consistency=0.5 * (mean(ab, 5) + mean(ba, 5)), dropped_ab=int(ab[0]), dropped_ba=int(ba[0]), thresholds=th)
+
+
+def compare(a: SurfaceSamples, b: SurfaceSamples, thresholds=DEFAULT_THRESHOLDS) -> SurfaceMetrics:
+    """The figures of :class:`SurfaceMetrics` from two :func:`nearest` calls, ``a`` -> ``b`` and ``b`` -> ``a``.  ``a`` is the surface under test,
+    ``b`` the reference.  The same samples give the same record, bit for bit.  One readback."""
+    name = "compare"
+    a = _check_samples(name, "a", a)
+    b = _check_samples(name, "b", b, a.points.device)
+    return _compare(name, a, b, _check_thresholds(name, thresholds))
+
+
+def compare_meshes(v_a, f_a, v_b, f_b, n: int = 100_000, seed: int = 0, thresholds=DEFAULT_THRESHOLDS) -> SurfaceMetrics:
+    """:func:`compare` of ``n`` samples of mesh ``a`` (the surface under test, drawn with ``seed + 2``) and ``n`` samples of mesh ``b`` (the
+    reference, drawn with ``seed``).  ``noise_floor``: the ``chamfer_l1`` of ``b`` sampled with ``seed`` against ``b`` sampled with ``seed + 1`` --
+    what two samplings of one surface are apart at this density; a ``chamfer_l1`` near it says "the same surface as far as ``n`` samples
+    can tell".  The three streams are independent, so a mesh against itself gives about its floor, not 0."""
+    name = "compare_meshes"
+    n = _check_count(name, "n", n, least=1)
+    seed = _check_seed(name, seed)
+    taus = _check_thresholds(name, thresholds)
+    v_a = _check_rows(name, "v_a", v_a, torch.float32, 3)
+    f_a = _check_rows(name, "f_a", f_a, torch.int32, 3, v_a.device)
+    v_b = _check_rows(name, "v_b", v_b, torch.float32, 3, v_a.device)
+    f_b = _check_rows(name, "f_b", f_b, torch.int32, 3, v_a.device)
+    a = sample_surface(v_a, f_a, n, seed + 2)
+    b = sample_surface(v_b, f_b, n, seed)
+    b2 = sample_surface(v_b, f_b, n, seed + 1)
+    rec = _compare(name, a, b, taus)
+    rec.noise_floor = _compare(name, b, b2, taus).chamfer_l1
+    return rec
