@@ -870,6 +870,55 @@ int tsamd_nearest_points_info(int64_t n, int64_t m, int32_t *block_out, int32_t 
 int tsamd_nearest_points(const float *query_dev, int64_t n, const float *ref_dev, int64_t m, int32_t ref_chunks, void *workspace_dev, float *d2_out_dev,
                          int32_t *idx_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Surface simplification: vertex clustering on a cube grid with quadric placement (tssplat_amd/simplify.py).  Semantics are
+ * fixed by tests/simplify_oracle.py, in separately rounded float64 operations, sequential sums and integers: bitwise repeatable
+ * and equal to the oracle.  Stateless, caller-owned buffers, nothing synchronises the host.  The two sorts between the stages
+ * are the caller's (their keys are unique, or the sort is stable).
+ *
+ * Grid: C = cells (1 .. 1024) per axis over the cube [lo, hi]^3, h = [hi - lo] / C in float64, cell [i, j, k] has the key
+ * [i C + j] C + k and the centre g = lo + [index + 0.5] h per axis.  T = n_triangles <= [2^31 - 1] / 3; S = 3 T record slots.
+ *
+ * tsamd_simplify_keys: v_dev [n_vertices, 3] f32, faces_dev [T, 3] i32.  vkey_out_dev [n_vertices] i32: -1 for a vertex with a
+ * coordinate that is not finite, else its cell key with the per-axis index floor[[x - lo] / h] clamped to 0 .. C - 1.
+ * state_out_dev [T] u8: 2 for a face with an index outside 0 .. n_vertices - 1 or an invalid vertex (nothing is read through a bad
+ * index), 1 for a valid face whose corners share a cell, 0 for one with three distinct cells.  records_out_dev [S] i64: slot
+ * 3 t + s holds [cell << 32] | t for corner s of a valid face t if no earlier corner has that cell, else INT64_MAX.
+ *
+ * tsamd_simplify_cells: records_dev [S] the records sorted ascending, perm_dev [S] i64 the slot each came from.  One lane per
+ * run of equal cells walks it serially in record order: with n = [b - a] x [c - a] of the record's face, a' = a - g and
+ * d = -[[nx a'x + ny a'y] + nz a'z], the sums of nx nx, nx ny, nx nz, ny ny, ny nz, nz nz [A], of d n [b], and for each corner of
+ * the face in this cell, in corner order, of p - g [P] and of 1 [count].  m = P / count.  TSAMD_SIMPLIFY_MEAN: x = m.
+ * TSAMD_SIMPLIFY_QUADRIC: tr = [A00 + A11] + A22, lam = stabilise tr, M = A + lam I, r = lam m - b, x = M^-1 r by the symmetric
+ * cofactor formula in the operation order of the oracle; x = m unless tr > 0, det > 0 and x is finite.  Each x_i is then
+ * clamped to [-h/2, h/2].  At the run's first record i: pos_out_dev [S, 3] f32 = g + x rounded once, head_out_dev [S] u8 = 1, or
+ * 3 when the clamp changed a coordinate (0 everywhere else); run_out_dev [S] i32, by ORIGINAL slot, = i for every slot of the run
+ * (-1 for an unused slot).  status_out_dev: one i32, zero-filled by the call itself; TSAMD_SIMPLIFY_STATUS_RECORDS afterwards
+ * means that the records, the permutation or the keys are not what tsamd_simplify_keys and a sort make of these faces -- the
+ * outputs are not to be used, and nothing was read or written out of bounds.  Every walk is bounded by S.
+ *
+ * tsamd_simplify_faces: tri_out_dev [T, 3] i32: for a face of state 0 its three runs, rotated, orientation kept, so that the
+ * smallest comes first [runs ascend with the cell key]; -1 -1 -1 otherwise.  key_ab_out_dev / key_c_out_dev [T] i64:
+ * [a << 32] | b and c of that triple, INT64_MAX otherwise -- sorting the faces stably by key_c and then stably by key_ab orders
+ * them by [triple, index].
+ *
+ * tsamd_simplify_dedupe: order_dev [T] i64, the faces in that order.  keep_out_dev [T] u8: 1 for a survivor whose predecessor
+ * in the order holds another triple, else 0; used_out_dev [S] u8: 1 at every run a kept face names, else 0; both filled by the
+ * call itself.  status_out_dev as above, TSAMD_SIMPLIFY_STATUS_ORDER for an order or triple entry out of range. */
+#define TSAMD_SIMPLIFY_QUADRIC 0
+#define TSAMD_SIMPLIFY_MEAN 1
+#define TSAMD_SIMPLIFY_STATUS_RECORDS 1
+#define TSAMD_SIMPLIFY_STATUS_ORDER 2
+int tsamd_simplify_keys(const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles, int32_t cells, double lo, double hi,
+                        int32_t *vkey_out_dev, int64_t *records_out_dev, uint8_t *state_out_dev, void *stream);
+int tsamd_simplify_cells(const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles, int32_t cells, double lo, double hi,
+                         int32_t placement, double stabilise, const int32_t *vkey_dev, const int64_t *records_dev, const int64_t *perm_dev, float *pos_out_dev,
+                         uint8_t *head_out_dev, int32_t *run_out_dev, int32_t *status_out_dev, void *stream);
+int tsamd_simplify_faces(const int32_t *run_dev, const uint8_t *state_dev, int64_t n_triangles, int32_t *tri_out_dev, int64_t *key_ab_out_dev,
+                         int64_t *key_c_out_dev, void *stream);
+int tsamd_simplify_dedupe(const int32_t *tri_dev, const int64_t *order_dev, int64_t n_triangles, uint8_t *keep_out_dev, uint8_t *used_out_dev,
+                          int32_t *status_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

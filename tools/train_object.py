@@ -16,7 +16,7 @@ absent):
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
                                  [--fit-normal off|operators|fused-loss --fit-normal-start N --normal-weight W] [--normal-bench PATH]
-                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer] [--eval-samples N]
+                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer --merge-simplify K] [--eval-samples N]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
 so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
@@ -47,6 +47,9 @@ seed, plus the normal stage timings (median of five windows of 200 calls, HIP ev
 solid's occupancy against `spheres_init.visual_hull` of the target silhouettes at the same grid and bounds.
 --merge-fill none|cavities|outer: `merge.fill_field` between the field and the extraction; `merged` then also holds `cavities`,
 `cavity_nodes`, `islands`, `island_nodes`, the Euler characteristic V - F / 2 and the triangle count before (`unfilled`) and after.
+--merge-simplify K (0: off; an integer >= 2): `tssplat_amd.simplify.simplify` clusters the extracted (and filled) surface on N // K cells per axis of the merge's
+bounds; `merged_surface.obj` is then the clustered mesh and `merged` gains `simplify`: the counts before and after, `edge_stats`, and with --eval-samples
+`vs_unsimplified` (`metrics.compare_meshes(simplified, unsimplified)`) next to `eval`'s `merged_simplified` against the target mesh.
 
 --eval-samples N (0: off, the record is what it was): `eval`, `tssplat_amd.metrics.compare_meshes` on N samples per surface against the TARGET MESH --
 Chamfer distance, accuracy / completeness, F-score, normal consistency, each with its `noise_floor` -- of `raw_union` (the concatenated tet-sphere
@@ -178,7 +181,7 @@ def surface_topology(field, level, n_vertices, n_triangles):
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
         fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None,
-        merge_fill="none", eval_samples=0):
+        merge_fill="none", eval_samples=0, merge_simplify=0):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -324,6 +327,19 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
                             unfilled=before, triangles_before=before["triangles"], triangles_after=int(mf.shape[0]))
         fill_rec.update(surface_topology(field, level, mv.shape[0], mf.shape[0]))
         occ = merge.occupancy(field, level)
+        if merge_simplify:     # vertex clustering of the surface extracted above on merge_grid // merge_simplify cells of the same cube
+            import dataclasses
+            from tssplat_amd import metrics, simplify
+            k = merge._check_simplify("merge_tets", merge_simplify, merge_grid)
+            simp = simplify.simplify(mv, mf, merge_grid // k, bounds)
+            fill_rec["simplify"] = {"factor": k, "cells": simp.cells, "placement": simp.placement, "vertices_before": int(mv.shape[0]), "triangles_before": int(mf.shape[0]),
+                                    "vertices_after": int(simp.v.shape[0]), "triangles_after": int(simp.faces.shape[0]), "cells_occupied": simp.cells_occupied,
+                                    "clamped": simp.clamped, "duplicates": simp.duplicates, "degenerate_faces": simp.degenerate_faces,
+                                    "invalid_faces": simp.invalid_faces, "edge_stats": dataclasses.asdict(simplify.edge_stats(simp.faces))}
+            if eval_samples:   # (d) the simplified surface: against the unsimplified one, and against the target like the others
+                fill_rec["simplify"]["vs_unsimplified"] = metrics.compare_meshes(simp.v, simp.faces, mv.contiguous(), mf.contiguous(), n=eval_samples, seed=0).as_dict()
+                evaluate("merged_simplified", simp.v, simp.faces)
+            mv, mf, closed = simp.v, simp.faces, simplify.edge_stats(simp.faces).closed
         merge_out = merge_out or os.path.join(ROOT, "bench_outputs", "train_object")
         os.makedirs(merge_out, exist_ok=True)
         merge.write_obj(os.path.join(merge_out, "merged_surface.obj"), mv, mf)
@@ -571,6 +587,8 @@ def main():
     ap.add_argument("--merge-out", default=None, metavar="DIR", help="where merged_surface.obj goes (bench_outputs/train_object)")
     ap.add_argument("--merge-fill", choices=["none", "cavities", "outer"], default="none",
                     help="flood fill before the extraction: fill enclosed cavities, or also keep only the largest solid component")
+    ap.add_argument("--merge-simplify", type=int, default=0, metavar="K",
+                    help="cluster the merged surface on N // K cells per axis (tssplat_amd.simplify; 0: off, else an integer >= 2)")
     ap.add_argument("--eval-samples", type=int, default=0, metavar="N",
                     help="surface metrics (tssplat_amd.metrics.compare_meshes) of the raw, merged and filled surfaces against the target mesh on N samples each (0: off)")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
@@ -596,7 +614,8 @@ def main():
     print(json.dumps(run(args.target, args.spheres, args.k, args.views, args.res, args.iters, verbose=args.verbose, silhouette=args.silhouette,
                          stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
                          fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
-                         merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill, eval_samples=args.eval_samples)))
+                         merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill, eval_samples=args.eval_samples,
+                         merge_simplify=args.merge_simplify)))
 
 
 if __name__ == "__main__":

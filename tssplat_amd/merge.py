@@ -16,12 +16,17 @@ unfilled one: the same vertex bits in the same order, without the removed compon
 Grid: the one of :mod:`tssplat_amd.spheres_init` -- ``G = grid`` nodes per axis (2 .. 512) over the cube ``[lo, hi]^3``,
 ``h = (hi - lo) / G``, node ``(i, j, k)`` at ``lo + (index + 0.5) h`` per axis (float64), flat index ``(i G + j) G + k``.
 
-Out of scope: simplifying, smoothing, re-tetrahedralising.
+Simplification: ``merge_tets(simplify=k)`` clusters the extracted surface on ``grid // k`` cells per axis of the same cube
+(:mod:`tssplat_amd.simplify`: vertex clustering with quadric placement; it does not preserve manifoldness, so ``closed`` is then
+what :func:`tssplat_amd.simplify.edge_stats` finds).
+
+Out of scope: smoothing, re-tetrahedralising.
 """
 from __future__ import annotations
 
 import dataclasses
 import math
+from typing import Optional
 
 import numpy as np
 import torch
@@ -41,7 +46,8 @@ FILL_MODES = {"cavities": 1, "outer": 2}      # include/tssplat_amd.h: TSAMD_FIL
 class MergedSurface:
     """One indexed triangle mesh around the union of all tets.  ``closed``: no grid-border node is inside, so every edge lies in
     exactly two triangles of opposite direction.  ``inside_fraction``: inside nodes over all nodes, of the field that was extracted.
-    ``fill``: ``"none"``, ``"cavities"`` or ``"outer"``, and what it changed (:class:`FilledField`)."""
+    ``fill``: ``"none"``, ``"cavities"`` or ``"outer"``, and what it changed (:class:`FilledField`).  ``simplified``: set by ``merge_tets(simplify=k)``;
+    ``v`` / ``faces`` then are the clustered mesh and ``closed`` is what ``simplify.edge_stats`` finds on it."""
     v: torch.Tensor                # float32 [Nv, 3]
     faces: torch.Tensor            # int32 [Nt, 3], normals point from inside to outside
     closed: bool
@@ -54,6 +60,7 @@ class MergedSurface:
     cavity_nodes: int = 0
     islands: int = 0
     island_nodes: int = 0
+    simplified: Optional["SimplifiedSurface"] = None      # tssplat_amd.simplify.SimplifiedSurface
 
 
 @dataclasses.dataclass
@@ -308,15 +315,27 @@ def volume_iou(a: torch.Tensor, b: torch.Tensor) -> float:
     return inter / union if union else 1.0
 
 
-def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=None, level=None, fill: str = "none") -> MergedSurface:
+def _check_simplify(name: str, simplify, grid: int):
+    """``None``, or the integer factor k with 2 <= k <= grid (so that ``grid // k >= 1``)."""
+    if simplify is None:
+        return None
+    if isinstance(simplify, bool) or not isinstance(simplify, (int, np.integer)) or not 2 <= int(simplify) <= grid:
+        _fail(name, f"simplify must be None or an integer in 2 .. grid = {grid}, got {simplify!r}")
+    return int(simplify)
+
+
+def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=None, level=None, fill: str = "none", simplify=None) -> MergedSurface:
     """The union of all contributing tets as one closed, consistently oriented triangle mesh: ``union_field`` then
     ``extract_surface``.  ``bounds=None``: :func:`default_bounds`; ``level=None``: :func:`default_level`.  ``fill``: ``"none"`` extracts
     the union field as it is (one closed surface per boundary between components); ``"cavities"`` and ``"outer"`` extract
-    :func:`fill_field` of it, at the price of one more readback."""
+    :func:`fill_field` of it, at the price of one more readback.  ``simplify=k`` (an integer >= 2): the extracted surface is clustered
+    on ``grid // k`` cells per axis over the same bounds (:func:`tssplat_amd.simplify.simplify`, after the fill); ``v`` / ``faces`` / ``closed``
+    then describe the clustered mesh and ``simplified`` holds its record."""
     name = "merge_tets"
     fill = _check_fill(name, fill, allow_none=True)
     tet_v, elem = _check_mesh(name, tet_v, elem)
     grid = _check_grid(name, grid)
+    simplify = _check_simplify(name, simplify, grid)
     lo, hi = default_bounds(tet_v, grid) if bounds is None else _check_bounds(name, bounds)
     level = default_level(grid, (lo, hi)) if level is None else _check_level(name, level)
     field = _union_field(name, tet_v, elem, grid, lo, hi)
@@ -326,7 +345,13 @@ def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=
         field, counts = filled.field, (fill, filled.cavities, filled.cavity_nodes, filled.islands, filled.island_nodes)
     v, faces, closed = _extract(field, lo, hi, level)
     n_inside = int((field > level).sum())
-    return MergedSurface(v, faces, closed, n_inside / float(grid ** 3), grid, (lo, hi), level, *counts)
+    merged = MergedSurface(v, faces, closed, n_inside / float(grid ** 3), grid, (lo, hi), level, *counts)
+    if simplify is not None:
+        from . import simplify as _simplify
+        merged.simplified = _simplify.simplify(v, faces, grid // simplify, (lo, hi))
+        merged.v, merged.faces = merged.simplified.v, merged.simplified.faces
+        merged.closed = _simplify.edge_stats(merged.faces).closed
+    return merged
 
 
 def write_obj(path: str, v, faces) -> None:
