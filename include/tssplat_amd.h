@@ -919,6 +919,46 @@ int tsamd_simplify_faces(const int32_t *run_dev, const uint8_t *state_dev, int64
 int tsamd_simplify_dedupe(const int32_t *tri_dev, const int64_t *order_dev, int64_t n_triangles, uint8_t *keep_out_dev, uint8_t *used_out_dev,
                           int32_t *status_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Voxelising triangle meshes: the integer winding number at the nodes of the merge's grid, and the occupancy made of it
+ * (tssplat_amd/voxelize.py).  Semantics are fixed by tests/voxel_oracle.py: exact int64 predicates on a 2^-10 lattice, float64
+ * operations rounded one by one, int32 sums -- bitwise repeatable and equal to the oracle.  Stateless, caller-owned buffers,
+ * nothing synchronises the host.
+ *
+ * Grid: G = grid (1 .. 512) nodes per axis over the cube [lo, hi]^3, h = [hi - lo] / G in float64, node [i, j, k] at
+ * lo + [index + 0.5] h, flat index [i G + j] G + k.  S = 2^10.  A ray axis a has the plane axes b = [a + 1] % 3, c = [a + 2] % 3.
+ *
+ * v_dev [n_vertices, 3] f32, faces_dev [n_triangles, 3] i32.  Per vertex and axis t = [x - lo] / h, u = floor[t S + 0.5] as an
+ * integer and r = t - 0.5; a vertex is usable iff |u| <= 2^29 on all three axes (a NaN or an infinity is not).  A face with an
+ * index outside 0 .. n_vertices - 1 or a corner that is not usable is invalid; nothing is read through a bad index.  On the
+ * ray's plane, area = [B_b - A_b][C_c - A_c] - [B_c - A_c][C_b - A_b]; area = 0: the face is degenerate on this ray and
+ * contributes nothing; sg = sign[area].  Column [p, q] sits at P = [p S + S/2, q S + S/2]; the edge function of Q -> R is
+ * E = [R_b - Q_b][P_c - Q_c] - [R_c - Q_c][P_b - Q_b]; with e = sg E and d = sg [R - Q] the column is on the edge's inner side iff
+ * e > 0, or e = 0 and [d_b > 0, or d_b = 0 and d_c > 0]; a face covers the columns 0 .. G - 1 for which BC, CA and AB all say so
+ * (a mesh sticking out of the cube is clipped).  It then deposits -sg at slab ceil[x] clamped to 0 .. G of that column,
+ * x = [[E_BC r_A + E_CA r_B] + E_AB r_C] / area in float64.  w is the inclusive prefix sum of the deposits along the ray: +1 inside
+ * a closed surface whose normals point outwards.  A column is open when its G + 1 slabs do not sum to 0.
+ *
+ * tsamd_voxel_workspace_bytes: 6144 + 3 [G + 1] G^2 x 4 bytes (64 copies of the counts, then three rays' deposits), or -1 for a
+ * grid out of range; it touches no device.  workspace_dev: 8-byte aligned, cleared by the calls themselves, contents undefined
+ * afterwards; tsamd_voxel_winding and rays = 1 use only the first 6144 + [G + 1] G^2 x 4 bytes of it.
+ * stats_out_dev: twelve i64, 8-byte aligned, written by the calls themselves: [0 .. 2] open columns per axis, [3] disputed,
+ * [4] invalid faces, [5 .. 7] degenerate faces per axis, [8 .. 10] deposits (covered face-column pairs) per axis, [11] faces whose
+ * box of candidate columns was walked by a whole wave (more than 16 columns), summed over the rays; a ray that did not run
+ * leaves its entries 0.
+ * tsamd_voxel_winding: w_out_dev [G, G, G] i32 in the [i, j, k] layout for every axis (0, 1 or 2).
+ * tsamd_voxel_occupancy: occ_out_dev [G, G, G] u8, 1 where the rule holds for w: TSAMD_VOXEL_NONZERO w != 0, _POSITIVE w > 0, _ODD
+ * w odd.  rays = 1: axis 0.  rays = 3: the majority of the three axes' bits; disputed counts the nodes at which they differ.  No w
+ * is written.  n_triangles = 0: everything is 0. */
+#define TSAMD_VOXEL_NONZERO 0
+#define TSAMD_VOXEL_POSITIVE 1
+#define TSAMD_VOXEL_ODD 2
+int64_t tsamd_voxel_workspace_bytes(int32_t grid);
+int tsamd_voxel_winding(const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles, int32_t grid, double lo, double hi, int32_t axis,
+                        void *workspace_dev, int32_t *w_out_dev, int64_t *stats_out_dev, void *stream);
+int tsamd_voxel_occupancy(const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles, int32_t grid, double lo, double hi, int32_t rule,
+                          int32_t rays, void *workspace_dev, uint8_t *occ_out_dev, int64_t *stats_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,11 +16,12 @@ absent):
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
                                  [--fit-normal off|operators|fused-loss --fit-normal-start N --normal-weight W] [--normal-bench PATH]
-                                 [--placement host|device --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer --merge-simplify K] [--eval-samples N]
+                                 [--placement host|device|mesh --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer --merge-simplify K] [--eval-samples N] [--eval-grid N]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
 so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
-the same algorithm as HIP kernels, stated in integers).  --grid: voxels per axis of the placement grid (72).
+the same algorithm as HIP kernels, stated in integers) or `mesh` (the same cover, `spheres_init.cover_occupancy`, of the target mesh's own
+occupancy, `tssplat_amd.voxelize.occupancy` on the cube (-1, 1), instead of the silhouettes' visual hull).  --grid: voxels per axis of the placement grid (72).
 
 --silhouette: how the loop renders alpha and takes the image loss -- `operators` (the default: rasterize, clamp, antialias, MSELoss),
 `fused` (MeshRasterizer(fused_silhouette=True): dr.silhouette, then MSELoss) or `fused-loss` (MeshRasterizer.silhouette_loss:
@@ -54,6 +55,11 @@ bounds; `merged_surface.obj` is then the clustered mesh and `merged` gains `simp
 --eval-samples N (0: off, the record is what it was): `eval`, `tssplat_amd.metrics.compare_meshes` on N samples per surface against the TARGET MESH --
 Chamfer distance, accuracy / completeness, F-score, normal consistency, each with its `noise_floor` -- of `raw_union` (the concatenated tet-sphere
 boundaries, interior sheets included), `merged` (with --merge-grid) and `merged_filled` (with --merge-fill).
+
+--eval-grid N (0: off, the record is what it was): `volume_iou_vs_target`, `tssplat_amd.voxelize.mesh_volume_iou` at N nodes per axis against the TARGET MESH (winding
+number, rule "nonzero", three rays, bounds spanning both meshes) of `raw_union`, `merged`, `merged_filled` and `merged_simplified`, each with its inside counts, open
+columns and disputed nodes; for `merged` and `merged_filled` also `on_merge_grid`: the surface voxelised on the merge's own grid and bounds, and the number of nodes
+at which that differs from `merge.occupancy` of the field it was extracted from.
 
 One JSON line: silhouette IoU over all views, inverted tets, seconds per iteration and the stand-alone stage times."""
 import argparse
@@ -181,7 +187,7 @@ def surface_topology(field, level, n_vertices, n_triangles):
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
         fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None,
-        merge_fill="none", eval_samples=0, merge_simplify=0):
+        merge_fill="none", eval_samples=0, merge_simplify=0, eval_grid=0):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -196,7 +202,7 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         raise ValueError(f"unknown --fit-normal mode {fit_normal!r}")
     if "off" not in (fit_normal, fit_depth) and fit_normal != fit_depth:
         raise ValueError(f"--fit-normal {fit_normal} with --fit-depth {fit_depth}: the two terms share one forward, so they must name the same mode")
-    if placement not in ("host", "device"):
+    if placement not in ("host", "device", "mesh"):
         raise ValueError(f"unknown --placement {placement!r}")
     target_npz = target_npz or os.path.join(ROOT, "tests", "golden", "mario_mesh.npz")
     tgt = np.load(target_npz)
@@ -213,9 +219,13 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
     if fit_normal != "off":
         with torch.no_grad():
             target_normal = render_normal(glctx, tv, tf, mvp, res).clone()
-    if placement == "device":
+    if placement in ("device", "mesh"):
         from tssplat_amd import spheres_init
-        kp = spheres_init.init_spheres(target, mvp, n_spheres, grid=grid)
+        if placement == "mesh":    # the target mesh is at hand: cover its own occupancy, not the visual hull of its silhouettes
+            from tssplat_amd import voxelize
+            kp = spheres_init.cover_occupancy(voxelize.occupancy(tv, tf, grid, (-1.0, 1.0)).occ, n_spheres, (-1.0, 1.0))
+        else:
+            kp = spheres_init.init_spheres(target, mvp, n_spheres, grid=grid)
         radii, hull_frac, left, S = kp.r, kp.hull_fraction, kp.uncovered_fraction, len(kp)
         flags = types.SimpleNamespace(smooth_eng_coeff=2e-4, barrier_coeff=2e-4, increase_order_iter=1000)   # gso.yaml:8-11; the class divides by S
         geo = geometry.TetMeshMultiSphereGeometry(kp, k=k, smooth_barrier_param=flags)
@@ -306,6 +316,20 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         evals[key] = {"triangles": int(f.shape[0]), **metrics.compare_meshes(v.contiguous(), f.contiguous(), tv, tf, n=eval_samples, seed=0).as_dict()}
     if eval_samples:           # (a) the raw concatenated tet-sphere boundary surface: interior sheets wherever spheres overlap
         evaluate("raw_union", geo.tet_v.detach()[geo.surface_vid.long()], geo.surface_fid)
+    vols = {}
+
+    def volume(key, v, f, field=None, grid_bounds_level=None):   # volume IoU against the target mesh: both voxelised (winding number, rule "nonzero", three rays)
+        from tssplat_amd import merge, voxelize
+        r = voxelize.mesh_volume_iou(v.contiguous(), f.contiguous(), tv, tf, grid=eval_grid)
+        vols[key] = {"iou": r["iou"], "inside": r["inside_a"], "inside_target": r["inside_b"], "bounds": list(r["bounds"]), "open_columns": list(r["a"].open_columns),
+                     "disputed": r["a"].disputed, "target_open_columns": list(r["b"].open_columns), "target_disputed": r["b"].disputed}
+        if field is not None:      # ... and, on the merge's own grid, the voxelised surface against the occupancy of the field it was extracted from
+            g, b, lv = grid_bounds_level
+            own = voxelize.occupancy(v.contiguous(), f.contiguous(), g, b)
+            vols[key]["on_merge_grid"] = {"nodes_differing_from_merge_occupancy": int((own.occ != merge.occupancy(field, lv)).sum()), "inside": int(own.occ.sum()),
+                                          "open_columns": list(own.open_columns), "disputed": own.disputed}
+    if eval_grid:
+        volume("raw_union", geo.tet_v.detach()[geo.surface_vid.long()], geo.surface_fid)
     if merge_grid:  # the fitted spheres as ONE closed surface, and a 3-D figure: its occupancy against the targets' visual hull
         from tssplat_amd import merge, spheres_init
         tet_v = geo.tet_v.detach()
@@ -315,6 +339,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         mv, mf, closed = merge.extract_surface(field, bounds, level)
         if eval_samples:       # (b) the merged surface
             evaluate("merged", mv, mf)
+        if eval_grid:
+            volume("merged", mv, mf, field, (merge_grid, bounds, level))
         fill_rec = {"fill": merge_fill}
         if merge_fill != "none":   # the flood fill: what it removed, in components, nodes, triangles and Euler characteristic (V - F / 2 on a closed mesh)
             filled = merge.fill_field(field, level, merge_fill)
@@ -323,6 +349,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             mv, mf, closed = merge.extract_surface(field, bounds, level)
             if eval_samples:   # (c) the filled merged surface
                 evaluate("merged_filled", mv, mf)
+            if eval_grid:
+                volume("merged_filled", mv, mf, field, (merge_grid, bounds, level))
             fill_rec.update(cavities=filled.cavities, cavity_nodes=filled.cavity_nodes, islands=filled.islands, island_nodes=filled.island_nodes,
                             unfilled=before, triangles_before=before["triangles"], triangles_after=int(mf.shape[0]))
         fill_rec.update(surface_topology(field, level, mv.shape[0], mf.shape[0]))
@@ -339,6 +367,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             if eval_samples:   # (d) the simplified surface: against the unsimplified one, and against the target like the others
                 fill_rec["simplify"]["vs_unsimplified"] = metrics.compare_meshes(simp.v, simp.faces, mv.contiguous(), mf.contiguous(), n=eval_samples, seed=0).as_dict()
                 evaluate("merged_simplified", simp.v, simp.faces)
+            if eval_grid:
+                volume("merged_simplified", simp.v, simp.faces)
             mv, mf, closed = simp.v, simp.faces, simplify.edge_stats(simp.faces).closed
         merge_out = merge_out or os.path.join(ROOT, "bench_outputs", "train_object")
         os.makedirs(merge_out, exist_ok=True)
@@ -347,6 +377,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         rec["merged"] = {"file": "merged_surface.obj", "grid": merge_grid, "bounds": list(bounds), "level": level,
                          "vertices": int(mv.shape[0]), "triangles": int(mf.shape[0]), "closed": closed,
                          "inside_fraction": int(occ.sum()) / float(merge_grid ** 3), "volume_iou_vs_hull": merge.volume_iou(occ, hull), **fill_rec}
+    if eval_grid:
+        rec["volume_iou_vs_target"] = {"grid": eval_grid, "rule": "nonzero", "rays": 3, "reference": os.path.basename(target_npz), **vols}
     if eval_samples:
         rec["eval"] = {"samples": eval_samples, "seed": 0, "reference": os.path.basename(target_npz), "a": "the surface named by the key", "b": "the target mesh", **evals}
     if stages:      # the stages on their own (HIP events; they overlap nothing, so their sum is close to one iteration)
@@ -581,7 +613,8 @@ def main():
     ap.add_argument("--no-stages", action="store_true", help="skip the stand-alone stage timings")
     ap.add_argument("--fit-depth", choices=["off", "operators", "fused-loss"], default="off")
     ap.add_argument("--fit-depth-start", type=int, default=0, help="the depth term enters once the iteration has passed this one")
-    ap.add_argument("--placement", choices=["host", "device"], default="host", help="place the tet-spheres with the host helper (default) or with tssplat_amd.spheres_init")
+    ap.add_argument("--placement", choices=["host", "device", "mesh"], default="host",
+                    help="place the tet-spheres with the host helper (default), with tssplat_amd.spheres_init from the silhouettes, or from the voxelised target mesh")
     ap.add_argument("--grid", type=int, default=72, help="voxels per axis of the placement grid")
     ap.add_argument("--merge-grid", type=int, default=0, metavar="N", help="merge the fitted spheres into one closed surface at N nodes per axis (0: off)")
     ap.add_argument("--merge-out", default=None, metavar="DIR", help="where merged_surface.obj goes (bench_outputs/train_object)")
@@ -591,6 +624,8 @@ def main():
                     help="cluster the merged surface on N // K cells per axis (tssplat_amd.simplify; 0: off, else an integer >= 2)")
     ap.add_argument("--eval-samples", type=int, default=0, metavar="N",
                     help="surface metrics (tssplat_amd.metrics.compare_meshes) of the raw, merged and filled surfaces against the target mesh on N samples each (0: off)")
+    ap.add_argument("--eval-grid", type=int, default=0, metavar="N",
+                    help="volume IoU (tssplat_amd.voxelize.mesh_volume_iou) of the raw, merged, filled and simplified surfaces against the target mesh at N nodes per axis (0: off)")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
     ap.add_argument("--fit-normal", choices=["off", "operators", "fused-loss"], default="off")
     ap.add_argument("--fit-normal-start", type=int, default=0, help="the normal term enters once the iteration has passed this one")
@@ -615,7 +650,7 @@ def main():
                          stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
                          fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
                          merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill, eval_samples=args.eval_samples,
-                         merge_simplify=args.merge_simplify)))
+                         merge_simplify=args.merge_simplify, eval_grid=args.eval_grid)))
 
 
 if __name__ == "__main__":

@@ -281,6 +281,14 @@ class TetMeshGeometry(torch.nn.Module):
         return metrics.compare_meshes(v, self.surface_fid.contiguous(), v_ref, f_ref, n=n, seed=seed,
                                       thresholds=metrics.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
 
+    def volume_iou(self, v_ref: torch.Tensor, f_ref: torch.Tensor, grid: int = 128, bounds=None):
+        """:func:`tssplat_amd.voxelize.mesh_volume_iou` of the boundary surface as :meth:`surface_metrics` takes it against the reference
+        mesh: both voxelised at ``grid`` nodes per axis (rule ``"nonzero"``, so the overlapping spheres of a multi-sphere geometry count
+        as their union; three rays), ``bounds=None`` spanning both.  Returns its dict."""
+        from . import voxelize
+        v = self.tet_v.detach()[self.surface_vid.long()].contiguous()
+        return voxelize.mesh_volume_iou(v, self.surface_fid.contiguous(), v_ref, f_ref, grid=grid, bounds=bounds)
+
     def forward(self, iter_num, **kwargs):
         if "permute_surface_v" in kwargs:                               # tetmesh_geometry.py:176-182
             assert "permute_surface_v_dev" in kwargs

@@ -312,6 +312,11 @@ def volume_iou(a: torch.Tensor, b: torch.Tensor) -> float:
     if a.shape != b.shape or a.device != b.device:
         _fail("volume_iou", f"b must have a's shape and device ({tuple(a.shape)}, {a.device}), got {tuple(b.shape)}, {b.device}")
     inter, union = (int(x) for x in torch.stack([(a & b).sum(), (a | b).sum()]).cpu().numpy())
+    return _iou_of_counts(inter, union)
+
+
+def _iou_of_counts(inter: int, union: int) -> float:
+    """What :func:`volume_iou` makes of its two counts (``voxelize.mesh_volume_iou`` reads them back with its own)."""
     return inter / union if union else 1.0
 
 

@@ -22,7 +22,7 @@ import torch
 
 from . import _capi
 
-__all__ = ["KeyPoints", "visual_hull", "distance_transform_sq", "greedy_cover", "init_spheres", "voxel_centres", "MAX_GRID"]
+__all__ = ["KeyPoints", "visual_hull", "distance_transform_sq", "greedy_cover", "init_spheres", "cover_occupancy", "voxel_centres", "MAX_GRID"]
 
 MAX_GRID = 512           # 3 x 511^2 < 2^31: squared distances are int32
 _MAX_SPHERES = 1 << 20   # include/tssplat_amd.h: tsamd_greedy_cover
@@ -229,14 +229,19 @@ def init_spheres(alpha: torch.Tensor, mvp: torch.Tensor, n_spheres: int, grid: i
     n_spheres, min_radius, shrink = _check_cover_params(name, n_spheres, min_radius, shrink)
     hull = _hull(name, alpha, mvp, grid, bounds, threshold, channel)
     lo, hi = _check_bounds(name, bounds)
-    G = int(hull.shape[0])
-    d2, status = _edt(hull)
-    flat, q, count, uncovered = _cover(hull, d2, n_spheres, lo, hi, min_radius, shrink)
+    return _cover_occupancy(name, hull, n_spheres, lo, hi, min_radius, shrink, "the visual hull")
+
+
+def _cover_occupancy(name, occ, n_spheres, lo, hi, min_radius, shrink, what) -> KeyPoints:
+    """The distance transform and the cover of a checked occupancy grid, enqueued back to back, and the one readback."""
+    G = int(occ.shape[0])
+    d2, status = _edt(occ)
+    flat, q, count, uncovered = _cover(occ, d2, n_spheres, lo, hi, min_radius, shrink)
     # one packed readback: status, count, hull voxels, uncovered voxels, then the records
-    head = torch.stack([status[0].long(), count[0].long(), hull.sum(), uncovered.sum()])
+    head = torch.stack([status[0].long(), count[0].long(), occ.sum(), uncovered.sum()])
     host = torch.cat([head, flat.long(), q.long()]).cpu().numpy()
     if int(host[0]) == 0:
-        raise ValueError("tssplat_amd.spheres_init.init_spheres: the visual hull fills the whole grid (no false voxel): nothing bounds the object")
+        raise ValueError(f"tssplat_amd.spheres_init.{name}: {what} fills the whole grid (no false voxel): nothing bounds the object")
     S, n_hull, n_left = int(host[1]), int(host[2]), int(host[3])
     flat_h, q_h = host[4:4 + S], host[4 + n_spheres:4 + n_spheres + S]
     c = voxel_centres(G, (lo, hi))
@@ -244,3 +249,14 @@ def init_spheres(alpha: torch.Tensor, mvp: torch.Tensor, n_spheres: int, grid: i
     ijk = np.stack(np.unravel_index(flat_h, (G, G, G)), axis=1).reshape(-1, 3)
     r = (np.sqrt(q_h.astype(np.float64)) * h * shrink).astype(np.float32)
     return KeyPoints(c[ijk].reshape(-1, 3), r, hull_fraction=n_hull / float(G ** 3), uncovered_fraction=n_left / float(max(1, n_hull)))
+
+
+def cover_occupancy(occ: torch.Tensor, n_spheres: int, bounds=(-1.0, 1.0), min_radius: float = 0.05, shrink: float = 0.92) -> KeyPoints:
+    """Key points from any occupancy grid ``occ`` bool ``[G, G, G]`` over ``bounds`` -- a visual hull, or the voxelised target mesh
+    (:func:`tssplat_amd.voxelize.occupancy`): the tail of :func:`init_spheres`, ``distance_transform_sq`` and ``greedy_cover`` enqueued back
+    to back with one readback.  ``hull_fraction`` is the occupied fraction of the grid.  A grid without a false voxel: ``ValueError``."""
+    name = "cover_occupancy"
+    occ = _check_volume(name, "occ", occ, torch.bool)
+    lo, hi = _check_bounds(name, bounds)
+    n_spheres, min_radius, shrink = _check_cover_params(name, n_spheres, min_radius, shrink)
+    return _cover_occupancy(name, occ, n_spheres, lo, hi, min_radius, shrink, "occ")
