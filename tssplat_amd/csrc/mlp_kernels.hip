@@ -145,7 +145,21 @@ __device__ __forceinline__ void pop(half8 (&hs)[kMlpMaxHidden][KS], half8 (&v)[K
         for (int ks = 0; ks < KS; ++ks) hs[i][ks] = hs[i + 1][ks];
 }
 
-__device__ __forceinline__ float sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+// e^x = 2^n 2^r with n = rint(x log2(e)) and r = x log2(e) - n from explicit fmas, log2(e) split in two floats: |r| <= 1/2
+// carries 0.2 ulp of error into the result and exp2f adds its own 1 ulp.  Not expf: the compiler expands it as
+// exp2((ph - rint(ph)) + pl) with ph + pl = x log2(e), and under -ffp-contract=fast (this file's mode, which no pragma
+// overrides in the backend) it fuses the difference with the product ph into fma(x, log2(e), -rint(ph)).  That counts the
+// rounding error of ph twice: ln 2 ulp(ph) / 2 relative in e^x, 7 ulp measured at x = 28, 22 ulp by the same count at x = 88.
+__device__ __forceinline__ float exp_by_fma(float x)
+{
+    constexpr float kLog2eHi = 0x1.715476p+0f, kLog2eLo = 0x1.4ae0c0p-26f;
+    const float n = rintf(x * kLog2eHi);
+    const float r = fmaf(x, kLog2eLo, fmaf(x, kLog2eHi, -n));
+    const float e = ldexpf(exp2f(r), static_cast<int>(n));
+    return x < -104.0f ? 0.0f : (x > 89.0f ? __builtin_inff() : e);      // past the float range r is no longer small
+}
+
+__device__ __forceinline__ float sigmoid(float v) { return 1.0f / (1.0f + exp_by_fma(-v)); }
 
 template <int W>
 __global__ __launch_bounds__(kThreads) void mlp_forward_kernel(const float *__restrict__ x, int64_t n, const float *__restrict__ params,
