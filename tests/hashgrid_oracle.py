@@ -20,6 +20,12 @@ Hash Encoding", SIGGRAPH 2022) as tiny-cuda-nn's ``Grid`` encoding implements it
 PARITY UNPINNED: tiny-cuda-nn is a CUDA-only library and cannot run here, so bit parity with the library itself is not
 checked; this file is the definition the HIP kernels are tested against.  The cell position is formed in float32 exactly as
 above (it decides the cell); interpolation and gradients are float64.
+
+DOMAIN: finite ``x`` with ``|scale_l * x + 0.5| < 2^31`` on every level.  Outside it (larger positions, +-inf, NaN) this file
+and the kernels disagree by construction -- the integer conversion wraps here and saturates on the device -- and the values
+of such rows (their outputs, their dL/dx and what they add to dL/dparams) are unspecified.  Every table index is still reduced
+modulo the level's entry count, so all accesses stay in bounds, and the other rows' outputs and dL/dx are not affected
+(tests/test_hashgrid_exact.py pins that).
 """
 from __future__ import annotations
 

@@ -6,6 +6,11 @@ PARITY UNPINNED against the library itself (CUDA only, not available here).  ``p
 layout (level-major, ``n_features_per_level`` contiguous fp32 values per entry); the per-level layout comes from the library's
 own host function (``tsamd_grid_layout``), so the Python and C layouts cannot drift apart.
 
+Domain: finite ``x`` with ``|scale_l * x + 0.5| < 2^31`` on every level (``scale_l`` at most 65535).  Rows outside it (larger
+positions, +-inf, NaN) have unspecified values -- their outputs, their dL/dx and what they add to dL/dparams; every table
+index is still reduced modulo the level's entry count, so all accesses stay in bounds, and the outputs and dL/dx of the other
+rows are what they are without them.
+
 What it does not do, loudly: ``Tiled`` grids, ``Nearest`` / ``Smoothstep`` interpolation, inputs other than 3-D,
 ``n_features_per_level`` outside {1, 2, 4, 8}, more than 32 levels, half precision, CPU tensors.  The initial parameters are
 uniform in [-1e-4, 1e-4] from a torch generator seeded with ``seed`` (tiny-cuda-nn's range; its PRNG stream is not reproduced).
