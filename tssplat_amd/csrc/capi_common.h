@@ -4,6 +4,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include <climits>
+#include <cmath>
+#include <cstdint>
 #include <initializer_list>
 #include <string>
 
@@ -44,6 +46,66 @@ inline int check_not_null(std::initializer_list<NamedPtr> args)
 {
     for (const NamedPtr &a : args)
         if (!a.ptr) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(a.name) + " is null");
+    return TSAMD_OK;
+}
+
+// ---- the surface stages' argument checks (init_capi.cpp, merge_capi.cpp, metrics_capi.cpp, simplify_capi.cpp, voxel_capi.cpp) ----
+inline int check_aligned(const void *ptr, const char *name, uintptr_t bytes)
+{
+    if (reinterpret_cast<uintptr_t>(ptr) % bytes != 0)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(name) + " must be " + std::to_string(bytes) + "-byte aligned");
+    return TSAMD_OK;
+}
+
+// A list of (pointer, name as in the header, alignment in bytes; 1 for bytes): the first null of the list, then the first misaligned one.
+struct Buffer {
+    const void *ptr;
+    const char *name;
+    uintptr_t align;
+};
+inline int check_buffers(std::initializer_list<Buffer> args)
+{
+    for (const Buffer &a : args)
+        if (!a.ptr) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(a.name) + " is null");
+    for (const Buffer &a : args)
+        if (int rc = check_aligned(a.ptr, a.name, a.align)) return rc;
+    return TSAMD_OK;
+}
+
+// "<word> out of range (<least> .. <most>)": nodes or cells per axis
+inline int check_grid(int32_t n, int32_t least, int32_t most, const char *word = "grid")
+{
+    if (n < least || n > most)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string(word) + " out of range (" + std::to_string(least) + " .. " + std::to_string(most) + ")");
+    return TSAMD_OK;
+}
+
+// The cube [lo, hi]^3 (lo < hi with a finite difference implies that both are finite) ...
+inline int check_cube(double lo, double hi)
+{
+    if (!(lo < hi) || !std::isfinite(hi - lo)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "lo must be below hi, both finite");
+    return TSAMD_OK;
+}
+
+// ... and where the spacing (hi - lo) / n must not underflow either; `word` is what n counts ("grid", "cells")
+inline int check_cube(double lo, double hi, int32_t n, const char *word)
+{
+    if (!(std::isfinite(lo) && std::isfinite(hi) && lo < hi && std::isfinite(hi - lo) && (hi - lo) / double(n) > 0.0))
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string("lo / hi must be finite with lo < hi and (hi - lo) / ") + word + " > 0");
+    return TSAMD_OK;
+}
+
+inline int check_level(float level)
+{
+    if (std::isnan(level)) return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, "level is NaN");
+    return TSAMD_OK;
+}
+
+// `what` ("faces", "elem") indexes the vertices with 32 bits
+inline int check_vertex_count(int64_t n_vertices, const char *what)
+{
+    if (n_vertices < 0 || n_vertices > INT32_MAX)
+        return capi_fail(TSAMD_ERR_INVALID_ARGUMENT, std::string("n_vertices out of range (0 .. 2^31 - 1: ") + what + " holds 32-bit indices)");
     return TSAMD_OK;
 }
 

@@ -25,15 +25,16 @@ Out of scope: smoothing, re-tetrahedralising.
 from __future__ import annotations
 
 import dataclasses
+import functools
 import math
 from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _capi
+from . import _args, _capi
 
-__all__ = ["MergedSurface", "FilledField", "union_field", "extract_surface", "merge_tets", "components", "fill_field", "occupancy", "volume_iou",
+__all__ = ["MergedSurface", "FilledField", "union_field", "extract_surface", "merge_tets", "components", "fill_field", "occupancy", "volume_iou", "iou_of_counts",
            "default_bounds", "default_level", "write_obj", "MIN_GRID", "MAX_GRID", "FILL_MODES"]
 
 MIN_GRID = 2
@@ -74,26 +75,8 @@ class FilledField:
     island_nodes: int
 
 
-def _fail(name: str, what: str):
-    raise RuntimeError(f"tssplat_amd.merge.{name}: {what}")
-
-
-def _check_grid(name: str, grid, least: int = MIN_GRID) -> int:
-    if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or not least <= int(grid) <= MAX_GRID:
-        _fail(name, f"grid must be an integer in {least} .. {MAX_GRID}, got {grid!r}")
-    return int(grid)
-
-
-def _check_bounds(name: str, bounds):
-    try:
-        lo, hi = float(bounds[0]), float(bounds[1])
-        two = len(bounds) == 2
-    except (TypeError, ValueError, IndexError):
-        lo = hi = math.nan
-        two = False
-    if not two or not (math.isfinite(lo) and math.isfinite(hi) and lo < hi and math.isfinite(hi - lo)):
-        _fail(name, f"bounds must be (lo, hi), finite, with lo < hi, got {bounds!r}")
-    return lo, hi
+# ---- argument checks: the shared ones live in tssplat_amd/_args.py; here are the order and what only this module checks ----
+_fail = functools.partial(_args.fail, "merge")
 
 
 def _check_level(name: str, level) -> float:
@@ -107,38 +90,28 @@ def _check_level(name: str, level) -> float:
     return level
 
 
-def _check_gpu(name: str, arg: str, t, dtype, device=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback)")
-    if t.dtype != dtype:
-        _fail(name, f"{arg} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-    if device is not None and t.device != device:
-        _fail(name, f"{arg} must live on the same device as the first tensor argument ({device}), got {t.device}")
-    return t.detach().contiguous()
+def _tensor(name: str, arg: str, t, dtype, device=None) -> torch.Tensor:
+    """On a GPU, of ``dtype``, on ``device``; a tensor that is not contiguous is copied."""
+    return _args.gpu_tensor(_fail, name, arg, t, dtype, device).contiguous()
 
 
 def _check_mesh(name: str, tet_v, elem):
-    tet_v = _check_gpu(name, "tet_v", tet_v, torch.float32)
-    if tet_v.dim() != 2 or tet_v.shape[1] != 3:
-        _fail(name, f"tet_v must be [V, 3], got {tuple(tet_v.shape)}")
-    elem = _check_gpu(name, "elem", elem, torch.int32, tet_v.device)
-    if elem.dim() != 2 or elem.shape[1] != 4 or elem.shape[0] > _MAX_TETS:
-        _fail(name, f"elem must be [T, 4] with T <= 2^30, got {tuple(elem.shape)}")
+    tet_v = _tensor(name, "tet_v", tet_v, torch.float32)
+    _args.rows(_fail, name, "tet_v", tet_v, 3, math.inf, "[V, 3]")
+    elem = _tensor(name, "elem", elem, torch.int32, tet_v.device)
+    _args.rows(_fail, name, "elem", elem, 4, _MAX_TETS, "[T, 4] with T <= 2^30")
     return tet_v, elem
 
 
 def _check_field(name: str, field) -> torch.Tensor:
-    field = _check_gpu(name, "field", field, torch.float32)
+    field = _tensor(name, "field", field, torch.float32)
     if field.dim() != 3 or not (field.shape[0] == field.shape[1] == field.shape[2]) or not MIN_GRID <= field.shape[0] <= MAX_GRID:
         _fail(name, f"field must be [G, G, G] with G in {MIN_GRID} .. {MAX_GRID}, got {tuple(field.shape)}")
     return field
 
 
 def _check_fill(name: str, mode, allow_none: bool) -> str:
-    allowed = (("none",) if allow_none else ()) + tuple(FILL_MODES)
-    if not isinstance(mode, str) or mode not in allowed:
-        _fail(name, f"{'fill' if allow_none else 'mode'} must be one of {', '.join(repr(m) for m in allowed)}, got {mode!r}")
-    return mode
+    return _args.choice(_fail, name, "fill" if allow_none else "mode", mode, (("none",) if allow_none else ()) + tuple(FILL_MODES))
 
 
 def _check_status(name: str, status: int) -> None:
@@ -147,17 +120,12 @@ def _check_status(name: str, status: int) -> None:
                     "csrc/fill_kernels.hip, not a property of the field")
 
 
-def _lib_and_stream(device):
-    from .tet_spheres_ext import _device_ctx, _stream_ptr
-    return _capi.load(), _device_ctx(device), _stream_ptr(device)
-
-
 def default_level(grid: int, bounds) -> float:
     """``float32(-h 2^-20)``: the surface of the union dilated by a millionth of a voxel.  A node lying on, or within rounding of, a
     face shared by two tets inside the solid reads <= 0 from both; at level 0 it would open a spurious cavity (sphere centres
     from ``init_spheres`` sit on voxel centres, so it happens in practice)."""
-    grid = _check_grid("default_level", grid)
-    lo, hi = _check_bounds("default_level", bounds)
+    grid = _args.integer(_fail, "default_level", "grid", grid, MIN_GRID, MAX_GRID)
+    lo, hi = _args.bounds(_fail, "default_level", bounds)
     return float(np.float32(-((hi - lo) / grid) * 2.0 ** -20))
 
 
@@ -167,8 +135,8 @@ def default_bounds(tet_v: torch.Tensor, grid: int):
     coordinates: ``c = (mn + mx) / 2``, ``E = mx - mn``, ``W = E / (1 - 4 / G)``, ``lo = c - W / 2``, ``hi = c + W / 2`` in float64.
     Needs ``G >= 5`` and ``E > 0``.  One readback of two numbers."""
     name = "default_bounds"
-    grid = _check_grid(name, grid, least=5)
-    tet_v = _check_gpu(name, "tet_v", tet_v, torch.float32)
+    grid = _args.integer(_fail, name, "grid", grid, 5, MAX_GRID)
+    tet_v = _tensor(name, "tet_v", tet_v, torch.float32)
     x = tet_v.reshape(-1)
     x = x[torch.isfinite(x)]
     if x.numel() == 0:
@@ -182,11 +150,10 @@ def default_bounds(tet_v: torch.Tensor, grid: int):
 
 
 def _union_field(name, tet_v, elem, grid, lo, hi) -> torch.Tensor:
-    lib, ctx, stream = _lib_and_stream(tet_v.device)
+    lib, ctx, stream = _args.lib_and_stream(tet_v.device)
     field = torch.empty((grid, grid, grid), dtype=torch.float32, device=tet_v.device)
-    ptr = lambda t: t.data_ptr() if t.numel() else None
     with ctx:
-        _capi.check(lib.tsamd_union_field(ptr(tet_v), int(tet_v.shape[0]), ptr(elem), int(elem.shape[0]), grid, lo, hi, field.data_ptr(), stream))
+        _capi.check(lib.tsamd_union_field(_args.ptr(tet_v), int(tet_v.shape[0]), _args.ptr(elem), int(elem.shape[0]), grid, lo, hi, field.data_ptr(), stream))
     return field
 
 
@@ -197,8 +164,8 @@ def union_field(tet_v: torch.Tensor, elem: torch.Tensor, grid: int, bounds) -> t
     and a positive signed volume ``(b - a) . ((c - a) x (d - a))``: inverted and degenerate tets contribute nothing."""
     name = "union_field"
     tet_v, elem = _check_mesh(name, tet_v, elem)
-    grid = _check_grid(name, grid)
-    lo, hi = _check_bounds(name, bounds)
+    grid = _args.integer(_fail, name, "grid", grid, MIN_GRID, MAX_GRID)
+    lo, hi = _args.bounds(_fail, name, bounds)
     return _union_field(name, tet_v, elem, grid, lo, hi)
 
 
@@ -206,7 +173,7 @@ def _count(field, level):
     """(vmask, vcount, tcount, flag): the count phase, enqueued; nothing synchronises."""
     G = int(field.shape[0])
     dev = field.device
-    lib, ctx, stream = _lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     n = G * G * G
     vmask, vcount, tcount = (torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(3))
     flag = torch.empty(1, dtype=torch.int32, device=dev)
@@ -219,13 +186,12 @@ def _emit(field, lo, hi, level, vmask, voffset, toffset, nv, nt):
     """(v, faces): the emit phase, enqueued."""
     G = int(field.shape[0])
     dev = field.device
-    lib, ctx, stream = _lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t.numel() else None
     with ctx:
-        _capi.check(lib.tsamd_surface_emit(field.data_ptr(), G, lo, hi, level, vmask.data_ptr(), voffset.data_ptr(), toffset.data_ptr(), nv, nt, ptr(v),
-                                           ptr(faces), stream))
+        _capi.check(lib.tsamd_surface_emit(field.data_ptr(), G, lo, hi, level, vmask.data_ptr(), voffset.data_ptr(), toffset.data_ptr(), nv, nt, _args.ptr(v),
+                                           _args.ptr(faces), stream))
     return v, faces
 
 
@@ -248,7 +214,7 @@ def extract_surface(field: torch.Tensor, bounds, level: float):
     triangles.  ``closed``: no node on the grid's border is inside."""
     name = "extract_surface"
     field = _check_field(name, field)
-    lo, hi = _check_bounds(name, bounds)
+    lo, hi = _args.bounds(_fail, name, bounds)
     return _extract(field, lo, hi, _check_level(name, level))
 
 
@@ -267,7 +233,7 @@ def components(field: torch.Tensor, level: float) -> torch.Tensor:
     field = _check_field(name, field)
     level = _check_level(name, level)
     G = int(field.shape[0])
-    lib, ctx, stream = _lib_and_stream(field.device)
+    lib, ctx, stream = _args.lib_and_stream(field.device)
     label = torch.empty((G, G, G), dtype=torch.int32, device=field.device)
     status = torch.empty(1, dtype=torch.int32, device=field.device)
     with ctx:
@@ -280,7 +246,7 @@ def _fill(name, field, level, mode) -> FilledField:
     """The fill, enqueued, and its one readback: the status word and the four counts together."""
     G = int(field.shape[0])
     dev = field.device
-    lib, ctx, stream = _lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     out = torch.empty_like(field)
     workspace = torch.empty(2 * G ** 3 + 2, dtype=torch.int32, device=dev)
     stats = torch.empty(5, dtype=torch.int32, device=dev)
@@ -312,10 +278,10 @@ def volume_iou(a: torch.Tensor, b: torch.Tensor) -> float:
     if a.shape != b.shape or a.device != b.device:
         _fail("volume_iou", f"b must have a's shape and device ({tuple(a.shape)}, {a.device}), got {tuple(b.shape)}, {b.device}")
     inter, union = (int(x) for x in torch.stack([(a & b).sum(), (a | b).sum()]).cpu().numpy())
-    return _iou_of_counts(inter, union)
+    return iou_of_counts(inter, union)
 
 
-def _iou_of_counts(inter: int, union: int) -> float:
+def iou_of_counts(inter: int, union: int) -> float:
     """What :func:`volume_iou` makes of its two counts (``voxelize.mesh_volume_iou`` reads them back with its own)."""
     return inter / union if union else 1.0
 
@@ -324,7 +290,7 @@ def _check_simplify(name: str, simplify, grid: int):
     """``None``, or the integer factor k with 2 <= k <= grid (so that ``grid // k >= 1``)."""
     if simplify is None:
         return None
-    if isinstance(simplify, bool) or not isinstance(simplify, (int, np.integer)) or not 2 <= int(simplify) <= grid:
+    if not _args.is_int(simplify, 2, grid):
         _fail(name, f"simplify must be None or an integer in 2 .. grid = {grid}, got {simplify!r}")
     return int(simplify)
 
@@ -339,9 +305,9 @@ def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=
     name = "merge_tets"
     fill = _check_fill(name, fill, allow_none=True)
     tet_v, elem = _check_mesh(name, tet_v, elem)
-    grid = _check_grid(name, grid)
+    grid = _args.integer(_fail, name, "grid", grid, MIN_GRID, MAX_GRID)
     simplify = _check_simplify(name, simplify, grid)
-    lo, hi = default_bounds(tet_v, grid) if bounds is None else _check_bounds(name, bounds)
+    lo, hi = default_bounds(tet_v, grid) if bounds is None else _args.bounds(_fail, name, bounds)
     level = default_level(grid, (lo, hi)) if level is None else _check_level(name, level)
     field = _union_field(name, tet_v, elem, grid, lo, hi)
     counts = ()

@@ -19,11 +19,12 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import functools
 
 import numpy as np
 import torch
 
-from . import _capi
+from . import _args, _capi
 
 __all__ = ["SurfaceSamples", "SurfaceMetrics", "ThresholdMetrics", "NearestInfo", "sample_surface", "nearest", "nearest_info", "compare", "compare_meshes",
            "MAX_COUNT", "DEFAULT_THRESHOLDS"]
@@ -87,39 +88,25 @@ class NearestInfo:
     auto_chunks: int
 
 
-def _fail(name: str, what: str):
-    raise RuntimeError(f"tssplat_amd.metrics.{name}: {what}")
+# ---- argument checks: the shared ones live in tssplat_amd/_args.py; here are the order and what only this module checks ----
+_fail = functools.partial(_args.fail, "metrics")
 
 
-def _check_gpu(name: str, arg: str, t, dtype, device=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback)")
-    if t.dtype != dtype:
-        _fail(name, f"{arg} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-    if device is not None and t.device != device:
-        _fail(name, f"{arg} must live on the same device as the first tensor argument ({device}), got {t.device}")
-    return t.detach()
-
-
-def _check_rows(name: str, arg: str, t, dtype, cols: int, device=None) -> torch.Tensor:
-    """``[rows, cols]`` (``cols = 0``: ``[rows]``), contiguous, at most MAX_COUNT rows."""
-    t = _check_gpu(name, arg, t, dtype, device)
-    shape = "[N]" if cols == 0 else f"[N, {cols}]"
-    if t.dim() != (1 if cols == 0 else 2) or (cols and t.shape[1] != cols) or t.shape[0] > MAX_COUNT:
-        _fail(name, f"{arg} must be {shape} with N <= 2^31 - 1, got {tuple(t.shape)}")
+def _check_n3(name: str, arg: str, t, dtype, device=None) -> torch.Tensor:
+    """On a GPU, of ``dtype``, on ``device``, ``[N, 3]`` with at most MAX_COUNT rows; a tensor that is not contiguous is refused."""
+    t = _args.gpu_tensor(_fail, name, arg, t, dtype, device)
+    _args.rows(_fail, name, arg, t, 3, MAX_COUNT, "[N, 3] with N <= 2^31 - 1")
     if not t.is_contiguous():
         _fail(name, f"{arg} must be contiguous")
     return t
 
 
 def _check_count(name: str, arg: str, n, least: int = 0) -> int:
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not least <= int(n) <= MAX_COUNT:
-        _fail(name, f"{arg} must be an integer in {least} .. 2^31 - 1, got {n!r}")
-    return int(n)
+    return _args.integer(_fail, name, arg, n, least, MAX_COUNT, "2^31 - 1")
 
 
 def _check_seed(name: str, seed) -> int:
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+    if not _args.is_int(seed):
         _fail(name, f"seed must be an integer, got {seed!r}")
     return int(seed) & (2 ** 64 - 1)
 
@@ -137,18 +124,13 @@ def _check_thresholds(name: str, thresholds) -> tuple:
 def _check_samples(name: str, arg: str, s, device=None) -> SurfaceSamples:
     if not isinstance(s, SurfaceSamples):
         _fail(name, f"{arg} must be SurfaceSamples")
-    points = _check_rows(name, f"{arg}.points", s.points, torch.float32, 3, device)
-    normals = _check_rows(name, f"{arg}.normals", s.normals, torch.float32, 3, points.device)
+    points = _check_n3(name, f"{arg}.points", s.points, torch.float32, device)
+    normals = _check_n3(name, f"{arg}.normals", s.normals, torch.float32, points.device)
     if normals.shape[0] != points.shape[0]:
         _fail(name, f"{arg}.normals must have {arg}.points' rows ({points.shape[0]}), got {normals.shape[0]}")
     if points.shape[0] == 0:
         _fail(name, f"{arg}.points holds no sample")
     return SurfaceSamples(points, normals, s.tri)
-
-
-def _lib_and_stream(device):
-    from .tet_spheres_ext import _device_ctx, _stream_ptr
-    return _capi.load(), _device_ctx(device), _stream_ptr(device)
 
 
 def nearest_info(n: int, m: int) -> NearestInfo:
@@ -165,20 +147,19 @@ def sample_surface(v: torch.Tensor, faces: torch.Tensor, n: int, seed: int = 0) 
     ``seed`` is the same whatever ``n`` is, on every run.  A surface without a triangle of positive area is an error.  One readback (the
     total weight)."""
     name = "sample_surface"
-    v = _check_rows(name, "v", v, torch.float32, 3)
-    faces = _check_rows(name, "faces", faces, torch.int32, 3, v.device)
+    v = _check_n3(name, "v", v, torch.float32)
+    faces = _check_n3(name, "faces", faces, torch.int32, v.device)
     n = _check_count(name, "n", n)
     seed = _check_seed(name, seed)
     T = int(faces.shape[0])
     if T == 0:
         _fail(name, "faces holds no triangle")
-    lib, ctx, stream = _lib_and_stream(v.device)
+    lib, ctx, stream = _args.lib_and_stream(v.device)
     dev = v.device
     q = torch.empty(T, dtype=torch.int64, device=dev)
     workspace = torch.empty(1, dtype=torch.int64, device=dev)
-    ptr = lambda t: t.data_ptr() if t.numel() else None
     with ctx:
-        _capi.check(lib.tsamd_sample_surface(_SAMPLE_WEIGHTS, ptr(v), int(v.shape[0]), faces.data_ptr(), T, q.data_ptr(), workspace.data_ptr(), 0, 0, None,
+        _capi.check(lib.tsamd_sample_surface(_SAMPLE_WEIGHTS, _args.ptr(v), int(v.shape[0]), faces.data_ptr(), T, q.data_ptr(), workspace.data_ptr(), 0, 0, None,
                                              None, None, stream))
     prefix = torch.cumsum(q, 0)                                     # integers: any scan order gives the same bits
     if int(prefix[-1].cpu()) <= 0:                                  # the one readback
@@ -187,7 +168,7 @@ def sample_surface(v: torch.Tensor, faces: torch.Tensor, n: int, seed: int = 0) 
                          torch.empty(n, dtype=torch.int32, device=dev))
     if n:
         with ctx:
-            _capi.check(lib.tsamd_sample_surface(_SAMPLE_DRAW, ptr(v), int(v.shape[0]), faces.data_ptr(), T, prefix.data_ptr(), None, n, seed,
+            _capi.check(lib.tsamd_sample_surface(_SAMPLE_DRAW, _args.ptr(v), int(v.shape[0]), faces.data_ptr(), T, prefix.data_ptr(), None, n, seed,
                                                  out.points.data_ptr(), out.normals.data_ptr(), out.tri.data_ptr(), stream))
     return out
 
@@ -199,7 +180,7 @@ def _nearest(name, query, ref, ref_chunks):
     idx = torch.empty(N, dtype=torch.int32, device=dev)
     if N == 0:
         return d2, idx
-    lib, ctx, stream = _lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     workspace = torch.empty(int(lib.tsamd_nearest_points_workspace_bytes(N)) // 8, dtype=torch.int64, device=dev)
     with ctx:
         _capi.check(lib.tsamd_nearest_points(query.data_ptr(), N, ref.data_ptr(), M, ref_chunks, workspace.data_ptr(), d2.data_ptr(), idx.data_ptr(), stream))
@@ -212,12 +193,12 @@ def nearest(query: torch.Tensor, ref: torch.Tensor, ref_chunks: int = 0):
     whose ``d2`` is NaN is skipped; ``+inf`` is an ordinary value; a query with no pair left gets ``(+inf, -1)``.  ``ref_chunks``: into how
     many parts the kernel splits ``ref`` (0: automatic, :func:`nearest_info`); the result does not depend on it.  Nothing synchronises."""
     name = "nearest"
-    query = _check_rows(name, "query", query, torch.float32, 3)
-    ref = _check_rows(name, "ref", ref, torch.float32, 3, query.device)
+    query = _check_n3(name, "query", query, torch.float32)
+    ref = _check_n3(name, "ref", ref, torch.float32, query.device)
     M = int(ref.shape[0])
     if M == 0:
         _fail(name, "ref holds no point")
-    if isinstance(ref_chunks, bool) or not isinstance(ref_chunks, (int, np.integer)) or not 0 <= int(ref_chunks) <= min(M, 65535):
+    if not _args.is_int(ref_chunks, 0, min(M, 65535)):
         _fail(name, f"ref_chunks must be 0 (automatic) or an integer in 1 .. min(M, 65535) = {min(M, 65535)}, got {ref_chunks!r}")
     return _nearest(name, query, ref, int(ref_chunks))
 
@@ -276,10 +257,10 @@ def compare_meshes(v_a, f_a, v_b, f_b, n: int = 100_000, seed: int = 0, threshol
     n = _check_count(name, "n", n, least=1)
     seed = _check_seed(name, seed)
     taus = _check_thresholds(name, thresholds)
-    v_a = _check_rows(name, "v_a", v_a, torch.float32, 3)
-    f_a = _check_rows(name, "f_a", f_a, torch.int32, 3, v_a.device)
-    v_b = _check_rows(name, "v_b", v_b, torch.float32, 3, v_a.device)
-    f_b = _check_rows(name, "f_b", f_b, torch.int32, 3, v_a.device)
+    v_a = _check_n3(name, "v_a", v_a, torch.float32)
+    f_a = _check_n3(name, "f_a", f_a, torch.int32, v_a.device)
+    v_b = _check_n3(name, "v_b", v_b, torch.float32, v_a.device)
+    f_b = _check_n3(name, "f_b", f_b, torch.int32, v_a.device)
     a = sample_surface(v_a, f_a, n, seed + 2)
     b = sample_surface(v_b, f_b, n, seed)
     b2 = sample_surface(v_b, f_b, n, seed + 1)

@@ -17,12 +17,13 @@ Out of scope: edge collapses, manifold repair, smoothing, re-tetrahedralising.
 from __future__ import annotations
 
 import dataclasses
+import functools
 import math
 
 import numpy as np
 import torch
 
-from . import _capi
+from . import _args, _capi
 
 __all__ = ["SimplifiedSurface", "EdgeStats", "simplify", "edge_stats", "run_lengths", "MAX_CELLS", "MAX_TRIANGLES", "PLACEMENTS", "DEFAULT_STABILISE"]
 
@@ -64,64 +65,15 @@ class EdgeStats:
         return iter((self.edges, self.boundary_edges, self.nonmanifold_edges, self.closed))
 
 
-def _fail(name: str, what: str):
-    raise RuntimeError(f"tssplat_amd.simplify.{name}: {what}")
-
-
-def _check_rows(name: str, arg: str, t, dtype, limit: int) -> torch.Tensor:
-    """A tensor of ``dtype`` and shape ``[N, 3]`` with ``N <= limit``."""
-    if not isinstance(t, torch.Tensor):
-        _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback), got {type(t).__name__}")
-    if t.dtype != dtype:
-        _fail(name, f"{arg} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] > limit:
-        _fail(name, f"{arg} must be [N, 3] with N <= {limit}, got {tuple(t.shape)}")
-    return t
-
-
-def _check_gpu(name: str, arg: str, t: torch.Tensor, device=None) -> torch.Tensor:
-    if not t.is_cuda:
-        _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback)")
-    if device is not None and t.device != device:
-        _fail(name, f"{arg} must live on the same device as the first tensor argument ({device}), got {t.device}")
-    return t.detach().contiguous()
+# ---- argument checks: the shared ones live in tssplat_amd/_args.py; here are the order and what only this module checks ----
+_fail = functools.partial(_args.fail, "simplify")
+_ptr = _args.ptr
 
 
 def _check_mesh(name: str, v, faces):
-    """Types and shapes of both first, then where they live: what is wrong with an argument is said before where it is."""
-    v = _check_rows(name, "v", v, torch.float32, 2 ** 31 - 1)
-    faces = _check_faces(name, faces, on_gpu=False)
-    v = _check_gpu(name, "v", v)
-    return v, _check_gpu(name, "faces", faces, v.device)
-
-
-def _check_faces(name: str, faces, on_gpu: bool = True):
-    faces = _check_rows(name, "faces", faces, torch.int32, MAX_TRIANGLES)
-    return _check_gpu(name, "faces", faces) if on_gpu else faces
-
-
-def _check_cells(name: str, cells) -> int:
-    if isinstance(cells, bool) or not isinstance(cells, (int, np.integer)) or not 1 <= int(cells) <= MAX_CELLS:
-        _fail(name, f"cells must be an integer in 1 .. {MAX_CELLS}, got {cells!r}")
-    return int(cells)
-
-
-def _check_bounds(name: str, bounds, cells: int):
-    try:
-        lo, hi = float(bounds[0]), float(bounds[1])
-        two = len(bounds) == 2
-    except (TypeError, ValueError, IndexError):
-        lo = hi = math.nan
-        two = False
-    if not two or not (math.isfinite(lo) and math.isfinite(hi) and lo < hi and math.isfinite(hi - lo) and (hi - lo) / cells > 0.0):
-        _fail(name, f"bounds must be (lo, hi), finite, with lo < hi, got {bounds!r}")
-    return lo, hi
-
-
-def _check_placement(name: str, placement) -> str:
-    if not isinstance(placement, str) or placement not in PLACEMENTS:
-        _fail(name, f"placement must be one of {', '.join(repr(p) for p in PLACEMENTS)}, got {placement!r}")
-    return placement
+    """Types and shapes of both first, then where they live; a tensor that is not contiguous is copied."""
+    v, faces = _args.triangle_mesh(_fail, name, v, faces, MAX_TRIANGLES)
+    return v.contiguous(), faces.contiguous()
 
 
 def _check_stabilise(name: str, stabilise) -> float:
@@ -140,11 +92,6 @@ def _check_status(name: str, status: int) -> None:
                     "error in csrc/simplify_kernels.hip or in the sorts between its stages, not a property of the mesh")
 
 
-def _lib_and_stream(device):
-    from .tet_spheres_ext import _device_ctx, _stream_ptr
-    return _capi.load(), _device_ctx(device), _stream_ptr(device)
-
-
 def _auto_bounds(name: str, v: torch.Tensor):
     """The min / max over all finite coordinates: one aminmax, one readback."""
     x = v.reshape(-1)
@@ -157,15 +104,11 @@ def _auto_bounds(name: str, v: torch.Tensor):
     return lo, hi
 
 
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
 def _keys(v, faces, cells, lo, hi):
     """(vkey, records, state): the cell keys and the three record slots per face, enqueued."""
     dev = v.device
     Nv, Nt = int(v.shape[0]), int(faces.shape[0])
-    lib, ctx, stream = _lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     vkey = torch.empty(Nv, dtype=torch.int32, device=dev)
     records = torch.empty(3 * Nt, dtype=torch.int64, device=dev)
     state = torch.empty(Nt, dtype=torch.uint8, device=dev)
@@ -178,7 +121,7 @@ def _cells(v, faces, cells, lo, hi, placement, stabilise, vkey, records, perm, s
     """(pos, head, run): the run walk and the solve over the SORTED records, enqueued."""
     dev = v.device
     S = int(records.shape[0])
-    lib, ctx, stream = _lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     pos = torch.empty((S, 3), dtype=torch.float32, device=dev)
     head = torch.empty(S, dtype=torch.uint8, device=dev)
     run = torch.empty(S, dtype=torch.int32, device=dev)
@@ -192,7 +135,7 @@ def _faces(run, state, status):
     """(tri, keep, used): the rotated run triples, the (triple, index) order by two stable sorts, the duplicate flags and used marks."""
     dev = run.device
     Nt = int(state.shape[0])
-    lib, ctx, stream = _lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     tri = torch.empty((Nt, 3), dtype=torch.int32, device=dev)
     key_ab = torch.empty(Nt, dtype=torch.int64, device=dev)
     key_c = torch.empty(Nt, dtype=torch.int64, device=dev)
@@ -244,13 +187,13 @@ def simplify(v: torch.Tensor, faces: torch.Tensor, cells: int, bounds=None, plac
     ``"mean"`` at the mean vertex.  An empty result (``cells=1``, say) has shapes ``[0, 3]``.  See the module text for what clustering
     does not preserve."""
     name = "simplify"
-    cells = _check_cells(name, cells)
-    placement = _check_placement(name, placement)
+    cells = _args.integer(_fail, name, "cells", cells, 1, MAX_CELLS)
+    placement = _args.choice(_fail, name, "placement", placement, PLACEMENTS)
     stabilise = _check_stabilise(name, stabilise)
     if bounds is not None:
-        bounds = _check_bounds(name, bounds, cells)
+        bounds = _args.bounds(_fail, name, bounds, cells)
     v, faces = _check_mesh(name, v, faces)
-    lo, hi = _check_bounds(name, _auto_bounds(name, v), cells) if bounds is None else bounds
+    lo, hi = _args.bounds(_fail, name, _auto_bounds(name, v), cells) if bounds is None else bounds
     return _simplify(name, v, faces, cells, lo, hi, placement, stabilise)
 
 
@@ -258,11 +201,11 @@ def run_lengths(v: torch.Tensor, faces: torch.Tensor, cells: int, bounds=None) -
     """int64 ``[cells_occupied]``: how many records each occupied cell's lane walks, in ascending cell order -- the serial depth of the
     cell stage.  Plain device torch ops on the sorted records."""
     name = "run_lengths"
-    cells = _check_cells(name, cells)
+    cells = _args.integer(_fail, name, "cells", cells, 1, MAX_CELLS)
     if bounds is not None:
-        bounds = _check_bounds(name, bounds, cells)
+        bounds = _args.bounds(_fail, name, bounds, cells)
     v, faces = _check_mesh(name, v, faces)
-    lo, hi = _check_bounds(name, _auto_bounds(name, v), cells) if bounds is None else bounds
+    lo, hi = _args.bounds(_fail, name, _auto_bounds(name, v), cells) if bounds is None else bounds
     if int(faces.shape[0]) == 0:
         return torch.zeros(0, dtype=torch.int64, device=v.device)
     records = torch.sort(_keys(v, faces, cells, lo, hi)[1])[0]
@@ -273,7 +216,7 @@ def edge_stats(faces: torch.Tensor) -> EdgeStats:
     """``(edges, boundary_edges, nonmanifold_edges, closed)`` of ``faces`` int32 ``[Nt, 3]`` (indices >= 0): sort and ``unique_consecutive`` of 64-bit
     edge keys on the device, one readback.  No triangle: ``(0, 0, 0, True)``."""
     name = "edge_stats"
-    faces = _check_faces(name, faces)
+    faces = _args.placed(_fail, name, "faces", _args.typed_rows(_fail, name, "faces", faces, torch.int32, MAX_TRIANGLES))    # torch ops only: any layout
     if int(faces.shape[0]) == 0:
         return EdgeStats(0, 0, 0, True)
     f = faces.long()

@@ -13,6 +13,7 @@ flat index ``(i G + j) G + k`` and the centre ``lo + (index + 0.5) h`` per axis.
 from __future__ import annotations
 
 import dataclasses
+import functools
 import json
 import math
 from typing import Optional
@@ -20,7 +21,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _capi
+from . import _args, _capi
 
 __all__ = ["KeyPoints", "visual_hull", "distance_transform_sq", "greedy_cover", "init_spheres", "cover_occupancy", "voxel_centres", "MAX_GRID"]
 
@@ -60,41 +61,17 @@ class KeyPoints:
         return cls(np.asarray(skel["pt"], dtype=np.float64).reshape(-1, 3), np.asarray(skel["r"], dtype=np.float64).reshape(-1))
 
 
-# ---- argument checks (the way tssplat_amd/dr.py checks its own: device, dtype, contiguity, shapes, the argument by name) ----
-def _fail(name: str, what: str):
-    raise RuntimeError(f"tssplat_amd.spheres_init.{name}: {what}")
+# ---- argument checks: the shared ones live in tssplat_amd/_args.py; here are the order and what only this module checks ----
+_fail = functools.partial(_args.fail, "spheres_init")
 
 
-def _check_grid(name: str, grid) -> int:
-    if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or not 1 <= int(grid) <= MAX_GRID:
-        _fail(name, f"grid must be an integer in 1 .. {MAX_GRID}, got {grid!r}")
-    return int(grid)
-
-
-def _check_bounds(name: str, bounds):
-    try:
-        lo, hi = float(bounds[0]), float(bounds[1])
-        two = len(bounds) == 2
-    except (TypeError, ValueError, IndexError):
-        lo = hi = math.nan
-        two = False
-    if not two or not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
-        _fail(name, f"bounds must be (lo, hi), finite, with lo < hi, got {bounds!r}")
-    return lo, hi
-
-
-def _check_gpu(name: str, arg: str, t, dtype, device=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback)")
-    if t.dtype != dtype:
-        _fail(name, f"{arg} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-    if device is not None and t.device != device:
-        _fail(name, f"{arg} must live on the same device as the first tensor argument ({device}), got {t.device}")
-    return t.contiguous()
+def _tensor(name: str, arg: str, t, dtype, device=None) -> torch.Tensor:
+    """On a GPU, of ``dtype``, on ``device``; a tensor that is not contiguous is copied."""
+    return _args.gpu_tensor(_fail, name, arg, t, dtype, device).contiguous()
 
 
 def _check_volume(name: str, arg: str, t, dtype, device=None, grid=None) -> torch.Tensor:
-    t = _check_gpu(name, arg, t, dtype, device)
+    t = _tensor(name, arg, t, dtype, device)
     if t.dim() != 3 or not (t.shape[0] == t.shape[1] == t.shape[2]) or not 1 <= t.shape[0] <= MAX_GRID or (grid is not None and t.shape[0] != grid):
         want = f"[{grid}, {grid}, {grid}]" if grid is not None else f"[G, G, G] with G in 1 .. {MAX_GRID}"
         _fail(name, f"{arg} must be {want}, got {tuple(t.shape)}")
@@ -102,25 +79,19 @@ def _check_volume(name: str, arg: str, t, dtype, device=None, grid=None) -> torc
 
 
 def _check_cover_params(name: str, n_spheres, min_radius, shrink):
-    if isinstance(n_spheres, bool) or not isinstance(n_spheres, (int, np.integer)) or not 0 <= int(n_spheres) <= _MAX_SPHERES:
-        _fail(name, f"n_spheres must be an integer in 0 .. 2^20, got {n_spheres!r}")
+    n_spheres = _args.integer(_fail, name, "n_spheres", n_spheres, 0, _MAX_SPHERES, "2^20")
     min_radius, shrink = float(min_radius), float(shrink)
     if not (math.isfinite(min_radius) and min_radius >= 0.0):
         _fail(name, f"min_radius must be finite and not negative, got {min_radius!r}")
     if not (math.isfinite(shrink) and shrink > 0.0):
         _fail(name, f"shrink must be finite and positive, got {shrink!r}")
-    return int(n_spheres), min_radius, shrink
-
-
-def _lib_and_stream(device):
-    from .tet_spheres_ext import _device_ctx, _stream_ptr
-    return _capi.load(), _device_ctx(device), _stream_ptr(device)
+    return n_spheres, min_radius, shrink
 
 
 def voxel_centres(grid: int, bounds=(-1.0, 1.0)) -> np.ndarray:
     """float32 ``[G]``: the voxel centres along one axis, ``lo + (index + 0.5) h`` in float64, rounded once."""
-    grid = _check_grid("voxel_centres", grid)
-    lo, hi = _check_bounds("voxel_centres", bounds)
+    grid = _args.integer(_fail, "voxel_centres", "grid", grid, 1, MAX_GRID)
+    lo, hi = _args.bounds(_fail, "voxel_centres", bounds)
     h = (hi - lo) / grid
     return (lo + (np.arange(grid, dtype=np.float64) + 0.5) * h).astype(np.float32)
 
@@ -132,25 +103,24 @@ def _cover_constants(grid: int, lo: float, hi: float, min_radius: float, shrink:
 
 # ---- the three stages ----
 def _hull(name, alpha, mvp, grid, bounds, threshold, channel) -> torch.Tensor:
-    grid = _check_grid(name, grid)
-    lo, hi = _check_bounds(name, bounds)
-    alpha = _check_gpu(name, "alpha", alpha, torch.float32)
+    grid = _args.integer(_fail, name, "grid", grid, 1, MAX_GRID)
+    lo, hi = _args.bounds(_fail, name, bounds)
+    alpha = _tensor(name, "alpha", alpha, torch.float32)
     if alpha.dim() != 4 or alpha.shape[0] < 1 or alpha.shape[3] < 1 or not (1 <= alpha.shape[1] <= 8192 and 1 <= alpha.shape[2] <= 8192):
         _fail(name, f"alpha must be [B, H, W, C] with B, C >= 1 and H, W in 1 .. 8192, got {tuple(alpha.shape)}")
     B, H, W, Cn = (int(s) for s in alpha.shape)
-    mvp = _check_gpu(name, "mvp", mvp, torch.float32, alpha.device)
+    mvp = _tensor(name, "mvp", mvp, torch.float32, alpha.device)
     if tuple(mvp.shape) != (B, 4, 4):
         _fail(name, f"mvp must be [{B}, 4, 4] (one matrix per view of alpha), got {tuple(mvp.shape)}")
-    if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or not 0 <= int(channel) < Cn:
-        _fail(name, f"channel must be an integer in 0 .. {Cn - 1}, got {channel!r}")
+    channel = _args.integer(_fail, name, "channel", channel, 0, Cn - 1)
     threshold = float(threshold)
     if math.isnan(threshold):
         _fail(name, "threshold is NaN")
-    lib, ctx, stream = _lib_and_stream(alpha.device)
+    lib, ctx, stream = _args.lib_and_stream(alpha.device)
     bits = torch.empty((B, H, (W + 31) // 32), dtype=torch.int32, device=alpha.device)
     hull = torch.empty((grid, grid, grid), dtype=torch.bool, device=alpha.device)
     with ctx:
-        _capi.check(lib.tsamd_hull_carve(alpha.data_ptr(), B, H, W, Cn, int(channel), threshold, mvp.data_ptr(), grid, lo, hi, bits.data_ptr(),
+        _capi.check(lib.tsamd_hull_carve(alpha.data_ptr(), B, H, W, Cn, channel, threshold, mvp.data_ptr(), grid, lo, hi, bits.data_ptr(),
                                          hull.data_ptr(), stream))
     return hull
 
@@ -168,7 +138,7 @@ def visual_hull(alpha: torch.Tensor, mvp: torch.Tensor, grid: int = 72, bounds=(
 def _edt(mask: torch.Tensor):
     """(d2, status): enqueues the three passes; ``status`` (one int32 on the device) is 1 when the mask has a false voxel."""
     G = int(mask.shape[0])
-    lib, ctx, stream = _lib_and_stream(mask.device)
+    lib, ctx, stream = _args.lib_and_stream(mask.device)
     d2 = torch.empty((G, G, G), dtype=torch.int32, device=mask.device)
     ws = torch.empty((G, G, G), dtype=torch.int32, device=mask.device)
     status = torch.empty(1, dtype=torch.int32, device=mask.device)
@@ -192,17 +162,16 @@ def _cover(hull, d2, n_spheres, lo, hi, min_radius, shrink):
     """(flat, q, count, uncovered) on the device: ``count`` launches record a ball, nothing synchronises."""
     G = int(hull.shape[0])
     _, s2, hs2, m2 = _cover_constants(G, lo, hi, min_radius, shrink)
-    lib, ctx, stream = _lib_and_stream(hull.device)
+    lib, ctx, stream = _args.lib_and_stream(hull.device)
     dev = hull.device
     ws = torch.empty(n_spheres + 1, dtype=torch.int64, device=dev)
     uncovered = torch.empty_like(hull)
     flat = torch.empty(n_spheres, dtype=torch.int32, device=dev)
     q = torch.empty(n_spheres, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t.numel() else None
     with ctx:
-        _capi.check(lib.tsamd_greedy_cover(hull.data_ptr(), d2.data_ptr(), G, n_spheres, s2, hs2, m2, ws.data_ptr(), uncovered.data_ptr(), ptr(flat), ptr(q),
-                                           count.data_ptr(), stream))
+        _capi.check(lib.tsamd_greedy_cover(hull.data_ptr(), d2.data_ptr(), G, n_spheres, s2, hs2, m2, ws.data_ptr(), uncovered.data_ptr(), _args.ptr(flat),
+                                           _args.ptr(q), count.data_ptr(), stream))
     return flat, q, count, uncovered
 
 
@@ -213,7 +182,7 @@ def greedy_cover(hull: torch.Tensor, d2: torch.Tensor, n_spheres: int, bounds=(-
     clear every voxel within ``sqrt(q) shrink`` voxels of it (``D2 <= q shrink^2``, one float64 product)."""
     hull = _check_volume("greedy_cover", "hull", hull, torch.bool)
     d2 = _check_volume("greedy_cover", "d2", d2, torch.int32, hull.device, int(hull.shape[0]))
-    lo, hi = _check_bounds("greedy_cover", bounds)
+    lo, hi = _args.bounds(_fail, "greedy_cover", bounds)
     n_spheres, min_radius, shrink = _check_cover_params("greedy_cover", n_spheres, min_radius, shrink)
     flat, q, count, uncovered = _cover(hull, d2, n_spheres, lo, hi, min_radius, shrink)
     S = int(count.item())                                    # the one readback
@@ -228,7 +197,7 @@ def init_spheres(alpha: torch.Tensor, mvp: torch.Tensor, n_spheres: int, grid: i
     name = "init_spheres"
     n_spheres, min_radius, shrink = _check_cover_params(name, n_spheres, min_radius, shrink)
     hull = _hull(name, alpha, mvp, grid, bounds, threshold, channel)
-    lo, hi = _check_bounds(name, bounds)
+    lo, hi = _args.bounds(_fail, name, bounds)
     return _cover_occupancy(name, hull, n_spheres, lo, hi, min_radius, shrink, "the visual hull")
 
 
@@ -257,6 +226,6 @@ def cover_occupancy(occ: torch.Tensor, n_spheres: int, bounds=(-1.0, 1.0), min_r
     to back with one readback.  ``hull_fraction`` is the occupied fraction of the grid.  A grid without a false voxel: ``ValueError``."""
     name = "cover_occupancy"
     occ = _check_volume(name, "occ", occ, torch.bool)
-    lo, hi = _check_bounds(name, bounds)
+    lo, hi = _args.bounds(_fail, name, bounds)
     n_spheres, min_radius, shrink = _check_cover_params(name, n_spheres, min_radius, shrink)
     return _cover_occupancy(name, occ, n_spheres, lo, hi, min_radius, shrink, "occ")

@@ -21,12 +21,11 @@ Out of scope: an exact float winding number, sparse workspaces, 16-bit deposits.
 from __future__ import annotations
 
 import dataclasses
-import math
+import functools
 
-import numpy as np
 import torch
 
-from . import _capi, merge
+from . import _args, _capi, merge
 
 __all__ = ["VoxelWinding", "VoxelOccupancy", "winding", "occupancy", "mesh_volume_iou", "workspace_bytes", "RULES", "MIN_GRID", "MAX_GRID", "SUBCELL_BITS",
            "LANE_COLUMNS"]
@@ -67,75 +66,32 @@ class VoxelOccupancy:
     wave_faces: int = 0
 
 
-def _fail(name: str, what: str):
-    raise RuntimeError(f"tssplat_amd.voxelize.{name}: {what}")
-
-
-def _check_grid(name: str, grid) -> int:
-    if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or not MIN_GRID <= int(grid) <= MAX_GRID:
-        _fail(name, f"grid must be an integer in {MIN_GRID} .. {MAX_GRID}, got {grid!r}")
-    return int(grid)
-
-
-def _check_bounds(name: str, bounds, grid: int):
-    try:
-        lo, hi = float(bounds[0]), float(bounds[1])
-        two = len(bounds) == 2
-    except (TypeError, ValueError, IndexError):
-        lo = hi = math.nan
-        two = False
-    if not two or not (math.isfinite(lo) and math.isfinite(hi) and lo < hi and math.isfinite(hi - lo) and (hi - lo) / grid > 0.0):
-        _fail(name, f"bounds must be (lo, hi), finite, with lo < hi, got {bounds!r}")
-    return lo, hi
-
-
-def _check_rows(name: str, arg: str, t, dtype) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback), got {type(t).__name__}")
-    if t.dtype != dtype:
-        _fail(name, f"{arg} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] > 2 ** 31 - 1:
-        _fail(name, f"{arg} must be [N, 3] with N <= {2 ** 31 - 1}, got {tuple(t.shape)}")
-    return t
+# ---- argument checks: the shared ones live in tssplat_amd/_args.py; here are the order and what only this module checks ----
+_fail = functools.partial(_args.fail, "voxelize")
+_ptr = _args.ptr
 
 
 def _check_mesh(name: str, v, faces, v_arg: str = "v", f_arg: str = "faces", device=None):
-    """Types and shapes of both first, then where they live."""
-    v, faces = _check_rows(name, v_arg, v, torch.float32), _check_rows(name, f_arg, faces, torch.int32)
-    for arg, t in ((v_arg, v), (f_arg, faces)):
-        if not t.is_cuda:
-            _fail(name, f"{arg} must be a GPU tensor (there is no CPU fallback)")
-        device = t.device if device is None else device
-        if t.device != device:
-            _fail(name, f"{arg} must live on the same device as the first tensor argument ({device}), got {t.device}")
-    return v.detach().contiguous(), faces.detach().contiguous()
-
-
-def _check_rule(name: str, rule) -> str:
-    if not isinstance(rule, str) or rule not in RULES:
-        _fail(name, f"rule must be one of {', '.join(repr(r) for r in RULES)}, got {rule!r}")
-    return rule
+    """Types and shapes of both first, then where they live; a tensor that is not contiguous is copied."""
+    v, faces = _args.triangle_mesh(_fail, name, v, faces, 2 ** 31 - 1, v_arg, f_arg, device)
+    return v.contiguous(), faces.contiguous()
 
 
 def _check_rays(name: str, rays) -> int:
-    if isinstance(rays, bool) or not isinstance(rays, (int, np.integer)) or int(rays) not in (1, 3):
+    if not _args.is_int(rays) or int(rays) not in (1, 3):
         _fail(name, f"rays must be 1 or 3, got {rays!r}")
     return int(rays)
 
 
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
 def workspace_bytes(grid: int) -> int:
     """``tsamd_voxel_workspace_bytes``: room for the counts' copies and three rays' deposits, ``6144 + 3 (G + 1) G^2 x 4`` bytes."""
-    return int(_capi.load().tsamd_voxel_workspace_bytes(_check_grid("workspace_bytes", grid)))
+    return int(_capi.load().tsamd_voxel_workspace_bytes(_args.integer(_fail, "workspace_bytes", "grid", grid, MIN_GRID, MAX_GRID)))
 
 
 def _winding(v, faces, grid, lo, hi, axis):
     """(w, stats): enqueued; ``stats`` is the int64 record on the device."""
     dev = v.device
-    lib, ctx, stream = merge._lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     ws = torch.empty(_COUNT_WORDS + (grid + 1) * grid * grid, dtype=torch.int32, device=dev)
     w = torch.empty((grid, grid, grid), dtype=torch.int32, device=dev)
     stats = torch.empty(_STATS, dtype=torch.int64, device=dev)
@@ -148,7 +104,7 @@ def _winding(v, faces, grid, lo, hi, axis):
 def _occupancy(v, faces, grid, lo, hi, rule, rays):
     """(occ, stats): enqueued."""
     dev = v.device
-    lib, ctx, stream = merge._lib_and_stream(dev)
+    lib, ctx, stream = _args.lib_and_stream(dev)
     ws = torch.empty(_COUNT_WORDS + rays * (grid + 1) * grid * grid, dtype=torch.int32, device=dev)
     occ = torch.empty((grid, grid, grid), dtype=torch.uint8, device=dev)
     stats = torch.empty(_STATS, dtype=torch.int64, device=dev)
@@ -168,9 +124,9 @@ def winding(v: torch.Tensor, faces: torch.Tensor, grid: int, bounds, axis: int =
     counted along ``axis`` (0: rays along i, 1: j, 2: k).  Parts of the mesh outside the cube are clipped; what lies before the first
     node of a column still counts for it.  One readback: the counts."""
     name = "winding"
-    grid = _check_grid(name, grid)
-    lo, hi = _check_bounds(name, bounds, grid)
-    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or int(axis) not in (0, 1, 2):
+    grid = _args.integer(_fail, name, "grid", grid, MIN_GRID, MAX_GRID)
+    lo, hi = _args.bounds(_fail, name, bounds, grid)
+    if not _args.is_int(axis, 0, 2):
         _fail(name, f"axis must be 0, 1 or 2, got {axis!r}")
     axis = int(axis)
     v, faces = _check_mesh(name, v, faces)
@@ -184,9 +140,9 @@ def occupancy(v: torch.Tensor, faces: torch.Tensor, grid: int, bounds, rule: str
     ``"positive"`` or ``"odd"``.  ``rays=1`` counts along axis 0; ``rays=3`` takes the majority of the three axes' bits, which out-votes a
     column spoilt by a hole or a fin of the mesh.  No winding array is written.  One readback: the counts."""
     name = "occupancy"
-    grid = _check_grid(name, grid)
-    lo, hi = _check_bounds(name, bounds, grid)
-    rule = _check_rule(name, rule)
+    grid = _args.integer(_fail, name, "grid", grid, MIN_GRID, MAX_GRID)
+    lo, hi = _args.bounds(_fail, name, bounds, grid)
+    rule = _args.choice(_fail, name, "rule", rule, RULES)
     rays = _check_rays(name, rays)
     v, faces = _check_mesh(name, v, faces)
     occ, stats = _occupancy(v, faces, grid, lo, hi, rule, rays)
@@ -199,18 +155,18 @@ def mesh_volume_iou(v_a: torch.Tensor, f_a: torch.Tensor, v_b: torch.Tensor, f_b
     :class:`VoxelOccupancy` records.  ``bounds=None``: :func:`tssplat_amd.merge.default_bounds` over both vertex sets (``grid >= 5``; one
     more readback).  One readback: both records and the four counts."""
     name = "mesh_volume_iou"
-    grid = _check_grid(name, grid)
-    rule = _check_rule(name, rule)
+    grid = _args.integer(_fail, name, "grid", grid, MIN_GRID, MAX_GRID)
+    rule = _args.choice(_fail, name, "rule", rule, RULES)
     rays = _check_rays(name, rays)
     if bounds is not None:
-        bounds = _check_bounds(name, bounds, grid)
+        bounds = _args.bounds(_fail, name, bounds, grid)
     v_a, f_a = _check_mesh(name, v_a, f_a, "v_a", "f_a")
     v_b, f_b = _check_mesh(name, v_b, f_b, "v_b", "f_b", v_a.device)
-    lo, hi = _check_bounds(name, merge.default_bounds(torch.cat([v_a, v_b]), grid), grid) if bounds is None else bounds
+    lo, hi = _args.bounds(_fail, name, merge.default_bounds(torch.cat([v_a, v_b]), grid), grid) if bounds is None else bounds
     occ_a, stats_a = _occupancy(v_a, f_a, grid, lo, hi, rule, rays)
     occ_b, stats_b = _occupancy(v_b, f_b, grid, lo, hi, rule, rays)
     counts = torch.stack([(occ_a & occ_b).sum(), (occ_a | occ_b).sum(), occ_a.sum(), occ_b.sum()])
     host = torch.cat([counts, stats_a, stats_b]).cpu().numpy()
     inter, union, inside_a, inside_b = (int(x) for x in host[:4])
-    return {"iou": merge._iou_of_counts(inter, union), "inside_a": inside_a, "inside_b": inside_b,
+    return {"iou": merge.iou_of_counts(inter, union), "inside_a": inside_a, "inside_b": inside_b,
             "a": _occupancy_record(occ_a, host[4:4 + _STATS], rays), "b": _occupancy_record(occ_b, host[4 + _STATS:], rays), "grid": grid, "bounds": (lo, hi)}
