@@ -92,6 +92,57 @@ MESHES = {"s1_sphere": lambda: _golden("s1_sphere"), "mario": lambda: _golden("m
           "tetrahedron": _tetrahedron, "plane": _plane, "collinear": _collinear, "fan": _fan}
 
 
+# ---- the launch edges ----
+TOP_KEY = 1024 ** 3 - 1                            # the last cell of the finest grid: 2^30 - 1
+
+
+def _corner_mesh():
+    """On the bounds (0, 1): vertices exactly on lo and exactly on hi on all three axes (cell 0, and the last cell through the clamp),
+    on one or two axes, and on interior cell faces of C = 1024 (0.5 = 512 h, 0.25 = 256 h, 0.75 = 768 h)."""
+    v = np.array([[0, 0, 0], [1, 1, 1], [1, 0, 0], [0, 1, 0], [0.5, 0.5, 0.5], [0.25, 0.75, 0.5], [1, 1, 0], [0, 0, 1], [0.75, 1, 0.25], [1, 0.5, 1]], F32)
+    f = np.array([[0, 2, 3], [1, 3, 2], [0, 4, 1], [4, 5, 1], [2, 6, 1], [7, 0, 4], [8, 1, 5], [9, 1, 4], [6, 8, 1], [7, 4, 9]], np.int32)
+    return v, f
+
+
+def _first_triangles(n):
+    v, f = _golden("s1_sphere")
+    return v, np.ascontiguousarray(f[:n])
+
+
+def _first_vertices(n):
+    """The golden sphere's first n vertices and the faces among them."""
+    v, f = _golden("s1_sphere")
+    return np.ascontiguousarray(v[:n]), np.ascontiguousarray(f[(f < n).all(axis=1)])
+
+
+DEDUPE_CELLS = 8
+
+
+def _sorted_survivors(v, f, cells, bounds=None):
+    """The input indices of the faces with three distinct cells, in the order of (rotated cell triple, input index): the order the
+    dedupe walks.  From the oracle's vertex keys alone."""
+    keys = SO.simplify(v, f, cells, bounds)["vertex_keys"][f]
+    assert (keys >= 0).all()
+    idx = np.nonzero((keys[:, 0] != keys[:, 1]) & (keys[:, 0] != keys[:, 2]) & (keys[:, 1] != keys[:, 2]))[0]
+    rot = np.stack([np.roll(row, -int(row.argmin())) for row in keys[idx]])
+    return idx[np.lexsort((idx, rot[:, 2], rot[:, 1], rot[:, 0]))], idx
+
+
+def _dedupe_boundary_mesh():
+    """The golden sphere with the survivor at sorted position 255 moved to input index 255 and a rotated copy of it inserted at input
+    index 256: the pair sits at input indices 255 | 256 and at sorted positions 255 | 256, either side of a workgroup."""
+    v, f = _golden("s1_sphere")
+    order, _ = _sorted_survivors(v, f, DEDUPE_CELLS)
+    f = f.copy()
+    x = int(order[255])
+    f[[255, x]] = f[[x, 255]]
+    return v, np.ascontiguousarray(np.insert(f, 256, f[255][[1, 2, 0]], axis=0))
+
+
+MESHES.update({"corners": _corner_mesh, "tri256": lambda: _first_triangles(256), "tri257": lambda: _first_triangles(257), "vert256": lambda: _first_vertices(256),
+               "vert257": lambda: _first_vertices(257), "dedupe_boundary": _dedupe_boundary_mesh})
+
+
 @functools.lru_cache(maxsize=None)
 def _oracle(mesh, cells, bounds=None, placement="quadric"):
     return SO.simplify(*MESHES[mesh](), cells, bounds, placement)
@@ -206,6 +257,74 @@ def test_oracle_other_cases_and_edge_stats():
     v = np.array([[0.1, 0.1, 0.1], [0.9, 0.1, 0.1], [0.1, 0.9, 0.1], [0.15, 0.12, 0.1]], F32)
     r = SO.simplify(v, np.array([[0, 1, 2], [2, 1, 0], [1, 2, 3], [3, 1, 2]], np.int32), 2, (0.0, 1.0))
     assert r["faces"].tolist() == [[0, 2, 1], [0, 1, 2]] and r["duplicates"] == 2
+
+
+# ---------------------------------------------------------------- CPU: the launch edges are reached ----------------------------------------------------------------
+FINE_CELLS = [1023, 1024]
+BLOCK_MESHES = ["tri256", "tri257", "vert256", "vert257"]
+BLOCK_CELLS = 64
+UNIT01 = (0.0, 1.0)
+
+
+def _fine_preconditions(mesh, cells):
+    """Keys need 30 bits: the decode in the run walk and every 32-bit product on the way are exercised."""
+    r = _oracle(mesh, cells)
+    assert r["cell_keys"].max() >= 2 ** 29 and r["faces"].shape[0] > 0.9 * MESHES[mesh]()[1].shape[0]
+    return r
+
+
+@pytest.mark.parametrize("cells", FINE_CELLS)
+@pytest.mark.parametrize("mesh", ["s1_sphere", "mario"])
+def test_edge_finest_grids_are_reached(mesh, cells):
+    _fine_preconditions(mesh, cells)
+
+
+def _corner_preconditions(cells, placement="quadric"):
+    r = _oracle("corners", cells, UNIT01, placement)
+    top = cells ** 3 - 1
+    v, f = _corner_mesh()
+    assert r["vertex_keys"][0] == 0 and r["vertex_keys"][1] == top == r["cell_keys"].max() == r["keys"].max() and r["keys"].min() == 0
+    assert (r["faces"] == r["v"].shape[0] - 1).any(axis=1).sum() >= 3                        # faces that survive with the last cell as a corner
+    assert r["invalid_faces"] == 0 and r["degenerate_faces"] == 0 and r["faces"].shape[0] == f.shape[0]
+    if cells == 1024:
+        assert top == TOP_KEY == 2 ** 30 - 1
+        on_face = (v * 1024 == np.floor(v * 1024)).all(axis=1) & ((v > 0) & (v < 1)).all(axis=1)
+        assert on_face.sum() >= 2                                                             # vertices on interior cell faces
+    return r
+
+
+@pytest.mark.parametrize("cells", FINE_CELLS + [4])
+def test_edge_corner_cells_are_reached(cells):
+    for placement in SO.PLACEMENTS:
+        r = _corner_preconditions(cells, placement)
+        print(f"corners C={cells} {placement}: clamped {r['clamped']} of {r['cells_occupied']} cells")
+    assert cells != 1023 or _corner_preconditions(cells, "quadric")["clamped"] > 0           # at 1023 the count is not trivially 0
+
+
+def _block_preconditions(mesh):
+    v, f = MESHES[mesh]()
+    r = _oracle(mesh, BLOCK_CELLS)
+    assert r["faces"].shape[0] > 0 and r["invalid_faces"] == 0
+    if mesh.startswith("tri"):
+        assert f.shape[0] == int(mesh[-3:]) and len(set(r["vertex_keys"][f[-1]].tolist())) == 3      # the last face has three cells: it survives
+    else:
+        assert v.shape[0] == int(mesh[-3:]) and (f == v.shape[0] - 1).any() and r["vertex_keys"][-1] in r["keys"]     # the last vertex's cell is in the output
+
+
+@pytest.mark.parametrize("mesh", BLOCK_MESHES)
+def test_edge_block_sized_meshes_are_reached(mesh):
+    """256: the last lane of a workgroup is the last item.  257: a workgroup of one lane."""
+    _block_preconditions(mesh)
+
+
+def test_edge_dedupe_across_a_workgroup_is_reached():
+    v, f = _dedupe_boundary_mesh()
+    assert f.shape[0] == 2997 and f[256].tolist() == f[255][[1, 2, 0]].tolist()
+    order, survivors = _sorted_survivors(v, f, DEDUPE_CELLS)
+    assert order[255] == 255 and order[256] == 256                                           # sorted positions 255 | 256: order[p - 1] is another workgroup's
+    before = _oracle("s1_sphere", DEDUPE_CELLS)
+    r = _oracle("dedupe_boundary", DEDUPE_CELLS)
+    assert r["duplicates"] == before["duplicates"] + 1 and r["faces"].shape[0] == before["faces"].shape[0]
 
 
 # ---------------------------------------------------------------- CPU: plumbing and argument checks ----------------------------------------------------------------
@@ -396,6 +515,43 @@ def test_edge_stats_equals_numpy():
     assert simplify.edge_stats(dev(_oracle("s1_sphere", 16)["faces"])).closed
     for faces in (_plane()[1], np.array([[0, 1, 2], [0, 1, 2]], np.int32), np.array([[0, 1, 2], [2, 1, 0]], np.int32), np.zeros((0, 3), np.int32)):
         assert tuple(simplify.edge_stats(dev(faces))) == _np_edge_stats(faces)
+
+
+# ---------------------------------------------------------------- GPU: the launch edges ----------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("cells", FINE_CELLS)
+@pytest.mark.parametrize("mesh", ["s1_sphere", "mario"])
+def test_edge_finest_grids(mesh, cells):
+    _fine_preconditions(mesh, cells)
+    _both(mesh, cells)
+
+
+@gpu
+@pytest.mark.parametrize("cells", FINE_CELLS + [4])
+def test_edge_corner_cells(cells):
+    want = _corner_preconditions(cells)
+    got = _both("corners", cells, UNIT01)
+    assert got.clamped == _oracle("corners", cells, UNIT01, "mean")["clamped"] and tuple(got.faces.shape) == want["faces"].shape
+    from tssplat_amd import simplify
+    quadric = simplify.simplify(*(dev(x) for x in _corner_mesh()), cells, bounds=UNIT01)
+    assert quadric.clamped == want["clamped"] and (cells != 1023 or quadric.clamped > 0)
+
+
+@gpu
+@pytest.mark.parametrize("mesh", BLOCK_MESHES)
+def test_edge_block_sized_meshes(mesh):
+    _block_preconditions(mesh)
+    assert tuple(_both(mesh, BLOCK_CELLS).faces.shape)[0] > 0
+    _both(mesh, 3, (-1.0, 1.0))
+
+
+@gpu
+def test_edge_dedupe_across_a_workgroup():
+    v, f = _dedupe_boundary_mesh()
+    order, _ = _sorted_survivors(v, f, DEDUPE_CELLS)
+    assert order[255] == 255 and order[256] == 256
+    got = _both("dedupe_boundary", DEDUPE_CELLS)
+    assert got.duplicates == _oracle("s1_sphere", DEDUPE_CELLS)["duplicates"] + 1
 
 
 # ---------------------------------------------------------------- GPU: end to end ----------------------------------------------------------------

@@ -170,6 +170,71 @@ def test_visual_hull_equals_oracle(G, B, HW):
         assert np.array_equal(other.cpu().numpy(), O.visual_hull(alpha, mvp, G, (-1.0, 1.0), THRESHOLD, 0))
 
 
+# The pack kernel writes two 32-bit words per 64 pixels, the second one only when the row has it.  Under the identity matrix clip_w = 1 and
+# ndc = (x, y) of the voxel centre, so with G >= max(H, W) every pixel decides some voxel and a wrong bit anywhere shows in the hull.
+PACK_HEIGHT = 5
+PACK_WIDTHS = [1, 31, 32, 33, 63, 64, 65, 96, 97, 128, 129]
+
+
+def _pack_grid(W):
+    return 33 if W <= 33 else min(G for G in (65, 129) if G >= W)
+
+
+@functools.lru_cache(maxsize=None)
+def _pack_scene(W):
+    """alpha [2, PACK_HEIGHT, W, 2]: random values around the threshold in both channels and both images, three pixels of channel 1 exactly
+    on it, one NaN and one pixel that is on in both images; two identity matrices."""
+    rng = np.random.default_rng(1000 + W)
+    alpha = (THRESHOLD + rng.uniform(-0.25, 0.4, (2, PACK_HEIGHT, W, 2))).astype(np.float32)
+    for n in range(3):
+        alpha[n % 2, (2 * n + 1) % PACK_HEIGHT, (7 * n + W // 2) % W, 1] = THRESHOLD
+    alpha[1, 2, W - 1, 1] = np.nan
+    alpha[:, 4, W - 1] = (0.125, 0.875)                                   # the row's last pixel: on in both images of channel 1, off in channel 0
+    return alpha, np.stack([np.eye(4, dtype=np.float32)] * 2)
+
+
+@functools.lru_cache(maxsize=None)
+def _pack_want(W):
+    alpha, mvp = _pack_scene(W)
+    return O.visual_hull(alpha, mvp, _pack_grid(W), (-1.0, 1.0), THRESHOLD, 1)
+
+
+def _pack_preconditions(W):
+    """Every pixel is the pixel of some voxel centre, and the pixels of the row's last word decide voxels of the hull."""
+    alpha, mvp = _pack_scene(W)
+    G, H = _pack_grid(W), PACK_HEIGHT
+    c = O.voxel_centres(G)
+    one, half = np.float32(1.0), np.float32(0.5)
+    px = np.minimum(W - 1, np.floor(((c + one) * half) * np.float32(W)).astype(np.int64))      # the oracle's pixel of ndc = c, c1 = c / 1
+    py = np.minimum(H - 1, np.floor(((c + one) * half) * np.float32(H)).astype(np.int64))
+    assert (np.abs(c) < 1).all() and set(px.tolist()) == set(range(W)) and set(py.tolist()) == set(range(H)) and G >= max(H, W)
+    assert (alpha[..., 1] == THRESHOLD).sum() == 3 and np.isnan(alpha[..., 1]).sum() == 1
+    words = (W + 31) // 32
+    cleared = alpha.copy()
+    cleared[:, :, 32 * (words - 1):, 1] = 0.0
+    want = _pack_want(W)
+    assert 0 < want.sum() < want.size
+    assert (O.visual_hull(cleared, mvp, G, (-1.0, 1.0), THRESHOLD, 1) != want).any()
+    assert (O.visual_hull(alpha, mvp, G, (-1.0, 1.0), THRESHOLD, 0) != want).any()             # the channel matters too
+
+
+@pytest.mark.parametrize("W", PACK_WIDTHS)
+def test_edge_pack_widths_are_reached(W):
+    _pack_preconditions(W)
+
+
+@gpu
+@pytest.mark.parametrize("W", PACK_WIDTHS)
+def test_edge_pack_widths(W):
+    """W <= 32: one word, the second must not be written.  65: two chunks, three words.  129: three chunks, five words."""
+    alpha, mvp = _pack_scene(W)
+    G, want = _pack_grid(W), _pack_want(W)
+    assert 0 < want.sum() < want.size
+    got = spheres_init.visual_hull(dev(alpha), dev(mvp), grid=G, threshold=THRESHOLD, channel=1)
+    assert got.dtype == torch.bool and tuple(got.shape) == (G, G, G)
+    assert np.array_equal(got.cpu().numpy(), want), (int(got.sum()), int(want.sum()))
+
+
 # ---------------------------------------------------------------- EDT ----------------------------------------------------------------
 @gpu
 @pytest.mark.parametrize("kind", ["random", "corner", "plane", "all_false"])
@@ -246,6 +311,85 @@ def test_greedy_cover_without_shrink_and_repeatable():
     b = spheres_init.greedy_cover(dev(hull), dev(d2), 12, min_radius=0.01)
     for x, y in zip(a, b):
         assert x.cpu().numpy().tobytes() == y.cpu().numpy().tobytes()
+
+
+# greedy_cover_kernel strides over kCoverBlocks * 256 voxels; at G = 96 the volume takes two trips.
+COVER_STRIDE = 2048 * 256
+STRIDE_GRID = 96
+
+
+@functools.lru_cache(maxsize=None)
+def _stride_balls():
+    """_two_balls at G = 96: the balls of radius 10 around i = 20 and i = 75 lie on either side of flat index COVER_STRIDE."""
+    G = STRIDE_GRID
+    i, j, k = np.meshgrid(*(np.arange(G),) * 3, indexing="ij")
+    hull = np.zeros((G, G, G), dtype=bool)
+    for ci in (20, G - 1 - 20):
+        hull |= (i - ci) ** 2 + (j - 48) ** 2 + (k - 47) ** 2 <= 100
+    return hull, O.distance_transform_sq(hull)
+
+
+def _upper_ball():
+    """Only the ball whose voxels all lie at or past COVER_STRIDE (d2 inside it is unchanged: the other ball is far away)."""
+    hull, d2 = _stride_balls()
+    upper = hull.copy()
+    upper[:STRIDE_GRID // 2] = False
+    return upper, np.where(upper, d2, 0).astype(np.int32)
+
+
+STRIDE_RUNS = {"defaults": dict(n=2), "min_radius": dict(n=64, min_radius=0.027), "no_shrink": dict(n=12, shrink=1.0, min_radius=0.02)}
+
+
+@functools.lru_cache(maxsize=None)
+def _stride_want(run, upper=False):
+    kw = dict(STRIDE_RUNS[run])
+    return O.greedy_cover(*(_upper_ball() if upper else _stride_balls()), kw.pop("n"), **kw)
+
+
+def _stride_preconditions():
+    hull, d2 = _stride_balls()
+    assert hull.size > COVER_STRIDE and hull.size <= 2 * COVER_STRIDE
+    top = np.nonzero(d2.reshape(-1) == d2.max())[0]
+    assert top.tolist() == [(20 * 96 + 48) * 96 + 47, (75 * 96 + 48) * 96 + 47] and top[0] < COVER_STRIDE <= top[1]       # the two maxima tie
+    flat, q, _ = _stride_want("defaults")
+    assert flat.tolist() == top.tolist() and q[0] == q[1] == d2.max()                          # ... and the lower index goes first
+    flat, q, unc = _stride_want("min_radius")
+    assert 2 < len(flat) < STRIDE_RUNS["min_radius"]["n"] and unc.any() and (flat < COVER_STRIDE).any() and (flat >= COVER_STRIDE).any()
+    flat, q, unc = _stride_want("no_shrink")
+    assert len(flat) >= 2
+    upper, _ = _upper_ball()
+    assert upper.any() and np.nonzero(upper.reshape(-1))[0].min() >= COVER_STRIDE
+    flat, q, unc = _stride_want("min_radius", True)
+    assert len(flat) > 1 and (flat >= COVER_STRIDE).all()
+
+
+def test_edge_cover_stride_is_reached():
+    _stride_preconditions()
+
+
+@gpu
+@pytest.mark.parametrize("run", sorted(STRIDE_RUNS))
+def test_edge_cover_stride(run):
+    hull, d2 = _stride_balls()
+    top = np.nonzero(d2.reshape(-1) == d2.max())[0]
+    assert len(top) == 2 and top[0] < COVER_STRIDE <= top[1]
+    kw = dict(STRIDE_RUNS[run])
+    n = kw.pop("n")
+    flat, q, unc = spheres_init.greedy_cover(dev(hull), dev(d2), n, **kw)
+    wf, wq, wu = _stride_want(run)
+    assert flat.dtype == torch.int64 and q.dtype == torch.int32 and unc.dtype == torch.bool
+    assert np.array_equal(flat.cpu().numpy(), wf) and np.array_equal(q.cpu().numpy(), wq) and np.array_equal(unc.cpu().numpy(), wu)
+    assert len(wf) >= 2 and wf[0] == top[0] and wf[1] == top[1]
+
+
+@gpu
+def test_edge_cover_finds_what_lies_past_the_first_stride():
+    hull, d2 = _upper_ball()
+    assert np.nonzero(hull.reshape(-1))[0].min() >= COVER_STRIDE
+    kw = dict(STRIDE_RUNS["min_radius"])
+    flat, q, unc = spheres_init.greedy_cover(dev(hull), dev(d2), kw.pop("n"), **kw)
+    wf, wq, wu = _stride_want("min_radius", True)
+    assert len(wf) > 1 and np.array_equal(flat.cpu().numpy(), wf) and np.array_equal(q.cpu().numpy(), wq) and np.array_equal(unc.cpu().numpy(), wu)
 
 
 # ---------------------------------------------------------------- end to end ----------------------------------------------------------------
