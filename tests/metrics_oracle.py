@@ -10,7 +10,7 @@ in area, never a triangle of weight 0.  Its barycentrics are the 24-bit integers
 ``ib = mix64(seed, 3 i + 2) >> 40``; if ``ia + ib > 2^24`` -- ``a + b > 1`` decided exactly, not after a float32 sum that would
 round ``1 + 2^-24`` to 1 -- both are replaced by ``2^24`` minus themselves, and ``a = ia 2^-24``, ``b = ib 2^-24`` are exact in
 float32.  The point is ``(A + a (B - A)) + b (C - A)`` in float32, every operation rounded on its own; the normal is the float64
-``(nx, ny, nz) / w`` cast to float32.
+``(nx, ny, nz) / w`` cast to float32.  ``draw`` is everything after the prefix sum, for prefix sums written by hand.
 
 ``mix64(seed, c)``: splitmix64's finaliser over ``seed + (c + 1) 0x9E3779B97F4A7C15`` modulo 2^64.
 
@@ -82,10 +82,21 @@ def sample_surface(v, faces, n: int, seed: int) -> SimpleNamespace:
     f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
     q = integer_weights(v, f)
     C = np.cumsum([int(x) for x in q], dtype=object) if q.size else np.zeros(0, dtype=object)      # Python integers
-    Q = int(C[-1]) if q.size else 0
-    if Q == 0:
+    if (int(C[-1]) if q.size else 0) == 0:
         raise RuntimeError("metrics_oracle.sample_surface: faces holds no triangle of positive area")
-    assert Q < 1 << 63
+    s = draw(v, f, C, n, seed)
+    s.q = q
+    return s
+
+
+def draw(v, faces, C, n: int, seed: int) -> SimpleNamespace:
+    """The part of ``sample_surface`` after the prefix sum: ``n`` samples under the inclusive prefix sums ``C`` (integers, ``[T]``,
+    non-decreasing from non-negative weights, ``0 < C[T - 1] < 2^63``), whatever weights they were summed from.  ``p`` is returned too."""
+    v = np.asarray(v, dtype=F32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    C = np.array([int(x) for x in C], dtype=object)
+    Q = int(C[-1])
+    assert C.shape[0] == f.shape[0] and 0 < Q < 1 << 63
     i = np.arange(n, dtype=np.uint64)
     u = mix64_array(seed, np.uint64(3) * i)
     p = np.array([(int(x) * Q) >> 64 for x in u], dtype=np.uint64)                                # (u Q) >> 64 with Python integers
@@ -100,7 +111,7 @@ def sample_surface(v, faces, n: int, seed: int) -> SimpleNamespace:
         points = ((A + a[:, None] * (B - A)) + b[:, None] * (Cc - A)).astype(F32)
         nrm, w, _ = face_normals(v, f)
         normals = (nrm[tri] / w[tri][:, None]).astype(F32)
-    return SimpleNamespace(points=points, normals=normals, tri=tri.astype(np.int32), a=a, b=b, q=q, Q=Q)
+    return SimpleNamespace(points=points, normals=normals, tri=tri.astype(np.int32), a=a, b=b, p=p, Q=Q)
 
 
 NAN_KEY = np.uint32(0xFFFFFFFF)

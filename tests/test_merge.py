@@ -306,9 +306,10 @@ def test_build_lists_carry_the_merge_sources():
 
 
 # ---------------------------------------------------------------- GPU: the field ----------------------------------------------------------------
-def _field_both(tet_v, elem, G, bounds=UNIT):
+def _field_both(tet_v, elem, G, bounds=UNIT, want=None):
     from tssplat_amd import merge
-    want = U.union_field(tet_v, elem, G, bounds)
+    if want is None:
+        want = U.union_field(tet_v, elem, G, bounds)
     got = merge.union_field(dev(np.asarray(tet_v, np.float32).reshape(-1, 3)), dev(np.asarray(elem, np.int32).reshape(-1, 4)), G, bounds)
     assert got.dtype == torch.float32 and tuple(got.shape) == (G, G, G)
     got = got.cpu().numpy()
@@ -498,3 +499,155 @@ def test_renderer_export_merged_bakes_the_material(tmp_path):
     assert not stored[~owned].any()
     with pytest.raises(AssertionError):
         renderers.MeshRasterizer(geo).export_merged(str(tmp_path), "none")
+
+
+# ---------------------------------------------------------------- edges: lattice tets, exact ties and box limits on nodes ----------------------------------------------------------------
+# Random float corners never put a node exactly on a face plane, give two tets exactly the same value at a node, or put a box limit
+# (mn - lo) / h - 0.5 on an exact integer.  Tets with corners on grid nodes do all three: the bounds (-0.5, G - 0.5) make h = 1 and the
+# node positions the integers 0 .. G - 1, so every coordinate, difference and cross product below is an exact integer in float64.
+def _lattice_bounds(G):
+    return (-0.5, G - 0.5)
+
+
+@functools.lru_cache(maxsize=None)
+def _kuhn_block(step):
+    """The 48 Kuhn tets of a 2 x 2 x 2 block of cubes whose edges are `step` node steps long, with a corner on node (0, 0, 0):
+    (corners int64 [27, 3], elem int32 [48, 4]), every tet of positive volume."""
+    v = np.stack(np.meshgrid(*[np.arange(3)] * 3, indexing="ij"), -1).reshape(-1, 3) * step
+    elem = []
+    for origin in itertools.product(range(2), repeat=3):
+        for perm in U.PERMS:
+            chain = [np.array(origin)]
+            for ax in perm:
+                chain.append(chain[-1] + np.eye(3, dtype=np.int64)[ax])
+            ids = [int((c[0] * 3 + c[1]) * 3 + c[2]) for c in chain]
+            if U.perm_sign(perm) < 0:
+                ids[2], ids[3] = ids[3], ids[2]
+            elem.append(ids)
+    return v.astype(np.int64), np.asarray(elem, dtype=np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def _random_lattice_tets(count=400, seed=7):
+    """`count` random tets of positive volume with corners on the nodes 0 .. 7: (corners int64 [4 count, 3], elem int32 [count, 4])."""
+    rng = np.random.default_rng(seed)
+    tets = []
+    while len(tets) < count:
+        tet = rng.integers(0, 8, size=(4, 3))
+        vol = _det3(tet[1] - tet[0], tet[2] - tet[0], tet[3] - tet[0])
+        if vol != 0:
+            tets.append(tet if vol > 0 else tet[[0, 2, 1, 3]])
+    return np.concatenate(tets).astype(np.int64), np.arange(4 * count, dtype=np.int32).reshape(-1, 4)
+
+
+# On grid 48 the fixture is repeated at these node offsets (the same on all three axes), so that the first and the last plane of a
+# tet's box -- its smallest node coordinate - 1 and its largest + 1 -- fall on the planes 14, 15, 16, 17 around the slab seam at 16, and
+# on 31 and 32 around the next one.
+LATTICE = {"kuhn2": (lambda: _kuhn_block(2), (11, 12, 15, 16, 27, 28, 31, 32)), "kuhn4": (lambda: _kuhn_block(4), (9, 10, 11, 12, 13, 14, 26, 27, 28, 29)),
+           "random": (_random_lattice_tets, (10, 13, 26, 29)), "sparse": (lambda: _random_lattice_tets(96), (10, 13, 26, 29))}
+SEAM_PLANES = {14, 15, 16, 17, 31, 32}
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice_tets(name, G):
+    make, offsets = LATTICE[name]
+    v, elem = make()
+    if G == 8:
+        return v.astype(np.float32), elem
+    assert G == 48
+    return (np.concatenate([v + o for o in offsets]).astype(np.float32), np.concatenate([elem + n * len(v) for n in range(len(offsets))]).astype(np.int32))
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice_field(name, G):
+    return U.union_field(*_lattice_tets(name, G), G, _lattice_bounds(G))
+
+
+def _per_tet_minima(tet_v, elem, G):
+    """float64 [T, G, G, G]: each tet's own min over its four faces, -inf outside its box."""
+    return np.stack([U.union_field_f64(tet_v, elem[t:t + 1], G, _lattice_bounds(G)) for t in range(len(elem))])
+
+
+@pytest.mark.parametrize("name", sorted(LATTICE))
+def test_edge_lattice_tets_are_reached(name):
+    G = 8
+    tet_v, elem = _lattice_tets(name, G)
+    assert np.array_equal(U.node_positions(G, _lattice_bounds(G)), np.arange(8.0)) and (tet_v == np.round(tet_v)).all()
+    assert all(U.tet_contributes(tet_v, tet) for tet in elem)
+    f = U.union_field_f64(tet_v, elem, G, _lattice_bounds(G))
+    per = _per_tet_minima(tet_v, elem, G)
+    assert np.array_equal(per.max(axis=0), f)
+    zero = f == 0
+    plus = ((per == 0) & ~np.signbit(per)).any(axis=0)                       # some tet gives +0.0 here
+    minus_only = zero & np.signbit(f) & ~plus                                # the winner is -0.0 whatever the order of the tets
+    ties = (((per == f[None]) & np.isfinite(per)).sum(axis=0) >= 2)
+    positive = f > 0
+    lo, h = -0.5, 1.0
+    on_integer = sum(1 for tet in elem if all(((tet_v[tet, ax].astype(np.float64).min() - lo) / h - 0.5) % 1.0 == 0 for ax in range(3)))
+    print(f"{name}: tets {len(elem)} zeros {int(zero.sum())} of them -0.0 with no +0.0 beside it {int(minus_only.sum())} ties {int(ties.sum())} "
+          f"positive {int(positive.sum())} uncovered {int(np.isinf(f).sum())} tets with box limits on integers {on_integer}")
+    assert on_integer == len(elem)
+    # 400 random tets leave few nodes where -0.0 wins with no +0.0 beside it (somebody's face or interior covers most nodes): the sparse set
+    # is there for those, the dense one for the ties
+    want = {"kuhn2": dict(zeros=100, ties=100), "kuhn4": dict(zeros=100, ties=100, positive=1), "random": dict(zeros=100, ties=100, minus=1, positive=1),
+            "sparse": dict(zeros=100, minus=5, positive=1)}[name]
+    assert int(zero.sum()) >= want["zeros"] and int(ties.sum()) >= want.get("ties", 0)
+    assert int(positive.sum()) >= want.get("positive", 0) and int(minus_only.sum()) >= want.get("minus", 0)
+    out = U.union_field(tet_v, elem, G, _lattice_bounds(G))
+    assert not np.signbit(out[zero]).any() and out.tobytes() == _lattice_field(name, G).tobytes()
+
+
+@pytest.mark.parametrize("name", sorted(LATTICE))
+def test_edge_lattice_boxes_meet_the_slab_seams(name):
+    G = 48
+    tet_v, elem = _lattice_tets(name, G)
+    firsts, lasts = set(), set()
+    for tet in elem:
+        (i0, i1), _, _ = U.tet_box(tet_v[tet].astype(np.float64), G, -0.5, 1.0)
+        firsts.add(i0)
+        lasts.add(i1)
+    print(f"{name}: tets {len(elem)} first planes {sorted(firsts)} last planes {sorted(lasts)}")
+    assert SEAM_PLANES <= firsts and SEAM_PLANES <= lasts
+    f = _lattice_field(name, G)
+    assert (f == 0).sum() >= 100 and not np.signbit(f[f == 0]).any()
+
+
+def test_edge_lattice_extraction_is_reached():
+    """The lattice field at level exactly 0: the nodes that read 0 are outside, an edge from an inside node to one of them gets t = 1, and
+    the triangles that meet there are degenerate.  At the default level they are inside."""
+    G = 48
+    f = _lattice_field("kuhn4", G)
+    zeros = f == 0
+    level = U.default_level(G, _lattice_bounds(G))
+    assert zeros.sum() >= 100 and not U.occupancy(f, 0.0)[zeros].any() and U.occupancy(f, level)[zeros].all() and G ** 3 > 100 * 256
+    v, faces, _ = U.extract_surface(f, _lattice_bounds(G), 0.0)
+    p = v[faces].astype(np.float64)
+    flat = int((np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1) == 0).sum())
+    v1, faces1, _ = U.extract_surface(f, _lattice_bounds(G), level)
+    print(f"zeros {int(zeros.sum())} level 0: triangles {len(faces)} degenerate {flat}; default level: triangles {len(faces1)}")
+    assert flat > 0 and len(faces1) > 0
+
+
+@gpu
+@pytest.mark.parametrize("G", [8, 48])
+@pytest.mark.parametrize("name", sorted(LATTICE))
+def test_edge_lattice_tets(name, G):
+    _field_both(*_lattice_tets(name, G), G, _lattice_bounds(G), want=_lattice_field(name, G))
+
+
+@gpu
+def test_edge_lattice_tets_wave_tail():
+    """1 .. 9 tets: the last block of four waves holds 1, 2, 3 or 4 of them."""
+    tet_v, elem = _lattice_tets("kuhn2", 8)
+    for n in range(1, 10):
+        _field_both(tet_v, elem[:n], 8, _lattice_bounds(8))
+
+
+@gpu
+def test_edge_extraction_at_many_workgroups():
+    v, faces, closed = _extract_both(_random_field(33, 0, False), 0.0)
+    assert not closed and len(faces) > 10000
+    G = 48
+    f = _lattice_field("kuhn4", G)
+    _extract_both(f, float(U.default_level(G, _lattice_bounds(G))), _lattice_bounds(G))
+    _extract_both(f, 0.0, _lattice_bounds(G))

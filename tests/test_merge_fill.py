@@ -4,6 +4,7 @@ device results are compared with tests/fill_oracle.py bit for bit, and the oracl
 scipy.ndimage.label, the tree identity between node components and surface components, and the sub-mesh property."""
 import functools
 import inspect
+import itertools
 import os
 import sys
 
@@ -512,3 +513,198 @@ def test_renderer_export_merged_outer_writes_that_mesh(tmp_path):
     rv, rf, _, _, _ = atlas.load_textured_obj(str(tmp_path / "material"), "merged_surface")
     assert rv.tobytes() == want["v"].tobytes() and rf.tobytes() == want["faces"].tobytes()
     assert F.count_mesh_components(len(rv), rf) == 1
+
+
+# ---------------------------------------------------------------- edges: every neighbourhood on every tile seam ----------------------------------------------------------------
+# Which owned edges the kernels unite depends on a node's neighbourhood (needed_edges prunes the implied ones) and on which faces of
+# its 4 x 8 x 16 tile it sits on (the tile kernel takes the edges that stay inside, the merge kernel those that leave).  What decides is
+# the node's own inside bit and whether each of ten neighbours shares it: the seven owned neighbours v + (di, dj, dk) and the three nodes
+# one step back along k from v, v + (1, 0, 0) and v + (0, 1, 0) -- an 11-bit pattern -- and the three booleans "on the tile's upper i / j / k
+# face" -- 8 classes.  Random fields alone leave thousands of the 16 384 combinations out, most of them on the tile's corner nodes
+# (315 per 64-grid) and its j-k edge; here the rare classes get their patterns planted.
+TILE = (4, 8, 16)
+SEAM_G, SEAM_FIELDS = 64, 7
+BACK = ((0, 0), (1, 0), (0, 1))                                              # (di, dj) of the three nodes one step back along k
+
+
+def _neighbourhood_codes(inside):
+    """int32 [G - 1, G - 1, G - 2]: 8 pattern + class for every node (i, j, k) with i, j < G - 1 and 1 <= k < G - 1, the nodes whose ten
+    neighbours all exist.  Pattern: bit 0 the inside bit, bit m (1 .. 7) "node + (m >> 2 & 1, m >> 1 & 1, m & 1) has the same bit", bits
+    8, 9, 10 the same for the three BACK nodes.  Class: 4 top_i + 2 top_j + top_k."""
+    G = inside.shape[0]
+    own = inside[:G - 1, :G - 1, 1:G - 1]
+    pattern = own.astype(np.int32)
+    for m, (di, dj, dk) in enumerate(F.OWNED, start=1):
+        pattern |= (inside[di:G - 1 + di, dj:G - 1 + dj, 1 + dk:G - 1 + dk] == own).astype(np.int32) << m
+    for n, (di, dj) in enumerate(BACK):
+        pattern |= (inside[di:G - 1 + di, dj:G - 1 + dj, 0:G - 2] == own).astype(np.int32) << (8 + n)
+    i, j, k = np.meshgrid(np.arange(G - 1), np.arange(G - 1), np.arange(1, G - 1), indexing="ij")
+    top = [(x & (t - 1)) == t - 1 for x, t in zip((i, j, k), TILE)]
+    return pattern * 8 + (top[0] * 4 + top[1] * 2 + top[2])
+
+
+def _plant(inside, node, pattern):
+    """Give `node` the 11-bit pattern: writes its 2 x 2 x 3 footprint's twelve nodes but (i + 1, j + 1, k - 1)."""
+    i, j, k = node
+    own = bool(pattern & 1)
+    inside[i, j, k] = own
+    for m, (di, dj, dk) in enumerate(F.OWNED, start=1):
+        inside[i + di, j + dj, k + dk] = own == bool((pattern >> m) & 1)
+    for n, (di, dj) in enumerate(BACK):
+        inside[i + di, j + dj, k - 1] = own == bool((pattern >> (8 + n)) & 1)
+
+
+def _plant_sites(G, cls):
+    """The nodes of class `cls` on a sub-lattice whose footprints are disjoint: i = 1 or 3 (top) mod 4, j = 1, 3, 5 or 7 (top) mod 8,
+    k = 2, 5, 8, 11 or 15 (top) mod 16 -- the footprint i .. i + 1, j .. j + 1, k - 1 .. k + 1 of one site ends before the next one's begins."""
+    def axis(top, tile, low, first=0):
+        rest = (tile - 1,) if top else low
+        return [x for x in range(first, G - 1) if x % tile in rest]
+    return list(itertools.product(axis(cls & 4, 4, (1,)), axis(cls & 2, 8, (1, 3, 5)), axis(cls & 1, 16, (2, 5, 8, 11), 1)))
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_fields():
+    """SEAM_FIELDS boolean grids of SEAM_G^3 nodes, random at p = 0.5.  In field f the c-th site of the corner class (all three faces) and
+    of the j-k edge class gets the pattern (sites per field x f + c) mod 2048, which runs through all 2048 in seven fields; whatever the
+    count then still reports missing is planted on unused sites of its class, round by round (a plant can take a random neighbour's
+    pattern away).  The coverage is asserted by test_edge_seam_fields_cover_every_neighbourhood, from the fields alone."""
+    G = SEAM_G
+    fields = [np.random.default_rng(4000 + f).random((G, G, G)) < 0.5 for f in range(SEAM_FIELDS)]
+    used = [set() for _ in fields]
+    for cls in (7, 3):
+        sites = _plant_sites(G, cls)
+        for f, inside in enumerate(fields):
+            for c, node in enumerate(sites):
+                _plant(inside, node, (len(sites) * f + c) % 2048)
+                used[f].add(node)
+    for _ in range(8):
+        seen = np.zeros(16384, dtype=bool)
+        for inside in fields:
+            seen[np.unique(_neighbourhood_codes(inside))] = True
+        missing = np.flatnonzero(~seen)
+        if not missing.size:
+            break
+        for n, code in enumerate(missing.tolist()):
+            f = n % SEAM_FIELDS
+            node = next(s for s in _plant_sites(G, code & 7) if s not in used[f])
+            _plant(fields[f], node, code >> 3)
+            used[f].add(node)
+    return tuple(fields)
+
+
+def _as_field(inside, border_outside=False):
+    f = np.where(inside, np.float32(1), np.float32(-1))
+    if border_outside:
+        f[0], f[-1], f[:, 0], f[:, -1], f[:, :, 0], f[:, :, -1] = -1, -1, -1, -1, -1, -1
+    return f
+
+
+def test_edge_seam_fields_cover_every_neighbourhood():
+    counts = np.zeros(16384, dtype=np.int64)
+    for inside in _seam_fields():
+        counts += np.bincount(_neighbourhood_codes(inside).reshape(-1), minlength=16384)
+    per_class = [(int((counts[c::8] > 0).sum()), int(counts[c::8].min())) for c in range(8)]
+    print(f"covered {int((counts > 0).sum())} of 16384; per class (top_i top_j top_k as bits 4 2 1) patterns seen, fewest nodes on one pattern: {per_class}")
+    assert (counts > 0).all()
+    # the counting itself, on a case small enough to read: one inside node in an outside grid
+    one = np.zeros((20, 20, 20), dtype=bool)
+    one[3, 7, 15] = True
+    codes = _neighbourhood_codes(one)                                        # indexed [i, j, k - 1]
+    assert codes[3, 7, 14] == 8 * 1 + 7                                      # inside, nobody shares the bit; the corner class
+    assert codes[2, 7, 14] == 8 * (0x7FE & ~(1 << 4)) + 3                    # its lower i neighbour: all share but node + (1, 0, 0); j-k edge class
+    assert codes[3, 7, 15] == 8 * (0x7FE & ~(1 << 8)) + 6                    # the node after it along k: all but the one straight back; i-j edge class
+
+
+def test_edge_random_fields_alone_leave_combinations_out():
+    """Why the plants: seven random 64-grids without them."""
+    seen = np.zeros(16384, dtype=bool)
+    for f in range(SEAM_FIELDS):
+        seen[np.unique(_neighbourhood_codes(np.random.default_rng(4000 + f).random((SEAM_G,) * 3) < 0.5))] = True
+    print(f"random alone: {int(seen.sum())} of 16384; corner class {int(seen[7::8].sum())}, j-k edge class {int(seen[3::8].sum())} of 2048")
+    assert seen[7::8].sum() < 2048 and seen[3::8].sum() < 2048
+
+
+DENSITY_CASES = [(G, p) for G in (16, 17, 32) for p in (0.03, 0.5, 0.97)]
+CONSTANT_CASES = [(G, value) for G in (16, 17, 33) for value in (1, -1)]
+
+
+def _density_field(G, p, border_outside=False):
+    return _as_field(np.random.default_rng(int(1000 * p) + G).random((G, G, G)) < p, border_outside)
+
+
+@pytest.mark.parametrize("G,p", DENSITY_CASES)
+def test_edge_grid_sizes_and_densities_are_reached(G, p):
+    """16 and 32 are whole tiles on every axis (no lane beyond the grid); 17 adds one valid plane, row and column of otherwise empty tiles.
+    At p = 0.03 the solid is dozens to hundreds of specks (about 0.03 (G - 2)^3 nodes, few of them adjacent), at 0.97 the outside is."""
+    assert [G % t for t in TILE] == ([0, 0, 0] if G != 17 else [1, 1, 1])
+    f = _density_field(G, p, border_outside=True)
+    inside = f > 0
+    label = F.components(f, 0.0)
+    n_in, n_out = len(np.unique(label[inside])), len(np.unique(label[~inside]))
+    r = F.fill_field(f, 0.0, "outer")
+    print(f"G {G} p {p}: inside {inside.mean():.3f} components inside {n_in} outside {n_out} cavities {r['cavities']} islands {r['islands']}")
+    if p == 0.03:
+        assert n_in > 20 and r["islands"] > 20
+    if p == 0.97:
+        assert n_out > 20 and r["cavities"] > 20
+
+
+def test_edge_many_equal_components_are_reached():
+    G = 33
+    f = np.full((G, G, G), -1, np.float32)
+    f[1:-1:2, 1:-1:2, 1:-1:2] = 1
+    label = F.components(f, 0.0)
+    labs, counts = np.unique(label[f > 0], return_counts=True)
+    assert len(labs) == 4096 and (counts == 1).all()                         # no two odd nodes are Kuhn-adjacent
+    r = F.fill_field(f, 0.0, "outer")
+    assert (r["cavities"], r["cavity_nodes"], r["islands"], r["island_nodes"]) == (0, 0, 4095, 4095)
+    assert r["field"][1, 1, 1] == 1 and int((r["field"] > 0).sum()) == 1     # the smallest label stays
+    g = _as_field(~(f > 0), border_outside=True)
+    r = F.fill_field(g, 0.0, "cavities")
+    print(f"solid components {len(labs)}; inverse field: cavities {r['cavities']} cavity nodes {r['cavity_nodes']}")
+    assert (r["cavities"], r["cavity_nodes"], r["islands"], r["island_nodes"]) == (2744, 2744, 0, 0)
+
+
+@gpu
+@pytest.mark.parametrize("f", range(SEAM_FIELDS))
+def test_edge_seam_fields_labels(f):
+    _labels_both(_as_field(_seam_fields()[f]), 0.0)
+
+
+@gpu
+@pytest.mark.parametrize("mode", F.MODES)
+@pytest.mark.parametrize("f", [0, SEAM_FIELDS - 1])
+def test_edge_seam_fields_fill(f, mode):
+    want, _ = _fill_both(_as_field(_seam_fields()[f], border_outside=True), 0.0, mode)
+    assert want["cavities"] > 0
+
+
+@gpu
+@pytest.mark.parametrize("G,p", DENSITY_CASES)
+def test_edge_grid_sizes_and_densities(G, p):
+    _labels_both(_density_field(G, p), 0.0)
+    _labels_both(_density_field(G, p, border_outside=True), 0.0)
+    if p != 0.5:
+        for mode in F.MODES:
+            _fill_both(_density_field(G, p, border_outside=True), 0.0, mode)
+            _fill_both(_density_field(G, p), 0.0, mode)
+
+
+@gpu
+@pytest.mark.parametrize("G,value", CONSTANT_CASES)
+def test_edge_constant_fields_over_many_tiles(G, value):
+    want = _labels_both(np.full((G, G, G), value, np.float32), 0.0)
+    assert not want.any()                                                    # one component: label 0 everywhere
+
+
+@gpu
+@pytest.mark.parametrize("mode", F.MODES)
+def test_edge_many_equal_components(mode):
+    G = 33
+    f = np.full((G, G, G), -1, np.float32)
+    f[1:-1:2, 1:-1:2, 1:-1:2] = 1
+    want, _ = _fill_both(f, 0.0, mode)
+    assert want["islands"] == (4095 if mode == "outer" else 0)
+    want, _ = _fill_both(_as_field(~(f > 0), border_outside=True), 0.0, mode)
+    assert want["cavities"] == want["cavity_nodes"] == 2744

@@ -514,3 +514,175 @@ def test_geometry_surface_metrics_is_compare_meshes_of_its_boundary():
     got = geo.surface_metrics(v, f, n=2000, seed=3)
     want = metrics.compare_meshes(geo.tet_v.detach()[geo.surface_vid.long()].contiguous(), geo.surface_fid, v, f, n=2000, seed=3)
     assert got.as_dict() == want.as_dict() and got.noise_floor > 0 and got.chamfer_l1 < 0.2
+
+
+# ---------------------------------------------------------------- edges: exact ties in the sampler ----------------------------------------------------------------
+# Random float data meets an equal pair of operands only by accident: through sample_surface the total weight Q is about T 2^32, so
+# p == C[t] has probability T / 2^32 per sample, and ia + ib == 2^24 has 2^-24.  Here the prefix sums are written by hand and handed to
+# the draw phase of the C ABI, the seeds are chosen so that sample 0 sits on the fold, and the weights phase is compared on its own.
+def _lattice_mesh(T):
+    """T isolated right triangles with unit legs on the integer lattice of the plane z = 0: equal areas, every coordinate exact."""
+    t = np.arange(T)
+    v = np.zeros((T, 3, 3), F32)
+    v[:, :, 0] = (2 * (t % 16))[:, None]
+    v[:, :, 1] = (2 * (t // 16))[:, None]
+    v[:, 1, 0] += 1
+    v[:, 2, 1] += 1
+    return v.reshape(-1, 3), np.arange(3 * T, dtype=np.int32).reshape(T, 3)
+
+
+def _tiny_weight_mesh():
+    """Right triangles with legs 2^10, 2^-7, 2^-6: w = 2^20, 2^-14, 2^-12, so w / w_max = 1, 2^-34, 2^-32 and q = 2^32, 0, 1 -- the
+    second one has a positive area and is never drawn, the third one is the smallest weight that is."""
+    legs = [2.0 ** 10, 2.0 ** -7, 2.0 ** -6]
+    v = np.array([[[0, 0, 0], [s, 0, 0], [0, s, 0]] for s in legs], F32).reshape(-1, 3)
+    return v, np.arange(9, dtype=np.int32).reshape(3, 3)
+
+
+PREFIXES = {"one": [1], "three": [1, 2, 3], "zeros": [0, 0, 1, 1, 2, 3, 3],                      # zero weights leading, in a run, trailing
+            "equal255": [2 * (t + 1) for t in range(255)], "equal256": [2 * (t + 1) for t in range(256)], "equal257": [2 * (t + 1) for t in range(257)],
+            "huge": [2 ** 60, 2 ** 60, 3 * 2 ** 60, 2 ** 62, 2 ** 62]}
+DRAW_N, DRAW_SEED = 4096, 0
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_draw(name):
+    return MO.draw(*_lattice_mesh(len(PREFIXES[name])), PREFIXES[name], DRAW_N, DRAW_SEED)
+
+
+@pytest.mark.parametrize("name", sorted(PREFIXES))
+def test_edge_hand_made_prefixes_are_reached(name):
+    """From the oracle and the prefix alone: every p in [0, Q) occurs where Q is small, so p == C[t - 1] (the first value that belongs to
+    t: `>=` for `>` in the search sends it to t - 1) and p == C[t] - 1 (the last) occur for every drawable t; no triangle of weight 0 is
+    drawn; and the triangle is the first with C[t] > p by Python's own bisection."""
+    import bisect
+    prefix = PREFIXES[name]
+    weight = np.diff([0] + prefix).tolist()
+    assert min(weight) >= 0 and prefix[-1] > 0                               # a genuine prefix
+    area = MO.face_normals(*_lattice_mesh(len(prefix)))[1]
+    assert (area == 1.0).all()                                               # valid triangles of positive area, zero weight or not
+    s = _oracle_draw(name)
+    drawable = [t for t, w in enumerate(weight) if w > 0]
+    p = [int(x) for x in s.p]
+    assert s.Q == prefix[-1] and 0 <= min(p) and max(p) < s.Q
+    assert s.tri.tolist() == [bisect.bisect_right(prefix, x) for x in p]
+    assert sorted(set(s.tri.tolist())) == drawable
+    first = sum(1 for t in drawable if prefix[t] - weight[t] in set(p))
+    last = sum(1 for t in drawable if prefix[t] - 1 in set(p))
+    print(f"{name}: Q {s.Q} distinct p {len(set(p))} drawable {len(drawable)} with p == C[t-1] {first} with p == C[t]-1 {last}")
+    if s.Q < 1024:
+        assert set(p) == set(range(s.Q)) and first == last == len(drawable)
+    else:
+        assert s.Q == 2 ** 62 and len(set(p)) == DRAW_N                      # 64-bit products: the high word of u Q, not a 32-bit shortcut
+    assert MO.draw(*_lattice_mesh(len(prefix)), prefix, 5, DRAW_SEED).tri.tolist() == s.tri[:5].tolist()
+    assert MO.draw(*_lattice_mesh(len(prefix)), prefix, 0, DRAW_SEED).points.shape == (0, 3)
+
+
+def test_edge_draw_is_the_tail_of_sample_surface():
+    """sample_surface is integer_weights, a prefix sum and draw: the same samples from the prefix handed over by hand."""
+    v, f = _golden("s1_sphere")
+    s = _oracle_samples("s1_sphere", 1000, 0)
+    d = MO.draw(v, f, np.cumsum([int(x) for x in MO.integer_weights(v, f)], dtype=object), 1000, 0)
+    for key in ("tri", "points", "normals", "a", "b"):
+        assert getattr(d, key).tobytes() == getattr(s, key).tobytes(), key
+    assert d.Q == s.Q and s.q.tolist() == MO.integer_weights(v, f).tolist()
+
+
+# sample i of seed 0 is sample 0 of seed 3 i GOLDEN mod 2^64: found by scanning i < 2^26 with mix64_array
+FOLD_SEEDS = {"sum == 2^24": 0x6F0B2F4A11BFEDF0, "sum == 2^24 + 1": 0xE1B751B607FDBFC7, "sum == 2^24 - 1": 0x1413E1F979F588EE, "ia == 0": 0xFD2DD52195A0B661,
+              "ib == 0": 0x931E3C944A5C6B0D}
+
+
+def _first_barycentrics(seed):
+    return MO.mix64(seed, 1) >> 40, MO.mix64(seed, 2) >> 40
+
+
+def test_edge_fold_seeds_are_reached():
+    one = 1 << 24
+    got = {name: _first_barycentrics(seed) for name, seed in FOLD_SEEDS.items()}
+    print(got)
+    assert got["sum == 2^24"] == (16032853, 744363) and sum(got["sum == 2^24"]) == one
+    assert sum(got["sum == 2^24 + 1"]) == one + 1 and sum(got["sum == 2^24 - 1"]) == one - 1
+    assert got["ia == 0"][0] == 0 and got["ib == 0"][1] == 0
+    v, f = _one_triangle()
+    for name, seed in FOLD_SEEDS.items():
+        s = MO.sample_surface(v, f, 1, seed)
+        ia, ib = got[name]
+        folded = ia + ib > one
+        assert folded == (name == "sum == 2^24 + 1")                         # a + b == 1 stays: the point lies on the edge B C
+        want = (one - ia, one - ib) if folded else (ia, ib)
+        assert (float(s.a[0]) * one, float(s.b[0]) * one) == want
+
+
+def test_edge_weights_are_reached():
+    for T in (255, 256, 257):
+        assert MO.integer_weights(*_lattice_mesh(T)).tolist() == [2 ** 32] * T
+    v, f = _tiny_weight_mesh()
+    assert MO.face_normals(v, f)[1].tolist() == [2.0 ** 20, 2.0 ** -14, 2.0 ** -12] and MO.integer_weights(v, f).tolist() == [2 ** 32, 0, 1]
+    assert set(MO.sample_surface(v, f, 4096, 0).tri.tolist()) == {0}         # weight 1 in 2^32 + 1: not in 4096 draws; weight 0: never
+
+
+def _draw_on_device(v, f, prefix, n, seed):
+    """Phase DRAW of tsamd_sample_surface with the caller's own prefix sums."""
+    from tssplat_amd import _args
+    vd, fd, cd = dev(v), dev(f), dev(np.asarray(prefix, dtype=np.int64))
+    lib, ctx, stream = _args.lib_and_stream(vd.device)
+    pts, nrm = torch.empty((n, 3), dtype=torch.float32, device=vd.device), torch.empty((n, 3), dtype=torch.float32, device=vd.device)
+    tri = torch.empty(n, dtype=torch.int32, device=vd.device)
+    with ctx:
+        _capi.check(lib.tsamd_sample_surface(1, vd.data_ptr(), v.shape[0], fd.data_ptr(), f.shape[0], cd.data_ptr(), None, n, seed, pts.data_ptr(), nrm.data_ptr(),
+                                             tri.data_ptr(), stream))
+    return tri.cpu().numpy(), pts.cpu().numpy(), nrm.cpu().numpy()
+
+
+def _weights_on_device(v, f):
+    """Phase WEIGHTS of tsamd_sample_surface: the int64 q, before any prefix sum."""
+    from tssplat_amd import _args
+    vd, fd = dev(v), dev(f)
+    lib, ctx, stream = _args.lib_and_stream(fd.device)
+    q = torch.full((f.shape[0],), -1, dtype=torch.int64, device=fd.device)
+    work = torch.empty(1, dtype=torch.int64, device=fd.device)
+    with ctx:
+        _capi.check(lib.tsamd_sample_surface(0, _args.ptr(vd), v.shape[0], fd.data_ptr(), f.shape[0], q.data_ptr(), work.data_ptr(), 0, 0, None, None, None, stream))
+    return q.cpu().numpy()
+
+
+@gpu
+@pytest.mark.parametrize("name", sorted(PREFIXES))
+def test_edge_hand_made_prefixes(name):
+    prefix = PREFIXES[name]
+    v, f = _lattice_mesh(len(prefix))
+    want = _oracle_draw(name)
+    tri, pts, nrm = _draw_on_device(v, f, prefix, DRAW_N, DRAW_SEED)
+    assert tri.tobytes() == want.tri.tobytes(), (int((tri != want.tri).sum()), tri[tri != want.tri][:8], want.tri[tri != want.tri][:8])
+    assert pts.tobytes() == want.points.tobytes() and nrm.tobytes() == want.normals.tobytes()
+
+
+@gpu
+@pytest.mark.parametrize("name", sorted(FOLD_SEEDS))
+def test_edge_fold_seeds(name):
+    seed = FOLD_SEEDS[name]
+    for mesh in ("one_triangle", "s1_sphere"):
+        _sample_both(mesh, 64, seed)
+    if name == "sum == 2^24":                                                # sample 0 keeps its barycentrics: folded, they would be exchanged
+        from tssplat_amd import metrics
+        v, f = _one_triangle()
+        ia, ib = _first_barycentrics(seed)
+        A, B, Cc = v[0], v[1], v[2]
+
+        def point(x, y):
+            return (A + F32(x * 2.0 ** -24) * (B - A)) + F32(y * 2.0 ** -24) * (Cc - A)
+        assert point(ia, ib).tobytes() != point(ib, ia).tobytes()
+        got = metrics.sample_surface(dev(v), dev(f), 1, seed).points.cpu().numpy()[0]
+        assert got.tobytes() == point(ia, ib).tobytes()
+
+
+@gpu
+def test_edge_weights_phase_equals_integer_weights():
+    cases = [(name, make()) for name, make in sorted(MESHES.items())] + [(f"lattice{T}", _lattice_mesh(T)) for T in (255, 256, 257)]
+    cases.append(("tiny", _tiny_weight_mesh()))
+    for name, (v, f) in cases:
+        want = MO.integer_weights(v, f)
+        got = _weights_on_device(v, f)
+        assert got.dtype == np.int64 and got.astype(np.uint64).tobytes() == want.tobytes(), (name, int((got.astype(np.uint64) != want).sum()))
+    assert got.tolist() == [2 ** 32, 0, 1]                                   # the last case: a positive area that is never drawn
