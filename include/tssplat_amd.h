@@ -871,6 +871,41 @@ int tsamd_nearest_points(const float *query_dev, int64_t n, const float *ref_dev
                          int32_t *idx_out_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Exact point-to-triangle search: for every query the closest triangle of a mesh, its squared distance and the closest point
+ * (tssplat_amd/metrics.py: nearest_on_mesh, compare_meshes_exact).  Semantics are fixed by tests/pointmesh_oracle.py, in
+ * separately rounded float64 operations and integer minima: bitwise repeatable and equal to the oracle.  Stateless, caller-owned
+ * buffers, nothing synchronises the host.
+ *
+ * tsamd_nearest_on_mesh: query_dev [n, 3] f32, v_dev [n_vertices, 3] f32, faces_dev [n_triangles, 3] i32, n_triangles >= 1.  A
+ * triangle is valid iff its indices lie in 0 .. n_vertices - 1, its nine coordinates are finite and the weight w of
+ * tsamd_sample_surface is > 0; an invalid triangle is never a result and nothing is read through a bad index.  Per query P and
+ * valid triangle A B C, in float64 on the float32 inputs, every operation rounded on its own, dot[u, v] = [ux vx + uy vy] + uz vz
+ * (Ericson, Real-Time Collision Detection, 5.1.5):
+ *   AB = B - A, AC = C - A, AP = P - A, BP = P - B, CP = P - C;
+ *   d1 = dot[AB, AP], d2 = dot[AC, AP], d3 = dot[AB, BP], d4 = dot[AC, BP], d5 = dot[AB, CP], d6 = dot[AC, CP];
+ *   vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, e = d4 - d3, g = d5 - d6;
+ * the first test that holds gives the barycentrics (a comparison with a NaN is false):
+ *   d1 <= 0 and d2 <= 0: v = 0, w = 0;    d3 >= 0 and d4 <= d3: v = 1, w = 0;    vc <= 0 and d1 >= 0 and d3 <= 0: v = d1 / [d1 - d3], w = 0;
+ *   d6 >= 0 and d5 <= d6: v = 0, w = 1;   vb <= 0 and d2 >= 0 and d6 <= 0: v = 0, w = d2 / [d2 - d6];
+ *   va <= 0 and e >= 0 and g >= 0: w = e / [e + g], v = 1 - w;    otherwise s = [va + vb] + vc, v = vb / s, w = vc / s;
+ * X = [A + AB v] + AC w per component and d2 = [[Px - Xx]^2 + [Py - Xy]^2] + [Pz - Xz]^2.  Per query the minimum over the valid
+ * triangles of fl32[d2], the float64 value rounded once (an overflow to +inf is an ordinary value); the lowest triangle index wins
+ * a tie; a pair whose d2 is NaN is skipped.  d2_out_dev [n] f32, tri_out_dev [n] i32, point_out_dev [n, 3] f32 (may be null: not
+ * written) = the winning triangle's X rounded once; a query with no pair left gives +inf, -1 and a NaN point -- a mesh without a
+ * valid triangle is not an error.  A float32 bounding-sphere test and a seed (tsamd_nearest_points over the sphere centres) decide
+ * which pairs are evaluated, never the result.  ref_chunks: into how many parts the triangles are split over the grid's second
+ * dimension (1 .. min[n_triangles, 65535]; 0: the automatic rule that tsamd_nearest_on_mesh_info reports); the result does not
+ * depend on it, bit for bit.  workspace_dev: tsamd_nearest_on_mesh_workspace_bytes[n, n_triangles] bytes (-1 for a count out of
+ * range), 16-byte aligned, filled by the call itself, contents undefined afterwards.  n = 0: nothing is launched.
+ * tsamd_nearest_on_mesh_info: the compiled lanes per workgroup, queries per lane and bounding spheres per LDS tile, and the chunk
+ * count the automatic rule picks for n queries and n_triangles triangles; it touches no device. */
+int64_t tsamd_nearest_on_mesh_workspace_bytes(int64_t n, int64_t n_triangles);
+int tsamd_nearest_on_mesh_info(int64_t n, int64_t n_triangles, int32_t *block_out, int32_t *queries_per_lane_out, int32_t *tri_tile_out,
+                               int32_t *auto_chunks_out);
+int tsamd_nearest_on_mesh(const float *query_dev, int64_t n, const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles,
+                          int32_t ref_chunks, void *workspace_dev, float *d2_out_dev, int32_t *tri_out_dev, float *point_out_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Surface simplification: vertex clustering on a cube grid with quadric placement (tssplat_amd/simplify.py).  Semantics are
  * fixed by tests/simplify_oracle.py, in separately rounded float64 operations, sequential sums and integers: bitwise repeatable
  * and equal to the oracle.  Stateless, caller-owned buffers, nothing synchronises the host.  The two sorts between the stages

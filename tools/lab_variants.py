@@ -333,6 +333,32 @@ VARIANTS["nearest_selects"] = ("nearest points: a compare and two selects per pa
                 }
             }""")])
 
+# ---- the exact point-to-triangle search (tools/bench_metrics.py --exact prices them; all but pointmesh_count give the product's bits) ----
+PM = "pointmesh_kernels.hip"
+for _q in (2, 4):
+    VARIANTS[f"pointmesh_q{_q}"] = (f"point to mesh: {_q} queries per lane instead of 1 (the automatic chunk rule still counts blocks of 1: pass ref_chunks)",
+                                    [(PM, "constexpr int kQ = kPointMeshQueriesPerLane;", f"constexpr int kQ = {_q};")])
+VARIANTS["pointmesh_tile256"] = ("point to mesh: LDS tiles of 256 bounding spheres instead of 1024", [(PM, "constexpr int kTile = kPointMeshTile;", "constexpr int kTile = 256;")])
+VARIANTS["pointmesh_noprune"] = ("point to mesh: no bounding-sphere test -- every pair of a query and a valid triangle takes the float64 evaluation (the same bits)", [
+    (PM, "    return (dx * dx + dy * dy) + dz * dz <= reach * reach;", "    (void)dx, (void)dy, (void)dz, (void)reach;\n    return s.w == s.w;")])
+VARIANTS["pointmesh_count"] = ("point to mesh: tri_out holds the number of float64 evaluations of the query's search (seed and finish not counted) instead of the "
+                               "triangle -- the share of pairs that pass the sphere test", [
+    (PM, "int64_t per_chunk,\n                                                                           unsigned long long *keys)",
+     "int64_t per_chunk,\n                                                                           unsigned long long *keys, unsigned *counts)"),
+    (PM, "    unsigned long long best[kQ];\n", "    unsigned long long best[kQ];\n    unsigned evaluated[kQ] = {};\n"),
+    (PM, "                        if (key < best[k]) {\n", "                        ++evaluated[k];\n                        if (key < best[k]) {\n"),
+    (PM, "        if (q < n && best[k] != kNoKey) atomicMin(keys + q, best[k]);\n",
+     "        if (q < n && best[k] != kNoKey) atomicMin(keys + q, best[k]);\n        if (q < n) atomicAdd(counts + q, evaluated[k]);\n"),
+    (PM, "                       corners, n_triangles, per_chunk, keys);\n",
+     "                       corners, n_triangles, per_chunk, keys, reinterpret_cast<unsigned *>(seed_idx));\n"),
+    (PM, "    hipLaunchKernelGGL(pointmesh_seed_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, query, n, corners, n_triangles, seed_idx, keys);\n",
+     "    hipLaunchKernelGGL(pointmesh_seed_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, query, n, corners, n_triangles, seed_idx, keys);\n"
+     "    if (hipMemsetAsync(seed_idx, 0, size_t(n) * sizeof(int32_t), stream) != hipSuccess) return hipErrorUnknown;   // dead after the seed kernel: the counters\n"),
+    (PM, "n_triangles, keys, d2_out, tri_out, point_out);\n    return hipGetLastError();",
+     "n_triangles, keys, d2_out, tri_out, point_out);\n"
+     "    if (hipMemcpyAsync(tri_out, seed_idx, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToDevice, stream) != hipSuccess) return hipErrorUnknown;\n"
+     "    return hipGetLastError();")])
+
 COMBOS = {"fs": ["fma4", "sdwa"], "stamps_rows8": ["stamps", "rows8"]}    # ("undef" -- inactive lanes' arrays left undefined -- was adopted by the product kernel)
 
 

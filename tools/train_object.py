@@ -16,7 +16,7 @@ absent):
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
                                  [--fit-normal off|operators|fused-loss --fit-normal-start N --normal-weight W] [--normal-bench PATH]
-                                 [--placement host|device|mesh --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer --merge-simplify K] [--eval-samples N] [--eval-grid N]
+                                 [--placement host|device|mesh --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer --merge-simplify K] [--eval-samples N [--eval-exact]] [--eval-grid N]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
 so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
@@ -55,6 +55,8 @@ bounds; `merged_surface.obj` is then the clustered mesh and `merged` gains `simp
 --eval-samples N (0: off, the record is what it was): `eval`, `tssplat_amd.metrics.compare_meshes` on N samples per surface against the TARGET MESH --
 Chamfer distance, accuracy / completeness, F-score, normal consistency, each with its `noise_floor` -- of `raw_union` (the concatenated tet-sphere
 boundaries, interior sheets included), `merged` (with --merge-grid) and `merged_filled` (with --merge-fill).
+--eval-exact (with --eval-samples): `eval_exact` next to `eval`, the same surfaces through `tssplat_amd.metrics.compare_meshes_exact` -- samples against the triangles
+themselves, so the figures have no sampling floor (`noise_floor` is then a rounding-level number) -- and `vs_unsimplified_exact` next to `vs_unsimplified`.
 
 --eval-grid N (0: off, the record is what it was): `volume_iou_vs_target`, `tssplat_amd.voxelize.mesh_volume_iou` at N nodes per axis against the TARGET MESH (winding
 number, rule "nonzero", three rays, bounds spanning both meshes) of `raw_union`, `merged`, `merged_filled` and `merged_simplified`, each with its inside counts, open
@@ -187,7 +189,7 @@ def surface_topology(field, level, n_vertices, n_triangles):
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
         fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None,
-        merge_fill="none", eval_samples=0, merge_simplify=0, eval_grid=0):
+        merge_fill="none", eval_samples=0, merge_simplify=0, eval_grid=0, eval_exact=False):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -309,11 +311,13 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
                    "schedule": "config/gso.yaml: lr 0.2 cosine, grad_limit 0.01, order 2 -> 4 at 1000, coeff_scheduler, smooth_eng_coeff / n_spheres"},
         "log": log,
     }
-    evals = {}
+    evals, exacts = {}, {}
 
     def evaluate(key, v, f):   # 3-D figures against the target mesh itself: Chamfer distance, F-score, normal consistency and their noise floor
         from tssplat_amd import metrics
         evals[key] = {"triangles": int(f.shape[0]), **metrics.compare_meshes(v.contiguous(), f.contiguous(), tv, tf, n=eval_samples, seed=0).as_dict()}
+        if eval_exact:         # the same samples against the triangles themselves: no sampling floor
+            exacts[key] = {"triangles": int(f.shape[0]), **metrics.compare_meshes_exact(v.contiguous(), f.contiguous(), tv, tf, n=eval_samples, seed=0).as_dict()}
     if eval_samples:           # (a) the raw concatenated tet-sphere boundary surface: interior sheets wherever spheres overlap
         evaluate("raw_union", geo.tet_v.detach()[geo.surface_vid.long()], geo.surface_fid)
     vols = {}
@@ -366,6 +370,9 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
                                     "invalid_faces": simp.invalid_faces, "edge_stats": dataclasses.asdict(simplify.edge_stats(simp.faces))}
             if eval_samples:   # (d) the simplified surface: against the unsimplified one, and against the target like the others
                 fill_rec["simplify"]["vs_unsimplified"] = metrics.compare_meshes(simp.v, simp.faces, mv.contiguous(), mf.contiguous(), n=eval_samples, seed=0).as_dict()
+                if eval_exact:
+                    fill_rec["simplify"]["vs_unsimplified_exact"] = metrics.compare_meshes_exact(simp.v, simp.faces, mv.contiguous(), mf.contiguous(), n=eval_samples,
+                                                                                                 seed=0).as_dict()
                 evaluate("merged_simplified", simp.v, simp.faces)
             if eval_grid:
                 volume("merged_simplified", simp.v, simp.faces)
@@ -381,6 +388,9 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         rec["volume_iou_vs_target"] = {"grid": eval_grid, "rule": "nonzero", "rays": 3, "reference": os.path.basename(target_npz), **vols}
     if eval_samples:
         rec["eval"] = {"samples": eval_samples, "seed": 0, "reference": os.path.basename(target_npz), "a": "the surface named by the key", "b": "the target mesh", **evals}
+        if eval_exact:
+            rec["eval_exact"] = {"samples": eval_samples, "seed": 0, "reference": os.path.basename(target_npz), "a": "the surface named by the key", "b": "the target mesh",
+                                 "distances": "samples against triangles (metrics.compare_meshes_exact)", **exacts}
     if stages:      # the stages on their own (HIP events; they overlap nothing, so their sum is close to one iteration)
         def timed(fn, reps=20):
             for j in range(3):
@@ -624,6 +634,8 @@ def main():
                     help="cluster the merged surface on N // K cells per axis (tssplat_amd.simplify; 0: off, else an integer >= 2)")
     ap.add_argument("--eval-samples", type=int, default=0, metavar="N",
                     help="surface metrics (tssplat_amd.metrics.compare_meshes) of the raw, merged and filled surfaces against the target mesh on N samples each (0: off)")
+    ap.add_argument("--eval-exact", action="store_true",
+                    help="with --eval-samples: also `eval_exact`, the same surfaces with exact sample-to-triangle distances (tssplat_amd.metrics.compare_meshes_exact)")
     ap.add_argument("--eval-grid", type=int, default=0, metavar="N",
                     help="volume IoU (tssplat_amd.voxelize.mesh_volume_iou) of the raw, merged, filled and simplified surfaces against the target mesh at N nodes per axis (0: off)")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
@@ -650,7 +662,7 @@ def main():
                          stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
                          fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
                          merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill, eval_samples=args.eval_samples,
-                         merge_simplify=args.merge_simplify, eval_grid=args.eval_grid)))
+                         merge_simplify=args.merge_simplify, eval_grid=args.eval_grid, eval_exact=args.eval_exact)))
 
 
 if __name__ == "__main__":

@@ -243,6 +243,11 @@ SIGNATURES = {
     "tsamd_nearest_points_workspace_bytes": (C.c_int64, [C.c_int64]),
     "tsamd_nearest_points_info": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tsamd_nearest_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the exact point-to-triangle search: closest triangle, squared distance and closest point per query
+    "tsamd_nearest_on_mesh_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "tsamd_nearest_on_mesh_info": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tsamd_nearest_on_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     # surface simplification: cell keys and record slots, the per-cell run walk and solve, the face triples, the duplicate flags
     "tsamd_simplify_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),

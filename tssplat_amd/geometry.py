@@ -271,15 +271,17 @@ class TetMeshGeometry(torch.nn.Module):
         merge.write_obj(os.path.join(path, filename + "_merged.obj"), merged.v, merged.faces)
         return merged
 
-    def surface_metrics(self, v_ref: torch.Tensor, f_ref: torch.Tensor, n: int = 100_000, seed: int = 0, thresholds=None):
+    def surface_metrics(self, v_ref: torch.Tensor, f_ref: torch.Tensor, n: int = 100_000, seed: int = 0, thresholds=None, exact: bool = False):
         """:func:`tssplat_amd.metrics.compare_meshes` of the boundary surface as it is (``tet_v[surface_vid]``, ``surface_fid``: for a
         multi-sphere geometry the raw union of the spheres' boundaries, interior sheets included) against the reference mesh
         ``v_ref`` float32 ``[V, 3]``, ``f_ref`` int32 ``[T, 3]``: Chamfer distance, F-score and normal consistency on ``n`` samples per
-        surface, with their ``noise_floor``."""
+        surface, with their ``noise_floor``.  ``exact=True``: :func:`tssplat_amd.metrics.compare_meshes_exact`, samples against the triangles
+        themselves, with no sampling floor."""
         from . import metrics
         v = self.tet_v.detach()[self.surface_vid.long()].contiguous()
-        return metrics.compare_meshes(v, self.surface_fid.contiguous(), v_ref, f_ref, n=n, seed=seed,
-                                      thresholds=metrics.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
+        compare = metrics.compare_meshes_exact if exact else metrics.compare_meshes
+        return compare(v, self.surface_fid.contiguous(), v_ref, f_ref, n=n, seed=seed,
+                       thresholds=metrics.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
 
     def volume_iou(self, v_ref: torch.Tensor, f_ref: torch.Tensor, grid: int = 128, bounds=None):
         """:func:`tssplat_amd.voxelize.mesh_volume_iou` of the boundary surface as :meth:`surface_metrics` takes it against the reference
