@@ -994,6 +994,77 @@ int tsamd_voxel_winding(const float *v_dev, int64_t n_vertices, const int32_t *f
 int tsamd_voxel_occupancy(const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles, int32_t grid, double lo, double hi, int32_t rule,
                           int32_t rays, void *workspace_dev, uint8_t *occ_out_dev, int64_t *stats_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Mesh quality: the exact self-intersection search and the topology of a triangle mesh (tssplat_amd/quality.py).  Semantics are
+ * fixed by tests/quality_oracle.py: exact int64 predicates on a 2^20 lattice, integer counts and labels, and a float64 shape
+ * record whose operations are rounded one by one -- bitwise repeatable and equal to the oracle.  Stateless, caller-owned buffers.
+ * Nothing synchronises the host except tsamd_quality_union.
+ *
+ * tsamd_quality_prepare: v_dev [n_vertices, 3] f32, faces_dev [n_triangles, 3] i32, the cube [lo, hi]^3.  With g = [2^20 - 1] /
+ * [hi - lo] in float64 a coordinate x snaps to X = floor[[double[x] - lo] g + 0.5], product and sum rounded separately.  A
+ * triangle is valid iff its indices lie in 0 .. n_vertices - 1, its nine coordinates are finite and every X lies in
+ * 0 .. 2^20 - 1; nothing is read through a bad index.  It is degenerate iff it is valid and the integer cross product
+ * [B - A] x [C - A] of its snapped corners is zero.  state_out_dev [n_triangles] u8: 0 valid, 1 degenerate, 2 invalid.
+ * corners_out_dev [n_triangles, 3] u64: a corner as X | Y << 21 | Z << 42, or ~0 three times for a triangle whose state is not 0.
+ * boxes_out_dev [n_triangles, 2] u64: the minimum corner of the triangle's lattice box in the same packing, then the maximum
+ * corner with the bits 20, 41 and 62 set; the box [2^20 - 1, 0] for a triangle whose state is not 0.  morton_out_dev
+ * [n_triangles] i64: the 60-bit Morton code of floor[[min + max] / 2] (x in the lowest bit), 2^63 - 1 where the state is not 0.
+ * shape_out_dev [n_triangles, 4] f64, in float64 on the float32 corners, every operation rounded on its own, dot[d] =
+ * [dx dx + dy dy] + dz dz and the cross product's components as differences of two products: dot[B - A], dot[C - B], dot[A - C],
+ * dot[[B - A] x [C - A]] (four times the squared area); NaN four times for an invalid triangle.  n_triangles = 0: nothing is
+ * launched.
+ *
+ * tsamd_quality_pairs: the outputs of tsamd_quality_prepare, in any order of the triangles as long as the three agree.
+ * orient[a, b, c, d] = det[b - a, c - a, d - a] in int64 (below 3 x 2^61 in magnitude).  A segment p q pierces a triangle a b c iff
+ * orient[a, b, c, p] and orient[a, b, c, q] are non-zero with opposite signs and orient[p, q, a, b], orient[p, q, b, c],
+ * orient[p, q, c, a] are all > 0 or all < 0.  Two triangles i < j of state 0 are a crossing pair iff an edge of one pierces the
+ * other.  Strict signs: a contact through a vertex or along an edge, a coplanar overlap, and a crossing whose piercings all pass
+ * exactly through edges of the other triangle are not counted.  crossings_out_dev [n_triangles] i32: the crossing pairs a
+ * triangle is in.  pairs_out_dev [max_pairs] i64 (may be null when max_pairs = 0): the keys i << 32 | j of the first max_pairs
+ * pairs found, in no order; when there are more pairs than max_pairs, which ones are listed depends on timing.  stats_out_dev:
+ * eight i64, 8-byte aligned, written by the call itself: [TSAMD_QUALITY_CROSSING_PAIRS], [_CROSSING_FACES] triangles in at least
+ * one pair, [_INVALID_FACES], [_DEGENERATE_FACES], [_BOX_PAIRS] pairs i < j of state 0 whose closed lattice boxes overlap,
+ * [_LISTED_PAIRS] = min[crossing pairs, max_pairs], [_TILE_VISITS] tiles loaded summed over the workgroups, [7] zero.
+ * tile_boxes_dev: null, or a workspace of 16 bytes per tile of the size tsamd_quality_info reports, 8-byte aligned: the call
+ * then writes every tile's box there and skips the pairs of a wave and a tile whose boxes are apart.  That decides which pairs
+ * are evaluated, never the result: every output but [_TILE_VISITS] is the same, bit for bit.  n_triangles = 0: the stats are
+ * zeroed.
+ * tsamd_quality_info: the compiled triangles per workgroup, triangles per LDS tile and queue entries per wave; it touches no
+ * device.
+ *
+ * Topology.  Half-edge 3 t + k runs from faces[t, k] to faces[t, [k + 1] % 3]; corner 3 t + k sits at faces[t, k].
+ * tsamd_quality_edges: per half-edge of a triangle whose state is not 2 and whose indices are in range, und_keys_out_dev
+ * [3 n_triangles] i64 = min << 32 | max of its ends, dir_keys_out_dev = from << 32 | to, vertex_pairs_out_dev [3 n_triangles, 2]
+ * i32 = its ends; for any other half-edge 2^63 - 1, 2^63 - 1 and [-1, -1].  referenced_out_dev [n_vertices] u8: 1 for the
+ * vertices of those triangles, else 0.
+ * tsamd_quality_fan_pairs: sorted_keys_dev [3 n_triangles] i64 the undirected keys in ascending order and order_dev
+ * [3 n_triangles] i64 the half-edge each came from.  corner_pairs_out_dev [3 n_triangles, 2, 2] i32: for a position whose key
+ * equals the one before and is not 2^63 - 1, with h1 the half-edge before and h2 this one, for each end x of h1 the pair of h1's
+ * corner at x and h2's corner at x (h2's first corner if that sits at x, else its second); [-1, -1] twice elsewhere.
+ * tsamd_quality_union: labels_out_dev [n] i32 = the lowest index of the class of each of n elements under the pairs pairs_dev
+ * [n_pairs, 2] i32 (a pair with an index outside 0 .. n - 1 is skipped).  Rounds of hooking the higher of two labels to the lower
+ * with an integer atomicMin and of pointer jumping; after each round the host reads one flag back, so this call SYNCHRONISES the
+ * host with the stream.  It never spins: past n + 1 rounds, which a correct build cannot need, it returns TSAMD_ERR_HIP.
+ * workspace_dev: 4 bytes, 4-byte aligned.  rounds_out (host, may be null): the rounds run.  The labels are a function of the
+ * pairs alone. */
+#define TSAMD_QUALITY_CROSSING_PAIRS 0
+#define TSAMD_QUALITY_CROSSING_FACES 1
+#define TSAMD_QUALITY_INVALID_FACES 2
+#define TSAMD_QUALITY_DEGENERATE_FACES 3
+#define TSAMD_QUALITY_BOX_PAIRS 4
+#define TSAMD_QUALITY_LISTED_PAIRS 5
+#define TSAMD_QUALITY_TILE_VISITS 6
+int tsamd_quality_info(int32_t *block_out, int32_t *tile_out, int32_t *queue_out);
+int tsamd_quality_prepare(const float *v_dev, int64_t n_vertices, const int32_t *faces_dev, int64_t n_triangles, double lo, double hi, uint64_t *corners_out_dev,
+                          uint64_t *boxes_out_dev, uint8_t *state_out_dev, double *shape_out_dev, int64_t *morton_out_dev, void *stream);
+int tsamd_quality_pairs(const uint64_t *corners_dev, const uint64_t *boxes_dev, const uint8_t *state_dev, int64_t n_triangles, uint64_t *tile_boxes_dev,
+                        int64_t max_pairs, int32_t *crossings_out_dev, int64_t *pairs_out_dev, int64_t *stats_out_dev, void *stream);
+int tsamd_quality_edges(const int32_t *faces_dev, const uint8_t *state_dev, int64_t n_triangles, int64_t n_vertices, int64_t *und_keys_out_dev,
+                        int64_t *dir_keys_out_dev, int32_t *vertex_pairs_out_dev, uint8_t *referenced_out_dev, void *stream);
+int tsamd_quality_fan_pairs(const int32_t *faces_dev, int64_t n_triangles, const int64_t *sorted_keys_dev, const int64_t *order_dev,
+                            int32_t *corner_pairs_out_dev, void *stream);
+int tsamd_quality_union(const int32_t *pairs_dev, int64_t n_pairs, int32_t *labels_out_dev, int64_t n, void *workspace_dev, int64_t *rounds_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ absent):
     python tools/train_object.py [--spheres 20 --k 8 --views 120 --res 512 --iters 1500 --silhouette operators|fused|fused-loss --no-stages]
                                  [--fit-depth off|operators|fused-loss --fit-depth-start N] [--depth-bench PATH]
                                  [--fit-normal off|operators|fused-loss --fit-normal-start N --normal-weight W] [--normal-bench PATH]
-                                 [--placement host|device|mesh --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer --merge-simplify K] [--eval-samples N [--eval-exact]] [--eval-grid N]
+                                 [--placement host|device|mesh --grid N] [--merge-grid N --merge-out DIR --merge-fill none|cavities|outer --merge-simplify K] [--eval-samples N [--eval-exact]] [--eval-grid N] [--eval-quality]
 
 --placement: where the tet-spheres are placed -- `host` (the default, `place_spheres` + `build_spheres` below: torch, scipy and numpy,
 so that recorded runs stay comparable) or `device` (`tssplat_amd.spheres_init.init_spheres` + `geometry.TetMeshMultiSphereGeometry`:
@@ -55,6 +55,8 @@ bounds; `merged_surface.obj` is then the clustered mesh and `merged` gains `simp
 --eval-samples N (0: off, the record is what it was): `eval`, `tssplat_amd.metrics.compare_meshes` on N samples per surface against the TARGET MESH --
 Chamfer distance, accuracy / completeness, F-score, normal consistency, each with its `noise_floor` -- of `raw_union` (the concatenated tet-sphere
 boundaries, interior sheets included), `merged` (with --merge-grid) and `merged_filled` (with --merge-fill).
+--eval-quality: `eval_quality`, the record of `tssplat_amd.quality.mesh_quality` (crossing pairs on a 2^20 lattice, edge / vertex manifoldness, components,
+orientation, Euler characteristic, area-length ratio and minimum angle) for `raw_union`, `target` and whichever of `merged`, `merged_filled`, `merged_simplified` the run makes.
 --eval-exact (with --eval-samples): `eval_exact` next to `eval`, the same surfaces through `tssplat_amd.metrics.compare_meshes_exact` -- samples against the triangles
 themselves, so the figures have no sampling floor (`noise_floor` is then a rounding-level number) -- and `vs_unsimplified_exact` next to `vs_unsimplified`.
 
@@ -189,7 +191,7 @@ def surface_topology(field, level, n_vertices, n_triangles):
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
         fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None,
-        merge_fill="none", eval_samples=0, merge_simplify=0, eval_grid=0, eval_exact=False):
+        merge_fill="none", eval_samples=0, merge_simplify=0, eval_grid=0, eval_exact=False, eval_quality=False):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -320,6 +322,14 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             exacts[key] = {"triangles": int(f.shape[0]), **metrics.compare_meshes_exact(v.contiguous(), f.contiguous(), tv, tf, n=eval_samples, seed=0).as_dict()}
     if eval_samples:           # (a) the raw concatenated tet-sphere boundary surface: interior sheets wherever spheres overlap
         evaluate("raw_union", geo.tet_v.detach()[geo.surface_vid.long()], geo.surface_fid)
+    quals = {}
+
+    def grade(key, v, f):      # what kind of mesh it is: crossing pairs on the 2^20 lattice, topology, triangle shape (tssplat_amd.quality)
+        from tssplat_amd import quality
+        quals[key] = {"triangles": int(f.shape[0]), **quality.mesh_quality(v.contiguous(), f.contiguous()).as_dict()}
+    if eval_quality:
+        grade("raw_union", geo.tet_v.detach()[geo.surface_vid.long()], geo.surface_fid)
+        grade("target", tv, tf)
     vols = {}
 
     def volume(key, v, f, field=None, grid_bounds_level=None):   # volume IoU against the target mesh: both voxelised (winding number, rule "nonzero", three rays)
@@ -343,6 +353,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
         mv, mf, closed = merge.extract_surface(field, bounds, level)
         if eval_samples:       # (b) the merged surface
             evaluate("merged", mv, mf)
+        if eval_quality:
+            grade("merged", mv, mf)
         if eval_grid:
             volume("merged", mv, mf, field, (merge_grid, bounds, level))
         fill_rec = {"fill": merge_fill}
@@ -353,6 +365,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             mv, mf, closed = merge.extract_surface(field, bounds, level)
             if eval_samples:   # (c) the filled merged surface
                 evaluate("merged_filled", mv, mf)
+            if eval_quality:
+                grade("merged_filled", mv, mf)
             if eval_grid:
                 volume("merged_filled", mv, mf, field, (merge_grid, bounds, level))
             fill_rec.update(cavities=filled.cavities, cavity_nodes=filled.cavity_nodes, islands=filled.islands, island_nodes=filled.island_nodes,
@@ -376,6 +390,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
                 evaluate("merged_simplified", simp.v, simp.faces)
             if eval_grid:
                 volume("merged_simplified", simp.v, simp.faces)
+            if eval_quality:
+                grade("merged_simplified", simp.v, simp.faces)
             mv, mf, closed = simp.v, simp.faces, simplify.edge_stats(simp.faces).closed
         merge_out = merge_out or os.path.join(ROOT, "bench_outputs", "train_object")
         os.makedirs(merge_out, exist_ok=True)
@@ -386,6 +402,8 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
                          "inside_fraction": int(occ.sum()) / float(merge_grid ** 3), "volume_iou_vs_hull": merge.volume_iou(occ, hull), **fill_rec}
     if eval_grid:
         rec["volume_iou_vs_target"] = {"grid": eval_grid, "rule": "nonzero", "rays": 3, "reference": os.path.basename(target_npz), **vols}
+    if eval_quality:
+        rec["eval_quality"] = {"lattice": "2^20 per axis over each surface's own min / max cube", "order": "the default of tssplat_amd.quality", **quals}
     if eval_samples:
         rec["eval"] = {"samples": eval_samples, "seed": 0, "reference": os.path.basename(target_npz), "a": "the surface named by the key", "b": "the target mesh", **evals}
         if eval_exact:
@@ -636,6 +654,8 @@ def main():
                     help="surface metrics (tssplat_amd.metrics.compare_meshes) of the raw, merged and filled surfaces against the target mesh on N samples each (0: off)")
     ap.add_argument("--eval-exact", action="store_true",
                     help="with --eval-samples: also `eval_exact`, the same surfaces with exact sample-to-triangle distances (tssplat_amd.metrics.compare_meshes_exact)")
+    ap.add_argument("--eval-quality", action="store_true",
+                    help="`eval_quality`: crossing pairs, topology and triangle shape (tssplat_amd.quality.mesh_quality) of the raw, merged, filled and simplified surfaces and the target")
     ap.add_argument("--eval-grid", type=int, default=0, metavar="N",
                     help="volume IoU (tssplat_amd.voxelize.mesh_volume_iou) of the raw, merged, filled and simplified surfaces against the target mesh at N nodes per axis (0: off)")
     ap.add_argument("--depth-bench", default=None, metavar="PATH", help="run both --fit-depth modes and the depth stage timings; write the record to PATH")
@@ -662,7 +682,7 @@ def main():
                          stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
                          fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
                          merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill, eval_samples=args.eval_samples,
-                         merge_simplify=args.merge_simplify, eval_grid=args.eval_grid, eval_exact=args.eval_exact)))
+                         merge_simplify=args.merge_simplify, eval_grid=args.eval_grid, eval_exact=args.eval_exact, eval_quality=args.eval_quality)))
 
 
 if __name__ == "__main__":

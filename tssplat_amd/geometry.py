@@ -291,6 +291,13 @@ class TetMeshGeometry(torch.nn.Module):
         v = self.tet_v.detach()[self.surface_vid.long()].contiguous()
         return voxelize.mesh_volume_iou(v, self.surface_fid.contiguous(), v_ref, f_ref, grid=grid, bounds=bounds)
 
+    def surface_quality(self, bounds=None, max_pairs: int = 65536, order=None):
+        """:func:`tssplat_amd.quality.mesh_quality` of the boundary surface as :meth:`surface_metrics` takes it: crossing pairs, topology and
+        triangle shape.  For a multi-sphere geometry that is the raw union of the spheres' boundaries, whose overlaps are crossings."""
+        from . import quality
+        v = self.tet_v.detach()[self.surface_vid.long()].contiguous()
+        return quality.mesh_quality(v, self.surface_fid.contiguous(), bounds=bounds, max_pairs=max_pairs, order=quality.DEFAULT_ORDER if order is None else order)
+
     def forward(self, iter_num, **kwargs):
         if "permute_surface_v" in kwargs:                               # tetmesh_geometry.py:176-182
             assert "permute_surface_v_dev" in kwargs
