@@ -1065,6 +1065,67 @@ int tsamd_quality_fan_pairs(const int32_t *faces_dev, int64_t n_triangles, const
                             int32_t *corner_pairs_out_dev, void *stream);
 int tsamd_quality_union(const int32_t *pairs_dev, int64_t n_pairs, int32_t *labels_out_dev, int64_t n, void *workspace_dev, int64_t *rounds_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Smoothing a triangle surface without touching its faces: Taubin's lambda | mu filter and tangential relaxation on the
+ * umbrella operator (tssplat_amd/smooth.py).  Semantics are fixed by tests/smooth_oracle.py: float64 operations rounded one by
+ * one, sums in ascending row order, no float atomics -- bitwise repeatable and equal to the oracle.  Stateless, caller-owned
+ * buffers, nothing synchronises the host.
+ *
+ * A face is valid iff its three indices lie in 0 .. n_vertices - 1 and are pairwise distinct; nothing else contributes.
+ * tsamd_smooth_keys: faces_dev [n_triangles, 3] i32 (at most 357913940 faces).  valid_out_dev [n_triangles] u8; edge_keys_out_dev
+ * [6 n_triangles] i64: src << 32 | dst for both directions of the face's three edges; face_keys_out_dev [3 n_triangles] i64:
+ * vertex << 32 | t per corner; 2^63 - 1 throughout for an invalid face.  The caller sorts both arrays.
+ * tsamd_smooth_rows: sorted_keys_dev [n_keys] i64, the edge keys ascending.  head_out_dev [n_keys] u8: 1 at the first position
+ * of every run of equal keys that is not 2^63 - 1 -- one neighbour; the heads in order are the rows of the adjacency, by source
+ * and then by neighbour.  The run's length is the number of valid faces at that edge; irregular_out_dev [n_vertices] u8, filled
+ * by the call: 1 for a vertex that is the source of a run whose length is not two (the opposite run marks the other end).
+ *
+ * tsamd_smooth_mesh names the connectivity (all i32): offsets [n_vertices + 1] and neighbours [n_neighbours], the rows in
+ * ascending order; face_offsets [n_vertices + 1] and faces_of [n_face_entries], a vertex's valid faces in ascending order, and
+ * faces [n_triangles, 3] -- these three are read in tangential mode only and may be null otherwise.  No entry is trusted: a row
+ * that leaves its array, a neighbour outside 0 .. n_vertices - 1 or a face outside 0 .. n_triangles - 1 holds the vertex.
+ * tsamd_smooth_classify: v_dev [n_vertices, 3] f32, irregular_dev [n_vertices] u8, pinned_dev [n_vertices] u8 or null.
+ * class_out_dev [n_vertices] u8, the first that applies: TSAMD_SMOOTH_HELD_OTHER a coordinate that is not finite, no neighbour, or
+ * a neighbour with a coordinate that is not finite; _HELD_PINNED; _HELD_IRREGULAR (boundary = TSAMD_SMOOTH_BOUNDARY_FIXED only);
+ * else TSAMD_SMOOTH_MOVES.
+ *
+ * State: n_vertices records of stride float64, x y z first; stride 3 (8-byte aligned) or 4 (32-byte aligned, the fourth is
+ * written as 0).  tsamd_smooth_step: one half-step from src_dev to dst_dev, which must be another buffer.  For a vertex that moves,
+ * L = S / double[deg] - p with S the sum of its neighbours' records in row order from 0.0, per component, and d = coef L.
+ * TSAMD_SMOOTH_TAUBIN: q = p + d.  TSAMD_SMOOTH_TANGENTIAL: n = the sum over its faces, in list order from 0.0, of
+ * [p_b - p_a] x [p_c - p_a] (each component a difference of two products); nn = [nx nx + ny ny] + nz nz; if nn > 0,
+ * s = [[dx nx + dy ny] + dz nz] / nn and q = p + [d - n s], else q = p.  v0_dev [n_vertices, 3] f32 or null: when given, each
+ * coordinate of q is then clamped into [double[v0] - max_move, double[v0] + max_move] (max_move finite, >= 0; a NaN passes
+ * through).  Every other vertex is copied, so dst_dev is complete.
+ * tsamd_smooth_run: `iterations` (0 .. 4096) iterations between state_a_dev, which holds the start, and state_b_dev: the
+ * half-step lam and, in Taubin mode, the half-step mu, each reading the result of the one before; a half-step whose coefficient
+ * is exactly 0 is skipped.  *result_in_b_out (host): 1 when the result is in state_b_dev, 0 when in state_a_dev. */
+#define TSAMD_SMOOTH_TAUBIN 0
+#define TSAMD_SMOOTH_TANGENTIAL 1
+#define TSAMD_SMOOTH_BOUNDARY_FIXED 0
+#define TSAMD_SMOOTH_BOUNDARY_FREE 1
+#define TSAMD_SMOOTH_MOVES 0
+#define TSAMD_SMOOTH_HELD_OTHER 1
+#define TSAMD_SMOOTH_HELD_PINNED 2
+#define TSAMD_SMOOTH_HELD_IRREGULAR 3
+typedef struct tsamd_smooth_mesh {
+    int32_t struct_size; /* sizeof(tsamd_smooth_mesh) */
+    int32_t reserved;
+    int64_t n_vertices, n_triangles, n_neighbours, n_face_entries;
+    const int32_t *offsets_dev, *neighbours_dev;
+    const int32_t *face_offsets_dev, *faces_of_dev, *faces_dev;
+} tsamd_smooth_mesh;
+
+int tsamd_smooth_keys(const int32_t *faces_dev, int64_t n_triangles, int64_t n_vertices, uint8_t *valid_out_dev, int64_t *edge_keys_out_dev,
+                      int64_t *face_keys_out_dev, void *stream);
+int tsamd_smooth_rows(const int64_t *sorted_keys_dev, int64_t n_keys, int64_t n_vertices, uint8_t *head_out_dev, uint8_t *irregular_out_dev, void *stream);
+int tsamd_smooth_classify(const float *v_dev, const tsamd_smooth_mesh *mesh, const uint8_t *irregular_dev, const uint8_t *pinned_dev, int32_t boundary,
+                          uint8_t *class_out_dev, void *stream);
+int tsamd_smooth_step(const double *src_dev, double *dst_dev, int32_t stride, const tsamd_smooth_mesh *mesh, const uint8_t *class_dev, int32_t mode, double coef,
+                      const float *v0_dev, double max_move, void *stream);
+int tsamd_smooth_run(double *state_a_dev, double *state_b_dev, int32_t stride, const tsamd_smooth_mesh *mesh, const uint8_t *class_dev, int32_t mode, double lam,
+                     double mu, int32_t iterations, const float *v0_dev, double max_move, int32_t *result_in_b_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

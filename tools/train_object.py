@@ -52,6 +52,11 @@ solid's occupancy against `spheres_init.visual_hull` of the target silhouettes a
 bounds; `merged_surface.obj` is then the clustered mesh and `merged` gains `simplify`: the counts before and after, `edge_stats`, and with --eval-samples
 `vs_unsimplified` (`metrics.compare_meshes(simplified, unsimplified)`) next to `eval`'s `merged_simplified` against the target mesh.
 
+--merge-smooth N (0: off): `tssplat_amd.smooth.smooth` runs N iterations on the surface handed out (after the fill and the simplification), once per mode; `merged`
+gains `smooth`: per mode who moved and who was held and, with --eval-quality, `quality.shape`'s figures, the crossing pairs and `watertight` before and after, with
+--eval-samples --eval-exact `vs_unsmoothed_exact` (`metrics.compare_meshes_exact(smoothed, unsmoothed)`), and `merged_smoothed_<mode>` in `eval`, `eval_exact`,
+`eval_quality` and `volume_iou_vs_target`.  `merged_surface.obj` holds the default mode's vertices.  Faces and `closed` are untouched; crossing pairs are reported as found.
+
 --eval-samples N (0: off, the record is what it was): `eval`, `tssplat_amd.metrics.compare_meshes` on N samples per surface against the TARGET MESH --
 Chamfer distance, accuracy / completeness, F-score, normal consistency, each with its `noise_floor` -- of `raw_union` (the concatenated tet-sphere
 boundaries, interior sheets included), `merged` (with --merge-grid) and `merged_filled` (with --merge-fill).
@@ -191,7 +196,7 @@ def surface_topology(field, level, n_vertices, n_triangles):
 
 def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_every=100, stages=True, verbose=False, silhouette="operators",
         fit_depth="off", fit_depth_start=0, depth_stage_reps=(20, 1), fit_normal="off", fit_normal_start=0, normal_weight=100.0, normal_stage_reps=(20, 1), placement="host", grid=72, merge_grid=0, merge_out=None,
-        merge_fill="none", eval_samples=0, merge_simplify=0, eval_grid=0, eval_exact=False, eval_quality=False):
+        merge_fill="none", eval_samples=0, merge_simplify=0, eval_grid=0, eval_exact=False, eval_quality=False, merge_smooth=0):
     import numpy as np
     import torch
     import tssplat_amd.dr as dr
@@ -393,6 +398,33 @@ def run(target_npz=None, n_spheres=20, k=8, views=120, res=512, iters=1500, log_
             if eval_quality:
                 grade("merged_simplified", simp.v, simp.faces)
             mv, mf, closed = simp.v, simp.faces, simplify.edge_stats(simp.faces).closed
+        if merge_smooth:       # tssplat_amd.smooth on the surface handed out: both modes are recorded, the file holds the default mode's vertices; faces and closed stay
+            from tssplat_amd import metrics, quality, smooth
+            mv, mf = mv.contiguous(), mf.contiguous()
+            adj = smooth.adjacency(mf, int(mv.shape[0]))
+            fill_rec["smooth"] = {"iterations": merge_smooth, "vertices": int(mv.shape[0]), "triangles": int(mf.shape[0]),
+                                  "promise": "faces are untouched; a result free of crossing pairs is reported, not promised"}
+            before = quality.mesh_quality(mv, mf) if eval_quality else None
+            outs = {}
+            for mode in smooth.MODES:
+                sm = smooth.smooth(mv, mf, iterations=merge_smooth, mode=mode, adjacency=adj)
+                outs[mode] = sm.v
+                r = {"lam": sm.lam, "mu": sm.mu, "boundary": sm.boundary, "moved": sm.moved, "held_other": sm.held_other, "held_pinned": sm.held_pinned,
+                     "held_irregular": sm.held_irregular}
+                if eval_quality:
+                    after = quality.mesh_quality(sm.v, mf)
+                    for key, q in (("before", before), ("after", after)):
+                        r[key] = {"alr_mean": q.shape.alr_mean, "alr_p05": q.shape.alr_p05, "alr_min": q.shape.alr_min, "min_angle_min": q.shape.min_angle_min,
+                                  "min_angle_mean": q.shape.min_angle_mean, "crossing_pairs": q.intersections.crossing_pairs, "watertight": q.watertight}
+                    grade("merged_smoothed_" + mode, sm.v, mf)
+                if eval_samples:
+                    if eval_exact:
+                        r["vs_unsmoothed_exact"] = metrics.compare_meshes_exact(sm.v, mf, mv, mf, n=eval_samples, seed=0).as_dict()
+                    evaluate("merged_smoothed_" + mode, sm.v, mf)
+                if eval_grid:
+                    volume("merged_smoothed_" + mode, sm.v, mf)
+                fill_rec["smooth"][mode] = r
+            mv = outs[smooth.DEFAULT_MODE]
         merge_out = merge_out or os.path.join(ROOT, "bench_outputs", "train_object")
         os.makedirs(merge_out, exist_ok=True)
         merge.write_obj(os.path.join(merge_out, "merged_surface.obj"), mv, mf)
@@ -650,6 +682,8 @@ def main():
                     help="flood fill before the extraction: fill enclosed cavities, or also keep only the largest solid component")
     ap.add_argument("--merge-simplify", type=int, default=0, metavar="K",
                     help="cluster the merged surface on N // K cells per axis (tssplat_amd.simplify; 0: off, else an integer >= 2)")
+    ap.add_argument("--merge-smooth", type=int, default=0, metavar="N",
+                    help="smooth the merged surface by N iterations (tssplat_amd.smooth, both modes recorded, the default mode written; 0: off)")
     ap.add_argument("--eval-samples", type=int, default=0, metavar="N",
                     help="surface metrics (tssplat_amd.metrics.compare_meshes) of the raw, merged and filled surfaces against the target mesh on N samples each (0: off)")
     ap.add_argument("--eval-exact", action="store_true",
@@ -682,7 +716,8 @@ def main():
                          stages=not args.no_stages, fit_depth=args.fit_depth, fit_depth_start=args.fit_depth_start, fit_normal=args.fit_normal,
                          fit_normal_start=args.fit_normal_start, normal_weight=args.normal_weight, placement=args.placement, grid=args.grid,
                          merge_grid=args.merge_grid, merge_out=args.merge_out, merge_fill=args.merge_fill, eval_samples=args.eval_samples,
-                         merge_simplify=args.merge_simplify, eval_grid=args.eval_grid, eval_exact=args.eval_exact, eval_quality=args.eval_quality)))
+                         merge_simplify=args.merge_simplify, eval_grid=args.eval_grid, eval_exact=args.eval_exact, eval_quality=args.eval_quality,
+                         merge_smooth=args.merge_smooth)))
 
 
 if __name__ == "__main__":

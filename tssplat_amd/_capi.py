@@ -82,6 +82,16 @@ class BlendPlanStruct(C.Structure):
     ]
 
 
+class SmoothMeshStruct(C.Structure):
+    """``tsamd_smooth_mesh``: sizes and device pointers of a vertex adjacency (tssplat_amd/smooth.py: VertexAdjacency)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("reserved", C.c_int32),
+        ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_neighbours", C.c_int64), ("n_face_entries", C.c_int64),
+        ("offsets_dev", C.c_void_p), ("neighbours_dev", C.c_void_p),
+        ("face_offsets_dev", C.c_void_p), ("faces_of_dev", C.c_void_p), ("faces_dev", C.c_void_p),
+    ]
+
+
 ABI_VERSION = 3          # include/tssplat_amd.h: TSAMD_ABI_VERSION
 
 # every symbol include/tssplat_amd.h declares: name -> (restype, argtypes)
@@ -269,6 +279,14 @@ SIGNATURES = {
     "tsamd_quality_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsamd_quality_fan_pairs": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsamd_quality_union": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    # surface smoothing: directed edge keys and vertex-face keys, the rows of the adjacency, who moves, one half-step, a whole run
+    "tsamd_smooth_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_smooth_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsamd_smooth_classify": (C.c_int, [C.c_void_p, C.POINTER(SmoothMeshStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "tsamd_smooth_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SmoothMeshStruct), C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_double,
+                                    C.c_void_p]),
+    "tsamd_smooth_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SmoothMeshStruct), C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                   C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.c_void_p]),
 }
 
 

@@ -258,16 +258,17 @@ class TetMeshGeometry(torch.nn.Module):
         v, t = scenes.read_veg(path)
         return cls(v, t, **kwargs)
 
-    def export_merged(self, path: str, filename: str, grid: int = 128, bounds=None, fill: str = "none", simplify=None):
+    def export_merged(self, path: str, filename: str, grid: int = 128, bounds=None, fill: str = "none", simplify=None, smooth=None):
         """Writes ``filename_merged.obj`` under ``path``: the union of all tets as ONE closed, consistently oriented triangle mesh
         (:func:`tssplat_amd.merge.merge_tets` at ``grid`` nodes per axis; plain ``v`` / ``f`` lines) and returns the
         ``MergedSurface``.  For a multi-sphere geometry this is the merge of the spheres into one shape.  ``fill``: ``"cavities"``
         fills enclosed voids first, ``"outer"`` also drops every solid component but the largest.  ``simplify=k``: the surface is then
-        clustered on ``grid // k`` cells per axis (``merge_tets(simplify=k)``) and the file holds the clustered mesh."""
+        clustered on ``grid // k`` cells per axis (``merge_tets(simplify=k)``) and the file holds the clustered mesh.  ``smooth=n``: ``n``
+        iterations of :func:`tssplat_amd.smooth.smooth` last of all (``merge_tets(smooth=n)``); the file holds the smoothed vertices."""
         import os
         from . import merge
         os.makedirs(path, exist_ok=True)
-        merged = merge.merge_tets(self.tet_v.detach(), self.tet_elem, grid=grid, bounds=bounds, fill=fill, simplify=simplify)
+        merged = merge.merge_tets(self.tet_v.detach(), self.tet_elem, grid=grid, bounds=bounds, fill=fill, simplify=simplify, smooth=smooth)
         merge.write_obj(os.path.join(path, filename + "_merged.obj"), merged.v, merged.faces)
         return merged
 

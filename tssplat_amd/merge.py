@@ -20,7 +20,10 @@ Simplification: ``merge_tets(simplify=k)`` clusters the extracted surface on ``g
 (:mod:`tssplat_amd.simplify`: vertex clustering with quadric placement; it does not preserve manifoldness, so ``closed`` is then
 what :func:`tssplat_amd.simplify.edge_stats` finds).
 
-Out of scope: smoothing, re-tetrahedralising.
+Smoothing: ``merge_tets(smooth=n)`` runs ``n`` iterations of the default mode of :mod:`tssplat_amd.smooth` (Taubin's filter) on the
+surface that is handed out, after the fill and the simplification.  It moves vertices only: ``faces``, and with them ``closed``, stay.
+
+Out of scope: re-tetrahedralising.
 """
 from __future__ import annotations
 
@@ -48,7 +51,8 @@ class MergedSurface:
     """One indexed triangle mesh around the union of all tets.  ``closed``: no grid-border node is inside, so every edge lies in
     exactly two triangles of opposite direction.  ``inside_fraction``: inside nodes over all nodes, of the field that was extracted.
     ``fill``: ``"none"``, ``"cavities"`` or ``"outer"``, and what it changed (:class:`FilledField`).  ``simplified``: set by ``merge_tets(simplify=k)``;
-    ``v`` / ``faces`` then are the clustered mesh and ``closed`` is what ``simplify.edge_stats`` finds on it."""
+    ``v`` / ``faces`` then are the clustered mesh and ``closed`` is what ``simplify.edge_stats`` finds on it.  ``smoothed``: set by
+    ``merge_tets(smooth=n)``; ``v`` then holds the smoothed vertices, ``faces`` and ``closed`` are untouched."""
     v: torch.Tensor                # float32 [Nv, 3]
     faces: torch.Tensor            # int32 [Nt, 3], normals point from inside to outside
     closed: bool
@@ -61,6 +65,7 @@ class MergedSurface:
     cavity_nodes: int = 0
     islands: int = 0
     island_nodes: int = 0
+    smoothed: Optional["SmoothedSurface"] = None          # tssplat_amd.smooth.SmoothedSurface
     simplified: Optional["SimplifiedSurface"] = None      # tssplat_amd.simplify.SimplifiedSurface
 
 
@@ -295,15 +300,28 @@ def _check_simplify(name: str, simplify, grid: int):
     return int(simplify)
 
 
-def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=None, level=None, fill: str = "none", simplify=None) -> MergedSurface:
+def _check_smooth(name: str, smooth):
+    """``None``, or the iterations of the default mode: an integer >= 1 (at most ``tssplat_amd.smooth.MAX_ITERATIONS``)."""
+    if smooth is None:
+        return None
+    if not _args.is_int(smooth, 1, 4096):
+        _fail(name, f"smooth must be None or an integer in 1 .. 4096, got {smooth!r}")
+    return int(smooth)
+
+
+def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=None, level=None, fill: str = "none", simplify=None,
+               smooth=None) -> MergedSurface:
     """The union of all contributing tets as one closed, consistently oriented triangle mesh: ``union_field`` then
     ``extract_surface``.  ``bounds=None``: :func:`default_bounds`; ``level=None``: :func:`default_level`.  ``fill``: ``"none"`` extracts
     the union field as it is (one closed surface per boundary between components); ``"cavities"`` and ``"outer"`` extract
     :func:`fill_field` of it, at the price of one more readback.  ``simplify=k`` (an integer >= 2): the extracted surface is clustered
     on ``grid // k`` cells per axis over the same bounds (:func:`tssplat_amd.simplify.simplify`, after the fill); ``v`` / ``faces`` / ``closed``
-    then describe the clustered mesh and ``simplified`` holds its record."""
+    then describe the clustered mesh and ``simplified`` holds its record.  ``smooth=n`` (an integer >= 1): ``n`` iterations of
+    :func:`tssplat_amd.smooth.smooth` with its defaults on the surface that is handed out, last of all; ``v`` then holds the smoothed
+    vertices, ``smoothed`` the record, and ``faces`` and ``closed`` are as without."""
     name = "merge_tets"
     fill = _check_fill(name, fill, allow_none=True)
+    smooth = _check_smooth(name, smooth)
     tet_v, elem = _check_mesh(name, tet_v, elem)
     grid = _args.integer(_fail, name, "grid", grid, MIN_GRID, MAX_GRID)
     simplify = _check_simplify(name, simplify, grid)
@@ -322,6 +340,10 @@ def merge_tets(tet_v: torch.Tensor, elem: torch.Tensor, grid: int = 128, bounds=
         merged.simplified = _simplify.simplify(v, faces, grid // simplify, (lo, hi))
         merged.v, merged.faces = merged.simplified.v, merged.simplified.faces
         merged.closed = _simplify.edge_stats(merged.faces).closed
+    if smooth is not None:
+        from . import smooth as _smooth
+        merged.smoothed = _smooth.smooth(merged.v, merged.faces, iterations=smooth)
+        merged.v = merged.smoothed.v
     return merged
 
 

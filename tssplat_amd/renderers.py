@@ -289,20 +289,23 @@ class MeshRasterizer(torch.nn.Module):
             tex = atlas.bake_material(self.materials, v_pos, t_pos_idx, texture_res)
         atlas.write_textured_obj(out_dir, "exported_surface", v_pos, t_pos_idx, v_tex, t_tex_idx, tex)
 
-    def export_merged(self, path: str, folder: str, texture_res: Optional[int] = None, grid: int = 128, fill: str = "none", simplify=None):
+    def export_merged(self, path: str, folder: str, texture_res: Optional[int] = None, grid: int = 128, fill: str = "none", simplify=None,
+                      smooth=None):
         """Writes ``merged_surface.obj``, ``.mtl`` and ``.png`` under ``path/folder``: the union of the geometry's tets as one closed
         surface (:func:`tssplat_amd.merge.merge_tets` at ``grid`` nodes per axis) with ``self.materials`` baked into the
         closed-form atlas.  The colour field is a function of position, so the bake is the one of :meth:`export`, unchanged.
         ``texture_res=None``: the smallest power of two >= 1024 whose atlas holds the triangles (marching tetrahedra makes many).
         ``fill``: as in ``merge_tets`` -- ``"cavities"`` and ``"outer"`` spare the atlas the triangles nobody can see.
         ``simplify=k``: the surface is clustered on ``grid // k`` cells per axis before the bake (``merge_tets(simplify=k)``); fewer
-        triangles, so ``texture_res=None`` picks a smaller atlas by itself.  Returns the ``MergedSurface``."""
+        triangles, so ``texture_res=None`` picks a smaller atlas by itself.  ``smooth=n``: ``n`` iterations of
+        :func:`tssplat_amd.smooth.smooth` on the surface before the bake (``merge_tets(smooth=n)``); the faces, and so the atlas layout,
+        are the same as without.  Returns the ``MergedSurface``."""
         from . import merge
         assert self.materials is not None
         out_dir = os.path.join(path, folder)
         os.makedirs(out_dir, exist_ok=True)
         with torch.no_grad():
-            merged = merge.merge_tets(self.geometry.tet_v.detach(), self.geometry.tet_elem, grid=grid, fill=fill, simplify=simplify)
+            merged = merge.merge_tets(self.geometry.tet_v.detach(), self.geometry.tet_elem, grid=grid, fill=fill, simplify=simplify, smooth=smooth)
             n_tri = int(merged.faces.shape[0])
             if n_tri == 0:
                 raise ValueError("MeshRasterizer.export_merged: the merged surface has no triangle (no tet contributes inside the grid)")

@@ -12,7 +12,7 @@ Limits.  Clustering does NOT preserve manifoldness: two sheets of the surface pa
 handle can collapse to an edge.  :func:`edge_stats` reports what came out; ``closed`` is reported, never promised.  A cell's records
 are summed serially by one lane, so a grid with very few cells on a large mesh (``cells=1`` at the extreme) is slow by construction.
 
-Out of scope: edge collapses, manifold repair, smoothing, re-tetrahedralising.
+Out of scope: edge collapses, manifold repair, re-tetrahedralising.  Smoothing is :mod:`tssplat_amd.smooth`.
 """
 from __future__ import annotations
 
