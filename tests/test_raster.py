@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import raster_f32_oracle as F
 from oracle import raster_oracle as R
 from tssplat_amd import _capi, scenes
 
@@ -339,16 +340,47 @@ def _surface_scene(kind, spheres, n_views, seed=0):
     return R.transform_pos(mvp, v), np.asarray(faces, dtype=np.int32), v
 
 
+def _both_oracles(pos_clip, tri, res):
+    """``R.rasterize`` (float64) and the float32 statement of the same values (tests/raster_f32_oracle.py) from ONE pass of the
+    oracle's coverage: ``(ref64, rast32, zero_sign)``."""
+    pos_clip = pos_clip[None] if pos_clip.ndim == 2 else pos_clip
+    keys = np.stack([R.rasterize_ids(pos_clip[b], tri, res[0], res[1]) for b in range(pos_clip.shape[0])])
+    ref = np.stack([R.resolve(pos_clip[b], tri, keys[b]) for b in range(pos_clip.shape[0])])
+    rast32, zero_sign = F.resolve32(pos_clip, tri, keys)
+    return ref, rast32, zero_sign
+
+
+def _assert_rast_bits(rast, rast32, zero_sign):
+    """All four channels of the device's ``rast`` against the float32 statement, on the raw bits -- no pixel excluded; the pixels whose
+    barycentric is exactly -0 before the clamp (where the clamp's +0 is the device's ordering of the zeros) are counted for the record."""
+    covered = int((rast32[..., 3] > 0).sum())
+    print(f"rast bits: {covered} covered pixels, {int(zero_sign.sum())} with a -0 barycentric before the clamp, none excluded")
+    assert F.same_bits(rast.detach().cpu().numpy(), rast32)
+
+
+def _assert_interpolate_gradients(attr_np, rast_np, tri, g, grad_attr, grad_rast):
+    """On top of the fixed tolerances: ``grad_rast`` bit for bit against the float32 statement, ``grad_attr`` within the any-order
+    summation bound ``gamma_(n-1) sum |c_i|`` of its float32 per-pixel terms (tests/raster_f32_oracle.py)."""
+    gr, (hit, ab, tt, terms) = F.interpolate_backward32(attr_np, rast_np, tri, g)
+    assert F.same_bits(grad_rast, gr)
+    channels = attr_np.shape[-1]
+    index = F.scatter_index(ab, tt, attr_np.shape[1], channels, np.arange(channels)).reshape(-1)
+    ok, ratio, zero_ok = F.any_order_sum_check(grad_attr, index, terms.reshape(-1), attr_np.shape)
+    print(f"grad_attr: {int(hit.sum())} contributing pixels, max error / any-order bound {ratio:.3f}")
+    assert ok and zero_ok
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,spheres,views,res", [("kuhn4", 3, 2, (48, 64)), ("kuhn8", 6, 3, (128, 128)), ("kuhn19", 2, 1, (256, 256))])
 def test_rasterize_ids_bit_exact_and_barycentrics(kind, spheres, views, res):
     import torch
     import tssplat_amd.dr as dr
     pos_clip, tri, _ = _surface_scene(kind, spheres, views)
-    ref = R.rasterize(pos_clip, tri, res)
+    ref, rast32, zero_sign = _both_oracles(pos_clip, tri, res)
     ctx = dr.RasterizeCudaContext()
     rast, db = dr.rasterize(ctx, torch.from_numpy(pos_clip).cuda(), torch.from_numpy(tri).cuda(), resolution=list(res), grad_db=False)
     assert rast.shape == (views, res[0], res[1], 4) and db.shape[-1] == 0
+    _assert_rast_bits(rast, rast32, zero_sign)
     got = rast.cpu().numpy().astype(np.float64)
     assert (ref[..., 3] > 0).mean() > 0.02                                       # the scene is in view
     assert np.array_equal(got[..., 3], ref[..., 3]), "triangle ids must be bit-exact"
@@ -377,8 +409,9 @@ def test_rasterize_edge_cases_on_gpu():
     tri = np.concatenate([tri, tri[:10], [[1, 1, 2]]]).astype(np.int32)          # duplicates (ties -> lower id) and a degenerate one
     pos = np.stack([pos, pos[::-1].copy()])
     for res in ((16, 16), (33, 20)):
-        ref = R.rasterize(pos, tri, res)
+        ref, rast32, zero_sign = _both_oracles(pos, tri, res)
         rast, _ = dr.rasterize(ctx, torch.from_numpy(pos).cuda(), torch.from_numpy(tri).cuda(), resolution=list(res), grad_db=False)
+        _assert_rast_bits(rast, rast32, zero_sign)
         got = rast.cpu().numpy().astype(np.float64)
         assert np.array_equal(got[..., 3], ref[..., 3])
         hit = ref[..., 3] > 0
@@ -412,8 +445,9 @@ def test_rasterize_large_triangles_take_the_64_bit_walk():
     tri = np.concatenate([big, n + np.arange(120).reshape(40, 3)]).astype(np.int32)
     pos[:4] = [[-3, -3, 0.5, 1], [3, -3, 0.5, 1], [3, 3, 0.5, 1], [-3, 3, 0.5, 1]]           # a screen-filling pair behind everything
     tri = np.concatenate([tri, [[0, 1, 2], [0, 2, 3]]]).astype(np.int32)
-    ref = R.rasterize(pos[None], tri, (H, W))
+    ref, rast32, zero_sign = _both_oracles(pos[None], tri, (H, W))
     rast, _ = dr.rasterize(ctx, torch.from_numpy(pos[None]).cuda(), torch.from_numpy(tri).cuda(), resolution=[H, W], grad_db=False)
+    _assert_rast_bits(rast, rast32, zero_sign)
     got = rast.cpu().numpy().astype(np.float64)
     assert (ref[..., 3] > 0).all()                                               # the backdrop covers the screen
     assert len(np.unique(ref[..., 3])) > 30                                      # and many triangles of both kinds are visible
@@ -446,6 +480,8 @@ def test_interpolate_forward_backward(attr_batch_is_one):
     assert np.abs(attr.grad.cpu().numpy() - ga).max() <= 2e-5 * np.abs(ga).max()            # fp32 atomics, arbitrary order
     assert np.abs(rast_in.grad.cpu().numpy() - gr).max() <= 2e-5 * max(np.abs(gr).max(), 1e-30)
     assert (rast_in.grad[..., 2:] == 0).all()
+    assert F.same_bits(out.detach().cpu().numpy(), F.interpolate32(attr_np, rast_np, tri))
+    _assert_interpolate_gradients(attr_np, rast_np, tri, g, attr.grad.cpu().numpy(), rast_in.grad.cpu().numpy())
 
 
 @pytest.mark.gpu
@@ -475,6 +511,8 @@ def test_interpolate_channel_counts(channels):
     assert np.abs(attr.grad.cpu().numpy() - ga).max() <= 2e-5 * np.abs(ga).max()            # fp32 atomics, arbitrary order
     assert np.abs(rast_in.grad.cpu().numpy() - gr).max() <= 2e-5 * max(np.abs(gr).max(), 1e-30)
     assert (rast_in.grad[..., 2:] == 0).all()
+    assert F.same_bits(out.detach().cpu().numpy(), F.interpolate32(attr_np, rast_np, tri))
+    _assert_interpolate_gradients(attr_np, rast_np, tri, g, attr.grad.cpu().numpy(), rast_in.grad.cpu().numpy())
 
 
 @pytest.mark.gpu
@@ -567,6 +605,13 @@ def test_rasterize_backward_through_interpolate():
     scale = np.abs(gp).max()
     assert np.abs(got - gp).max() <= 2e-3 * scale
     assert np.abs(got - gp).mean() <= 2e-5 * scale
+    # and within the any-order summation bound of the float32 per-pixel contributions (tests/raster_f32_oracle.py)
+    gr32, _ = F.interpolate_backward32(attr_np, rast_np, tri, g)
+    bb, tv, d = F.rasterize_backward32(pos_clip, tri, rast_np, gr32)
+    index = F.scatter_index(bb, tv, pos_clip.shape[1], 4, np.array([0, 1, 3])).reshape(-1)
+    ok, ratio, zero_ok = F.any_order_sum_check(got, index, d.reshape(-1), pos_clip.shape)
+    print(f"grad_pos: {len(bb)} contributing pixels, max error / any-order bound {ratio:.3f}")
+    assert ok and zero_ok
 
 
 @pytest.mark.gpu
