@@ -1,5 +1,6 @@
-"""The float32 statement of the rasteriser's VALUE path (tssplat_amd/csrc/raster_kernels.hip): numpy, every operation rounded to
-``np.float32`` on its own, in the kernel's order -- TEST INFRASTRUCTURE.
+"""The float32 statement of the rasteriser's VALUE path (tssplat_amd/csrc/raster_kernels.hip, interpolate_kernels.hip and
+the helpers they share, raster_device.h): numpy, every operation rounded to ``np.float32`` on its own, in the kernel's order -- TEST
+INFRASTRUCTURE.
 
 Coverage and depth stay defined by ``oracle/raster_oracle.py::rasterize_ids`` (integers and a float32 depth plane, already bit for
 bit); this module takes its winning ids and restates what the kernels compute from them:
@@ -10,7 +11,7 @@ bit); this module takes its winning ids and restates what the kernels compute fr
     interpolate_backward32  interpolate_backward_kernel: grad_rast per pixel and the per-pixel scatter terms of grad_attr
     rasterize_backward32    rasterize_backward_kernel: the nine per-pixel contributions of edge_functions_backward
 
-The kernel file is compiled without contraction and float32 division is correctly rounded, so a numpy float32 array operation
+The kernel files are compiled without contraction and float32 division is correctly rounded, so a numpy float32 array operation
 (one IEEE operation, round to nearest even) is the same function of the same bits: the results must agree with the device BIT FOR
 BIT.  The one place where C leaves a choice is the sign of ``fmaxf(-0, +0)`` in the clamp of a barycentric that is exactly ``-0``:
 gfx9's ``v_max_f32`` / ``v_med3_f32`` order -0 below +0 (IEEE 754-2019 ``maximumNumber``), so the clamp gives +0, and that is what is

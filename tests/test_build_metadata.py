@@ -50,10 +50,10 @@ def test_tile_kernels_have_no_static_lds_and_do_not_spill():
 
 
 def test_renderer_kernels_are_built_without_fp_contraction():
-    """Bit-exact triangle ids / identical silhouette decisions need separately rounded multiplies and adds: the two renderer
+    """Bit-exact triangle ids / identical silhouette decisions need separately rounded multiplies and adds: the four renderer
     translation units must be compiled with -ffp-contract=off AFTER the global -ffp-contract=fast (the last flag wins)."""
     from tssplat_amd import _build
-    for src in ("raster_kernels.hip", "aa_kernels.hip"):
+    for src in ("raster_kernels.hip", "interpolate_kernels.hip", "term_kernels.hip", "aa_kernels.hip"):
         assert src in _build.SOURCES
         assert _build.SOURCE_FLAGS.get(src) == ["-ffp-contract=off"]
     assert "-ffp-contract=fast" in _build.DEVICE_FLAGS                      # the energy kernels want the fused forms

@@ -1,5 +1,5 @@
-"""The rasteriser core (tssplat_amd/csrc/raster_kernels.hip: snap, bin, clip, resolve, silhouette_cover, rasterize_backward,
-interpolate, interpolate_backward) pinned BIT FOR BIT and at every walk and launch edge.
+"""The rasteriser core (tssplat_amd/csrc/raster_kernels.hip: snap, bin, clip, resolve, silhouette_cover, rasterize_backward;
+interpolate_kernels.hip: interpolate, interpolate_backward) pinned BIT FOR BIT and at every walk and launch edge.
 
 Values: tests/raster_f32_oracle.py states the kernels' float32 operations in numpy; a CPU test ties it to the float64 oracle
 (oracle/raster_oracle.py) within a derived rounding bound, the GPU tests compare the device with it by ``np.array_equal`` on
@@ -73,8 +73,9 @@ def subpixel_vertices(points, res):
     return p.astype(np.float32)
 
 
-def device_rasterize(pos, tri, res):
-    """``(keys, rast, pair masks)`` of tsamd_rasterize as numpy; the depth keys are the head of the workspace."""
+def device_rasterize(pos, tri, res, want_masks=True):
+    """``(keys, rast, pair masks)`` of tsamd_rasterize as numpy; the depth keys are the head of the workspace.  ``want_masks=False``:
+    the call passes no mask buffer (the resolve pass then loads no neighbour key), and the buffer comes back untouched."""
     import torch
     from tssplat_amd import _capi
     lib = _capi.load()
@@ -85,7 +86,8 @@ def device_rasterize(pos, tri, res):
     nm = int(lib.tsamd_pair_masks_bytes(B, H, W))
     assert nm == (B * H * W + 63) // 64 * 16
     masks = torch.full((nm,), 0xAB, dtype=torch.uint8, device="cuda")
-    _capi.check(lib.tsamd_rasterize(pos_d.data_ptr(), B, V, tri_d.data_ptr(), T, H, W, ws.data_ptr(), rast.data_ptr(), masks.data_ptr(), None))
+    _capi.check(lib.tsamd_rasterize(pos_d.data_ptr(), B, V, tri_d.data_ptr(), T, H, W, ws.data_ptr(), rast.data_ptr(),
+                                    masks.data_ptr() if want_masks else None, None))
     torch.cuda.synchronize()
     keys = ws[:B * H * W * 8].cpu().numpy().view(np.uint64).reshape(B, H, W)
     return keys, rast.cpu().numpy(), masks.cpu().numpy().view(np.uint64).reshape(-1, 2)
@@ -504,6 +506,23 @@ def test_tiny_image_table_reaches_the_small_image_path():
 def test_tiny_images_bit_exact(batch, res):
     pos, tri = _tiny_scene(batch)
     check_device(pos, tri, res, full_alpha=True)
+
+
+# The resolve pass WITHOUT pair masks, in every placement regime of a wave of 4 x 64 pixels: several views per wave (H W < 256), a wave
+# that straddles one view boundary, full chunks only, a wave that ends in mid-row (where the masked pass makes its extra load of the
+# right-hand key), a short last wave.  (With masks, and for the cover pass, test_tiny_images_bit_exact reaches all five.)
+NO_MASK_CASES = [(5, (6, 8)), (5, (8, 8)), (3, (33, 50)), (1, (32, 32)), (2, (7, 192))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batch,res", NO_MASK_CASES)
+def test_resolve_without_masks_bit_exact(batch, res):
+    pos, tri = _tiny_scene(batch)
+    want, zero_sign, keys = oracle_rast(pos, tri, res)
+    got_keys, got, masks = device_rasterize(pos, tri, res, want_masks=False)
+    assert np.array_equal(got_keys, keys)
+    assert F.same_bits(got, want), f"{int(zero_sign.sum())} pixels with a -0 barycentric"
+    assert (masks.view(np.uint8) == 0xAB).all()                                                # nothing was written through a null pointer's twin
 
 
 # ------------------------------------------------ C. the fragment queue of the pixel walk ------------------------------------------------

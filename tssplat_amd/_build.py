@@ -21,12 +21,12 @@ _OBJ = os.path.join(_HERE, "_obj")
 ARCH = "gfx950"
 
 SOURCES = ["plan.cpp", "plan_mesh.cpp", "plan_tiling.cpp", "plan_layout.cpp", "plan_planes.cpp", "partition.cpp", "conflict_opt.cpp", "regular_batch.cpp", "capi.cpp", "tile_kernel.hip", "step_kernels.hip", "eval_launch.cpp", "surface.cpp", "surface_capi.cpp", "surface_kernels.hip",
-           "raster_capi.cpp", "raster_kernels.hip", "aa_kernels.hip", "grid_capi.cpp", "grid_kernels.hip",
+           "raster_capi.cpp", "raster_kernels.hip", "interpolate_kernels.hip", "term_kernels.hip", "aa_kernels.hip", "grid_capi.cpp", "grid_kernels.hip",
            "mlp_capi.cpp", "mlp_kernels.hip", "texture_capi.cpp", "texture_kernels.hip", "shade_capi.cpp", "shade_kernels.hip",
            "init_capi.cpp", "init_kernels.hip", "merge_capi.cpp", "merge_kernels.hip", "fill_kernels.hip",
            "metrics_capi.cpp", "metrics_kernels.hip", "pointmesh_capi.cpp", "pointmesh_kernels.hip", "simplify_capi.cpp", "simplify_kernels.hip", "voxel_capi.cpp", "voxel_kernels.hip",
            "quality_capi.cpp", "quality_kernels.hip", "smooth_capi.cpp", "smooth_kernels.hip"]
-HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "launch_args.h", "regular_batch.h", "surface.h", "raster.h", "grid.h", "mlp.h", "texture.h", "shade.h", "init.h", "merge.h", "metrics.h", "mesh_triangle.h", "pointmesh.h", "simplify.h", "voxel.h", "quality.h", "smooth.h", "det_mean.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
+HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "launch_args.h", "regular_batch.h", "surface.h", "raster.h", "raster_device.h", "grid.h", "mlp.h", "texture.h", "shade.h", "init.h", "merge.h", "metrics.h", "mesh_triangle.h", "pointmesh.h", "simplify.h", "voxel.h", "quality.h", "smooth.h", "det_mean.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
 
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-pthread"]
 # -fno-slp-vectorize: SLP packs the 3x3 algebra into v_pk_*_f32, which runs at the scalar-fp32 rate on
@@ -48,7 +48,8 @@ DEVICE_FLAGS = [f"--offload-arch={ARCH}", "-ffp-contract=fast", "-fno-slp-vector
 # voxel_kernels.hip: the lattice snap and the crossing coordinate round like tests/voxel_oracle.py, bit for bit;
 # quality_kernels.hip: the lattice snap and the float64 shape record round like tests/quality_oracle.py, bit for bit;
 # smooth_kernels.hip: the umbrella sums, the division, the face normals and the tangential projection round like tests/smooth_oracle.py, bit for bit)
-SOURCE_FLAGS = {"raster_kernels.hip": ["-ffp-contract=off"], "aa_kernels.hip": ["-ffp-contract=off"],
+SOURCE_FLAGS = {"raster_kernels.hip": ["-ffp-contract=off"], "interpolate_kernels.hip": ["-ffp-contract=off"], "term_kernels.hip": ["-ffp-contract=off"],
+                "aa_kernels.hip": ["-ffp-contract=off"],
                 "texture_kernels.hip": ["-ffp-contract=off"], "shade_kernels.hip": ["-ffp-contract=off"],
                 "init_kernels.hip": ["-ffp-contract=off"], "merge_kernels.hip": ["-ffp-contract=off"],
                 "metrics_kernels.hip": ["-ffp-contract=off"], "pointmesh_kernels.hip": ["-ffp-contract=off"], "simplify_kernels.hip": ["-ffp-contract=off"],

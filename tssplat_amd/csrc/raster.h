@@ -1,4 +1,4 @@
-// Launch interface between the C ABI (raster_capi.cpp) and the renderer-slice kernels (raster_kernels.hip).
+// Launch interface between the C ABI (raster_capi.cpp) and the renderer-slice kernels (raster_, interpolate_, term_, aa_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -52,7 +52,7 @@ hipError_t launch_silhouette_backward(const float *pos_clip, const int32_t *tri,
 // loss = mean((alpha - target)^2) over n floats, bitwise repeatable; n = 0 stores 0
 int64_t silhouette_mse_workspace_bytes(int64_t n);
 hipError_t launch_silhouette_mse(const float *alpha, const float *target, int64_t n, void *workspace, float *loss, hipStream_t stream);
-// The id-driven image terms (raster_kernels.hip): loss = mean over batch * height * width pixels and the term's channels of
+// The id-driven image terms (term_kernels.hip): loss = mean over batch * height * width pixels and the term's channels of
 // (x_c m - t_c m)^2, x a value of y = interpolate(attr) for attr [n_vertices, 3] from the alpha stage's ids (y = 0 on background), target
 // [batch, height, width, channels], mask [batch, height, width]; bitwise repeatable; the output image (optional): x per pixel.  No pixel
 // or no triangle: loss 0, nothing else written.  backward: the attribute's gradient [n_vertices, 3] is zero-filled by the launch, grad_pos
@@ -74,7 +74,7 @@ hipError_t launch_normal_mse_backward(const float *pos_clip, int64_t batch, int6
                                       float *grad_attr, float *grad_pos, hipStream_t stream);
 hipError_t launch_interpolate(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels, const float *rast, const int32_t *tri,
                               int64_t n_tri, int64_t batch, int height, int width, float *out, hipStream_t stream);
-// grad_attr is zero-filled by the launch; grad_rast may be null
+// (these two launches: interpolate_kernels.hip)  grad_attr is zero-filled by the launch; grad_rast may be null
 hipError_t launch_interpolate_backward(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels, const float *rast, const int32_t *tri,
                                        int64_t n_tri, int64_t batch, int height, int width, const float *grad_out, float *grad_attr, float *grad_rast,
                                        hipStream_t stream);

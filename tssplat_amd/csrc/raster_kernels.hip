@@ -1,6 +1,7 @@
-// gfx950 kernels of the renderer slice: rasterize + interpolate, the two nvdiffrast operators
+// gfx950 kernels of the renderer slice: rasterize, the first of the two nvdiffrast operators
 // /root/reference/renderers/mesh_rasterizer.py:103,117,145,153 calls: forward rasterisation (triangle id, perspective-correct
-// barycentrics, z/w) and its backward, interpolate forward and backward.  (antialias: aa_kernels.hip.)
+// barycentrics, z/w) and its backward.  (interpolate: interpolate_kernels.hip; the id-driven image terms: term_kernels.hip;
+// antialias: aa_kernels.hip; what they share on the device: raster_device.h.)
 //
 // The specification these kernels implement is oracle/raster_oracle.py (a restatement of nvdiffrast's published
 // algorithm with every open choice fixed there); coverage and the depth test repeat its float64 / integer operations
@@ -15,10 +16,7 @@
 //   rasterize_resolve_kernel  one lane per pixel: winning triangle -> (u, v, z/w, id + 1); optional by-product: the pair masks
 //                          (which pixels differ from their right / upper neighbour) that the antialias kernels start from
 //   silhouette_cover_kernel  the alpha stage's resolve pass: id, coverage 0 / 1 and the coverage masks per pixel, from the keys alone
-//   interpolate_kernel / interpolate_backward_kernel  one lane per pixel
-//   term_mse_kernel<Term> / term_mse_backward_kernel<Term>  an image term without an image chain: masked MSE (det_mean.h) of a value
-//                          of the interpolated 3-channel vertex attribute and both of its scatters, from the alpha stage's ids.
-//                          DepthTerm: the distance of the interpolated world position to the camera; NormalTerm: the attribute itself
+//   rasterize_backward_kernel  one lane per pixel: the quotient rule of (u, v), summed over runs of one triangle, fp32 atomics
 //
 // Bound: the depth image -- L2 atomics and the reads in front of them (pricing builds, profiles/r04_raster_experiments.md: walk
 // 0.46 ms, fragment queue + depth reads 0.23, atomics 0.31 of 1.10 ms on the 512-sphere surface); 12 B of indices + 3 x 16 B of
@@ -27,8 +25,8 @@
 
 #include <algorithm>
 
-#include "det_mean.h"
 #include "raster.h"
+#include "raster_device.h"
 
 // Coverage, depth and silhouette decisions repeat the oracle's operations one by one: a multiply and an add must round
 // separately.  The __fmul_rn / __dmul_rn family are plain operators in this toolchain's headers, so this file is compiled with
@@ -40,7 +38,6 @@ namespace {
 constexpr int kSubBits = 8;
 constexpr long long kSub = 1ll << kSubBits;
 constexpr long long kCoordLimit = 1ll << 22;
-constexpr unsigned long long kNoFragment = 0xFFFFFFFFFFFFFFFFull;
 
 // One snapped vertex of one view, 16 bytes: window coordinates in 1/256 pixel (|x|, |y| <= 2^22) and z/w rounded to float32.
 // x == kDropped: the vertex is not finite, behind the eye (w <= 0) or out of the coordinate range -- its triangles are dropped.
@@ -396,49 +393,6 @@ __global__ __launch_bounds__(256) void rasterize_clip_kernel(const float4 *pos, 
     }
 }
 
-// The homogeneous edge functions of a pixel centre against the clip-space triangle (v0, v1, v2): what the barycentrics of the
-// resolve pass are ratios of and what rasterize_backward's quotient rule differentiates.  ONE statement of the expressions for
-// every kernel that needs (u, v): the operations and their order are part of the contract (this file is compiled without
-// contraction), so the kernels agree to the bit.
-struct EdgeFunctions {
-    float fx, fy;                           // the pixel centre in normalised device coordinates
-    float p0x, p0y, p1x, p1y, p2x, p2y;     // v_k.xy - f v_k.w
-    float a0, a1;                           // u = a0 / s, v = a1 / s
-    float s;                                // a0 + a1 + a2, 1 where that sum is 0
-};
-
-__device__ __forceinline__ EdgeFunctions edge_functions(const float4 v0, const float4 v1, const float4 v2, int px, int py, int height, int width)
-{
-    EdgeFunctions e;
-    e.fx = (float(px) + 0.5f) / float(width) * 2.f - 1.f, e.fy = (float(py) + 0.5f) / float(height) * 2.f - 1.f;
-    e.p0x = v0.x - e.fx * v0.w, e.p0y = v0.y - e.fy * v0.w;
-    e.p1x = v1.x - e.fx * v1.w, e.p1y = v1.y - e.fy * v1.w;
-    e.p2x = v2.x - e.fx * v2.w, e.p2y = v2.y - e.fy * v2.w;
-    e.a0 = e.p1x * e.p2y - e.p1y * e.p2x, e.a1 = e.p2x * e.p0y - e.p2y * e.p0x;
-    const float a2 = e.p0x * e.p1y - e.p0y * e.p1x;
-    const float s = e.a0 + e.a1 + a2;
-    e.s = s == 0.f ? 1.f : s;
-    return e;
-}
-
-__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
-
-// d (u, v) / d clip-space (x, y, w) of the three vertices, times the gradient (gu, gv): the quotient rule of u = a0 / s, v = a1 / s
-// (oracle/raster_oracle.py::rasterize_backward), the clamps of the forward treated as inactive.  d[3 k ..] = (x, y, w) of vertex k.
-__device__ __forceinline__ void edge_functions_backward(const EdgeFunctions &e, float gu, float gv, float d[9])
-{
-    const float is = 1.f / e.s;
-    const float u = e.a0 * is, v = e.a1 * is;
-    const float dot = gu * u + gv * v;
-    const float da0 = (gu - dot) * is, da1 = (gv - dot) * is, da2 = -dot * is;
-    d[0] = da1 * -e.p2y + da2 * e.p1y, d[1] = da1 * e.p2x + da2 * -e.p1x;
-    d[3] = da0 * e.p2y + da2 * -e.p0y, d[4] = da0 * -e.p2x + da2 * e.p0x;
-    d[6] = da0 * -e.p1y + da1 * e.p0y, d[7] = da0 * e.p1x + da1 * -e.p0x;
-    d[2] = -e.fx * d[0] - e.fy * d[1];
-    d[5] = -e.fx * d[3] - e.fy * d[4];
-    d[8] = -e.fx * d[6] - e.fy * d[7];
-}
-
 // A wave holds 64 consecutive pixels of the flattened [view, row, column] image -- what the pair masks are indexed by, and the
 // order in which keys are read and `rast` is written as one stream.  (Four rows x 64 columns per workgroup, the upper neighbour
 // handed over in LDS, was tried: the strided streams alone cost 138 -> 172 us on 120 views x 512^2.)
@@ -451,87 +405,33 @@ __global__ __launch_bounds__(256) void rasterize_resolve_kernel(const float4 *po
     constexpr int K = kResolvePixels;
     const int64_t hw = int64_t(height) * width, total = batch * hw;
     const int lane = int(threadIdx.x) & 63;
-    // pixel k of this lane: chunk (first chunk of the wave + k), lane-th pixel -- every load of a wave is one contiguous 512 bytes
     const int64_t gid0 = (int64_t(blockIdx.x) * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6))) * (64 * K);
-    int64_t gid[K], b[K];
-    int px[K], py[K];
-    bool have[K];
-    // view / row / column without a per-lane 64-bit division: the view of the wave's first pixel on the scalar unit (a wave crosses
-    // at most one view boundary unless the image has fewer than 64 K pixels)
-    const int64_t b0 = hw >= 64 * K ? gid0 / hw : 0;
+    const WavePixels<K> p = wave_pixels<K>(gid0, lane, total, hw, width);
+    const WaveKeys<K> q = load_keys(keys, p, lane, height, width, pair_masks != nullptr);
+    // by-product for tsamd_antialias_prepare: does the pixel's triangle differ from its right / upper neighbour's?  What
+    // antialias_detect_kernel would otherwise find by reading the whole `rast` image back.
+    if (pair_masks) store_pair_masks(pair_masks, p, q, lane, height, width, [](unsigned long long key) { return uint32_t(key); });
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        gid[k] = gid0 + 64 * k + lane;
-        have[k] = gid[k] < total;
-        uint32_t pix;
-        if (hw >= 64 * K) {
-            const int64_t off = gid[k] - b0 * hw;
-            b[k] = off >= hw ? b0 + 1 : b0;
-            pix = uint32_t(off >= hw ? off - hw : off);
-        } else {
-            b[k] = gid[k] / hw;
-            pix = uint32_t(gid[k] - b[k] * hw);
-        }
-        py[k] = int(pix / uint32_t(width));   // (pix < 2^26: height, width <= 8192)
-        px[k] = int(pix - uint32_t(py[k]) * uint32_t(width));
-    }
-    // all global loads first, together: the kernel is bound by the latency of its key loads (a second round trip behind the first
-    // costs as much again)
-    unsigned long long key[K], key_up[K], key_right = 0ull;
-    bool want_up[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        want_up[k] = pair_masks && have[k] && py[k] + 1 < height;
-        key[k] = have[k] ? keys[gid[k]] : kNoFragment;
-        key_up[k] = want_up[k] ? keys[gid[k] + width] : 0ull;
-    }
-    // (the right neighbour of a chunk's last pixel is the next chunk's first: a lane of this wave, except behind the last chunk)
-    const bool want_right = pair_masks && have[K - 1] && px[K - 1] + 1 < width && lane == 63;
-    if (want_right) key_right = keys[gid[K - 1] + 1];
-    if (pair_masks) {
-        // by-product for tsamd_antialias_prepare: does the pixel's triangle differ from its right / upper neighbour's?  Two 64-bit
-        // words per 64 pixels, what antialias_detect_kernel would otherwise find by reading the whole `rast` image back.
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const uint32_t id = uint32_t(key[k]);
-            const uint32_t next = uint32_t(__shfl_down(int(id), 1));   // (every lane takes part: lane 62 reads lane 63)
-            uint32_t beyond = id;                                       // lane 63's right neighbour
-            if (k + 1 < K)
-                beyond = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(key[k + 1 < K ? k + 1 : k]))));
-            else if (want_right)
-                beyond = uint32_t(key_right);
-            const uint32_t right = lane == 63 ? beyond : next;
-            const uint32_t up = want_up[k] ? uint32_t(key_up[k]) : id;
-            const bool c0 = have[k] && px[k] + 1 < width && right != id;
-            const bool c1 = have[k] && py[k] + 1 < height && up != id;
-            const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1);
-            if (lane == 0 && have[k]) {
-                pair_masks[2 * (gid[k] >> 6)] = m0;
-                pair_masks[2 * (gid[k] >> 6) + 1] = m1;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (!have[k]) continue;
-        if (key[k] == kNoFragment) {
-            rast[gid[k]] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!p.have[k]) continue;
+        if (q.key[k] == kNoFragment) {
+            rast[p.gid[k]] = make_float4(0.f, 0.f, 0.f, 0.f);
             continue;
         }
-        const int64_t t = int64_t(key[k] & 0xFFFFFFFFull);
-        const float4 *pv = pos + b[k] * n_vertices;
+        const int64_t t = int64_t(q.key[k] & 0xFFFFFFFFull);
+        const float4 *pv = pos + p.b[k] * n_vertices;
         const float4 v0 = pv[tri[3 * t]], v1 = pv[tri[3 * t + 1]], v2 = pv[tri[3 * t + 2]];
-        const EdgeFunctions e = edge_functions(v0, v1, v2, px[k], py[k], height, width);
+        const EdgeFunctions e = edge_functions(v0, v1, v2, p.px[k], p.py[k], height, width);
         const float b0f = e.a0 / e.s, b1f = e.a1 / e.s, b2f = 1.f - b0f - b1f;
         const float z = b0f * v0.z + b1f * v1.z + b2f * v2.z;
         float w = b0f * v0.w + b1f * v1.w + b2f * v2.w;
         w = w == 0.f ? 1.f : w;
-        rast[gid[k]] = make_float4(clamp01(b0f), clamp01(b1f), fminf(fmaxf(z / w, -1.f), 1.f), float(t + 1));
+        rast[p.gid[k]] = make_float4(clamp01(b0f), clamp01(b1f), fminf(fmaxf(z / w, -1.f), 1.f), float(t + 1));
     }
 }
 
 // The alpha stage's resolve pass (tsamd_silhouette): per pixel the id the pass above would write (triangle + 1, 0 on background) as
-// an int32, its coverage as a float 0 / 1, and the coverage masks -- the layout, chunking and guards of the pair masks above, but
+// an int32, its coverage as a float 0 / 1, and the coverage masks -- the pair masks above with covered / background as the class, so
 // bit l says that exactly ONE pixel of the pair is background.  Nothing is read but the keys: no vertex, no barycentric, no z/w.
 __global__ __launch_bounds__(256) void silhouette_cover_kernel(int64_t batch, int height, int width, const unsigned long long *keys, int32_t *ids,
                                                                unsigned long long *cover_masks, float *alpha)
@@ -540,91 +440,16 @@ __global__ __launch_bounds__(256) void silhouette_cover_kernel(int64_t batch, in
     const int64_t hw = int64_t(height) * width, total = batch * hw;
     const int lane = int(threadIdx.x) & 63;
     const int64_t gid0 = (int64_t(blockIdx.x) * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6))) * (64 * K);
-    int64_t gid[K];
-    int px[K], py[K];
-    bool have[K];
-    const int64_t b0 = hw >= 64 * K ? gid0 / hw : 0;   // (as in the resolve pass: the view of the wave's first pixel on the scalar unit)
+    const WavePixels<K> p = wave_pixels<K>(gid0, lane, total, hw, width);
+    const WaveKeys<K> q = load_keys(keys, p, lane, height, width, true);
+    store_pair_masks(cover_masks, p, q, lane, height, width, [](unsigned long long key) { return uint32_t(key != kNoFragment); });
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        gid[k] = gid0 + 64 * k + lane;
-        have[k] = gid[k] < total;
-        uint32_t pix;
-        if (hw >= 64 * K) {
-            const int64_t off = gid[k] - b0 * hw;
-            pix = uint32_t(off >= hw ? off - hw : off);
-        } else {
-            pix = uint32_t(gid[k] % hw);
-        }
-        py[k] = int(pix / uint32_t(width));
-        px[k] = int(pix - uint32_t(py[k]) * uint32_t(width));
+        if (!p.have[k]) continue;
+        const bool cov = q.key[k] != kNoFragment;
+        ids[p.gid[k]] = cov ? int32_t(uint32_t(q.key[k])) + 1 : 0;
+        alpha[p.gid[k]] = cov ? 1.f : 0.f;
     }
-    unsigned long long key[K], key_up[K], key_right = kNoFragment;
-    bool want_up[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        want_up[k] = have[k] && py[k] + 1 < height;
-        key[k] = have[k] ? keys[gid[k]] : kNoFragment;
-        key_up[k] = want_up[k] ? keys[gid[k] + width] : kNoFragment;
-    }
-    const bool want_right = have[K - 1] && px[K - 1] + 1 < width && lane == 63 && gid[K - 1] + 1 < total;
-    if (want_right) key_right = keys[gid[K - 1] + 1];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const bool cov = key[k] != kNoFragment;
-        const unsigned long long covered = __ballot(cov);
-        // lane 63's right neighbour: the next chunk's first pixel (lane 0 of this wave), behind the last chunk the extra load
-        bool beyond = key_right != kNoFragment;
-        if (k + 1 < K) beyond = __builtin_amdgcn_readfirstlane(int(key[k + 1 < K ? k + 1 : k] != kNoFragment)) != 0;
-        const bool right = lane == 63 ? beyond : ((covered >> ((lane + 1) & 63)) & 1ull) != 0ull;
-        const bool up = want_up[k] ? key_up[k] != kNoFragment : cov;
-        const bool c0 = have[k] && px[k] + 1 < width && right != cov;
-        const bool c1 = have[k] && py[k] + 1 < height && up != cov;
-        const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1);
-        if (lane == 0 && have[k]) {
-            cover_masks[2 * (gid[k] >> 6)] = m0;
-            cover_masks[2 * (gid[k] >> 6) + 1] = m1;
-        }
-        if (have[k]) {
-            ids[gid[k]] = cov ? int32_t(uint32_t(key[k])) + 1 : 0;
-            alpha[gid[k]] = cov ? 1.f : 0.f;
-        }
-    }
-}
-
-// ---- scatter with runs ----
-// The backward scatters add one value per pixel to the three vertices of the pixel's triangle.  Consecutive pixels of a row
-// mostly belong to the same triangle (a 41 k-tet object at 512^2: runs of ~5), so the lanes of a run are summed inside the wave
-// first -- a segmented scan over equal keys -- and only the last lane of every run issues the atomics.  A wave without any run
-// (a dense scene of sub-pixel triangles) skips the scan.  EVERY lane of the wave must call these (no early return before).
-struct Runs {
-    int start;      // lane index of the first lane of this lane's run
-    bool last;      // this lane ends its run: it holds the run's sums after run_sum()
-    bool any;       // wave-uniform: some run is longer than one lane
-};
-
-__device__ __forceinline__ Runs find_runs(long long key)
-{
-    const int lane = int(threadIdx.x) & 63;
-    const long long prev = __shfl_up(key, 1);
-    const bool head = lane == 0 || key != prev;
-    const unsigned long long heads = __ballot(head);
-    Runs r;
-    r.start = 63 - __clzll(heads & (~0ull >> (63 - lane)));
-    r.last = lane == 63 || ((heads >> (lane + 1)) & 1ull) != 0ull;
-    r.any = heads != ~0ull;
-    return r;
-}
-
-__device__ __forceinline__ float run_sum(const Runs &r, float v)
-{
-    if (!r.any) return v;
-    const int lane = int(threadIdx.x) & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float up = __shfl_up(v, d);
-        if (lane - d >= r.start) v += up;
-    }
-    return v;
 }
 
 // d (u, v) / d clip-space positions of the winning triangle (oracle/raster_oracle.py::rasterize_backward): the barycentrics
@@ -639,6 +464,7 @@ __global__ __launch_bounds__(256) void rasterize_backward_kernel(const float4 *p
     int64_t t = -1;
     float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
     if (valid) {
+        // (not triangle_of: it refuses w > 2^24, which this decode accepts when n_tri > 2^24 -- tsamd_rasterize_backward does not bound n_tri)
         t = int64_t(rast[gid].w) - 1;
         valid = t >= 0 && t < n_tri;
     }
@@ -646,18 +472,15 @@ __global__ __launch_bounds__(256) void rasterize_backward_kernel(const float4 *p
         g = grad_rast[gid];
         valid = !(g.x == 0.f && g.y == 0.f);
     }
-    const int64_t b = valid ? gid / hw : 0, pix = valid ? gid - b * hw : 0;
     int32_t i0 = 0, i1 = 0, i2 = 0;
-    if (valid) {
-        i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-        valid = !(i0 < 0 || i1 < 0 || i2 < 0 || i0 >= n_vertices || i1 >= n_vertices || i2 >= n_vertices);
-    }
+    valid = valid && triangle_indices(tri, t, n_vertices, i0, i1, i2);
+    int64_t b = 0;
     float d[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, w) of the three vertices
     if (valid) {
-        const int py = int(pix / width), px = int(pix - int64_t(py) * width);
+        int px, py;
+        locate_pixel(gid, hw, width, false, 0, b, px, py);
         const float4 *pv = pos + b * n_vertices;
-        const float4 v0 = pv[i0], v1 = pv[i1], v2 = pv[i2];
-        edge_functions_backward(edge_functions(v0, v1, v2, px, py, height, width), g.x, g.y, d);
+        edge_functions_backward(edge_functions(pv[i0], pv[i1], pv[i2], px, py, height, width), g.x, g.y, d);
     }
     // lanes of one triangle (and view) in a row: one set of atomics per run
     const Runs runs = find_runs(valid ? b * (int64_t(1) << 32) + t : -1 - int64_t(threadIdx.x));
@@ -671,295 +494,6 @@ __global__ __launch_bounds__(256) void rasterize_backward_kernel(const float4 *p
             atomicAdd(gp + at[k] + 0, d[3 * k]);
             atomicAdd(gp + at[k] + 1, d[3 * k + 1]);
             atomicAdd(gp + at[k] + 3, d[3 * k + 2]);
-        }
-    }
-}
-
-// Triangle named by a rast pixel's fourth channel (id + 1 as a float, exact up to 2^24 - 1 triangles: tsamd_rasterize
-// refuses longer lists), or -1 for background / an id outside [0, n_tri) / a non-finite value.
-__device__ __forceinline__ int64_t triangle_of(float w, int64_t n_tri)
-{
-    if (!(w >= 1.f) || !(w <= 16777216.f)) return -1;
-    const int64_t t = int64_t(w) - 1;
-    return t < n_tri ? t : -1;
-}
-// The three vertex indices of triangle t; false when one of them lies outside [0, n_vertices).
-__device__ __forceinline__ bool triangle_indices(const int32_t *tri, int64_t t, int64_t n_vertices, int32_t &i0, int32_t &i1, int32_t &i2)
-{
-    i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-    return uint64_t(i0) < uint64_t(n_vertices) && uint64_t(i1) < uint64_t(n_vertices) && uint64_t(i2) < uint64_t(n_vertices)
-           && i0 >= 0 && i1 >= 0 && i2 >= 0;
-}
-
-__global__ __launch_bounds__(256) void interpolate_kernel(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels,
-                                                          const float4 *rast, const int32_t *tri, int64_t n_tri, int64_t batch, int64_t hw, float *out)
-{
-    const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (gid >= batch * hw) return;
-    const float4 r = rast[gid];
-    float *o = out + gid * channels;
-    const int64_t t = triangle_of(r.w, n_tri);
-    int32_t i0 = 0, i1 = 0, i2 = 0;
-    // a pixel whose id names no triangle of THIS list, or a triangle with a vertex index outside the attribute array, is
-    // background (what nvdiffrast does with them): the rast image may come from another triangle list, or from the caller
-    if (t < 0 || !triangle_indices(tri, t, n_vertices, i0, i1, i2)) {
-        for (int c = 0; c < channels; ++c) o[c] = 0.f;
-        return;
-    }
-    const int64_t b = gid / hw;
-    const float *a = attr + (attr_batch > 1 ? b : 0) * n_vertices * channels;
-    const float *a0 = a + int64_t(i0) * channels, *a1 = a + int64_t(i1) * channels, *a2 = a + int64_t(i2) * channels;
-    const float u = r.x, v = r.y, w = 1.f - r.x - r.y;
-    for (int c = 0; c < channels; ++c) o[c] = u * a0[c] + v * a1[c] + w * a2[c];
-}
-
-// d out / d attr: scatter of the three barycentric weights, summed over runs of equal triangles inside the wave first (fp32
-// global atomics: the order of the additions, and so the last bits of the result, vary from run to run -- like nvdiffrast's
-// own backward); d out / d (u, v) per pixel.
-__global__ __launch_bounds__(256) void interpolate_backward_kernel(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels,
-                                                                   const float4 *rast, const int32_t *tri, int64_t n_tri, int64_t batch, int64_t hw,
-                                                                   const float *grad_out, float *grad_attr, float4 *grad_rast)
-{
-    const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    const bool inside = gid < batch * hw;
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (inside) r = rast[gid];
-    const int64_t t = triangle_of(r.w, n_tri);
-    int32_t i0 = 0, i1 = 0, i2 = 0;
-    const bool valid = inside && t >= 0 && triangle_indices(tri, t, n_vertices, i0, i1, i2);   // (else background: no reads, no atomics)
-    if (inside && !valid && grad_rast) grad_rast[gid] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int64_t b = valid ? gid / hw : 0;
-    const int64_t base = (attr_batch > 1 ? b : 0) * n_vertices * channels;
-    int64_t o0 = 0, o1 = 0, o2 = 0;
-    if (valid) o0 = base + int64_t(i0) * channels, o1 = base + int64_t(i1) * channels, o2 = base + int64_t(i2) * channels;
-    const float u = r.x, v = r.y, w = 1.f - r.x - r.y;
-    // lanes of one triangle (and attribute batch) in a row: one set of atomics per run
-    const Runs runs = find_runs(valid ? (attr_batch > 1 ? b : 0) * (int64_t(1) << 32) + t : -1 - int64_t(threadIdx.x));
-    float du = 0.f, dv = 0.f;
-    for (int c = 0; c < channels; ++c) {
-        const float gc = valid ? grad_out[gid * channels + c] : 0.f;
-        const float s0 = run_sum(runs, u * gc), s1 = run_sum(runs, v * gc), s2 = run_sum(runs, w * gc);
-        if (valid) {
-            if (runs.last) {
-                atomicAdd(grad_attr + o0 + c, s0);
-                atomicAdd(grad_attr + o1 + c, s1);
-                atomicAdd(grad_attr + o2 + c, s2);
-            }
-            const float a2 = attr[o2 + c];
-            du += gc * (attr[o0 + c] - a2);
-            dv += gc * (attr[o1 + c] - a2);
-        }
-    }
-    if (valid && grad_rast) grad_rast[gid] = make_float4(du, dv, 0.f, 0.f);
-}
-
-// ---- the id-driven image terms: masked MSE of a value of the interpolated vertex attribute, without an image chain ----
-// A term takes a value x[kChannels] of the point y = interpolate(attr, rast) of a [V, 3] vertex attribute; its loss is the mean over
-// pixels and channels of (x_c m - t_c m)^2, the mask broadcast over the channels.  The depth term is what the reference's
-// trainer.py:104-115 builds from out["d"] = ||interpolate(v_pos, rast) - campos|| (mesh_rasterizer.py:151-161); the normal term what
-// MeshRasterizer.forward(fit_normal=True) and a masked MSELoss build from out["n"] = interpolate(attr, rast) (mesh_rasterizer.py:137-149;
-// `attr` is any [V, 3] attribute: the normal is the use).  Per pixel those chains move a 16-byte rast pixel, a 12-byte interpolated
-// pixel, the masked products and their gradients; here a pixel is its triangle id (the alpha stage's by-product), kChannels target floats
-// and a mask -- 12 or 20 bytes -- plus cached vertex gathers.  (u, v) are the clamped barycentrics of the resolve pass (edge_functions,
-// the same operations), w = 1 - u - v and the interpolation are interpolate_kernel's; a background pixel has y = 0, so d = ||campos||
-// and n = 0, as in the chains.
-
-// What every id-driven term starts from at a covered pixel (px, py) of a view with clip-space vertices pv: the clamped barycentrics
-// of the resolve pass, w = (1 - u) - v as interpolate_kernel forms it, and the three rows of a 3-channel vertex attribute,
-// a[3 k + c] = channel c of vertex i_k.  (ONE statement of these operations for every term and both directions.)
-__device__ __forceinline__ EdgeFunctions weights_and_gather(const float4 *pv, const float *attr, int32_t i0, int32_t i1, int32_t i2, int px, int py, int height,
-                                                            int width, float &u, float &v, float &w, float a[9])
-{
-    const EdgeFunctions e = edge_functions(pv[i0], pv[i1], pv[i2], px, py, height, width);
-    u = clamp01(e.a0 / e.s), v = clamp01(e.a1 / e.s);
-    w = 1.f - u - v;
-    const float *a0 = attr + 3 * int64_t(i0), *a1 = attr + 3 * int64_t(i1), *a2 = attr + 3 * int64_t(i2);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] = a0[k], a[3 + k] = a1[k], a[6 + k] = a2[k];
-    return e;
-}
-
-// Triangle named by an id of the alpha stage (triangle + 1, 0 = background) and its vertex indices; false for background, an id
-// outside [1, n_tri] and a vertex index outside [0, n_vertices): nothing is read through those (as triangle_of / triangle_indices)
-__device__ __forceinline__ bool triangle_of_id(int32_t id, const int32_t *tri, int64_t n_tri, int64_t n_vertices, int32_t &i0, int32_t &i1, int32_t &i2)
-{
-    if (id < 1 || int64_t(id) > n_tri) return false;
-    return triangle_indices(tri, int64_t(id) - 1, n_vertices, i0, i1, i2);
-}
-
-// view, row and column of pixel gid; b0 = the view of the wave's first pixel (a wave of `span` pixels crosses at most one view
-// boundary when hw >= span), as in the resolve pass
-__device__ __forceinline__ void locate_pixel(int64_t gid, int64_t hw, int width, bool one_boundary, int64_t b0, int64_t &b, int &px, int &py)
-{
-    uint32_t pix;
-    if (one_boundary) {
-        const int64_t off = gid - b0 * hw;
-        b = off >= hw ? b0 + 1 : b0;
-        pix = uint32_t(off >= hw ? off - hw : off);
-    } else {
-        b = gid / hw;
-        pix = uint32_t(gid - b * hw);
-    }
-    py = int(pix / uint32_t(width));
-    px = int(pix - uint32_t(py) * uint32_t(width));
-}
-
-// A term is the only place that knows "distance to a camera" from "the attribute itself": its channel count, its per-view constants,
-// its value x at the interpolated point y of a view, and the pull-back of dL/dx to g = dL/dy.  The operations and their order are the
-// result's bits (this file is compiled without contraction).
-struct DepthTerm {
-    static constexpr int kChannels = 1;
-    const float *campos;   // [batch, 3]
-
-    __device__ __forceinline__ void value(int64_t view, const float y[3], float x[1]) const
-    {
-        const float *c = campos + 3 * view;
-        const float dx = y[0] - c[0], dy = y[1] - c[1], dz = y[2] - c[2];
-        x[0] = sqrtf(dx * dx + dy * dy + dz * dz);
-    }
-    // d = ||y - c||: g = g_d (y - c) / d, 0 where d = 0
-    __device__ __forceinline__ void pull(int64_t view, const float y[3], const float x[1], const float gx[1], float g[3]) const
-    {
-        const float *c = campos + 3 * view;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) g[k] = x[0] == 0.f ? 0.f : gx[0] * ((y[k] - c[k]) / x[0]);
-    }
-};
-
-struct NormalTerm {
-    static constexpr int kChannels = 3;
-
-    __device__ __forceinline__ void value(int64_t, const float y[3], float x[3]) const { x[0] = y[0], x[1] = y[1], x[2] = y[2]; }
-    __device__ __forceinline__ void pull(int64_t, const float *, const float *, const float gx[3], float g[3]) const { g[0] = gx[0], g[1] = gx[1], g[2] = gx[2]; }
-};
-
-constexpr int kTermPixels = 4;                                  // 64-pixel chunks per wave and round, all their loads in flight together
-constexpr int kTermPerBlock = kMeanBlock * kTermPixels;         // pixels per workgroup and round
-constexpr int kTermMaxBlocks = 8192;                            // (the loss's bits depend on these two: det_mean.h)
-
-// One lane per pixel; a workgroup strides over rounds of kTermPerBlock pixels and stores one double: the sum over its pixels and the
-// term's channels of (x_c m - t_c m)^2, each product rounded on its own, squared and added in float64 (channel 0, 1, .. in turn).
-// x_out (optional): the term's image [B, H, W, kChannels], every pixel of it.
-template <class Term>
-__global__ __launch_bounds__(kMeanBlock) void term_mse_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
-                                                              int width, const int32_t *ids, const float *attr, Term term, const float *target, const float *mask,
-                                                              double *partials, float *x_out)
-{
-    constexpr int K = kTermPixels, C = Term::kChannels;
-    __shared__ double lds[kMeanBlock / 64];
-    const int64_t hw = int64_t(height) * width, total = batch * hw;
-    const int lane = int(threadIdx.x) & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
-    const bool one_boundary = hw >= 64 * K;
-    double acc = 0.0;
-    for (int64_t first = int64_t(blockIdx.x) * kTermPerBlock; first < total; first += int64_t(gridDim.x) * kTermPerBlock) {
-        const int64_t gid0 = first + int64_t(wave) * (64 * K);
-        int32_t id[K];
-        float tg[K][C], m[K];
-        bool want[K];
-        // all global loads first, together (the latency of one round trip, not of three)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int64_t gid = gid0 + 64 * k + lane;
-            const bool have = gid < total;
-            id[k] = have ? ids[gid] : 0;
-            m[k] = have ? mask[gid] : 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) tg[k][c] = have ? target[C * gid + c] : 0.f;
-            want[k] = have && (m[k] != 0.f || x_out != nullptr);     // a masked-out pixel adds 0: no vertex work unless its x is asked for
-        }
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < K; ++k) any = any || want[k];
-        if (__ballot(any) == 0ull) continue;                          // wave-uniform: nothing in these chunks enters the loss
-        const int64_t b0 = one_boundary ? gid0 / hw : 0;              // (on the scalar unit)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            if (!want[k]) continue;
-            const int64_t gid = gid0 + 64 * k + lane;
-            int64_t b;
-            int px, py;
-            locate_pixel(gid, hw, width, one_boundary, b0, b, px, py);
-            float y[3] = {0.f, 0.f, 0.f}, x[C];
-            int32_t i0, i1, i2;
-            if (triangle_of_id(id[k], tri, n_tri, n_vertices, i0, i1, i2)) {
-                float u, v, w, a[9];
-                weights_and_gather(pos + b * n_vertices, attr, i0, i1, i2, px, py, height, width, u, v, w, a);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) y[c] = u * a[c] + v * a[3 + c] + w * a[6 + c];
-            }
-            term.value(b, y, x);
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if (x_out) x_out[C * gid + c] = x[c];
-                const float r = x[c] * m[k] - tg[k][c] * m[k];
-                acc += double(r) * double(r);
-            }
-        }
-    }
-    const double sum = block_sum(acc, lds);
-    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
-}
-
-// One lane per pixel, one pass: (u, v, y, x) recomputed, g_c = grad_loss 2 (x_c m - t_c m) m / (kChannels pixels) pulled back to g = dL/dy,
-// then BOTH scatters behind one run detection -- interpolate_backward's (u, v, w) g into grad_attr[V, 3] and, through
-// (du, dv) = (g . (a0 - a2), g . (a1 - a2)) and the quotient rule of rasterize_backward, (x, y, w) into grad_pos[B, V, 4].
-// The run key holds the view: grad_pos is per view, and a wave of a small image spans several views that show the same triangle.
-// No gradient image and no grad_rast exist; background and masked-out pixels add nothing.  EVERY lane reaches find_runs.
-template <class Term>
-__global__ __launch_bounds__(256) void term_mse_backward_kernel(const float4 *pos, const int32_t *tri, int64_t n_vertices, int64_t n_tri, int64_t batch, int height,
-                                                                int width, const int32_t *ids, const float *attr, Term term, const float *target,
-                                                                const float *mask, const float *grad_loss, float *grad_attr, float4 *grad_pos)
-{
-    constexpr int C = Term::kChannels;
-    const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int64_t hw = int64_t(height) * width, total = batch * hw;
-    bool valid = gid < total;
-    int32_t id = 0, i0 = 0, i1 = 0, i2 = 0;
-    float tg[C] = {}, m = 0.f;
-    if (valid) {
-        id = ids[gid], m = mask[gid];
-#pragma unroll
-        for (int c = 0; c < C; ++c) tg[c] = target[C * gid + c];
-    }
-    valid = valid && m != 0.f && triangle_of_id(id, tri, n_tri, n_vertices, i0, i1, i2);   // (background: y = 0 is a constant)
-    int64_t b = 0;
-    float da[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // the three channels of the three attribute rows
-    float dc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // (x, y, w) of the three clip-space positions
-    if (valid) {
-        int px, py;
-        locate_pixel(gid, hw, width, false, 0, b, px, py);
-        float u, v, w, a[9], y[3], x[C], gx[C], g[3];
-        const EdgeFunctions e = weights_and_gather(pos + b * n_vertices, attr, i0, i1, i2, px, py, height, width, u, v, w, a);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) y[c] = u * a[c] + v * a[3 + c] + w * a[6 + c];
-        term.value(b, y, x);
-        const float scale = grad_loss[0] / float(C * total);
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float r = x[c] * m - tg[c] * m;
-            gx[c] = (2.f * r * m) * scale;
-        }
-        term.pull(b, y, x, gx, g);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) da[c] = u * g[c], da[3 + c] = v * g[c], da[6 + c] = w * g[c];
-        const float du = g[0] * (a[0] - a[6]) + g[1] * (a[1] - a[7]) + g[2] * (a[2] - a[8]);
-        const float dv = g[0] * (a[3] - a[6]) + g[1] * (a[4] - a[7]) + g[2] * (a[5] - a[8]);
-        edge_functions_backward(e, du, dv, dc);
-    }
-    const Runs runs = find_runs(valid ? b * (int64_t(1) << 32) + int64_t(id) : -1 - int64_t(threadIdx.x));
-#pragma unroll
-    for (int k = 0; k < 9; ++k) da[k] = run_sum(runs, da[k]), dc[k] = run_sum(runs, dc[k]);
-    if (valid && runs.last) {
-        float *gp = reinterpret_cast<float *>(grad_pos + b * n_vertices);
-        const int64_t at[3] = {int64_t(i0), int64_t(i1), int64_t(i2)};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            atomicAdd(grad_attr + 3 * at[k] + 0, da[3 * k]);
-            atomicAdd(grad_attr + 3 * at[k] + 1, da[3 * k + 1]);
-            atomicAdd(grad_attr + 3 * at[k] + 2, da[3 * k + 2]);
-            atomicAdd(gp + 4 * at[k] + 0, dc[3 * k]);
-            atomicAdd(gp + 4 * at[k] + 1, dc[3 * k + 1]);
-            atomicAdd(gp + 4 * at[k] + 3, dc[3 * k + 2]);
         }
     }
 }
@@ -1038,95 +572,6 @@ hipError_t launch_rasterize_backward(const float *pos_clip, int64_t batch, int64
                        n_tri, batch, height, width, reinterpret_cast<const float4 *>(rast), reinterpret_cast<const float4 *>(grad_rast),
                        reinterpret_cast<float4 *>(grad_pos));
     return hipGetLastError();
-}
-
-hipError_t launch_interpolate(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels, const float *rast, const int32_t *tri,
-                              int64_t n_tri, int64_t batch, int height, int width, float *out, hipStream_t stream)
-{
-    const int64_t hw = int64_t(height) * width;
-    if (batch * hw <= 0) return hipSuccess;
-    hipLaunchKernelGGL(interpolate_kernel, dim3(blocks_for(batch * hw)), dim3(256), 0, stream, attr, attr_batch, n_vertices, channels,
-                       reinterpret_cast<const float4 *>(rast), tri, n_tri, batch, hw, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_interpolate_backward(const float *attr, int64_t attr_batch, int64_t n_vertices, int channels, const float *rast, const int32_t *tri,
-                                       int64_t n_tri, int64_t batch, int height, int width, const float *grad_out, float *grad_attr, float *grad_rast,
-                                       hipStream_t stream)
-{
-    const int64_t hw = int64_t(height) * width;
-    hipError_t e = hipMemsetAsync(grad_attr, 0, size_t(attr_batch) * size_t(n_vertices) * size_t(channels) * sizeof(float), stream);
-    if (e != hipSuccess) return e;
-    if (batch * hw <= 0) return hipSuccess;
-    hipLaunchKernelGGL(interpolate_backward_kernel, dim3(blocks_for(batch * hw)), dim3(256), 0, stream, attr, attr_batch, n_vertices, channels,
-                       reinterpret_cast<const float4 *>(rast), tri, n_tri, batch, hw, grad_out, grad_attr, reinterpret_cast<float4 *>(grad_rast));
-    return hipGetLastError();
-}
-
-namespace {
-
-template <class Term>
-hipError_t launch_term_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
-                           const float *attr, Term term, const float *target, const float *mask, void *workspace, float *loss, float *x_out, hipStream_t stream)
-{
-    const int64_t pixels = pixel_count(batch, height, width);
-    if (pixels <= 0 || n_tri <= 0) return hipMemsetAsync(loss, 0, sizeof(float), stream);
-    const int blocks = mean_blocks(pixels, kTermPerBlock, kTermMaxBlocks);
-    hipLaunchKernelGGL(term_mse_kernel<Term>, dim3(blocks), dim3(kMeanBlock), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices, n_tri, batch,
-                       height, width, ids, attr, term, target, mask, static_cast<double *>(workspace), x_out);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_mean_final(workspace, blocks, Term::kChannels * pixels, loss, stream);
-}
-
-template <class Term>
-hipError_t launch_term_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
-                                    const int32_t *ids, const float *attr, Term term, const float *target, const float *mask, const float *grad_loss,
-                                    int accumulate_pos, float *grad_attr, float *grad_pos, hipStream_t stream)
-{
-    hipError_t e;
-    if (n_vertices > 0 && (e = hipMemsetAsync(grad_attr, 0, size_t(n_vertices) * 3 * sizeof(float), stream)) != hipSuccess) return e;
-    if (!accumulate_pos && batch * n_vertices > 0 &&
-        (e = hipMemsetAsync(grad_pos, 0, size_t(batch) * size_t(n_vertices) * 4 * sizeof(float), stream)) != hipSuccess)
-        return e;
-    const int64_t pixels = pixel_count(batch, height, width);
-    if (pixels <= 0 || n_tri <= 0 || n_vertices <= 0) return hipSuccess;
-    hipLaunchKernelGGL(term_mse_backward_kernel<Term>, dim3(blocks_for(pixels)), dim3(256), 0, stream, reinterpret_cast<const float4 *>(pos_clip), tri, n_vertices,
-                       n_tri, batch, height, width, ids, attr, term, target, mask, grad_loss, grad_attr, reinterpret_cast<float4 *>(grad_pos));
-    return hipGetLastError();
-}
-
-}  // namespace
-
-int64_t depth_mse_workspace_bytes(int64_t n) { return mean_workspace_bytes(mean_blocks(n, kTermPerBlock, kTermMaxBlocks)); }
-int64_t normal_mse_workspace_bytes(int64_t n) { return depth_mse_workspace_bytes(n); }
-
-hipError_t launch_depth_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
-                            const float *world_pos, const float *campos, const float *target, const float *mask, void *workspace, float *loss, float *depth_out,
-                            hipStream_t stream)
-{
-    return launch_term_mse(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, world_pos, DepthTerm{campos}, target, mask, workspace, loss, depth_out, stream);
-}
-
-hipError_t launch_depth_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
-                                     const int32_t *ids, const float *world_pos, const float *campos, const float *target, const float *mask, const float *grad_loss,
-                                     int accumulate_pos, float *grad_world, float *grad_pos, hipStream_t stream)
-{
-    return launch_term_mse_backward(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, world_pos, DepthTerm{campos}, target, mask, grad_loss, accumulate_pos,
-                                    grad_world, grad_pos, stream);
-}
-
-hipError_t launch_normal_mse(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width, const int32_t *ids,
-                             const float *attr, const float *target, const float *mask, void *workspace, float *loss, float *normal_out, hipStream_t stream)
-{
-    return launch_term_mse(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, attr, NormalTerm{}, target, mask, workspace, loss, normal_out, stream);
-}
-
-hipError_t launch_normal_mse_backward(const float *pos_clip, int64_t batch, int64_t n_vertices, const int32_t *tri, int64_t n_tri, int height, int width,
-                                      const int32_t *ids, const float *attr, const float *target, const float *mask, const float *grad_loss, int accumulate_pos,
-                                      float *grad_attr, float *grad_pos, hipStream_t stream)
-{
-    return launch_term_mse_backward(pos_clip, batch, n_vertices, tri, n_tri, height, width, ids, attr, NormalTerm{}, target, mask, grad_loss, accumulate_pos, grad_attr,
-                                    grad_pos, stream);
 }
 
 }  // namespace tsamd
