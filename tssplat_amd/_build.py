@@ -26,7 +26,8 @@ SOURCES = ["plan.cpp", "plan_mesh.cpp", "plan_tiling.cpp", "plan_layout.cpp", "p
            "init_capi.cpp", "init_kernels.hip", "merge_capi.cpp", "merge_kernels.hip", "fill_kernels.hip",
            "metrics_capi.cpp", "metrics_kernels.hip", "pointmesh_capi.cpp", "pointmesh_kernels.hip", "simplify_capi.cpp", "simplify_kernels.hip", "voxel_capi.cpp", "voxel_kernels.hip",
            "quality_capi.cpp", "quality_kernels.hip", "smooth_capi.cpp", "smooth_kernels.hip"]
-HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "launch_args.h", "regular_batch.h", "surface.h", "raster.h", "raster_device.h", "grid.h", "mlp.h", "texture.h", "shade.h", "init.h", "merge.h", "metrics.h", "mesh_triangle.h", "pointmesh.h", "simplify.h", "voxel.h", "quality.h", "smooth.h", "det_mean.h", "capi_common.h", os.path.join("..", "..", "include", "tssplat_amd.h")]
+HEADERS = ["plan.h", "planner.h", "conflict_opt.h", "kernels.h", "launch_args.h", "regular_batch.h", "surface.h", "raster.h", "raster_device.h", "grid.h", "mlp.h", "texture.h", "shade.h", "init.h", "merge.h", "metrics.h", "mesh_triangle.h", "pointmesh.h", "simplify.h", "voxel.h", "quality.h", "smooth.h", "det_mean.h", "capi_common.h"]
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "tssplat_amd.h")      # the public header: the contract, and what _capi.py reads
 
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-pthread"]
 # -fno-slp-vectorize: SLP packs the 3x3 algebra into v_pk_*_f32, which runs at the scalar-fp32 rate on
@@ -69,6 +70,8 @@ def _digest() -> str:
     for name in SOURCES + HEADERS:
         with open(os.path.join(CSRC, name), "rb") as fh:
             h.update(fh.read())
+    with open(HEADER, "rb") as fh:
+        h.update(fh.read())
     h.update(" ".join(HOST_FLAGS + DEVICE_FLAGS + [f"{k}:{' '.join(v)}" for k, v in sorted(SOURCE_FLAGS.items())]).encode())
     return h.hexdigest()
 
@@ -183,7 +186,7 @@ def build_torch_ext(force: bool = False, verbose: bool = False) -> str:
     from torch.utils import cpp_extension as ce
     h = hashlib.sha256(open(src, "rb").read())
     h.update(open(os.path.join(CSRC, "torch_exchange.cpp"), "rb").read())
-    h.update(open(os.path.join(CSRC, "..", "..", "include", "tssplat_amd.h"), "rb").read())   # the entry-point types it hard-codes
+    h.update(open(HEADER, "rb").read())   # the entry-point types it takes from there
     h.update(torch.__version__.encode())
     digest = h.hexdigest()
     if not force and os.path.exists(TORCH_EXT) and os.path.exists(stamp) and open(stamp).read() == digest:

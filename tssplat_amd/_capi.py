@@ -1,13 +1,20 @@
-"""ctypes binding of include/tssplat_amd.h (libtssplat_amd.so).
+"""ctypes binding of include/tssplat_amd.h (libtssplat_amd.so), read from the header itself.
 
 The library is the product; this file is plumbing.  There is deliberately no
 Python/CPU fallback: if the shared library cannot be loaded, importing the
 operator surface raises.
+
+Nothing of the header is restated here.  :func:`read_header` reads the structs, the constants and the declarations of
+include/tssplat_amd.h at import -- the header as it is written and no more general C; what it does not understand is an
+``ImportError``, never a guess -- and the Structure classes, ``SIGNATURES`` and the ``TSAMD_*`` names below come from that reading.
+A new entry point is declared in the header and defined in csrc/; there is no Python table to extend.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
+import re
 
 from . import _build
 
@@ -23,271 +30,165 @@ class TsamdError(RuntimeError):
         self.code = code
 
 
+# ---- the reader ----
+Header = collections.namedtuple("Header", "structs opaque constants functions")
+Header.__doc__ = """What include/tssplat_amd.h declares: ``structs`` name -> Structure class, ``opaque`` the names of the handle types,
+``constants`` name -> int (enum members and integer #defines), ``functions`` name -> (restype, [(parameter, ctype), ...])."""
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "uint16_t": C.c_uint16,
+            "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_CPLUSPLUS = re.compile(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b", re.S | re.M)     # extern "C" { and its }
+_DIRECTIVE = re.compile(r"^[ \t]*#[ \t]*(\w+)[ \t]*(.*?)[ \t]*$", re.M)
+_DEFINE = re.compile(r"(TSAMD_\w+)\s+(-?(?:0[xX][0-9a-fA-F]+|[1-9][0-9]*|0))")
+_MEMBER = re.compile(r"\s*(TSAMD_\w+)\s*=\s*(-?[0-9]+)\s*")
+_ITEM = re.compile(r"\s*(?:typedef\s+struct\s+(\w+)\s+(\w+)"                           # 1, 2: an opaque type
+                   r"|typedef\s+(struct|enum)\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)"       # 3-6: a struct or the enum
+                   r"|([^;(){}]+)\(([^;(){}]*)\))\s*;")                               # 7, 8: a function
+_TYPE = re.compile(r"(const\s+)?(\w+)\b\s*(.+)", re.S)
+_NAME = re.compile(r"((?:\s*\*)*)\s*(\w+)\s*")
+_END = re.compile(r"\s*\Z")
+
+
+def _flat(text: str) -> str:
+    return " ".join(text.split())[:200]
+
+
+def _declare(text: str, where: str) -> list:
+    """``const int32_t *a, *b`` -> [(True, "int32_t", 1, "a"), (True, "int32_t", 1, "b")]: const, base type, pointer depth, name."""
+    m = _TYPE.fullmatch(text.strip())
+    names = [_NAME.fullmatch(part) for part in m[3].split(",")] if m else [None]
+    if not all(names):
+        raise ImportError(f"{where}: cannot read '{_flat(text)}'")
+    return [(bool(m[1]), m[2], n[1].count("*"), n[2]) for n in names]
+
+
+def _ctype(decl: tuple, where: str, header: Header, parameter: bool):
+    """The ctypes type of one declarator.  A pointer to a parsed struct is POINTER(its class); ``const char *`` is c_char_p; a
+    pointer is c_void_p when it is ``void *``, points to an opaque struct, is named ``*_dev`` or -- for a parameter -- points to
+    a const scalar (input arrays: callers pass addresses); ``opaque **`` is POINTER(c_void_p); any other ``T *`` / ``T **`` is typed."""
+    const, base, depth, name = decl
+    if depth == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if depth == 1 and base in header.structs:
+        return C.POINTER(header.structs[base])
+    if depth == 1 and base == "char" and const:
+        return C.c_char_p
+    if depth == 1 and (base == "void" or base in header.opaque):
+        return C.c_void_p
+    if depth == 2 and base in header.opaque:
+        return C.POINTER(C.c_void_p)
+    if base not in _SCALARS or not 1 <= depth <= 2:
+        raise ImportError(f"{where}: no ctypes type for '{'const ' if const else ''}{base} {'*' * depth}{name}'")
+    if depth == 1 and (name.endswith("_dev") or (parameter and const)):
+        return C.c_void_p
+    return C.POINTER(_SCALARS[base]) if depth == 1 else C.POINTER(C.POINTER(_SCALARS[base]))
+
+
+def read_header(text: str, classes: dict | None = None, path: str = "header") -> Header:
+    """Read the text of include/tssplat_amd.h.  ``classes``: C struct name -> a ``ctypes.Structure`` subclass without ``_fields_``
+    that is to receive them (a struct without one gets a class of its own name)."""
+    header = Header({}, set(), {}, {})
+    guard = []
+
+    def directive(m):
+        word, rest = m[1], m[2]
+        value = _DEFINE.fullmatch(rest) if word == "define" else None
+        if value:
+            header.constants[value[1]] = int(value[2], 0)
+        elif word == "ifndef":
+            guard.append(rest)
+        elif not (word in ("endif", "include") or (word == "define" and rest in guard)):     # (#define GUARD: the include guard)
+            raise ImportError(f"{path}: cannot read '#{word} {_flat(rest)}'")
+        return ""
+
+    text = _DIRECTIVE.sub(directive, _CPLUSPLUS.sub("", _COMMENT.sub(" ", text)))
+    pos = 0
+    while not _END.match(text, pos):
+        m = _ITEM.match(text, pos)
+        if not m or m[1] != m[2] or m[4] != m[6]:
+            raise ImportError(f"{path}: cannot read the declaration '{_flat(text[pos:].split(';')[0])}'")
+        pos = m.end()
+        if m[1]:
+            header.opaque.add(m[1])
+        elif m[3] == "enum":
+            for part in m[5].split(","):
+                member = _MEMBER.fullmatch(part)
+                if not member:
+                    raise ImportError(f"{path}: {m[4]}: cannot read the member '{_flat(part)}'")
+                header.constants[member[1]] = int(member[2])
+        elif m[3] == "struct":
+            where = f"{path}: {m[4]}"
+            fields = [(d[3], _ctype(d, where, header, False)) for line in m[5].split(";") if line.strip() for d in _declare(line, where)]
+            cls = (classes or {}).get(m[4]) or type(m[4], (C.Structure,), {})
+            cls._fields_ = fields                         # in the header's order
+            header.structs[m[4]] = cls
+        else:
+            head = _declare(m[7], path)
+            if len(head) != 1:
+                raise ImportError(f"{path}: cannot read the declaration '{_flat(m[0])}'")
+            *result, name = head[0]
+            where = f"{path}: {name}"
+            params = [] if m[8].strip() == "void" else [d for part in m[8].split(",") for d in _declare(part, where)]
+            restype = None if tuple(result) == (False, "void", 0) else _ctype((*result, name), where, header, False)
+            header.functions[name] = (restype, [(d[3], _ctype(d, where, header, True)) for d in params])
+    missing = sorted(set(classes or {}) - set(header.structs))
+    if missing:
+        raise ImportError(f"{path}: does not declare the structs {missing}")
+    return header
+
+
+# ---- the header's structs as classes: the fields are the header's, in its order ----
 class Options(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_int32),
-        ("device", C.c_int32),
-        ("lds_budget_bytes", C.c_int32),
-        ("max_threads", C.c_int32),
-        ("target_owned", C.c_int32),
-        ("lane_search_sweeps", C.c_int32),
-        ("host_only", C.c_int32),
-        ("num_threads", C.c_int32),
-        ("debug_flags", C.c_int32),
-        ("slots_per_thread", C.c_int32),
-        ("rebuild_dminv", C.c_int32),
-        ("abi_version", C.c_int32),
-    ]
+    """``tsamd_options``"""
 
 
 class PlanInfo(C.Structure):
-    _fields_ = [
-        ("n_vertices", C.c_int64), ("n_tets", C.c_int64), ("n_tiles", C.c_int64),
-        ("n_components", C.c_int64), ("total_slots", C.c_int64), ("total_tile_vertices", C.c_int64),
-        ("shared_vertex_copies", C.c_int64), ("finish_vertices", C.c_int64), ("device_bytes", C.c_int64),
-        ("max_slots", C.c_int32), ("max_tile_vertices", C.c_int32), ("block_threads", C.c_int32),
-        ("lds_bytes", C.c_int32), ("slots_per_thread", C.c_int32), ("n_planes", C.c_int32),
-    ]
+    """``tsamd_plan_info``"""
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class PartitionInfo(C.Structure):
-    _fields_ = [
-        ("owned_tets", C.c_int64), ("halo_slots", C.c_int64), ("staged_rows", C.c_int64), ("n_tiles", C.c_int64),
-        ("tile_capacity", C.c_int64), ("min_tiles", C.c_int64), ("cut_components", C.c_int64),
-        ("bisection_components", C.c_int64), ("cut_templates", C.c_int64), ("mean_fill", C.c_double), ("max_fill", C.c_double),
-    ]
+    """``tsamd_partition_info``"""
 
 
 class TileView(C.Structure):
-    _fields_ = [
-        ("n_slots", C.c_int32), ("n_owned", C.c_int32), ("s_pad", C.c_int32), ("n_verts", C.c_int32),
-        ("n_excl", C.c_int32), ("stage_off", C.c_int64), ("n_rows", C.c_int32), ("rec_base", C.c_int32),
-        ("planes", C.POINTER(C.c_uint32)), ("row_start", C.POINTER(C.c_uint16)),
-        ("gvid", C.POINTER(C.c_int32)), ("vdst", C.POINTER(C.c_int32)), ("slot_tet", C.POINTER(C.c_int32)), ("rest", C.POINTER(C.c_float)),
-    ]
+    """``tsamd_tile_view``: host pointers, typed -- tests/tile_emulator.py indexes them."""
 
 
 class BlendPlanStruct(C.Structure):
     """``tsamd_blend_plan``: device pointers and sizes of a blend plan (tssplat_amd/dr.py: BlendPlan)."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
-        ("batch", C.c_int64), ("n_points", C.c_int64), ("n_blends", C.c_int64), ("n_dst", C.c_int64), ("n_src", C.c_int64),
-        ("pix_point_dev", C.c_void_p), ("pix_dst_dev", C.c_void_p),
-        ("dst_ptr_dev", C.c_void_p), ("dst_src_pix_dev", C.c_void_p), ("dst_src_point_dev", C.c_void_p), ("dst_weight_dev", C.c_void_p),
-        ("src_ptr_dev", C.c_void_p), ("src_dst_pix_dev", C.c_void_p), ("src_dst_slot_dev", C.c_void_p), ("src_weight_dev", C.c_void_p),
-        ("point_pix_dev", C.c_void_p), ("point_dst_dev", C.c_void_p), ("point_src_dev", C.c_void_p),
-    ]
 
 
 class SmoothMeshStruct(C.Structure):
     """``tsamd_smooth_mesh``: sizes and device pointers of a vertex adjacency (tssplat_amd/smooth.py: VertexAdjacency)."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("reserved", C.c_int32),
-        ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_neighbours", C.c_int64), ("n_face_entries", C.c_int64),
-        ("offsets_dev", C.c_void_p), ("neighbours_dev", C.c_void_p),
-        ("face_offsets_dev", C.c_void_p), ("faces_of_dev", C.c_void_p), ("faces_dev", C.c_void_p),
-    ]
 
 
-ABI_VERSION = 3          # include/tssplat_amd.h: TSAMD_ABI_VERSION
+with open(_build.HEADER) as _fh:
+    HEADER = read_header(_fh.read(), {"tsamd_options": Options, "tsamd_plan_info": PlanInfo, "tsamd_partition_info": PartitionInfo,
+                                      "tsamd_tile_view": TileView, "tsamd_blend_plan": BlendPlanStruct,
+                                      "tsamd_smooth_mesh": SmoothMeshStruct}, "include/tssplat_amd.h")
+
+# Parameters whose type is NOT what _ctype's rule gives, keyed (function, parameter); tests/test_capi_bindings.py fails an entry
+# that names nothing in the header or that the rule has caught up with.
+_FLOATS, _INTS = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+EXCEPTIONS = {
+    # the schedule of a launch: host arrays that callers pass as ctypes arrays, so the element type is checked
+    ("tsamd_train_loop_launch", "c1"): _FLOATS, ("tsamd_train_loop_launch", "c2"): _FLOATS,
+    ("tsamd_train_loop_launch", "order"): _INTS, ("tsamd_train_loop_launch", "grad_limit"): _FLOATS,
+    # host output arrays that callers pass as ndarray.ctypes.data, a plain address
+    ("tsamd_extract_surface", "surface_vid"): C.c_void_p, ("tsamd_extract_surface", "faces"): C.c_void_p,
+    # the same: four numpy arrays by address
+    ("tsamd_grid_layout", "offsets_out"): C.c_void_p, ("tsamd_grid_layout", "resolution_out"): C.c_void_p,
+    ("tsamd_grid_layout", "hashed_out"): C.c_void_p, ("tsamd_grid_layout", "scale_out"): C.c_void_p,
+}
 
 # every symbol include/tssplat_amd.h declares: name -> (restype, argtypes)
-SIGNATURES = {
-    "tsamd_last_error": (C.c_char_p, []),
-    "tsamd_version": (C.c_char_p, []),
-    "tsamd_abi_version": (C.c_int32, []),
-    "tsamd_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Options), C.POINTER(C.c_void_p)]),
-    "tsamd_create_with_operator": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.POINTER(Options), C.POINTER(C.c_void_p)]),
-    "tsamd_create_from_veg": (C.c_int, [C.c_char_p, C.POINTER(Options), C.POINTER(C.c_void_p)]),
-    "tsamd_destroy": (None, [C.c_void_p]),
-    "tsamd_num_vertices": (C.c_int64, [C.c_void_p]),
-    "tsamd_num_tets": (C.c_int64, [C.c_void_p]),
-    "tsamd_get_plan_info": (C.c_int, [C.c_void_p, C.POINTER(PlanInfo)]),
-    "tsamd_get_partition_info": (C.c_int, [C.c_void_p, C.POINTER(PartitionInfo)]),
-    "tsamd_get_tile": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(TileView)]),
-    "tsamd_get_finish_lists": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int32)),
-                                         C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]),
-    "tsamd_get_index_reps": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32))]),
-    "tsamd_get_regular_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
-    "tsamd_get_adjacency": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32))]),
-    "tsamd_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
-    "tsamd_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p,
-                                 C.c_void_p]),
-    "tsamd_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_evaluate_dev_coef": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]),
-    "tsamd_graph_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "tsamd_graph_launch": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
-    "tsamd_graph_launch_to": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_graph_destroy": (None, [C.c_void_p]),
-    "tsamd_read_energy_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
-    "tsamd_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
-    "tsamd_get_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "tsamd_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "tsamd_adam_uniform_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
-                                        C.c_float, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
-    "tsamd_grad_limit_workspace_bytes": (C.c_int64, []),
-    "tsamd_grad_limit": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
-    "tsamd_train_loop_workspace_bytes": (C.c_int64, [C.c_int32]),
-    "tsamd_train_loop_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                          C.POINTER(C.c_void_p)]),
-    "tsamd_train_loop_launch": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_float, C.c_float,
-                                          C.c_float, C.c_int64, C.POINTER(C.c_float), C.c_void_p]),
-    "tsamd_train_loop_destroy": (None, [C.c_void_p]),
-    # renderer slice (SURVEY 8(f) row 4)
-    "tsamd_rasterize_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
-    "tsamd_pair_masks_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
-    "tsamd_rasterize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]),
-    "tsamd_interpolate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
-                                    C.c_void_p, C.c_void_p]),
-    "tsamd_interpolate_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
-                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_rasterize_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]),
-    "tsamd_antialias_topology_workspace_bytes": (C.c_int64, [C.c_int64]),
-    "tsamd_antialias_topology": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_antialias_prepared_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
-    "tsamd_antialias_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
-                                          C.c_int32, C.c_void_p, C.c_void_p]),
-    "tsamd_antialias": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
-                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "tsamd_antialias_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                           C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_silhouette": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_silhouette_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
-    "tsamd_silhouette_mse_workspace_bytes": (C.c_int64, [C.c_int64]),
-    "tsamd_silhouette_mse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_silhouette_mse_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
-    # the depth term from the alpha stage's ids
-    "tsamd_depth_mse_workspace_bytes": (C.c_int64, [C.c_int64]),
-    "tsamd_depth_mse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_depth_mse_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # the normal term (any [V, 3] vertex attribute) from the alpha stage's ids
-    "tsamd_normal_mse_workspace_bytes": (C.c_int64, [C.c_int64]),
-    "tsamd_normal_mse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_normal_mse_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # the texture stage's image side under a blend plan
-    "tsamd_shade_plan_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
-                                         C.c_void_p, C.c_void_p]),
-    "tsamd_shade_plan_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_shade": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_shade_backward": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_shade_l1_workspace_bytes": (C.c_int64, [C.c_int64]),
-    "tsamd_shade_l1": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_shade_l1_backward": (C.c_int, [C.POINTER(BlendPlanStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # surface glue (SURVEY 8(f) row 2)
-    "tsamd_extract_surface": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
-                                      C.POINTER(C.c_int64)]),
-    "tsamd_surface_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
-    "tsamd_surface_destroy": (None, [C.c_void_p]),
-    "tsamd_surface_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_surface_positions_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_vertex_normals_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # hash-grid encoding (the texture stage's colour field)
-    "tsamd_grid_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.POINTER(C.c_int64)]),
-    "tsamd_grid_encode": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
-                                    C.c_void_p, C.c_void_p]),
-    "tsamd_grid_encode_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_grid_sorted_chunk_points": (C.c_int64, []),
-    "tsamd_grid_backward_sorted_workspace_bytes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
-                                                             C.POINTER(C.c_int64)]),
-    "tsamd_grid_encode_backward_sorted": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "tsamd_grid_plan_bytes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_int64)]),
-    "tsamd_grid_plan_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
-                                        C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "tsamd_grid_backward_planned_workspace_bytes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
-                                                              C.POINTER(C.c_int64)]),
-    "tsamd_grid_encode_backward_planned": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    # fully fused MLP (the colour MLP of a tcnn network config)
-    "tsamd_mlp_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
-                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "tsamd_mlp_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "tsamd_mlp_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                    C.c_void_p, C.c_void_p]),
-    "tsamd_mlp_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # texture atlas and texture sampling (the texture stage's export)
-    "tsamd_atlas_layout": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "tsamd_atlas_bake_positions": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_texture": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                C.c_int32, C.c_void_p, C.c_void_p]),
-    "tsamd_texture_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
-                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # sphere initialisation: visual hull, squared distance transform, greedy ball cover
-    "tsamd_hull_carve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_double,
-                                   C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_edt_squared": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_greedy_cover": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # merging tet-spheres: union field on the voxel grid, marching tetrahedra in a count and an emit phase
-    "tsamd_union_field": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
-    "tsamd_surface_count": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_surface_emit": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                     C.c_void_p, C.c_void_p, C.c_void_p]),
-    # the merge's flood fill: connected components of the field's nodes, cavities filled, islands dropped
-    "tsamd_grid_components": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_field_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # surface metrics: area-uniform surface samples (weights; draw) and the all-pairs nearest-point search
-    "tsamd_sample_surface": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_nearest_points_workspace_bytes": (C.c_int64, [C.c_int64]),
-    "tsamd_nearest_points_info": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "tsamd_nearest_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # the exact point-to-triangle search: closest triangle, squared distance and closest point per query
-    "tsamd_nearest_on_mesh_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
-    "tsamd_nearest_on_mesh_info": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "tsamd_nearest_on_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]),
-    # surface simplification: cell keys and record slots, the per-cell run walk and solve, the face triples, the duplicate flags
-    "tsamd_simplify_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]),
-    "tsamd_simplify_cells": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_simplify_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_simplify_dedupe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # voxelising triangle meshes: the integer winding number on the merge's grid, and the occupancy made of it
-    "tsamd_voxel_workspace_bytes": (C.c_int64, [C.c_int32]),
-    "tsamd_voxel_winding": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p]),
-    "tsamd_voxel_occupancy": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]),
-    # mesh quality: lattice snap and per-triangle record, the crossing-pair search, edge keys, fan pairs, union-find
-    "tsamd_quality_info": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "tsamd_quality_prepare": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]),
-    "tsamd_quality_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_quality_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_quality_fan_pairs": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_quality_union": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
-    # surface smoothing: directed edge keys and vertex-face keys, the rows of the adjacency, who moves, one half-step, a whole run
-    "tsamd_smooth_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_smooth_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "tsamd_smooth_classify": (C.c_int, [C.c_void_p, C.POINTER(SmoothMeshStruct), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "tsamd_smooth_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SmoothMeshStruct), C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_double,
-                                    C.c_void_p]),
-    "tsamd_smooth_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SmoothMeshStruct), C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
-                                   C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.c_void_p]),
-}
+SIGNATURES = {name: (restype, [EXCEPTIONS.get((name, p), t) for p, t in params]) for name, (restype, params) in HEADER.functions.items()}
+globals().update(HEADER.constants)          # every TSAMD_* enum member and integer #define by name: _capi.TSAMD_SMOOTH_TAUBIN
+ABI_VERSION = HEADER.constants["TSAMD_ABI_VERSION"]
 
 
 def lib_path() -> str:

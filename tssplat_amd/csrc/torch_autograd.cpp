@@ -16,12 +16,14 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include "../../include/tssplat_amd.h"
+
 namespace {
 
-using launch_fn = int (*)(void *graph, float c1, float c2, void *stream);
-using fwdbwd_fn = int (*)(void *handle, const float *x, const float *grad_out, float c1, float c2, int order, void *stream, float *energy,
-                          float *grad);
-using err_fn = const char *(*)();
+// the types of the three entry points are the header's own: a signature that changes there fails to compile here
+using launch_fn = decltype(&tsamd_graph_launch);
+using fwdbwd_fn = decltype(&tsamd_forward_backward);
+using err_fn = decltype(&tsamd_last_error);
 
 launch_fn g_graph_launch = nullptr;
 fwdbwd_fn g_forward_backward = nullptr;
@@ -54,7 +56,7 @@ struct ReplayFunction : public torch::autograd::Function<ReplayFunction> {
                               const at::Tensor &energy, const at::Tensor &grad, const at::Tensor &ticket)
     {
         TORCH_CHECK(g_graph_launch, "tssplat_amd._tsamd_autograd: entry points not set");
-        check(g_graph_launch(reinterpret_cast<void *>(graph), float(c1), float(c2), current_stream(x)), "tsamd_graph_launch");
+        check(g_graph_launch(reinterpret_cast<tsamd_graph *>(graph), float(c1), float(c2), current_stream(x)), "tsamd_graph_launch");
         int64_t *t = ticket.data_ptr<int64_t>();   // (a CPU counter shared with the Python owner of the buffers)
         ctx->saved_data["ticket_value"] = ++*t;
         ctx->saved_data["ticket"] = ticket;
@@ -90,7 +92,7 @@ struct EvalFunction : public torch::autograd::Function<EvalFunction> {
         const at::Tensor xc = x.contiguous();
         at::Tensor energy = at::empty({}, xc.options());
         at::Tensor grad = at::empty_like(xc);
-        check(g_forward_backward(reinterpret_cast<void *>(handle), xc.data_ptr<float>(), nullptr, float(c1), float(c2), int(order),
+        check(g_forward_backward(reinterpret_cast<tsamd_handle *>(handle), xc.data_ptr<float>(), nullptr, float(c1), float(c2), int(order),
                                  current_stream(xc), energy.data_ptr<float>(), grad.data_ptr<float>()),
               "tsamd_forward_backward");
         ctx->saved_data["grad"] = grad;

@@ -783,8 +783,8 @@ def shade_l1(color: torch.Tensor, blend_plan: BlendPlan, background: torch.Tenso
     return (loss, image.detach()) if return_image else loss
 
 
-_TEX_FILTERS = {"nearest": 0, "linear": 1}                  # TSAMD_TEX_FILTER_* of include/tssplat_amd.h
-_TEX_BOUNDARIES = {"wrap": 0, "clamp": 1, "zero": 2}        # TSAMD_TEX_BOUNDARY_*
+_TEX_FILTERS = {"nearest": _capi.TSAMD_TEX_FILTER_NEAREST, "linear": _capi.TSAMD_TEX_FILTER_LINEAR}                  # include/tssplat_amd.h
+_TEX_BOUNDARIES = {"wrap": _capi.TSAMD_TEX_BOUNDARY_WRAP, "clamp": _capi.TSAMD_TEX_BOUNDARY_CLAMP, "zero": _capi.TSAMD_TEX_BOUNDARY_ZERO}
 
 
 class _TextureFunc(torch.autograd.Function):

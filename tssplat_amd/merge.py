@@ -43,7 +43,7 @@ __all__ = ["MergedSurface", "FilledField", "union_field", "extract_surface", "me
 MIN_GRID = 2
 MAX_GRID = 512           # flat node indices < 2^27; 7 vertices and 12 triangles per node stay below 2^31
 _MAX_TETS = 1 << 30      # include/tssplat_amd.h: tsamd_union_field
-FILL_MODES = {"cavities": 1, "outer": 2}      # include/tssplat_amd.h: TSAMD_FILL_CAVITIES, TSAMD_FILL_OUTER
+FILL_MODES = {"cavities": _capi.TSAMD_FILL_CAVITIES, "outer": _capi.TSAMD_FILL_OUTER}      # include/tssplat_amd.h
 
 
 @dataclasses.dataclass

@@ -39,7 +39,7 @@ __all__ = ["SurfaceSamples", "SurfaceMetrics", "ThresholdMetrics", "NearestInfo"
 
 MAX_COUNT = 2 ** 31 - 1                 # triangles, samples, queries, ref points (include/tssplat_amd.h)
 DEFAULT_THRESHOLDS = (0.01, 0.02)
-_SAMPLE_WEIGHTS, _SAMPLE_DRAW = 0, 1    # include/tssplat_amd.h: TSAMD_SAMPLE_WEIGHTS, TSAMD_SAMPLE_DRAW
+_SAMPLE_WEIGHTS, _SAMPLE_DRAW = _capi.TSAMD_SAMPLE_WEIGHTS, _capi.TSAMD_SAMPLE_DRAW    # include/tssplat_amd.h
 
 
 @dataclasses.dataclass

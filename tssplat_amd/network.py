@@ -27,7 +27,7 @@ __all__ = ["FusedMLP", "parse_mlp_config", "mlp_layout", "ACTIVATIONS", "OUTPUT_
 _lib = _capi.load()
 
 NETWORK_OTYPES = ("fullyfusedmlp", "cutlassmlp", "mlp")
-ACTIVATIONS = {"relu": 1, "none": 0}                  # include/tssplat_amd.h: TSAMD_MLP_ACT_*
+ACTIVATIONS = {"relu": _capi.TSAMD_MLP_ACT_RELU, "none": _capi.TSAMD_MLP_ACT_NONE}                  # include/tssplat_amd.h
 OUTPUT_ACTIVATIONS = {"none": 0, "sigmoid": 2}
 WIDTHS = (16, 32, 64, 128)
 LOSS_SCALE = 128.0

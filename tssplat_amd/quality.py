@@ -47,7 +47,9 @@ MAX_PAIRS = 2 ** 31 - 1
 ORDERS = ("none", "morton")
 DEFAULT_ORDER = "morton"
 _SENTINEL = 2 ** 63 - 1
-_STATS = ("crossing_pairs", "crossing_faces", "invalid_faces", "degenerate_faces", "box_pairs", "listed_pairs", "tile_visits")
+# the words of the stats record: the header's TSAMD_QUALITY_* names in value order ("crossing_pairs", ..., "tile_visits")
+_STATS = tuple(name[len("TSAMD_QUALITY_"):].lower()
+               for name in sorted((n for n in _capi.HEADER.constants if n.startswith("TSAMD_QUALITY_")), key=_capi.HEADER.constants.get))
 
 
 @dataclasses.dataclass

@@ -29,7 +29,7 @@ __all__ = ["SimplifiedSurface", "EdgeStats", "simplify", "edge_stats", "run_leng
 
 MAX_CELLS = 1024                          # cell keys stay below 2^30
 MAX_TRIANGLES = (2 ** 31 - 1) // 3        # three record slots per triangle, indexed with 32 bits (include/tssplat_amd.h)
-PLACEMENTS = {"quadric": 0, "mean": 1}    # include/tssplat_amd.h: TSAMD_SIMPLIFY_QUADRIC, TSAMD_SIMPLIFY_MEAN
+PLACEMENTS = {"quadric": _capi.TSAMD_SIMPLIFY_QUADRIC, "mean": _capi.TSAMD_SIMPLIFY_MEAN}    # include/tssplat_amd.h
 DEFAULT_STABILISE = 2.0 ** -10
 _SENTINEL = 2 ** 63 - 1
 

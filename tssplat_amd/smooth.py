@@ -40,9 +40,9 @@ from . import _args, _capi
 
 __all__ = ["VertexAdjacency", "SmoothedSurface", "adjacency", "smooth", "MODES", "DEFAULT_MODE", "BOUNDARIES", "MAX_ITERATIONS", "MAX_TRIANGLES", "STATE_STRIDE"]
 
-MODES = {"taubin": 0, "tangential": 1}        # include/tssplat_amd.h: TSAMD_SMOOTH_TAUBIN, TSAMD_SMOOTH_TANGENTIAL
+MODES = {"taubin": _capi.TSAMD_SMOOTH_TAUBIN, "tangential": _capi.TSAMD_SMOOTH_TANGENTIAL}        # include/tssplat_amd.h
 DEFAULT_MODE = "taubin"
-BOUNDARIES = {"fixed": 0, "free": 1}          # TSAMD_SMOOTH_BOUNDARY_FIXED, TSAMD_SMOOTH_BOUNDARY_FREE
+BOUNDARIES = {"fixed": _capi.TSAMD_SMOOTH_BOUNDARY_FIXED, "free": _capi.TSAMD_SMOOTH_BOUNDARY_FREE}
 MAX_ITERATIONS = 4096
 MAX_TRIANGLES = 2 ** 31 // 6 - 1              # six directed keys per face, positions are 32-bit (include/tssplat_amd.h)
 STATE_STRIDE = 3                              # float64 per state record: 24 bytes beat the padded 32 on every mesh measured (DESIGN section 19 has both figures)

@@ -34,7 +34,7 @@ MIN_GRID = 1
 MAX_GRID = 512
 SUBCELL_BITS = 10
 LANE_COLUMNS = 16         # csrc/voxel.h: a face with more candidate columns is walked by its whole wave
-RULES = {"nonzero": 0, "positive": 1, "odd": 2}     # include/tssplat_amd.h: TSAMD_VOXEL_NONZERO, _POSITIVE, _ODD
+RULES = {"nonzero": _capi.TSAMD_VOXEL_NONZERO, "positive": _capi.TSAMD_VOXEL_POSITIVE, "odd": _capi.TSAMD_VOXEL_ODD}     # include/tssplat_amd.h
 _STATS = 12
 _COUNT_WORDS = 64 * _STATS * 2       # csrc/voxel.h: 64 copies of the counts, in int32 words, ahead of the deposits
 
